@@ -12,7 +12,18 @@ step      one pass of the fused HIP kernel over every stream of the rank (65536 
 
 Inputs are resident in HBM before the timed region.  One JSON line on rank 0.
 
-    python bench.py                       # N=1
+A plain run measures the headline only: set-up, spin-up and W warm-up steps, K timed steps, the outputs of the last
+step (--dump-outputs), the line.  Everything else the line can carry -- the other log mode, the sustained run, the
+FFT+smooth chains, the GL_R16 output, the `configs` key, the HBM traffic collected with rocprofv3, the window
+self-test and the CPU baseline -- is measured under --full only (the --no-* options still switch single parts off).
+
+--dump-outputs DIR writes the spectra of the last timed step as DIR/spectra.npy (float32 [k][2][n]): a fixed, seeded
+sample of k streams (the first and the last among them) of at most 32 MiB; rank r > 0 writes DIR/spectra_rank<r>.npy.
+The PCM is seeded and stateful chains start from a reset state after the spin-up, so the same arguments give the same
+inputs and outputs from run to run.
+
+    python bench.py                       # N=1, headline only
+    python bench.py --full                # N=1, everything
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -29,6 +40,26 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md (6.29 TB/s measured copy)
+DUMP_BYTES = 32 << 20     # --dump-outputs: bytes of spectra written per run (all ranks together)
+DUMP_SEED = 2024          # --dump-outputs: seed of the sampled stream indices
+
+
+def dump_outputs(path: str, d_out, rank: int, world: int) -> None:
+    """--dump-outputs: a fixed, seeded sample of the streams of d_out (float32 [streams][2][n]) as <path>/spectra.npy
+    (<path>/spectra_rank<r>.npy for rank r > 0); the first and the last stream are always in it."""
+    import numpy as np
+    import torch
+    streams = d_out.shape[0]
+    per_stream = d_out[0].numel() * d_out.element_size()
+    k = max(1, min(streams, DUMP_BYTES // world // per_stream))
+    idx = {0, streams - 1}
+    if k > len(idx):
+        rest = np.random.default_rng(DUMP_SEED).permutation(np.arange(1, streams - 1))
+        idx.update(int(i) for i in rest[:k - len(idx)])
+    idx = np.array(sorted(idx)[:k], dtype=np.int64)
+    sample = d_out.index_select(0, torch.from_numpy(idx).to(d_out.device)).cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "spectra.npy" if rank == 0 else f"spectra_rank{rank}.npy"), sample)
 
 
 def usable_cores() -> tuple[int, str]:
@@ -490,13 +521,20 @@ def main() -> None:
                          "found outside the timed region; profiles/r06/modes.txt) and time whatever placement the allocation happened to give")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--spinup-s", type=float, default=0.3, help="untimed clock spin-up before the W warm-up steps")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: other log mode, sustained run, FFT+smooth chains, GL_R16 output, "
+                         "`configs`, HBM traffic collected with rocprofv3, window self-test, CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of the last step's spectra to DIR/spectra.npy (float32)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
 
     # --gpus N started as a PLAIN process (no launcher around it: RANK unset) must still drive N GPUs, or refuse -- never measure one GPU and
-    # print n_gpus 1 (VERDICT r5 missing 5).  It re-executes itself under torch.distributed.run with one rank per GPU; fewer than N visible
+    # print n_gpus 1 (VERDICT r5 missing 5).  It runs itself under torch.distributed.run, a child process, with one rank per GPU; fewer than N visible
     # devices is an error.  (GLV_BENCH_DEVICE_COUNT overrides the visible-device count and GLV_BENCH_SPAWN_DRYRUN=1 prints the command instead of
     # running it: test hooks, tests/test_bench_cli.py.)
     if a.gpus < 1:
@@ -516,7 +554,8 @@ def main() -> None:
             return
         env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         sys.stdout.flush(); sys.stderr.flush()
-        os.execve(sys.executable, cmd, env)
+        import subprocess
+        raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -563,7 +602,7 @@ def main() -> None:
     if a.grid: batch.set_grid(a.grid)
     alt_batch = None
     alt_mode = 0 if a.log_mode == 1 else 1
-    if a.log_mode in (0, 1) and not a.no_alt:  # secondary measurement: the other log mode of the same pass
+    if a.full and a.log_mode in (0, 1) and not a.no_alt:  # secondary measurement: the other log mode of the same pass
         alt_batch = G.Batch(G.Params(n=n, log_mode=alt_mode), streams, ops, device=device)
         if a.grid: alt_batch.set_grid(a.grid)
     gen = torch.Generator(device="cuda"); gen.manual_seed(12345 + lo)     # the PCM of a shard is a function of its first global stream
@@ -571,16 +610,20 @@ def main() -> None:
     d_out = torch.empty((streams, 2, n), dtype=torch.float32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
 
-    def timed(b):
+    def timed(b, reset_state=False):
         """Spin-up, W warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides.
 
         The spin-up (same launches, untimed, `--spinup-s` seconds of wall clock) brings the GPU to its
         sustained clock/power state: the first few dozen launches after idle run ~20 % slower on MI355X
-        (ms/step 1.27 at K=3 vs 1.04 at K=50 without it), which would make `value` depend on K."""
+        (ms/step 1.27 at K=3 vs 1.04 at K=50 without it), which would make `value` depend on K.
+        reset_state: zero a stateful chain's state after the spin-up, so that its last output depends on W + K only."""
         t_end = time.perf_counter() + a.spinup_s
         while time.perf_counter() < t_end:
             for _ in range(8):
                 b.process_s16(d_pcm, d_out, ops, stream)
+            torch.cuda.synchronize()
+        if reset_state:
+            b.reset()
             torch.cuda.synchronize()
         for _ in range(a.warmup):
             b.process_s16(d_pcm, d_out, ops, stream)
@@ -602,11 +645,13 @@ def main() -> None:
             dt = float(t.item())
         return dt, kms, nl
 
-    elapsed, kernel_ms, launches = timed(batch)
+    elapsed, kernel_ms, launches = timed(batch, reset_state=ops != G.OP_FFT)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, d_out, rank, world)
     # the same launch back to back for --sustained-s seconds (N=1 only): the headline is a 13 ms burst after 0.3 s of spin-up, this is
     # what the part holds at its power limit (say which one a claim is made on)
     sustained = None
-    if world == 1 and a.sustained_s > 0:
+    if a.full and world == 1 and a.sustained_s > 0:
         batch.timing_begin()
         t0 = time.perf_counter(); nl = 0
         while time.perf_counter() - t0 < a.sustained_s:
@@ -633,7 +678,7 @@ def main() -> None:
     # tertiary measurement (N=1 only): the chain GLava's spectrum modules actually request --
     # window,fft,gravity,avg (bars/1.frag:12-24) -- i.e. the same pass + gravity + F=5 windowed average
     chain = None
-    if world == 1 and ops == G.OP_FFT and not a.no_alt:
+    if a.full and world == 1 and ops == G.OP_FFT and not a.no_alt:
         if alt_batch is not None: alt_batch.close(); alt_batch = None
         cops = G.OP_FFT | G.OP_GRAVITY | G.OP_AVERAGE
         cb = G.Batch(params, streams, cops, device=device)
@@ -656,7 +701,7 @@ def main() -> None:
 
     # the same pass with the output as GL_R16 texels (what handle_audio uploads, render.c:521-524): 8N bytes per frame
     r16 = None
-    if world == 1 and ops == G.OP_FFT and not a.no_alt:
+    if a.full and world == 1 and ops == G.OP_FFT and not a.no_alt:
         rb = G.Batch(params, streams, G.OP_FFT, device=device)
         ops_saved, ops = ops, G.OP_FFT | G.OP_R16
         r_el, r_kms, r_nl = timed(rb)
@@ -671,7 +716,7 @@ def main() -> None:
     # BASELINE configs[2], configs[4] and the two large stateless sizes, each with its own kernel time and roofline fraction
     # (SURVEY 8d bytes per frame) -- the figures below the headline's that VERDICT r2 wants in the driver's record
     configs = None
-    if world == 1 and ops == G.OP_FFT and not a.no_alt and not a.no_configs:
+    if a.full and world == 1 and ops == G.OP_FFT and not a.no_alt and not a.no_configs:
         configs = extra_configs(G, torch, device, a, HBM_PEAK_GBS)
 
     frames_rank = streams * a.steps
@@ -691,8 +736,8 @@ def main() -> None:
     if rank == 0:
         total_frames = sum(s["frames"] for s in stats)
         value = total_frames / elapsed
-        traffic_now, traffic_detail = (None, {"skipped": "--no-live-traffic, or more than one rank"})
-        if a.live_traffic and world == 1:
+        traffic_now, traffic_detail = (None, {"skipped": "no --full, --no-live-traffic, or more than one rank"})
+        if a.full and a.live_traffic and world == 1:
             torch.cuda.synchronize()
             traffic_now, traffic_detail = live_traffic(a)
         alg_bytes = batch.algorithmic_bytes(ops)           # per launch (all streams of the rank)
@@ -766,14 +811,15 @@ def main() -> None:
             chains["sm_out"] = chain_rec(g.get("sm_out"), streams, "... + the pre-smoothing pass (render.c:2277-2303) -> `sm` texels: what GLava ships end to end, two launches, 28 N B/frame")
             chains["sm_out_live"] = chain_rec(g.get("sm_out_live"), streams, "the same `sm` texels with the state kept only for the bins the pass samples (GLV_OP_BARS_ONLY); frac on ITS OWN bytes, frac_of_28N for comparison")
         line["roofline"]["chains"] = {k: v for k, v in chains.items() if v}
-        try:
-            mism, shifted = batch.window_selftest()
-            line["window_selftest"] = {"mismatches": mism, "shifted_positions": shifted,
-                                       "note": f"every (s16 sample value, window position) pair of N={n}: the kernels' float-pair window product "
-                                               "against the reference's float x double -> double -> float product, on the device, outside the timed region"}
-        except Exception as ex:                    # a diagnostic, never a reason to lose the line
-            line["window_selftest"] = {"error": str(ex)}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            try:
+                mism, shifted = batch.window_selftest()
+                line["window_selftest"] = {"mismatches": mism, "shifted_positions": shifted,
+                                           "note": f"every (s16 sample value, window position) pair of N={n}: the kernels' float-pair window product "
+                                                   "against the reference's float x double -> double -> float product, on the device, outside the timed region"}
+            except Exception as ex:                    # a diagnostic, never a reason to lose the line
+                line["window_selftest"] = {"error": str(ex)}
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n, a.cpu_seconds)
         else:
             line["cpu_baseline"] = None

@@ -75,10 +75,9 @@ def test_host_bar_tables_equal_the_shader_evaluation(emu, n, bars, factor, seed)
     """tap tables and work lists of GLV_OP_BARS (glv_tables.h) through the host emulator, 16 groups as glv_bars_kernel"""
     want = GOLD[f"bars_n{n}_b{bars}_f{factor}_s{seed}"]
     tex = tex_row(n, seed)
-    got = np.empty(bars, np.float32)
-    emu.glvemu_bars.argtypes = [np.ctypeslib.ndpointer(np.float32), C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int,
-                                np.ctypeslib.ndpointer(np.float32), C.c_void_p, C.c_float]
-    assert emu.glvemu_bars(tex, 1, n, bars, factor, 16, got, None, 0.0) == 0
+    # through the shared helper: the session's emulator library is used by other tests too, its argtypes are not set here
+    from emu_lib import emu_bars
+    got = emu_bars(emu, tex, n, bars, factor, groups=16)[0][0]
     assert np.abs(got - want).max() <= 4 * ULPS * np.abs(want).max()
 
 

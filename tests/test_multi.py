@@ -206,7 +206,7 @@ def _run_bench_plain(gpus, env_extra):
 
 def test_bench_gpus_n_without_a_launcher_spawns_n_ranks():
     """VERDICT r5 missing 5: `python bench.py --gpus 2` as a plain process (RANK unset) must not take the single-rank path.  With two devices
-    visible (mocked: GLV_BENCH_DEVICE_COUNT) it re-executes itself under torch.distributed.run with two ranks (the command is printed instead of
+    visible (mocked: GLV_BENCH_DEVICE_COUNT) it runs itself under torch.distributed.run (a child process) with two ranks (the command is printed instead of
     run: GLV_BENCH_SPAWN_DRYRUN); with one device it exits non-zero and says why.  No JSON bench line in either case."""
     r = _run_bench_plain(2, {"GLV_BENCH_DEVICE_COUNT": "2", "GLV_BENCH_SPAWN_DRYRUN": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
@@ -271,7 +271,7 @@ def test_bench_line_collects_its_hbm_traffic_in_the_same_run():
     import shutil
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("no rocprofv3 on this box")
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-configs", "--no-cpu-baseline", "--no-alt", "--sustained-s", "0"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-configs", "--no-cpu-baseline", "--no-alt", "--sustained-s", "0"]
     env = {k: v for k, v in os.environ.items() if not k.startswith(("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_"))}
     r = subprocess.run(base, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

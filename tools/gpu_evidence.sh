@@ -4,7 +4,7 @@
 # Everything lands in gpurun_out/<round>/ (scratch; copy what is to be judged into profiles/<round>/).  Sections:
 #   tests            the whole GPU suite                      -> pytest_gpu.txt
 #   tests:<expr>     pytest -k <expr>                         -> pytest_<expr>.txt
-#   bench            python bench.py                          -> bench_line.json
+#   bench            python bench.py --full                   -> bench_line.json
 #   headline         rocprofv3 stats + PMC of the headline launch (tools/profile.sh)         -> gpurun_out/prof_<round>/
 #   prof:<cfg>       rocprofv3 stats + PMC of tools/cfg_run.py <cfg> 150 (gl_default | gl_bars | gl_sm | gl_sm64 | configs2 | chain | n1024bars | ring)
 #   size:<n>:<s>     the stateless pass at another size (tools/profile.sh --n <n> --streams <s>)
@@ -22,7 +22,7 @@ for sec in "$@"; do
   case $sec in
     tests)      timeout 2400 python -m pytest tests -q -m gpu > "$O/pytest_gpu.txt" 2>&1; grep -E "passed|failed|error" "$O/pytest_gpu.txt" | tail -2 ;;
     tests:*)    k=${sec#tests:}; timeout 1800 python -m pytest tests -q -m gpu -k "$k" > "$O/pytest_$k.txt" 2>&1; tail -5 "$O/pytest_$k.txt" | cut -c1-300 ;;
-    bench)      timeout 1500 python bench.py > "$O/bench_line.json" 2> "$O/bench.err"; echo "bench rc $?"; python - "$O/bench_line.json" <<'PY'
+    bench)      timeout 1500 python bench.py --full > "$O/bench_line.json" 2> "$O/bench.err"; echo "bench rc $?"; python - "$O/bench_line.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 print("headline", round(d["value"] / 1e6, 2), "M frames/s", round(d["roofline"]["frac"], 4))
