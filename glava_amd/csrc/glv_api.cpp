@@ -102,14 +102,7 @@ std::vector<WisdomEntry> g_wisdom;
 std::atomic<uint64_t> g_wisdom_gen{1};      // bumped by every change of the table: invalidates the per-batch caches
 bool g_wisdom_env_loaded = false;
 
-constexpr unsigned kOpGl16 = 1u << 31;     // internal: the chain runs as the fused GL_R16 kernel (gl_storage == 1)
-uint32_t ops_class_of(unsigned ops) {      // the kernel instantiation a chain selects (glv_kernel_tmpl.h launch_variant)
-    if (ops & kOpGl16) return (ops & GLV_OP_BARS) ? 6 : 5;
-    if (ops & GLV_OP_BARS) return 2;
-    if (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) return (ops & GLV_OP_R16) ? 4 : 1;
-    return (ops & GLV_OP_R16) ? 3 : 0;
-}
-constexpr int kOpsClasses = 7, kInKinds = 5;
+constexpr int kOpsClasses = 7, kInKinds = 5;     // wisdom classes (wisdom_class): glv::FrameClass 0..6
 uint32_t log2_round(uint32_t v) { uint32_t l = 0; while ((2u << l) <= v) ++l; return ((v >> l << l) * 3 / 2 <= v && l < 31) ? l + 1 : l; }
 bool same_key(const WisdomKey& a, const WisdomKey& b) {
     return a.n == b.n && a.in_kind == b.in_kind && a.ops_class == b.ops_class && a.log_mode == b.log_mode && a.streams_log2 == b.streams_log2
@@ -487,12 +480,31 @@ int batch_alloc(glv_batch* b, uint32_t rows) {
     return GLV_OK;
 }
 
+// does `ops` run as the fused GL_R16 kernel?  (gl_storage 1, an FFT chain with state; RAW / SMOOTH / the audit log take the passes one by one)
+bool gl_fused_chain(const glv_batch* b, unsigned ops) {
+    return b->p.gl_storage == 1 && (ops & GLV_OP_FFT) && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !(ops & (GLV_OP_RAW | GLV_OP_SMOOTH)) && b->p.log_mode != 2;
+}
+// ... or the GL passes one by one (gl_storage 2; RAW / SMOOTH / the audit log of 1)?
+bool gl_passes_chain(const glv_batch* b, unsigned ops) {
+    return b->p.gl_storage != 0 && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !gl_fused_chain(b, ops);
+}
+// the operators of an FFT chain the frame kernel runs: the GL passes one by one leave it the transform alone (GLV_OP_RAW: the passes then
+// run on the raw values)
+unsigned frame_ops(const glv_batch* b, unsigned ops) { return gl_passes_chain(b, ops) ? GLV_OP_FFT | (ops & GLV_OP_RAW) : ops; }
+// The launch wisdom's class of an FFT chain: its frame kernel's class with the bars fused and every bin live.  The key is chosen before the
+// configuration, and whether the bars fuse depends on the configuration (bar_fusable[variant]): a chain with GLV_OP_BARS is class 2 or 6
+// even where its bars run as a second launch.  The values are part of the wisdom file format (0..6).
+uint32_t wisdom_class(const glv_batch* b, unsigned ops) {
+    const unsigned f = frame_ops(b, ops);
+    return (uint32_t) glv::frame_class(gl_fused_chain(b, ops), (f & GLV_OP_BARS) != 0, false, f);
+}
+
 WisdomKey wisdom_key(const glv_batch* b, int in_mode, unsigned ops) {
     WisdomKey k;
     std::memset(&k, 0, sizeof(k));
-    k.n = b->p.n; k.in_kind = (uint32_t) in_mode; k.ops_class = ops_class_of(ops); k.log_mode = b->p.log_mode;
+    k.n = b->p.n; k.in_kind = (uint32_t) in_mode; k.ops_class = wisdom_class(b, ops); k.log_mode = b->p.log_mode;
     k.streams_log2 = log2_round(b->streams);
-    k.avg_frames = (ops & GLV_OP_AVERAGE) ? b->p.avg_frames : 0;          // F changes what a stateful launch moves
+    k.avg_frames = (frame_ops(b, ops) & GLV_OP_AVERAGE) ? b->p.avg_frames : 0;          // F changes what a stateful launch moves
     key_set_device(k, b->device_name, (uint32_t) b->num_cus);
     return k;
 }
@@ -517,7 +529,7 @@ int default_grid(const glv_batch* b, uint32_t units, int variant) {
 // (kernel configuration, workgroups) of the next frame-kernel launch: explicit overrides, else the wisdom, else the defaults
 void launch_plan(glv_batch* b, uint32_t units, int in_mode, unsigned ops, int* variant, int* grid) {
     int v = 0, g = 0;
-    const uint32_t cls = ops_class_of(ops);
+    const uint32_t cls = wisdom_class(b, ops);
     if (b->variant_override < 0 || b->grid_override <= 0) {
         glv_batch::PlanCache& pc = b->plan_cache[in_mode][cls];
         const uint64_t gen = g_wisdom_gen.load(std::memory_order_acquire);
@@ -731,6 +743,16 @@ bool same_params(const glv_params& a, const glv_params& b) {
            && same_bits(a.bar_phase, b.bar_phase) && same_shape(a, b);
 }
 
+// Can the bars of a chain -- or of every chain a creation mask announces -- be computed inside the frame kernel, from the finished row in LDS?
+// The part that does not depend on the kernel configuration (bar_fusable[variant]: whole-wave rows, the bars fit the slack behind the row):
+// a chain with state and no smoothing pass, whose kernel class takes them -- the float chain's bars as GL_R16 texels leave through
+// glv_bars_kernel, the GL_R16 chain stores them itself, the GL passes one by one (gl_storage 2, the audit log) never fuse; GLV_UNFUSED_BARS
+// (diagnostics) forces two launches.  process() adds that the chain transforms (GLV_OP_FFT) and is not run pass by pass (GLV_OP_RAW).
+bool bars_fusable(const glv_batch* b, unsigned ops) {
+    return (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !(ops & GLV_OP_SMOOTH) && !b->unfused_bars
+           && (b->p.gl_storage == 0 ? !(ops & GLV_OP_R16) : b->p.gl_storage == 1 && b->p.log_mode != 2);
+}
+
 // Everything the process calls need besides the state arrays, made from b->p: tilt table, the gravity step on texels, and -- as
 // announced by the creation mask -- bar tables, smooth bounds, the internal spectra rows.  Called by creation and by
 // glv_batch_set_params (and by the single-stream drop-ins when their caller changes a knob): the ONLY place that allocates or
@@ -753,39 +775,28 @@ int batch_prepare(glv_batch* b) {
         if (rc != GLV_OK) { if (b->ops_mask & GLV_OP_BARS) return rc; g_err = said; }
     }
     if (b->ops_mask & GLV_OP_BARS) {
-        // the internal spectra rows: needed whenever bars are not computed inside the transform's launch from a row in LDS
-        // (stateless chains, rows whose bars do not fit the slack behind them, SMOOTH | BARS) and no state array holds the spectra
-        // -- the test must cover EVERY chain process() would run unfused (its `fused_bars`): the float chain's bars as texels
-        // (BARS | R16 with gl_storage 0) leave through glv_bars_kernel, the audit log (log_mode 2) takes the GL passes one by one, and
-        // GLV_UNFUSED_BARS forces two launches; only the GL_R16 chain whose every kernel configuration takes the bars goes without
-        // A FLOAT chain (gl_storage 0) whose every kernel configuration takes the bars goes without as well (16384 stereo streams of
-        // N = 4096 would hold 512 MiB nothing reads) -- unless the creation mask announces GLV_OP_R16: its bars as GL_R16 texels leave
-        // through glv_bars_kernel, from the scratch rows (the mask's R16 bit is that hint and nothing else; gravity-only chains read the
-        // state).  gl_storage 2 takes the GL passes one by one and always parks the rows.
-        bool all_fused = (b->ops_mask & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0 && !(b->ops_mask & GLV_OP_SMOOTH)
-                         && (b->p.gl_storage == 1 || (b->p.gl_storage == 0 && !(b->ops_mask & GLV_OP_R16)))
-                         && b->p.log_mode != 2 && !b->unfused_bars;
+        // the internal spectra rows: needed whenever bars are not computed inside the transform's launch from a row in LDS and no state
+        // array holds the spectra -- unless every chain the creation mask announces fuses its bars in every kernel configuration
+        // (bars_fusable: 16384 stereo streams of N = 4096 would hold 512 MiB nothing reads).  The mask's R16 bit is the hint that a float
+        // chain's bars are wanted as GL_R16 texels (they leave through glv_bars_kernel, from the scratch rows); gravity-only chains read the
+        // state.  One difference from process(): under the audit log (log_mode 2) a float chain fuses its bars and gets the rows all the
+        // same -- which batches hold them is kept as it was.
+        bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
         for (int v = 0; v < glv::frame_variants(b->log_nn) && v < glv_batch::kMaxVariants; ++v) all_fused = all_fused && b->bar_fusable[v];
         if (!all_fused && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * b->p.n));
         b->update_live_bins();
     }
     // function attributes (the > 64 KiB dynamic-LDS opt-in) of every frame kernel this batch can launch: set here, once per device
-    // and instantiation, so that a process call is a plain launch (launch_variant with grid 0 = attribute only; combinations
-    // that are not built answer hipErrorInvalidValue, which is not an error here)
+    // and instantiation, so that a process call is a plain launch (launch_variant with grid 0 = attribute only; classes a
+    // configuration is not built for answer hipErrorInvalidValue, which is not an error here)
     if (b->attr_log_mode != (int) b->p.log_mode) {
         b->attr_log_mode = (int) b->p.log_mode;
         glv::FrameArgs a;
         std::memset(&a, 0, sizeof(a));
-        const struct { unsigned ops; bool bars; uint32_t gl, live; } cls[] = {
-            {GLV_OP_FFT, false, 0, 0}, {GLV_OP_FFT | GLV_OP_R16, false, 0, 0}, {GLV_OP_FFT | GLV_OP_GRAVITY, false, 0, 0}, {GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_R16, false, 0, 0},
-            {GLV_OP_FFT | GLV_OP_GRAVITY, true, 0, 0}, {GLV_OP_FFT | GLV_OP_GRAVITY, false, 1, 0}, {GLV_OP_FFT | GLV_OP_GRAVITY, true, 1, 0}, {GLV_OP_FFT | GLV_OP_GRAVITY, false, 1, 1},
-            {GLV_OP_FFT | GLV_OP_GRAVITY, true, 0, 1}, {GLV_OP_FFT | GLV_OP_GRAVITY, true, 1, 1}};
         for (int in_mode = 0; in_mode < kInKinds; ++in_mode)
             for (int v = 0; v < glv::frame_variants(b->log_nn); ++v)
-                for (const auto& c : cls) {
-                    a.ops = c.ops; a.gl_storage = c.gl; a.bars_out = c.bars ? reinterpret_cast<float*>(16) : nullptr; a.live_points = c.live;
-                    (void) glv::launch_frame(b->log_nn, in_mode, (int) b->p.log_mode, v, a, 0, nullptr);
-                }
+                for (int c = 0; c < glv::kFrameClasses; ++c)
+                    (void) glv::launch_frame(b->log_nn, in_mode, (int) b->p.log_mode, v, (glv::FrameClass) c, a, 0, nullptr);
         (void) hipGetLastError();
     }
     // the pass-by-pass GL chain parks the transform's f32 spectra when the caller's buffer cannot take them (texel / bar outputs)
@@ -826,68 +837,101 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
     return GLV_OK;
 }
 
-// does `ops` run as the fused GL_R16 kernel?  (gl_storage 1, an FFT chain with state; RAW / SMOOTH / the audit log take the passes one by one)
-bool gl_fused_chain(const glv_batch* b, unsigned ops) {
-    return b->p.gl_storage == 1 && (ops & GLV_OP_FFT) && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !(ops & (GLV_OP_RAW | GLV_OP_SMOOTH)) && b->p.log_mode != 2;
-}
-// the chain as the launch plan / wisdom sees it
-unsigned plan_ops(const glv_batch* b, unsigned ops) {
-    if (gl_fused_chain(b, ops)) return ops | kOpGl16;
-    if (b->p.gl_storage && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) return GLV_OP_FFT | (ops & GLV_OP_RAW);     // pass by pass: the frame kernel runs the transform alone
-    return ops;
-}
+// How one process call runs, decided once before anything is launched (plan_chain) and then carried out (run_chain).
+struct ChainPlan {
+    enum Route {
+        GL_FUSED,       // render.c:2188-2265 (+ :2277-2303 with bars) in ONE launch on uint16 state (gl_fused_chain)
+        GL_PASSES,      // the transform, then gravity / average as the post kernel's pass over GL_R16-quantised values (gl_passes_chain)
+        FRAME,          // the frame kernel
+        POST,           // operators on planar rows (no GLV_OP_FFT)
+        COPY,           // smooth / bars only: on a copy of the input rows
+    } route = FRAME;
+    enum Bars { NO_BARS, BARS_F32, BARS_I8, BARS_I8_FLOATS } bars = NO_BARS;   // the second bars launch: over f32 rows, over texel rows (the
+                                                                               // integer matrix-core pass), over texel values as floats c / 65535
+    int variant = 0, grid = 0;                  // the frame kernel's configuration and workgroups (FFT chains)
+    glv::FrameClass cls = glv::FC_PLAIN;        // ... and its class
+    unsigned ops = 0;                           // what the first kernel runs (FrameArgs::ops)
+    bool fused_bars = false;                    // the bars computed in the frame kernel, from the finished row in LDS
+    float* out = nullptr;                       // where the first kernel writes its rows (NULL: the state is the output, or only bars leave)
+    float* rows = nullptr;                      // the finished rows: what the smooth pass and the second bars launch work on
+    uint32_t out_limit = 0, live_points = 0;    // FrameArgs::out_limit / live_points
+};
 
-// One update of `units` channel rows through the fused kernel (or the post kernel when no FFT is asked).
-// Stream-ordered: launches and asynchronous device-to-device copies only.
-int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units,
-            uint32_t rot, hipStream_t st) {
-    if (!d_in) return fail(GLV_ERR_INVALID, "NULL device pointer");
-    if (int rc = check_ops(b, ops, d_out)) return rc;
-    const bool state_is_output = (ops & GLV_OP_GRAVITY) && !(ops & (GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_RAW));
-    // transform_gravity keeps ONE `applied` buffer per slot (render.c:724).  Here it lives in d_grav when gravity runs
-    // without average and in the newest ring slot when both run fused; a batch that mixed the two forms would silently
-    // continue from a stale state, so that is refused (reset the batch, or use one batch per operator chain).
-    if (ops & GLV_OP_GRAVITY) {
-        const int mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
-        if (b->grav_mode != 0 && b->grav_mode != mode)
-            return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
-                                       "their state in different buffers (glv_batch_reset, or one batch per chain)",
-                        b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
-    }
-    float* d_final = d_out;
-    b->last_launches = 0;
-    HIP_TRY(hipSetDevice(b->device));
-    const bool stateful = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
-    const bool gl_fused = gl_fused_chain(b, ops);                            // gl_storage 1: the GL passes are the transform's epilogue
-    const bool gl_split = b->p.gl_storage != 0 && stateful && !gl_fused;     // the GL passes one by one (gl_storage 2; RAW / SMOOTH / audit log of 1)
+int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, float* d_out, ChainPlan& pl) {
+    const bool gl_passes = gl_passes_chain(b, ops);
+    if (gl_fused_chain(b, ops)) pl.route = ChainPlan::GL_FUSED;
+    else if (ops & GLV_OP_FFT) pl.route = gl_passes ? ChainPlan::GL_PASSES : ChainPlan::FRAME;
+    else pl.route = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_WRANGE | GLV_OP_MAGNITUDE | GLV_OP_R16)) ? ChainPlan::POST : ChainPlan::COPY;
     // which kernel configuration of this size runs, on how many workgroups (wisdom, overrides, defaults)
-    int variant = 0, grid = 0;
-    if (ops & GLV_OP_FFT) launch_plan(b, units, in_mode, plan_ops(b, ops), &variant, &grid);
+    if (ops & GLV_OP_FFT) launch_plan(b, units, in_mode, ops, &pl.variant, &pl.grid);
     // GLV_OP_BARS: d_out receives the bars.  Stateful FFT chains whose rows are owned by whole waves compute
     // them inside the frame kernel from the finished row in LDS (the spectra never reach HBM, apart from
     // the state the operators keep anyway); otherwise the spectra stay internal -- in the gravity state
-    // when the chain ends in gravity, in the scratch rows else -- and glv_bars_kernel runs after.
-    // (the float chain's bars as GL_R16 texels leave through glv_bars_kernel; the GL_R16 chain stores them itself)
-    const bool fused_bars = (ops & GLV_OP_BARS) && (ops & GLV_OP_FFT) && stateful && !(ops & GLV_OP_SMOOTH) && !gl_split
-                            && (gl_fused || !(ops & GLV_OP_R16)) && variant < glv_batch::kMaxVariants && b->bar_fusable[variant]
-                            && !b->unfused_bars;                         // diagnostics: force the two-kernel path
+    // when the chain ends in gravity, in the scratch rows else -- and a bars kernel runs after.
+    pl.fused_bars = (ops & GLV_OP_BARS) && (ops & GLV_OP_FFT) && !gl_passes && bars_fusable(b, ops) && pl.variant < glv_batch::kMaxVariants
+                    && b->bar_fusable[pl.variant];
+    pl.out = d_out;
     if (ops & GLV_OP_BARS) {
-        if (fused_bars || (state_is_output && !b->p.gl_storage)) d_out = nullptr;
+        const bool state_is_output = (ops & GLV_OP_GRAVITY) && !(ops & (GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_RAW));
+        if (pl.fused_bars || (state_is_output && !b->p.gl_storage)) pl.out = nullptr;
         else {
             if (!b->d_scratch) return fail(GLV_ERR_STATE, "this GLV_OP_BARS chain needs the internal spectra rows: announce it in glv_batch_create's ops_mask (GLV_OP_BARS together with the chain's other operators; GLV_OP_R16 too when a float chain's bars are wanted as texels)");
-            d_out = b->d_scratch;
+            pl.out = b->d_scratch;
         }
     }
-    if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
-        return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
-    if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+    if (pl.route == ChainPlan::GL_PASSES) {
+        // the frame kernel delivers the float spectra into the caller's buffer when that is what it will hold in the end, else into the
+        // scratch rows; the GL passes write the caller's buffer (NULL: the state is the output), or the same rows when bars sample them
+        pl.out = d_out && !(ops & (GLV_OP_BARS | GLV_OP_R16)) ? d_out : b->d_scratch;
+        pl.rows = (ops & GLV_OP_BARS) ? pl.out : d_out;
+    } else pl.rows = pl.out ? pl.out : b->d_grav;           // no rows out: a chain that ends in gravity, whose state is its output
+    // many bars of texel rows: the integer matrix-core pass -- on the GL_R16 chain's texels, or on the texel values of the GL passes
+    if (!(ops & GLV_OP_BARS) || pl.fused_bars) pl.bars = ChainPlan::NO_BARS;
+    else if (b->p.bars >= glv::kBarSeqMin && b->bars_i8() && (pl.route == ChainPlan::GL_FUSED || (gl_passes && !(ops & GLV_OP_SMOOTH))))
+        pl.bars = pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_I8 : ChainPlan::BARS_I8_FLOATS;
+    else pl.bars = ChainPlan::BARS_F32;
+    if (pl.route == ChainPlan::GL_PASSES) pl.ops = frame_ops(b, ops);
+    else {
+        pl.ops = ops & ~(unsigned) (GLV_OP_PRIVATE_STATE | GLV_OP_OUTPUT_IS_STATE);
+        if (ops & GLV_OP_BARS) pl.ops &= ~(unsigned) GLV_OP_R16;     // with bars the texel conversion applies to the bars, the spectra stay f32
+        if (pl.bars == ChainPlan::BARS_I8) pl.ops |= glv::OP_R16;   // ... but the GL_R16 chain hands the integer pass its rows as 16-bit texels
+    }
+    // the GL_R16 chain's rows go to the bars of a second launch and nowhere else (the scratch rows): what those bars do not sample is not stored
+    if (pl.route == ChainPlan::GL_FUSED && pl.bars != ChainPlan::NO_BARS && b->bar_bins_needed != 0 && b->bar_bins_needed < b->p.n)
+        pl.out_limit = b->bar_bins_needed * 4u;
+    // GLV_OP_BARS_ONLY: ... and what they do not sample is not computed, nor is its state kept -- the GL_R16 chain, and a float chain with
+    // the bars fused (check_ops vetted the call)
+    if (b->live_bins() != 0 && (pl.route == ChainPlan::GL_FUSED || pl.fused_bars)) pl.live_points = b->live_bins() / 2u;
+    pl.cls = glv::frame_class(pl.route == ChainPlan::GL_FUSED, pl.fused_bars, pl.live_points != 0, pl.ops);
+    return GLV_OK;
+}
 
+// the second bars launch of a chain (ChainPlan::bars) over its finished rows
+int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, uint32_t units, bool r16, hipStream_t st) {
+    hipError_t e;
+    if (pl.bars == ChainPlan::NO_BARS) return GLV_OK;
+    if (pl.bars == ChainPlan::BARS_F32) {
+        const glv::BarRowsTables rt = b->rows_tables();
+        e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w, st, r16, &rt);
+    } else {
+        const glv::BarIRowsTables irt = b->irows_tables();
+        e = glv::launch_bars_i8(pl.rows, pl.bars == ChainPlan::BARS_I8_FLOATS, d_bars, units, b->p.n, b->p.bars, &irt, st, r16);
+    }
+    ++b->last_launches;
+    return e == hipSuccess ? GLV_OK : fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
+}
+
+// Carries out a plan: the first kernel (and the GL passes), the batch's state bookkeeping, the smooth pass, the second bars launch --
+// one HIP-event window around every launch of the chain.  Stream-ordered: launches and asynchronous device-to-device copies only.
+int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units, uint32_t rot,
+              hipStream_t st) {
     glv::FrameArgs a;
     fill_common(a, b->p, b->tab);
-    a.in = d_in; a.out = d_out; a.grav = b->grav_cur; a.grav_w = b->d_grav; a.hist = b->d_hist;
-    a.units = units; a.ops = ops & ~(unsigned) (GLV_OP_PRIVATE_STATE | GLV_OP_OUTPUT_IS_STATE); a.head = b->head; a.rot = rot; a.log_mode = b->p.log_mode;
+    a.in = d_in; a.out = pl.out; a.grav = b->grav_cur; a.grav_w = b->d_grav; a.hist = b->d_hist;
+    a.units = units; a.ops = pl.ops; a.head = b->head; a.rot = rot; a.log_mode = b->p.log_mode;
     a.grav_sub = b->grav_sub; a.grav_int = b->grav_int ? 1u : 0u;
-    if (ops & GLV_OP_BARS) { a.ops &= ~(unsigned) GLV_OP_R16; a.bars_r16 = (ops & GLV_OP_R16) ? 1u : 0u; }   // with bars the texel conversion applies to the bars, the spectra stay f32
+    a.bars_r16 = (ops & GLV_OP_BARS) && (ops & GLV_OP_R16) ? 1u : 0u;
+    a.out_limit = pl.out_limit;
     // GLV_OP_OUTPUT_IS_STATE: a chain that ends in gravity writes ONE copy of its result (SURVEY 8d row B, 20 N bytes per frame) --
     // transform_gravity stores the same value to its `applied` array and to the buffer (render.c:733-734), so the caller's output
     // buffer can BE the state the next update reads.  Opt-in: the caller promises to leave the buffer alone until then.
@@ -898,120 +942,72 @@ int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned 
         a.grav_w = d_out; a.out = nullptr;
     }
     const float* grav_next = gravity_only ? (out_is_state ? d_out : b->d_grav) : b->grav_cur;
-    if (fused_bars) {
-        a.bar_desc = b->d_bar_desc; a.bar_items = b->d_bar_fitems[variant]; a.bar_nsteps = b->bar_fnsteps[variant]; a.bar_w = b->d_bar_w;
-        a.bars = b->p.bars; a.bars_out = d_final;
+    if (pl.fused_bars) {
+        a.bar_desc = b->d_bar_desc; a.bar_items = b->d_bar_fitems[pl.variant]; a.bar_nsteps = b->bar_fnsteps[pl.variant]; a.bar_w = b->d_bar_w;
+        a.bars = b->p.bars; a.bars_out = d_out;
     }
-
-    hipError_t e;
-    if (gl_fused) {
-        // render.c:2188-2265 (+ :2277-2303 with bars) in ONE launch on uint16 state.  Bars that do not fit the row's slack in LDS
-        // (bars == n: the pre-smoothing pass) sample the finished rows' floats from the scratch rows in a second launch.
-        a.gl_storage = 1;
-        // the rows go to the bars of a second launch and nowhere else (the scratch rows): what those bars do not sample is not stored
-        if ((ops & GLV_OP_BARS) && !fused_bars && d_out == b->d_scratch && b->bar_bins_needed != 0 && b->bar_bins_needed < b->p.n)
-            a.out_limit = b->bar_bins_needed * 4u;
-        // GLV_OP_BARS_ONLY: ... and what they do not sample is not computed, nor is its state kept (kernel class 7; check_ops vetted the call)
-        if (b->live_bins() != 0) { a.live_points = b->live_bins() / 2u; b->ran_live = true; }
-        // ... and they go there as what they are, 16-bit texels (uint16 [rows][n] in the scratch rows), when the second launch is the
-        // integer matrix-core pass (many bars: the pre-smoothing pass)
-        const bool bars_i8 = (ops & GLV_OP_BARS) && !fused_bars && b->p.bars >= glv::kBarSeqMin && b->bars_i8();
-        if (bars_i8) a.ops |= glv::OP_R16;
-        if (int rc = timed_launch_begin(b, st)) return rc;
-        b->last_grid = grid; b->last_variant = variant;
-        e = glv::launch_frame(b->log_nn, in_mode, (int) b->p.log_mode, variant, a, grid, st); ++b->last_launches;
-        if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-        b->kernel_name = "glv_frame_kernel";
-        if (ops & GLV_OP_AVERAGE) b->head = (b->head + 1) % b->p.avg_frames;
-        b->grav_cur = grav_next;
-        if (bars_i8) {
-            const glv::BarIRowsTables irt = b->irows_tables();
-            e = glv::launch_bars_i8(d_out, false, d_final, units, b->p.n, b->p.bars, &irt, st, (ops & GLV_OP_R16) != 0); ++b->last_launches;
-            if (e != hipSuccess) return fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
-        } else if ((ops & GLV_OP_BARS) && !fused_bars) {
-            const glv::BarRowsTables rt = b->rows_tables();
-            e = glv::launch_bars(d_out, d_final, units, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w, st, (ops & GLV_OP_R16) != 0, &rt); ++b->last_launches;
-            if (e != hipSuccess) return fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
-        }
-        return timed_launch_end(b, st);
-    }
-    // many bars of rows that hold texel values as floats c / 65535 (the GL passes one by one): the same integer pass, converting back
-    auto bars_of_texel_floats = [&](const float* rows) -> int {
-        const glv::BarIRowsTables irt = b->irows_tables();
-        const hipError_t e2 = glv::launch_bars_i8(rows, true, d_final, units, b->p.n, b->p.bars, &irt, st, (ops & GLV_OP_R16) != 0); ++b->last_launches;
-        return e2 == hipSuccess ? GLV_OK : fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e2));
-    };
-    const bool texel_bars_i8 = gl_split && (ops & GLV_OP_BARS) && !(ops & GLV_OP_SMOOTH) && b->p.bars >= glv::kBarSeqMin && b->bars_i8();
-    // The GL twin's pass structure (render.c:2188-2265), pass by pass -- the transform first, then gravity / average as their own
-    // pass over GL_R16-quantised values (glv_frame.h apply_state; state as floats with gl_storage 2, as texels with 1).  The frame
-    // kernel delivers the float spectra into the caller's buffer when that is what it will hold in the end, else into the scratch rows.
-    if (gl_split && (ops & GLV_OP_FFT)) {
-        const bool direct = d_final && !(ops & (GLV_OP_BARS | GLV_OP_R16));
-        float* d_tmp = direct ? d_final : b->d_scratch;
-        if (!d_tmp) return fail(GLV_ERR_STATE, "this gl_storage chain needs the internal spectra rows (created for gl_storage 2 batches with state, and with GLV_OP_BARS in the ops_mask)");
-        glv::FrameArgs a1 = a;
-        a1.ops = GLV_OP_FFT | (ops & GLV_OP_RAW); a1.out = d_tmp; a1.bars_out = nullptr;     // GLV_OP_RAW: the passes then run on the raw values
-        if (int rc = timed_launch_begin(b, st)) return rc;
-        b->last_grid = grid; b->last_variant = variant;
-        e = glv::launch_frame(b->log_nn, in_mode, (int) b->p.log_mode, variant, a1, grid, st); ++b->last_launches;
-        if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-        glv::FrameArgs a2 = a;
-        a2.in = d_tmp; a2.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE | ((ops & GLV_OP_BARS) ? 0u : (unsigned) GLV_OP_R16)); a2.gl_storage = b->p.gl_storage;
-        a2.out = (ops & GLV_OP_BARS) ? d_tmp : d_final;            // bars sample the finished rows; NULL = the state is the output
-        a2.bars_out = nullptr;
-        e = glv::launch_post(a2, b->p.n, st); ++b->last_launches;
-        if (e != hipSuccess) return fail(GLV_ERR_HIP, "GL-storage pass launch failed: %s", hipGetErrorString(e));
-        b->kernel_name = "glv_frame_kernel";
-        if (ops & GLV_OP_AVERAGE) b->head = (b->head + 1) % b->p.avg_frames;
-        b->grav_cur = grav_next;
-        if (ops & GLV_OP_SMOOTH) {                 // render.c:694-718 on the finished rows (a SMOOTH chain always has an output buffer)
-            e = glv::launch_smooth(a2.out, units, b->p.n, b->d_smin, b->d_smax, b->smooth_asz, b->smooth_reach, b->smooth_window, st); ++b->last_launches;
-            if (e != hipSuccess) return fail(GLV_ERR_HIP, "smooth launch failed: %s", hipGetErrorString(e));
-        }
-        if (texel_bars_i8) {
-            if (int rc = bars_of_texel_floats(d_tmp)) return rc;
-        } else if (ops & GLV_OP_BARS) {
-            const glv::BarRowsTables rt = b->rows_tables();
-            e = glv::launch_bars(d_tmp, d_final, units, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w, st, (ops & GLV_OP_R16) != 0, &rt); ++b->last_launches;
-            if (e != hipSuccess) return fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
-        }
-        return timed_launch_end(b, st);            // the HIP-event window covers every launch of the chain
-    }
-    if (gl_split) a.gl_storage = b->p.gl_storage;                    // operators on planar rows: the post kernel models it directly
-    // GLV_OP_BARS_ONLY on a float chain with the bars fused (kernel class 8): magnitude, state and the row in LDS for the live blocks only
-    if (b->live_bins() != 0 && fused_bars && !gl_split && (ops & GLV_OP_FFT)) { a.live_points = b->live_bins() / 2u; b->ran_live = true; }
+    if (pl.route == ChainPlan::GL_FUSED) a.gl_storage = 1;
+    if (pl.route == ChainPlan::POST && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) a.gl_storage = b->p.gl_storage;   // the post kernel models it directly
+    if (pl.route == ChainPlan::GL_PASSES && !pl.out)
+        return fail(GLV_ERR_STATE, "this gl_storage chain needs the internal spectra rows (created for gl_storage 2 batches with state, and with GLV_OP_BARS in the ops_mask)");
+    if (pl.live_points != 0) { a.live_points = pl.live_points; b->ran_live = true; }
 
     if (int rc = timed_launch_begin(b, st)) return rc;
-    const unsigned core = ops & (GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_WRANGE | GLV_OP_MAGNITUDE | GLV_OP_R16);
-    if (!core) {                                   // smooth / bars only: operate on a copy of the input rows
+    hipError_t e = hipSuccess;
+    if (pl.route == ChainPlan::POST || pl.route == ChainPlan::COPY) {
         if (in_mode != glv::IN_F32_PLANAR) return fail(GLV_ERR_INVALID, "operators without GLV_OP_FFT take planar f32 input");
-        e = (const void*) d_out == d_in ? hipSuccess
-            : hipMemcpyAsync(d_out, d_in, sizeof(float) * (size_t) units * b->p.n, hipMemcpyDeviceToDevice, st);
-        b->kernel_name = "glv_smooth_kernel";
-    } else if (ops & GLV_OP_FFT) {
-        b->last_grid = grid; b->last_variant = variant;
-        e = glv::launch_frame(b->log_nn, in_mode, (int) b->p.log_mode, variant, a, grid, st); ++b->last_launches;
-        b->kernel_name = "glv_frame_kernel";
+        if (pl.route == ChainPlan::POST) { e = glv::launch_post(a, b->p.n, st); ++b->last_launches; }
+        else if ((const void*) pl.out != d_in) e = hipMemcpyAsync(pl.out, d_in, sizeof(float) * (size_t) units * b->p.n, hipMemcpyDeviceToDevice, st);
+        b->kernel_name = pl.route == ChainPlan::POST ? "glv_post_kernel" : "glv_smooth_kernel";
     } else {
-        if (in_mode != glv::IN_F32_PLANAR) return fail(GLV_ERR_INVALID, "operators without GLV_OP_FFT take planar f32 input");
-        e = glv::launch_post(a, b->p.n, st); ++b->last_launches;
-        b->kernel_name = "glv_post_kernel";
+        b->last_grid = pl.grid; b->last_variant = pl.variant;
+        e = glv::launch_frame(b->log_nn, in_mode, (int) b->p.log_mode, pl.variant, pl.cls, a, pl.grid, st); ++b->last_launches;
+        if (pl.route == ChainPlan::FRAME) b->kernel_name = "glv_frame_kernel";     // (the GL routes name it once every launch went through)
     }
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    if (pl.route == ChainPlan::GL_PASSES) {
+        // the GL twin's pass structure (render.c:2188-2265): gravity / average as their own pass over GL_R16-quantised values
+        // (glv_frame.h apply_state; state as floats with gl_storage 2, as texels with 1)
+        glv::FrameArgs a2 = a;
+        a2.in = pl.out; a2.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE | ((ops & GLV_OP_BARS) ? 0u : (unsigned) GLV_OP_R16)); a2.gl_storage = b->p.gl_storage;
+        a2.out = pl.rows;
+        e = glv::launch_post(a2, b->p.n, st); ++b->last_launches;
+        if (e != hipSuccess) return fail(GLV_ERR_HIP, "GL-storage pass launch failed: %s", hipGetErrorString(e));
+    }
+    if (pl.route == ChainPlan::GL_FUSED || pl.route == ChainPlan::GL_PASSES) b->kernel_name = "glv_frame_kernel";
     if (ops & GLV_OP_AVERAGE) b->head = (b->head + 1) % b->p.avg_frames;
     b->grav_cur = grav_next;
-    if (ops & GLV_OP_SMOOTH) {                     // render.c:694-718, in place on the finished rows
-        e = glv::launch_smooth(d_out, units, b->p.n, b->d_smin, b->d_smax, b->smooth_asz, b->smooth_reach, b->smooth_window, st); ++b->last_launches;
+    if (ops & GLV_OP_SMOOTH) {                     // render.c:694-718, in place on the finished rows (a SMOOTH chain always has them)
+        e = glv::launch_smooth(pl.rows, units, b->p.n, b->d_smin, b->d_smax, b->smooth_asz, b->smooth_reach, b->smooth_window, st); ++b->last_launches;
         if (e != hipSuccess) return fail(GLV_ERR_HIP, "smooth launch failed: %s", hipGetErrorString(e));
     }
-    if (texel_bars_i8 && !(ops & GLV_OP_FFT) && d_out != nullptr) {      // gravity / average on planar rows with the GL storage, then many bars: texel values
-        if (int rc = bars_of_texel_floats(d_out)) return rc;
-    } else if ((ops & GLV_OP_BARS) && !fused_bars) {
-        const glv::BarRowsTables rt = b->rows_tables();
-        e = glv::launch_bars(d_out ? d_out : b->grav_cur, d_final, units, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w, st, (ops & GLV_OP_R16) != 0, &rt); ++b->last_launches;
-        if (e != hipSuccess) return fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
-    }
+    if (int rc = launch_bars_pass(b, pl, d_out, units, (ops & GLV_OP_R16) != 0, st)) return rc;
     return timed_launch_end(b, st);
+}
+
+// One update of `units` channel rows through the fused kernel (or the post kernel when no FFT is asked).
+int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units,
+            uint32_t rot, hipStream_t st) {
+    if (!d_in) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (int rc = check_ops(b, ops, d_out)) return rc;
+    // transform_gravity keeps ONE `applied` buffer per slot (render.c:724).  Here it lives in d_grav when gravity runs
+    // without average and in the newest ring slot when both run fused; a batch that mixed the two forms would silently
+    // continue from a stale state, so that is refused (reset the batch, or use one batch per operator chain).
+    if (ops & GLV_OP_GRAVITY) {
+        const int mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+        if (b->grav_mode != 0 && b->grav_mode != mode)
+            return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
+                                       "their state in different buffers (glv_batch_reset, or one batch per chain)",
+                        b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
+    }
+    b->last_launches = 0;
+    HIP_TRY(hipSetDevice(b->device));
+    ChainPlan pl;
+    if (int rc = plan_chain(b, in_mode, ops, units, d_out, pl)) return rc;
+    if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
+        return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
+    if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+    return run_chain(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
 }
 
 int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, int device, bool single_row, glv_batch** out) {
@@ -1457,7 +1453,7 @@ int glv_batch_autotune(glv_batch* b, const int16_t* d_pcm, float* d_out, unsigne
     (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
     if (rc != GLV_OK) return rc;
     if (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) { if (int r2 = glv_batch_reset(b)) return r2; }
-    wisdom_store(wisdom_key(b, glv::IN_S16_STEREO, plan_ops(b, ops)), best.variant, best.grid, bms);
+    wisdom_store(wisdom_key(b, glv::IN_S16_STEREO, ops), best.variant, best.grid, bms);
     if (best_grid) *best_grid = best.grid;
     if (best_ms) *best_ms = bms;
     return GLV_OK;

@@ -49,6 +49,41 @@ struct alignas(8) BarIFin { uint32_t c, s; };
 constexpr uint32_t kBarIFinNone = 16;
 constexpr uint32_t kBarILookAhead = 4;      // steps of zero weights behind the last tile's: the kernel's weight requests run ahead of the step it computes
 
+// The kernel classes of glv_frame_kernel (its STATEFUL template parameter: the numbers are part of the kernel symbols).  Stateless and
+// stateful chains are separate kernels: the history loads of gravity/average need ~60 more VGPRs in the epilogue, and having them in the
+// same kernel costs the plain FFT+magnitude pass 15-30 % (register allocation is per kernel, not per path).
+enum FrameClass : int {
+    FC_PLAIN = 0,            // no state (FFT + magnitude only)
+    FC_STATE = 1,            // gravity / average
+    FC_STATE_BARS = 2,       // gravity / average with the bars computed in the kernel (fused GLV_OP_BARS): the finished row is written to the slot's
+                             // LDS exchange region (idle between a row's last exchange and the next row's first) instead of HBM
+    FC_R16 = 3,              // no state, output as GL_R16 texels (GLV_OP_R16: uint16 [units][n], 8N instead of 12N bytes per frame)
+    FC_STATE_R16 = 4,        // gravity / average with the output as GL_R16 texels (the state stays f32).  Separate kernels, not a run-time
+                             // branch: a second copy of the epilogue in the stateful kernel cost N=16384 176 more bytes of scratch per lane
+    FC_GL16 = 5,             // the GL_R16 chain (glv_params.gl_storage == 1): upload quantisation, GL_MAX + gravity pass, ring, average pass on uint16
+                             // state (glv_frame.h epilogue_gl16); output GL_R16 texels or their floats (a.ops & OP_R16, uniform)
+    FC_GL16_BARS = 6,        // the same with the bars computed in the kernel (the finished row's floats go to the slot's LDS region), bars as floats
+                             // or texels (a.bars_r16)
+    FC_GL16_LIVE = 7,        // FC_GL16 for GLV_OP_BARS_ONLY batches (a.live_points != 0): state, average and output for the row's live blocks only
+                             // (glv_frame.h epilogue_gl16 LIVE)
+    FC_STATE_BARS_LIVE = 8,  // FC_STATE_BARS / FC_GL16_BARS for GLV_OP_BARS_ONLY batches: magnitude, state and the row in LDS for the live
+    FC_GL16_BARS_LIVE = 9,   //   blocks only
+};
+constexpr int kFrameClasses = 10;
+GLV_HD constexpr bool fc_fused_bars(int c) { return c == FC_STATE_BARS || c == FC_GL16_BARS || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE; }
+GLV_HD constexpr bool fc_gl16(int c) { return c == FC_GL16 || c == FC_GL16_BARS || c == FC_GL16_LIVE || c == FC_GL16_BARS_LIVE; }
+GLV_HD constexpr bool fc_live(int c) { return c == FC_GL16_LIVE || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE; }
+GLV_HD constexpr bool fc_has_state(int c) { return c != FC_PLAIN && c != FC_R16; }
+GLV_HD constexpr bool fc_texel_out(int c) { return c == FC_R16 || c == FC_STATE_R16; }     // rows out as uint16 texels, always
+// the class of a launch: the GL_R16 chain (gl_storage 1), the bars fused, the live blocks only (the float chains have a live class with the
+// bars fused only), else the ops the kernel sees (state: OP_GRAVITY / OP_AVERAGE; texel rows: OP_R16)
+GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, uint32_t ops) {
+    if (gl16) return fused_bars ? (live ? FC_GL16_BARS_LIVE : FC_GL16_BARS) : (live ? FC_GL16_LIVE : FC_GL16);
+    if (fused_bars) return live ? FC_STATE_BARS_LIVE : FC_STATE_BARS;
+    if (ops & (OP_GRAVITY | OP_AVERAGE)) return (ops & OP_R16) ? FC_STATE_R16 : FC_STATE;
+    return (ops & OP_R16) ? FC_R16 : FC_PLAIN;
+}
+
 struct FrameArgs {
     const void* in;        // s16: int16 [units/2][n][2] (a unit is one channel row of a frame);  f32 planar: float [units][n];
                            // f32 stereo (PulseAudio layout, pulse_input.c:155-178): float [units/2][n][2]
@@ -131,7 +166,7 @@ GLV_HD constexpr uint32_t bar_chunk_of(uint32_t n) { return (uint32_t) (bar_lane
 // fp64-rate ones) measured +5 % (N=4096 -> GL_R16), +6 % (N=8192), +4..9 % (N=16384 gravity chains and bars), +2..15 % (N=32768)
 // and 0 % on the N=4096 f32 pass; the one loser is the stateless f32 pass of N=16384 (-2.3 %, 20.8 vs 20.3 M frames/s on the
 // same box, profiles/r03/ab_split.txt), which keeps the fp64 product.  Same bits either way.
-GLV_HD constexpr bool win_split_of(int log_nn, int stateful) { return !(log_nn == 13 && stateful == 0); }
+GLV_HD constexpr bool win_split_of(int log_nn, int cls) { return !(log_nn == 13 && cls == FC_PLAIN); }
 constexpr int kBarBatch = 2;           // work-list steps whose loads are issued together (glv_bars_kernel; the fused loop: bar_batch_of)
 // The fused loop's batch per transform size: a batch is one exposed L2 round trip (the weights; ~0.5 us per row that nothing in
 // the workgroup covers), so the large sizes, whose rows are 10 steps of 32 groups, take six steps per trip (N=16384

@@ -68,52 +68,52 @@ static bool variant_built(int in_mode, int log_mode, int variant) {
 }
 
 template <int IN_MODE, int LOG_MODE, int V>
-static hipError_t launch_one(const FrameArgs& a, int grid, hipStream_t st) {
+static hipError_t launch_one(FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     using TU = Tuned<GLV_LOG_NN, V>;
-    return launch_variant<GLV_LOG_NN, IN_MODE, LOG_MODE, TU::slots, TU::nbuf, TU::twreg, TU::winlds, TU::occ, TU::prefetch, TU::tiltreg, TU::log_e, TU::wpre, TU::wpre_s>(a, grid, st);
+    return launch_variant<GLV_LOG_NN, IN_MODE, LOG_MODE, TU::slots, TU::nbuf, TU::twreg, TU::winlds, TU::occ, TU::prefetch, TU::tiltreg, TU::log_e, TU::wpre, TU::wpre_s>(cls, a, grid, st);
 }
 
 // the three parts' entry points (each defined by the translation unit compiled with that GLV_INST_PART)
-hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(int in_mode, int log_mode, const FrameArgs& a, int grid, hipStream_t st);
-hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part1)(int in_mode, int log_mode, const FrameArgs& a, int grid, hipStream_t st);
-hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(int in_mode, int log_mode, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(int in_mode, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part1)(int in_mode, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(int in_mode, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 
 template <int IN_MODE, int V>
-static hipError_t launch_log(int log_mode, const FrameArgs& a, int grid, hipStream_t st) {
+static hipError_t launch_log(int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     switch (log_mode) {
-        case 0: return launch_one<IN_MODE, 0, V>(a, grid, st);
-        case 1: return launch_one<IN_MODE, 1, V>(a, grid, st);
-        case 2: if constexpr (V == 0) return launch_one<IN_MODE, 2, 0>(a, grid, st); else return hipErrorInvalidValue;
+        case 0: return launch_one<IN_MODE, 0, V>(cls, a, grid, st);
+        case 1: return launch_one<IN_MODE, 1, V>(cls, a, grid, st);
+        case 2: if constexpr (V == 0) return launch_one<IN_MODE, 2, 0>(cls, a, grid, st); else return hipErrorInvalidValue;
     }
     return hipErrorInvalidValue;
 }
 
 #if GLV_INST_PART == 0
-hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(int in_mode, int log_mode, const FrameArgs& a, int grid, hipStream_t st) {
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(int in_mode, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     switch (in_mode) {
-        case IN_S16_STEREO: return launch_log<IN_S16_STEREO, 0>(log_mode, a, grid, st);
-        case IN_S16_RING:   return launch_log<IN_S16_RING, 0>(log_mode, a, grid, st);
+        case IN_S16_STEREO: return launch_log<IN_S16_STEREO, 0>(log_mode, cls, a, grid, st);
+        case IN_S16_RING:   return launch_log<IN_S16_RING, 0>(log_mode, cls, a, grid, st);
     }
     return hipErrorInvalidValue;
 }
 #elif GLV_INST_PART == 1
-hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part1)(int in_mode, int log_mode, const FrameArgs& a, int grid, hipStream_t st) {
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part1)(int in_mode, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     switch (in_mode) {
-        case IN_F32_PLANAR: return launch_log<IN_F32_PLANAR, 0>(log_mode, a, grid, st);
-        case IN_F32_STEREO: return launch_log<IN_F32_STEREO, 0>(log_mode, a, grid, st);
-        case IN_F32_RING:   return launch_log<IN_F32_RING, 0>(log_mode, a, grid, st);
+        case IN_F32_PLANAR: return launch_log<IN_F32_PLANAR, 0>(log_mode, cls, a, grid, st);
+        case IN_F32_STEREO: return launch_log<IN_F32_STEREO, 0>(log_mode, cls, a, grid, st);
+        case IN_F32_RING:   return launch_log<IN_F32_RING, 0>(log_mode, cls, a, grid, st);
     }
     return hipErrorInvalidValue;
 }
 #else
-hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(int in_mode, int log_mode, const FrameArgs& a, int grid, hipStream_t st) {
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(int in_mode, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     if constexpr (kNV > 1) {
         switch (in_mode) {
-            case IN_S16_STEREO: return launch_log<IN_S16_STEREO, 1>(log_mode, a, grid, st);
-            case IN_S16_RING:   return launch_log<IN_S16_RING, 1>(log_mode, a, grid, st);
-            case IN_F32_PLANAR: return launch_log<IN_F32_PLANAR, 1>(log_mode, a, grid, st);
-            case IN_F32_STEREO: return launch_log<IN_F32_STEREO, 1>(log_mode, a, grid, st);
-            case IN_F32_RING:   return launch_log<IN_F32_RING, 1>(log_mode, a, grid, st);
+            case IN_S16_STEREO: return launch_log<IN_S16_STEREO, 1>(log_mode, cls, a, grid, st);
+            case IN_S16_RING:   return launch_log<IN_S16_RING, 1>(log_mode, cls, a, grid, st);
+            case IN_F32_PLANAR: return launch_log<IN_F32_PLANAR, 1>(log_mode, cls, a, grid, st);
+            case IN_F32_STEREO: return launch_log<IN_F32_STEREO, 1>(log_mode, cls, a, grid, st);
+            case IN_F32_RING:   return launch_log<IN_F32_RING, 1>(log_mode, cls, a, grid, st);
         }
     }
     return hipErrorInvalidValue;
@@ -121,11 +121,11 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(int in_mode, int 
 #endif
 
 #if GLV_INST_PART == 0
-hipError_t GLV_CAT(launch_frame_, GLV_LOG_NN)(int in_mode, int log_mode, int variant, const FrameArgs& a, int grid, hipStream_t st) {
-    if (variant == 1) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(in_mode, log_mode, a, grid, st);
+hipError_t GLV_CAT(launch_frame_, GLV_LOG_NN)(int in_mode, int log_mode, int variant, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 1) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(in_mode, log_mode, cls, a, grid, st);
     if (variant != 0) return hipErrorInvalidValue;
-    if (in_mode == IN_S16_STEREO || in_mode == IN_S16_RING) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(in_mode, log_mode, a, grid, st);
-    return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part1)(in_mode, log_mode, a, grid, st);
+    if (in_mode == IN_S16_STEREO || in_mode == IN_S16_RING) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(in_mode, log_mode, cls, a, grid, st);
+    return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part1)(in_mode, log_mode, cls, a, grid, st);
 }
 
 // what the host needs to know about configuration `variant` of this size (glv_launch.h FrameGeometry)

@@ -48,6 +48,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "glv_frame.h"
 
@@ -268,31 +269,18 @@ glv_frame_kernel(const FrameArgs a) {
         tilt_reg[0].y = 0.0f;
     }
 
-    // operator chain, uniform for the launch.  Stateless and stateful chains are separate kernels
-    // (STATEFUL): the history loads of gravity/average need ~60 more VGPRs in the epilogue, and having
-    // them in the same kernel costs the plain FFT+magnitude pass 15-30 % (register allocation is per
-    // kernel, not per path).
+    // operator chain, uniform for the launch; the kernel class (STATEFUL, glv_frame.h FrameClass) fixes everything else
     const bool raw_out = (a.ops & OP_RAW) != 0;
-    // STATEFUL 0: no state (FFT + magnitude only)   1: gravity / average   2: gravity / average with the
-    // bars computed in the kernel (fused GLV_OP_BARS): the finished row is written to the slot's LDS
-    // exchange region (idle between a row's last exchange and the next row's first) instead of HBM.
-    // 3: no state, output as GL_R16 texels (GLV_OP_R16: uint16 [units][n], 8N instead of 12N bytes per frame)
-    // 4: gravity / average with the output as GL_R16 texels (the state stays f32).  Separate kernels, not a run-time
-    // branch: a second copy of the epilogue in the stateful kernel cost N=16384 176 more bytes of scratch per lane.
-    // 5: the GL_R16 chain (glv_params.gl_storage == 1): upload quantisation, GL_MAX + gravity pass, ring, average pass on uint16
-    // state (glv_frame.h epilogue_gl16); output GL_R16 texels or their floats (a.ops & OP_R16, uniform).  6: the same with the
-    // bars computed in the kernel (the finished row's floats go to the slot's LDS region), bars as floats or texels (a.bars_r16)
-    // 7: class 5 for GLV_OP_BARS_ONLY batches (a.live_points != 0): state, average and output for the row's live blocks only (glv_frame.h epilogue_gl16 LIVE)
-    // 8 / 9: classes 2 / 6 (bars fused) for GLV_OP_BARS_ONLY batches: magnitude, state and the row in LDS for the live blocks only
-    constexpr bool FUSED_BARS = STATEFUL == 2 || STATEFUL == 6 || STATEFUL == 8 || STATEFUL == 9;
-    constexpr bool GL16 = STATEFUL == 5 || STATEFUL == 6 || STATEFUL == 7 || STATEFUL == 9;
-    constexpr bool GL16_LIVE = STATEFUL == 7 || STATEFUL == 9;
-    constexpr bool F32_LIVE = STATEFUL == 8;
-    constexpr bool HAS_STATE = STATEFUL == 1 || STATEFUL == 2 || STATEFUL == 4 || STATEFUL == 8 || GL16;
+    constexpr bool FUSED_BARS = fc_fused_bars(STATEFUL);
+    constexpr bool GL16 = fc_gl16(STATEFUL);
+    constexpr bool GL16_LIVE = GL16 && fc_live(STATEFUL);
+    constexpr bool F32_LIVE = !GL16 && fc_live(STATEFUL);
+    constexpr bool HAS_STATE = fc_has_state(STATEFUL);
+    constexpr bool TEXELS = fc_texel_out(STATEFUL);
     static_assert(!FUSED_BARS || WAVE_SLOT, "fused bars need whole waves per row");
     static_assert(!GL16 || LOG_MODE != 2, "the GL_R16 chain is built for log modes 0 and 1");
     static_assert(!FUSED_BARS || NBUF == 1, "fused bars park the finished row in exchange region 0: needs the full-size, two-barrier region");
-    // class 7 in the s16 frame pipeline: the row's old state is requested before its transform (glv_frame.h gl16_state_prefetch)
+    // FC_GL16_LIVE in the s16 frame pipeline: the row's old state is requested before its transform (glv_frame.h gl16_state_prefetch)
     constexpr bool LIVE_PRE = GL16_LIVE && FR::LIVE_PREFETCH && S16 && PREFETCH == 1;
     typename FR::LivePre live_pre;
     const typename FR::LivePre* live_pre_ptr = nullptr;
@@ -305,7 +293,7 @@ glv_frame_kernel(const FrameArgs a) {
             float* o = FUSED_BARS ? reinterpret_cast<float*>(xslot)
                                   : ((a.ops & OP_R16) ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(a.out) + row * N) : a.out + row * N);
             FR::template epilogue_gl16<LOG_MODE, TILTREG, NF, FUSED_BARS, GL16_LIVE>(v, o, row, tid, a, logtab, tilt_reg, live_pre_ptr);
-        } else if constexpr (STATEFUL == 4) {
+        } else if constexpr (TEXELS && HAS_STATE) {
             float* out16 = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(a.out) + row * N);
             if (raw_out) FR::template epilogue<LOG_MODE, EPI_RAW_STATE, 0, true, NF>(v, out16, row, tid, a, logtab);
             else FR::template epilogue<LOG_MODE, EPI_MAG_STATE, TILTREG, true, NF>(v, out16, row, tid, a, logtab, tilt_reg);
@@ -314,7 +302,7 @@ glv_frame_kernel(const FrameArgs a) {
         } else if constexpr (HAS_STATE) {
             if (raw_out) FR::template epilogue<LOG_MODE, EPI_RAW_STATE, 0, false, NF>(v, out_row, row, tid, a, logtab);
             else FR::template epilogue<LOG_MODE, EPI_MAG_STATE, TILTREG, false, NF>(v, out_row, row, tid, a, logtab, tilt_reg);
-        } else if constexpr (STATEFUL == 3) {
+        } else if constexpr (TEXELS) {
             float* out16 = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(a.out) + row * N);
             if (raw_out) FR::template epilogue<LOG_MODE, EPI_RAW, 0, true, NF>(v, out16, row, tid, a, logtab);
             else FR::template epilogue<LOG_MODE, EPI_MAG, TILTREG, true, NF>(v, out16, row, tid, a, logtab, tilt_reg);
@@ -575,7 +563,7 @@ glv_frame_kernel(const FrameArgs a) {
 
 template <int LOG_NN, int IN_MODE, int LOG_MODE, int SLOTS, int NBUF, int TWREG, bool WINLDS, int OCC, int PREFETCH, int TILTREG,
           int LOG_E = 4, int WPRE = 0, int WPRE_S = 0>
-hipError_t launch_variant(const FrameArgs& a, int grid, hipStream_t st) {
+hipError_t launch_variant(FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     using FR = Frame<LOG_NN, LOG_E>;
     constexpr size_t lds = frame_lds_bytes<LOG_NN, LOG_E, SLOTS, NBUF, WINLDS, TWREG>();
     static_assert(lds <= 160 * 1024, "exchange regions + window exceed the 160 KiB LDS of a gfx950 CU");
@@ -600,41 +588,31 @@ hipError_t launch_variant(const FrameArgs& a, int grid, hipStream_t st) {
         hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, st, a);
         return hipGetLastError();
     };
-    static AttrDone done_plain, done_state, done_r16, done_state_r16;   // per instantiation
+    static AttrDone done[kFrameClasses];   // per instantiation and class
     // the stateful epilogue needs the registers a resident last pass (TWREG 3) would occupy
     constexpr int TW_STATEFUL = TWREG == 3 ? 2 : TWREG;
-    // the GL_R16 chain (gl_storage == 1: uint16 state): built for log modes 0 and 1
-    if (a.gl_storage == 1 && (a.ops & (OP_GRAVITY | OP_AVERAGE))) {
-        if constexpr (LOG_MODE != 2) {
-            static AttrDone done_gl16, done_gl16_bars, done_gl16_live, done_gl16_bars_live;
-            if (a.live_points != 0 && a.bars_out == nullptr)
-                return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 7, WPRE_S>, done_gl16_live);
-            if (a.bars_out != nullptr) {
-                if constexpr (FR::T % 64 == 0 && NBUF == 1) {
-                    if (a.live_points != 0)
-                        return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 9, WPRE_S>, done_gl16_bars_live);
-                    return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 6, WPRE_S>, done_gl16_bars);
-                } else return hipErrorInvalidValue;
-            }
-            return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 5, WPRE_S>, done_gl16);
-        } else return hipErrorInvalidValue;
+    // the classes this configuration is not built for: fused bars need whole waves per row and the full-size, two-barrier exchange
+    // region (NBUF 1); the GL_R16 chain is built for log modes 0 and 1
+    auto launch_class = [&](auto c) -> hipError_t {
+        constexpr int C = decltype(c)::value;
+        if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2)) return hipErrorInvalidValue;
+        else if constexpr (fc_has_state(C))
+            return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE_S>, done[C]);
+        else return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TWREG, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE>, done[C]);
+    };
+    switch (cls) {     // (in the order of the kernels in the code object)
+        case FC_GL16_LIVE:       return launch_class(std::integral_constant<int, FC_GL16_LIVE>{});
+        case FC_GL16_BARS_LIVE:  return launch_class(std::integral_constant<int, FC_GL16_BARS_LIVE>{});
+        case FC_GL16_BARS:       return launch_class(std::integral_constant<int, FC_GL16_BARS>{});
+        case FC_GL16:            return launch_class(std::integral_constant<int, FC_GL16>{});
+        case FC_STATE_BARS_LIVE: return launch_class(std::integral_constant<int, FC_STATE_BARS_LIVE>{});
+        case FC_STATE_BARS:      return launch_class(std::integral_constant<int, FC_STATE_BARS>{});
+        case FC_STATE_R16:       return launch_class(std::integral_constant<int, FC_STATE_R16>{});
+        case FC_STATE:           return launch_class(std::integral_constant<int, FC_STATE>{});
+        case FC_R16:             return launch_class(std::integral_constant<int, FC_R16>{});
+        case FC_PLAIN:           return launch_class(std::integral_constant<int, FC_PLAIN>{});
     }
-    if (a.bars_out != nullptr) {
-        if constexpr (FR::T % 64 == 0 && NBUF == 1) {
-            static AttrDone done_bars, done_bars_live;
-            if (!(a.ops & (OP_GRAVITY | OP_AVERAGE))) return hipErrorInvalidValue;
-            if (a.live_points != 0)
-                return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 8, WPRE_S>, done_bars_live);
-            return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 2, WPRE_S>, done_bars);
-        } else return hipErrorInvalidValue;
-    }
-    if ((a.ops & (OP_GRAVITY | OP_AVERAGE)) && (a.ops & OP_R16))
-        return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 4, WPRE_S>, done_state_r16);
-    if (a.ops & (OP_GRAVITY | OP_AVERAGE))
-        return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 1, WPRE_S>, done_state);
-    if (a.ops & OP_R16)
-        return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TWREG, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 3, WPRE>, done_r16);
-    return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TWREG, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, 0, WPRE>, done_plain);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace glv

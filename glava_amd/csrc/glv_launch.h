@@ -22,7 +22,7 @@ struct FrameGeometry {
 
 // per-size production launchers, one translation unit each (glv_inst.hip -DGLV_LOG_NN=k)
 #define GLV_DECL_INST(K) \
-    hipError_t launch_frame_##K(int in_mode, int log_mode, int variant, const FrameArgs& a, int grid, hipStream_t st); \
+    hipError_t launch_frame_##K(int in_mode, int log_mode, int variant, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st); \
     int frame_variants_##K(); \
     int frame_variant_ok_##K(int in_mode, int log_mode, int variant); \
     FrameGeometry frame_geometry_##K(int variant);
@@ -30,7 +30,7 @@ GLV_DECL_INST(7) GLV_DECL_INST(8) GLV_DECL_INST(9) GLV_DECL_INST(10) GLV_DECL_IN
 #undef GLV_DECL_INST
 
 // glv_misc.hip
-hipError_t launch_frame(int log_nn, int in_mode, int log_mode, int variant, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t launch_frame(int log_nn, int in_mode, int log_mode, int variant, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 int frame_variants(int log_nn);                                        // kernel configurations built for this size (>= 1)
 bool frame_variant_ok(int log_nn, int in_mode, int log_mode, int variant);   // is `variant` built for this input / log mode
 FrameGeometry frame_geometry(int log_nn, int variant);

@@ -1201,8 +1201,8 @@ hipError_t launch_bars(const float* spec, float* bars_out, size_t nrows, uint32_
     }                                                                                                                   \
     return DEFAULT
 
-hipError_t launch_frame(int log_nn, int in_mode, int log_mode, int variant, const FrameArgs& a, int grid, hipStream_t st) {
-#define GLV_CALL(K) launch_frame_##K(in_mode, log_mode, variant, a, grid, st)
+hipError_t launch_frame(int log_nn, int in_mode, int log_mode, int variant, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+#define GLV_CALL(K) launch_frame_##K(in_mode, log_mode, variant, cls, a, grid, st)
     GLV_BY_SIZE(log_nn, GLV_CALL, hipErrorInvalidValue);
 #undef GLV_CALL
 }

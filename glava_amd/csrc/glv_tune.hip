@@ -25,10 +25,11 @@ template <int SLOTS, int NBUF, int TWREG, bool WINLDS, int OCC, int PF = 0, int 
 hipError_t launch_v(int in_mode, int log_mode, const FrameArgs& a, int grid, hipStream_t st) {
     constexpr int K = GLV_TUNE_LOG_NN;
     if (in_mode != IN_S16_STEREO) return hipErrorInvalidValue;
+    const FrameClass cls = frame_class(false, false, false, a.ops);      // the plain and float-state classes: extra_ops of glv_tune_run*
 #if !defined(GLV_TUNE_NO_LOG0)
-    if (log_mode == 0) return launch_variant<K, IN_S16_STEREO, 0, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(a, grid, st);
+    if (log_mode == 0) return launch_variant<K, IN_S16_STEREO, 0, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(cls, a, grid, st);
 #endif
-    return launch_variant<K, IN_S16_STEREO, 1, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(a, grid, st);
+    return launch_variant<K, IN_S16_STEREO, 1, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(cls, a, grid, st);
 }
 
 #define V(S, NB, TR, WL, OC) { "slots=" #S " nbuf=" #NB " twreg=" #TR " winlds=" #WL " occ=" #OC, launch_v<S, NB, TR, WL, OC>, S }

@@ -12,7 +12,7 @@
 
 namespace glv {
 #define GLV_STUB(K)                                                                                                        \
-    hipError_t launch_frame_##K(int, int, int, const FrameArgs&, int, hipStream_t) { return hipErrorUnknown; }            \
+    hipError_t launch_frame_##K(int, int, int, FrameClass, const FrameArgs&, int, hipStream_t) { return hipErrorUnknown; }\
     int frame_variants_##K() { return 1; }                                                                                 \
     int frame_variant_ok_##K(int, int, int) { return 0; }                                                                  \
     FrameGeometry frame_geometry_##K(int) { return FrameGeometry{}; }
