@@ -341,13 +341,16 @@ struct glv_batch {
     bool ran_live = false;                          // a live kernel class has run since creation / the last reset: the state beyond the live bins is stale
     void update_live_bins() {
         live_bins_now = 0u;
-        if (!(ops_mask & GLV_OP_BARS_ONLY) || bar_bins_sampled == 0 || bar_bins_sampled >= p.n || p.gl_storage > 1u || p.log_mode == 2u) return;
+        // (snapped bars sample positions in [0, 1) -- the unsnapped bars' last taps reach scale_audio(1) n once smooth_factor >= 1 / bars; a smaller
+        // factor can leave the last snapped taps beyond them, and the live bins then grow to cover them)
+        const uint32_t sampled = snapped() && snap_bins > bar_bins_sampled ? snap_bins : bar_bins_sampled;
+        if (!(ops_mask & GLV_OP_BARS_ONLY) || sampled == 0 || sampled >= p.n || p.gl_storage > 1u || p.log_mode == 2u) return;
         for (int v = 0; v < glv::frame_variants(log_nn); ++v)
-            if ((uint32_t) glv::frame_geometry(log_nn, v).live_points * 2u < bar_bins_sampled) return;
+            if ((uint32_t) glv::frame_geometry(log_nn, v).live_points * 2u < sampled) return;
         // (a float chain's live class is the fused one: the production configuration must take the bars; a call that runs a configuration which cannot
         // -- forced, or from the wisdom -- takes the full chain for that call: it maintains every bin, the live calls the sampled ones, the bars see no difference)
         if (p.gl_storage == 0u && (!bar_fusable[0] || unfused_bars)) return;
-        live_bins_now = bar_bins_sampled;
+        live_bins_now = sampled;
     }
     glv::BarRowsTables rows_tables() const {
         glv::BarRowsTables t{d_bar_mtiles, bar_ntiles, d_bar_wt, d_bar_wsum, d_bar_rounds, bar_nrounds, bar_ring_bins};
@@ -362,6 +365,22 @@ struct glv_batch {
     bool bar_i8_off = false;     // GLV_NO_BARS_I8 in the environment at creation (diagnostics: the f32 matrix-core kernel on texel rows too)
     glv::BarIRowsTables irows_tables() const { return glv::BarIRowsTables{d_bar_itiles, bar_intiles, d_bar_wq, d_bar_fin, d_bar_irounds, bar_inrounds, bar_iring_bins}; }
     bool bars_i8() const { return d_bar_irounds != nullptr && bar_inrounds != 0; }
+    // glv_batch_set_bar_texels: bar k is texel snap_tex[k] of the pre-smoothing pass (the twin: bars = n, bar_phase 0.5); empty = off.  The tables
+    // follow the snapped taps: average -- snapped desc (weight_sum 1, NaN where the weights sum to 0), W' in tap_w's layout plus a zero chunk, one
+    // fused work list per kernel configuration; maximum / hybrid -- the snapped desc and glv_bars_mode_kernel's blocks
+    std::vector<uint32_t> snap_tex;
+    glv::BarDesc* d_snap_desc = nullptr; uint32_t* d_snap_w = nullptr;
+    glv::BarItem* d_snap_fitems[kMaxVariants] = {};
+    uint32_t snap_fnsteps[kMaxVariants] = {}; bool snap_fusable[kMaxVariants] = {};
+    glv::BarModeBlock* d_snap_mblocks = nullptr; float* d_snap_mw = nullptr; uint32_t snap_nmblocks = 0;
+    uint32_t snap_bins = 0;                  // bins of a row the snapped bars sample (whole 64s)
+    glv_params snap_of{};                    // the parameters the snapped tables were made for (smooth_factor, the shape, bars)
+    bool snapped() const { return !snap_tex.empty(); }
+    glv::BarRowsTables snap_rows_tables() const {
+        glv::BarRowsTables t = rows_tables();
+        t.mblocks = d_snap_mblocks; t.nmblocks = snap_nmblocks; t.mw = d_snap_mw; t.mode_bins = snap_bins < p.n ? snap_bins : p.n;
+        return t;
+    }
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;  // start/stop pairs
@@ -595,6 +614,18 @@ int ensure_smooth_tables(glv_batch* b) {
     return GLV_OK;
 }
 
+// the integer tables of a pass over texel rows for the smallest LDS ring that takes them (glv_misc.hip launch_bars_i8: the rings the kernel is
+// built for); returns that ring, 0 (irounds empty) when none does
+uint32_t make_itiles_any_ring(std::vector<glv::BarMTile>& itiles, std::vector<int8_t>& wq, std::vector<glv::BarIFin>& fin, std::vector<glv::BarTile>& irounds,
+                              const std::vector<glv::BarDesc>& desc, const std::vector<float>& w, uint32_t n) {
+    for (uint32_t bins : {160u, 288u, 448u, 832u, 1600u}) {
+        if (!glv::make_bar_itiles(itiles, wq, fin, irounds, desc, w, n, bins, 4u)) { irounds.clear(); break; }
+        if (!irounds.empty()) return bins;
+    }
+    irounds.clear();
+    return 0;
+}
+
 // GLV_OP_BARS tables: taps, weights, the work lists of glv_bars_kernel and one fused work list per kernel configuration of the
 // size (their lanes per row differ).  Host generation + synchronous upload: creation / glv_batch_set_params only.
 int ensure_bar_tables(glv_batch* b) {
@@ -702,10 +733,7 @@ int ensure_bar_tables(glv_batch* b) {
             std::vector<glv::BarTile> irounds;
             std::vector<int8_t> wq;
             std::vector<glv::BarIFin> fin;
-            for (uint32_t bins : {160u, 288u, 448u, 832u, 1600u}) {
-                if (!glv::make_bar_itiles(itiles, wq, fin, irounds, desc, w, b->p.n, bins, 4u)) { irounds.clear(); break; }
-                if (!irounds.empty()) { b->bar_iring_bins = bins; break; }
-            }
+            b->bar_iring_bins = make_itiles_any_ring(itiles, wq, fin, irounds, desc, w, b->p.n);
             if (irounds.empty()) b->bar_i8_none = true;
             else {
                 HIP_TRY(hipMalloc(&b->d_bar_itiles, sizeof(glv::BarMTile) * itiles.size()));
@@ -723,6 +751,99 @@ int ensure_bar_tables(glv_batch* b) {
         }
     }
     return GLV_OK;
+}
+
+void drop_snap_tables(glv_batch* b) {
+    auto drop = [](auto*& ptr) { if (ptr) { (void) hipFree(ptr); ptr = nullptr; } };
+    drop(b->d_snap_desc); drop(b->d_snap_w); drop(b->d_snap_mblocks); drop(b->d_snap_mw);
+    for (int v = 0; v < glv_batch::kMaxVariants; ++v) { drop(b->d_snap_fitems[v]); b->snap_fusable[v] = false; b->snap_fnsteps[v] = 0; }
+    b->snap_nmblocks = 0; b->snap_bins = 0;
+}
+bool bars_fusable(const glv_batch* b, unsigned ops);
+
+// The tables of bars at texels `tex` of the pre-smoothing pass (glv_batch_set_bar_texels; glv_tables.h make_bar_snap_weights): every check first,
+// then the device tables are replaced -- a refused table leaves the batch as it was.  Synchronous; creation / set calls only.
+int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex) {
+    const uint32_t n = b->p.n, bars = (uint32_t) tex.size();
+    const bool averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;
+    const glv::BarShape shape = bar_shape(b->p);
+    if (averaging) {
+        // the twin's texels must be the exact integer means (GLV_BARS_I8_EXACT): its integer tables have to exist
+        if (b->bar_i8_off) return fail(GLV_ERR_INVALID, "bar texels: GLV_NO_BARS_I8 is set, so the pre-smoothing pass runs GLV_BARS_F32_MATRIX, which snapped bars do not reproduce");
+        std::vector<glv::BarDesc> td;
+        std::vector<float> tw;
+        glv::make_bar_taps(td, tw, n, n, b->p.smooth_factor, 0.5f, shape);
+        std::vector<glv::BarMTile> itiles;
+        std::vector<glv::BarTile> irounds;
+        std::vector<int8_t> wq;
+        std::vector<glv::BarIFin> fin;
+        if (!glv::bar_chunks_in_row(td, n) || make_itiles_any_ring(itiles, wq, fin, irounds, td, tw, n) == 0)
+            return fail(GLV_ERR_INVALID, "bar texels: the pre-smoothing pass of these parameters (n=%u smooth_factor=%g) has no integer tables (a bar wider than the largest "
+                                         "LDS ring, or more than 2^31 in its weight scale): its arithmetic is GLV_BARS_F32_MATRIX, which snapped bars do not reproduce", n, (double) b->p.smooth_factor);
+    }
+    std::vector<glv::BarDesc> desc;
+    std::vector<float> w;
+    glv::make_bar_taps(desc, w, n, bars, b->p.smooth_factor, 0.5f, shape, tex.data());
+    if (!glv::bar_chunks_in_row(desc, n)) return fail(GLV_ERR_INVALID, "bar texels: a tap chunk would leave the row (n=%u smooth_factor=%g)", n, (double) b->p.smooth_factor);
+    uint32_t sampled = 0;
+    for (const glv::BarDesc& d : desc) sampled = d.first_bin + d.count > sampled ? d.first_bin + d.count : sampled;
+    sampled = sampled == 0 ? 64u : (sampled + 63u) & ~63u;
+    std::vector<uint32_t> wi;
+    std::vector<std::vector<glv::BarItem>> fitems(glv_batch::kMaxVariants);
+    uint32_t fnsteps[glv_batch::kMaxVariants] = {};
+    bool fusable[glv_batch::kMaxVariants] = {};
+    std::vector<glv::BarModeBlock> blocks;
+    std::vector<float> mw;
+    const int nv = glv::frame_variants(b->log_nn);
+    if (averaging) {
+        if (!glv::make_bar_snap_weights(wi, desc, w)) return fail(GLV_ERR_INVALID, "bar texels: a bar's integer weights do not exist for these parameters");
+        const uint32_t zero_off = (uint32_t) wi.size(), chunk = glv::bar_chunk_of(n), gl = (uint32_t) glv::bar_lanes_of(n);
+        wi.resize(wi.size() + chunk, 0u);
+        for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) {
+            const glv::FrameGeometry geo = glv::frame_geometry(b->log_nn, v);
+            // every result is 4 bytes behind the row, as the unsnapped totals: bars + the dump slot in the 2 * lanes floats of slack
+            fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && bars + 1 <= 2 * (uint32_t) geo.lanes;
+            if (fusable[v]) fnsteps[v] = glv::make_bar_items(fitems[v], desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
+        }
+    } else {
+        glv::make_bar_mode_blocks(blocks, mw, desc, w);
+        if (mw.empty()) mw.push_back(0.0f);
+    }
+    // a second launch needs the chain's rows: the internal rows, unless every chain the creation mask announces fuses in every configuration
+    bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
+    for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) all_fused = all_fused && fusable[v];
+    if (!all_fused && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * n));
+    drop_snap_tables(b);
+    HIP_TRY(hipMalloc(&b->d_snap_desc, sizeof(glv::BarDesc) * desc.size()));
+    HIP_TRY(hipMemcpy(b->d_snap_desc, desc.data(), sizeof(glv::BarDesc) * desc.size(), hipMemcpyHostToDevice));
+    if (averaging) {
+        HIP_TRY(hipMalloc(&b->d_snap_w, sizeof(uint32_t) * wi.size()));
+        HIP_TRY(hipMemcpy(b->d_snap_w, wi.data(), sizeof(uint32_t) * wi.size(), hipMemcpyHostToDevice));
+        for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) {
+            if (!fusable[v]) continue;
+            HIP_TRY(hipMalloc(&b->d_snap_fitems[v], sizeof(glv::BarItem) * fitems[v].size()));
+            HIP_TRY(hipMemcpy(b->d_snap_fitems[v], fitems[v].data(), sizeof(glv::BarItem) * fitems[v].size(), hipMemcpyHostToDevice));
+            b->snap_fusable[v] = true; b->snap_fnsteps[v] = fnsteps[v];
+        }
+    } else {
+        HIP_TRY(hipMalloc(&b->d_snap_mblocks, sizeof(glv::BarModeBlock) * blocks.size()));
+        HIP_TRY(hipMemcpy(b->d_snap_mblocks, blocks.data(), sizeof(glv::BarModeBlock) * blocks.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&b->d_snap_mw, sizeof(float) * mw.size()));
+        HIP_TRY(hipMemcpy(b->d_snap_mw, mw.data(), sizeof(float) * mw.size(), hipMemcpyHostToDevice));
+        b->snap_nmblocks = (uint32_t) blocks.size();
+    }
+    if (&b->snap_tex != &tex) b->snap_tex = tex;
+    b->snap_of = b->p; b->snap_bins = sampled;
+    b->update_live_bins();
+    return GLV_OK;
+}
+// the snapped tables follow smooth_factor and the shape (glv_batch_set_params; bar_phase does not enter them)
+bool snap_current(const glv_batch* b) {
+    return b->d_snap_desc && b->snap_of.bars == b->p.bars && same_bits(b->snap_of.smooth_factor, b->p.smooth_factor) && same_shape(b->snap_of, b->p);
+}
+int ensure_snap_tables(glv_batch* b) {
+    if (!b->snapped() || snap_current(b)) return GLV_OK;
+    return build_snap_tables(b, b->snap_tex);
 }
 
 // the gravity step on texels (only the GL_R16 state needs it: 65 536 evaluations on the host whenever g changes -- for the
@@ -784,6 +905,7 @@ int batch_prepare(glv_batch* b) {
         bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
         for (int v = 0; v < glv::frame_variants(b->log_nn) && v < glv_batch::kMaxVariants; ++v) all_fused = all_fused && b->bar_fusable[v];
         if (!all_fused && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * b->p.n));
+        if (int rc = ensure_snap_tables(b)) return rc;
         b->update_live_bins();
     }
     // function attributes (the > 64 KiB dynamic-LDS opt-in) of every frame kernel this batch can launch: set here, once per device
@@ -832,6 +954,13 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
         return fail(GLV_ERR_STATE, "GLV_OP_BARS: the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created; tables are built at creation and by glv_batch_set_params, process calls never allocate)");
     if ((ops & GLV_OP_BARS) && (b->bar_count != b->p.bars || b->bar_factor != b->p.smooth_factor || b->bar_phase != b->p.bar_phase || !same_shape(b->bar_shape_of, b->p)))
         return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
+    if ((ops & GLV_OP_BARS) && b->snapped()) {
+        // bars at texels of the pre-smoothing pass: the chain's rows must be what that pass samples -- a GL chain's texels, not smoothed
+        if (!(ops & GLV_OP_FFT) || !(gl_fused_chain(b, ops) || gl_passes_chain(b, ops)) || (ops & GLV_OP_SMOOTH))
+            return fail(GLV_ERR_STATE, "GLV_OP_BARS with bar texels set (glv_batch_set_bar_texels) needs a GL chain's texel rows: GLV_OP_FFT with gravity / average on "
+                                       "gl_storage 1 or 2, without GLV_OP_SMOOTH (ops 0x%x)", ops);
+        if (!snap_current(b)) return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
+    }
     if ((ops & GLV_OP_SMOOTH) && (!b->d_smin || b->smooth_d != b->p.smooth_distance || b->smooth_r != b->p.smooth_ratio))
         return fail(GLV_ERR_STATE, "GLV_OP_SMOOTH: the batch has no window bounds for these parameters (unusable smooth_ratio at creation, or changed without glv_batch_set_params)");
     return GLV_OK;
@@ -846,8 +975,10 @@ struct ChainPlan {
         POST,           // operators on planar rows (no GLV_OP_FFT)
         COPY,           // smooth / bars only: on a copy of the input rows
     } route = FRAME;
-    enum Bars { NO_BARS, BARS_F32, BARS_I8, BARS_I8_FLOATS } bars = NO_BARS;   // the second bars launch: over f32 rows, over texel rows (the
-                                                                               // integer matrix-core pass), over texel values as floats c / 65535
+    enum Bars { NO_BARS, BARS_F32, BARS_I8, BARS_I8_FLOATS,                    // the second bars launch: over f32 rows, over texel rows (the
+                                                                               // integer matrix-core pass), over texel values as floats c / 65535;
+                BARS_SNAP, BARS_SNAP_FLOATS, BARS_SNAP_MODE } bars = NO_BARS;   // bars at texels of the pre-smoothing pass: over texel rows, over
+                                                                               // c / 65535, and sample_mode maximum / hybrid (glv_bars_mode_kernel)
     int variant = 0, grid = 0;                  // the frame kernel's configuration and workgroups (FFT chains)
     glv::FrameClass cls = glv::FC_PLAIN;        // ... and its class
     unsigned ops = 0;                           // what the first kernel runs (FrameArgs::ops)
@@ -868,8 +999,9 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, float* d
     // them inside the frame kernel from the finished row in LDS (the spectra never reach HBM, apart from
     // the state the operators keep anyway); otherwise the spectra stay internal -- in the gravity state
     // when the chain ends in gravity, in the scratch rows else -- and a bars kernel runs after.
+    const bool snap = (ops & GLV_OP_BARS) && b->snapped();      // (check_ops: a GL chain's texel rows)
     pl.fused_bars = (ops & GLV_OP_BARS) && (ops & GLV_OP_FFT) && !gl_passes && bars_fusable(b, ops) && pl.variant < glv_batch::kMaxVariants
-                    && b->bar_fusable[pl.variant];
+                    && (snap ? b->snap_fusable[pl.variant] : b->bar_fusable[pl.variant]);
     pl.out = d_out;
     if (ops & GLV_OP_BARS) {
         const bool state_is_output = (ops & GLV_OP_GRAVITY) && !(ops & (GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_RAW));
@@ -887,6 +1019,7 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, float* d
     } else pl.rows = pl.out ? pl.out : b->d_grav;           // no rows out: a chain that ends in gravity, whose state is its output
     // many bars of texel rows: the integer matrix-core pass -- on the GL_R16 chain's texels, or on the texel values of the GL passes
     if (!(ops & GLV_OP_BARS) || pl.fused_bars) pl.bars = ChainPlan::NO_BARS;
+    else if (snap) pl.bars = b->p.sample_mode != GLV_SAMPLE_AVERAGE ? ChainPlan::BARS_SNAP_MODE : pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_FLOATS;
     else if (b->p.bars >= glv::kBarSeqMin && b->bars_i8() && (pl.route == ChainPlan::GL_FUSED || (gl_passes && !(ops & GLV_OP_SMOOTH))))
         pl.bars = pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_I8 : ChainPlan::BARS_I8_FLOATS;
     else pl.bars = ChainPlan::BARS_F32;
@@ -894,15 +1027,16 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, float* d
     else {
         pl.ops = ops & ~(unsigned) (GLV_OP_PRIVATE_STATE | GLV_OP_OUTPUT_IS_STATE);
         if (ops & GLV_OP_BARS) pl.ops &= ~(unsigned) GLV_OP_R16;     // with bars the texel conversion applies to the bars, the spectra stay f32
-        if (pl.bars == ChainPlan::BARS_I8) pl.ops |= glv::OP_R16;   // ... but the GL_R16 chain hands the integer pass its rows as 16-bit texels
+        if (pl.bars == ChainPlan::BARS_I8 || pl.bars == ChainPlan::BARS_SNAP) pl.ops |= glv::OP_R16;   // ... but the GL_R16 chain hands the integer pass its rows as 16-bit texels
     }
     // the GL_R16 chain's rows go to the bars of a second launch and nowhere else (the scratch rows): what those bars do not sample is not stored
-    if (pl.route == ChainPlan::GL_FUSED && pl.bars != ChainPlan::NO_BARS && b->bar_bins_needed != 0 && b->bar_bins_needed < b->p.n)
-        pl.out_limit = b->bar_bins_needed * 4u;
+    const uint32_t bins_needed = snap ? b->snap_bins : b->bar_bins_needed;
+    if (pl.route == ChainPlan::GL_FUSED && pl.bars != ChainPlan::NO_BARS && bins_needed != 0 && bins_needed < b->p.n)
+        pl.out_limit = bins_needed * 4u;
     // GLV_OP_BARS_ONLY: ... and what they do not sample is not computed, nor is its state kept -- the GL_R16 chain, and a float chain with
     // the bars fused (check_ops vetted the call)
     if (b->live_bins() != 0 && (pl.route == ChainPlan::GL_FUSED || pl.fused_bars)) pl.live_points = b->live_bins() / 2u;
-    pl.cls = glv::frame_class(pl.route == ChainPlan::GL_FUSED, pl.fused_bars, pl.live_points != 0, pl.ops);
+    pl.cls = glv::frame_class(pl.route == ChainPlan::GL_FUSED, pl.fused_bars, pl.live_points != 0, pl.ops, snap);
     return GLV_OK;
 }
 
@@ -913,6 +1047,11 @@ int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, uint32_t 
     if (pl.bars == ChainPlan::BARS_F32) {
         const glv::BarRowsTables rt = b->rows_tables();
         e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w, st, r16, &rt);
+    } else if (pl.bars == ChainPlan::BARS_SNAP || pl.bars == ChainPlan::BARS_SNAP_FLOATS) {
+        e = glv::launch_bars_snap(pl.rows, pl.bars == ChainPlan::BARS_SNAP_FLOATS, d_bars, units, b->p.n, b->p.bars, b->d_snap_desc, b->d_snap_w, st, r16);
+    } else if (pl.bars == ChainPlan::BARS_SNAP_MODE) {
+        const glv::BarRowsTables rt = b->snap_rows_tables();
+        e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, 0, nullptr, b->d_snap_desc, nullptr, st, r16, &rt);
     } else {
         const glv::BarIRowsTables irt = b->irows_tables();
         e = glv::launch_bars_i8(pl.rows, pl.bars == ChainPlan::BARS_I8_FLOATS, d_bars, units, b->p.n, b->p.bars, &irt, st, r16);
@@ -942,7 +1081,11 @@ int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, 
         a.grav_w = d_out; a.out = nullptr;
     }
     const float* grav_next = gravity_only ? (out_is_state ? d_out : b->d_grav) : b->grav_cur;
-    if (pl.fused_bars) {
+    if (pl.fused_bars && (ops & GLV_OP_BARS) && b->snapped()) {
+        a.bar_desc = b->d_snap_desc; a.bar_items = b->d_snap_fitems[pl.variant]; a.bar_nsteps = b->snap_fnsteps[pl.variant];
+        a.bar_w = reinterpret_cast<const float*>(b->d_snap_w);     // (the uint32 weights W' travel as the bits of the float weights; kernel class FC_GL16_SNAP*)
+        a.bars = b->p.bars; a.bars_out = d_out;
+    } else if (pl.fused_bars) {
         a.bar_desc = b->d_bar_desc; a.bar_items = b->d_bar_fitems[pl.variant]; a.bar_nsteps = b->bar_fnsteps[pl.variant]; a.bar_w = b->d_bar_w;
         a.bars = b->p.bars; a.bars_out = d_out;
     }
@@ -1098,6 +1241,9 @@ int glv_batch_set_params(glv_batch* b, const glv_params* p) {
         return fail(GLV_ERR_STATE, "params (n=%u, F=%u) do not match the batch (n=%u, F=%u): fixed at creation", p->n, p->avg_frames, b->p.n, b->p.avg_frames);
     if ((p->gl_storage == 1) != b->state16)
         return fail(GLV_ERR_STATE, "gl_storage=%u: the state of this batch was created as %s", p->gl_storage, b->state16 ? "GL_R16 texels (gl_storage 1)" : "floats (gl_storage 0 / 2)");
+    if (b->snapped() && (p->bars != b->p.bars || p->gl_storage == 0))
+        return fail(GLV_ERR_STATE, "bar texels are set (glv_batch_set_bar_texels): bars (%u -> %u) must keep the table's length and gl_storage must stay non-zero "
+                                   "(a float chain has no pre-smoothed texture); clear the table first", b->p.bars, p->bars);
     HIP_TRY(hipSetDevice(b->device));
     // the tables are rewritten in place: every kernel already queued on any stream of the device must have read them first (a
     // blocking copy from pageable memory does not order against a caller's non-blocking stream)
@@ -1154,6 +1300,7 @@ int glv_batch_destroy(glv_batch* b) {
     if (b->d_bar_irounds) (void) hipFree(b->d_bar_irounds);
     if (b->d_bar_mblocks) (void) hipFree(b->d_bar_mblocks);
     if (b->d_bar_mw) (void) hipFree(b->d_bar_mw);
+    drop_snap_tables(b);
     for (hipEvent_t e : b->ev) (void) hipEventDestroy(e);
     delete b;
     return GLV_OK;
@@ -1282,11 +1429,42 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
     if (b->p.bars == 0 || b->p.bars > b->p.n) return fail(GLV_ERR_INVALID, "bars=%u out of range", b->p.bars);
     HIP_TRY(hipSetDevice(b->device));
     if (!b->d_bar_desc) return fail(GLV_ERR_STATE, "the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created)");
+    if (b->snapped()) return fail(GLV_ERR_STATE, "glv_batch_bars takes float spectra, not a GL chain's texels: refused while bar texels are set (glv_batch_set_bar_texels)");
     const glv::BarRowsTables rt = b->rows_tables();
     hipError_t e = glv::launch_bars(d_spec, d_bars, (size_t) b->streams * 2, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w,
                                     (hipStream_t) hip_stream, false, &rt);
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
     return GLV_OK;
+}
+
+int glv_batch_set_bar_texels(glv_batch* b, const uint32_t* texels, uint32_t count) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    HIP_TRY(hipSetDevice(b->device));
+    // the tables are replaced in place: every kernel already queued on the device must have read them first (as glv_batch_set_params)
+    HIP_TRY(hipDeviceSynchronize());
+    if (texels == nullptr || count == 0) {                 // off: the unsnapped tables, untouched meanwhile, serve again
+        drop_snap_tables(b);
+        b->snap_tex.clear();
+        b->update_live_bins();
+        return GLV_OK;
+    }
+    if (!(b->ops_mask & GLV_OP_BARS) || !b->d_bar_desc)
+        return fail(GLV_ERR_STATE, "bar texels: the batch was created without GLV_OP_BARS (or has no bar tables)");
+    if (b->p.gl_storage == 0)
+        return fail(GLV_ERR_STATE, "bar texels: gl_storage 0 -- a float chain has no pre-smoothed texture to sample");
+    if (count != b->p.bars) return fail(GLV_ERR_INVALID, "bar texels: %u entries for bars=%u", count, b->p.bars);
+    for (uint32_t k = 0; k < count; ++k)
+        if (texels[k] >= b->p.n) return fail(GLV_ERR_INVALID, "bar texels: t[%u] = %u is not a texel of the n=%u pass", k, texels[k], b->p.n);
+    const uint32_t live_before = b->live_bins();
+    const std::vector<uint32_t> before = b->snap_tex;
+    int rc = build_snap_tables(b, std::vector<uint32_t>(texels, texels + count));
+    // (as glv_batch_set_params: a GLV_OP_BARS_ONLY batch that ran its live class cannot start sampling beyond the bins it kept)
+    if (rc == GLV_OK && b->ran_live && b->live_bins() != live_before) {
+        if (before.empty()) { drop_snap_tables(b); b->snap_tex.clear(); b->update_live_bins(); }
+        else (void) build_snap_tables(b, before);
+        rc = fail(GLV_ERR_STATE, "bar texels: these taps reach beyond the live bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first");
+    }
+    return rc;
 }
 
 int glv_prelude_bufscale(int device, const float* d_in, float* d_out, size_t rows, uint32_t n_out, uint32_t k, void* hip_stream) {
@@ -1363,6 +1541,7 @@ const char* glv_batch_kernel_name(const glv_batch* b) { return b ? b->kernel_nam
 
 int glv_batch_bars_arithmetic(const glv_batch* b) {
     if (!b || b->bar_count == 0 || !b->d_bar_desc) return GLV_BARS_NONE;
+    if (b->snapped()) return b->p.sample_mode != GLV_SAMPLE_AVERAGE ? GLV_BARS_F32_SEQ : GLV_BARS_I8_EXACT;   // the twin's (set_bar_texels made sure)
     if (b->p.sample_mode != GLV_SAMPLE_AVERAGE) return GLV_BARS_F32_SEQ;
     if (b->p.bars < glv::kBarSeqMin) return GLV_BARS_F32_CHAIN;
     return b->p.gl_storage != 0 && b->bars_i8() ? GLV_BARS_I8_EXACT : GLV_BARS_F32_MATRIX;

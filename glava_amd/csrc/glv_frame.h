@@ -68,16 +68,21 @@ enum FrameClass : int {
                              // (glv_frame.h epilogue_gl16 LIVE)
     FC_STATE_BARS_LIVE = 8,  // FC_STATE_BARS / FC_GL16_BARS for GLV_OP_BARS_ONLY batches: magnitude, state and the row in LDS for the live
     FC_GL16_BARS_LIVE = 9,   //   blocks only
+    FC_GL16_SNAP = 10,       // FC_GL16_BARS / FC_GL16_BARS_LIVE with the bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels: exact
+    FC_GL16_SNAP_LIVE = 11,  //   integer sums, glv_frame.h bar_snap_*).  Own classes, not a run-time flag: the flag cost the unsnapped live class
+                             //   1.3 % (68.2 vs 69.1 M frames/s, N = 4096, 64 K streams, same box alternating: profiles/r07/snapped_bars.txt)
 };
-constexpr int kFrameClasses = 10;
-GLV_HD constexpr bool fc_fused_bars(int c) { return c == FC_STATE_BARS || c == FC_GL16_BARS || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE; }
-GLV_HD constexpr bool fc_gl16(int c) { return c == FC_GL16 || c == FC_GL16_BARS || c == FC_GL16_LIVE || c == FC_GL16_BARS_LIVE; }
-GLV_HD constexpr bool fc_live(int c) { return c == FC_GL16_LIVE || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE; }
+constexpr int kFrameClasses = 12;
+GLV_HD constexpr bool fc_snap(int c) { return c == FC_GL16_SNAP || c == FC_GL16_SNAP_LIVE; }
+GLV_HD constexpr bool fc_fused_bars(int c) { return c == FC_STATE_BARS || c == FC_GL16_BARS || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE || fc_snap(c); }
+GLV_HD constexpr bool fc_gl16(int c) { return c == FC_GL16 || c == FC_GL16_BARS || c == FC_GL16_LIVE || c == FC_GL16_BARS_LIVE || fc_snap(c); }
+GLV_HD constexpr bool fc_live(int c) { return c == FC_GL16_LIVE || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE || c == FC_GL16_SNAP_LIVE; }
 GLV_HD constexpr bool fc_has_state(int c) { return c != FC_PLAIN && c != FC_R16; }
 GLV_HD constexpr bool fc_texel_out(int c) { return c == FC_R16 || c == FC_STATE_R16; }     // rows out as uint16 texels, always
 // the class of a launch: the GL_R16 chain (gl_storage 1), the bars fused, the live blocks only (the float chains have a live class with the
 // bars fused only), else the ops the kernel sees (state: OP_GRAVITY / OP_AVERAGE; texel rows: OP_R16)
-GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, uint32_t ops) {
+GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, uint32_t ops, bool snap = false) {
+    if (gl16 && fused_bars && snap) return live ? FC_GL16_SNAP_LIVE : FC_GL16_SNAP;
     if (gl16) return fused_bars ? (live ? FC_GL16_BARS_LIVE : FC_GL16_BARS) : (live ? FC_GL16_LIVE : FC_GL16);
     if (fused_bars) return live ? FC_STATE_BARS_LIVE : FC_STATE_BARS;
     if (ops & (OP_GRAVITY | OP_AVERAGE)) return (ops & OP_R16) ? FC_STATE_R16 : FC_STATE;
@@ -130,6 +135,7 @@ struct FrameArgs {
     float* bars_out;            // [units][bars], nullptr = not fused
     uint32_t bars;
     uint32_t bar_nsteps;        // multiple of bar_batch_of(log2 nn)
+                                // (kernel classes FC_GL16_SNAP*: bar_w holds the uint32 weights W' of bar_snap_lane_sum as float bits)
 };
 
 // ---- GLV_OP_BARS arithmetic (smooth.glsl:25-40; tex clamped to [0,1] like the GL_R16 texture the
@@ -234,6 +240,26 @@ GLV_HD float bar_item_lane_sum(const BarTaps& s) {
     return e + o;
 #endif
 }
+// ---- GLV_OP_BARS at texels of the pre-smoothing pass (glv_batch_set_bar_texels; weights: glv_tables.h make_bar_snap_weights) ----------------
+// Bar k is texel t[k] of the bars = n, bar_phase 0.5 pass over the chain's GL_R16 texels c: sum_j W'_j c_j in 64 bits, exact and order-free,
+// with every bar's integer weights scaled to 2^31 (W' = W << (31 - P)).  The chunk work lists and the lane's eight consecutive taps are those of
+// the float epilogue (bar_item_load: the weights travel as the bits of BarTaps::w); the row in LDS holds c / 65535, which the packed unorm16
+// conversion returns to c exactly for every 16-bit c (values a zero-weight tap reads past the row's live blocks clamp, and add 0).
+GLV_HD uint64_t bar_snap_lane_sum(const BarTaps& s) {
+    uint64_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < kBarTaps; i += 2) {
+        const uint32_t c2 = pack_unorm16(s.t[i], s.t[i + 1]);
+        acc += (uint64_t) __builtin_bit_cast(uint32_t, s.w[i]) * (c2 & 0xffffu);
+        acc += (uint64_t) __builtin_bit_cast(uint32_t, s.w[i + 1]) * (c2 >> 16);
+    }
+    return acc;
+}
+// the results, as the twin's i8 pass gives them (glv_misc.hip glv_bars_rows_i8_kernel, oracle glvo_bars_int_at): floor(T / 2^31 + 1/2), and the float
+// form ldexp((double) T, -31) / 65535 (which the caller divides by the bar's weight_sum, 1 -- or NaN for a bar whose weights sum to 0)
+GLV_HD uint32_t bar_snap_texel(uint64_t total) { return (uint32_t) ((total + (1ull << 30)) >> 31); }
+GLV_HD float bar_snap_float(uint64_t total) { return (float) (__builtin_ldexp((double) total, -31) / 65535.0); }
+
 #if defined(__HIPCC__)
 // sum over each group of GL = 2 / 4 / 8 lanes (aligned inside a DPP row), result in every lane of the group: VALU-speed cross-lane
 // adds (a ds_bpermute shuffle is an LDS round trip each)
@@ -245,6 +271,19 @@ template <int GL> __device__ __forceinline__ float group_sum(float v) {
     v = v + dpp_move<0xB1>(v);                             // quad_perm [1,0,3,2]: neighbours
     if constexpr (GL >= 4) v = v + dpp_move<0x4E>(v);      // quad_perm [2,3,0,1]: pairs of pairs
     if constexpr (GL >= 8) v = v + dpp_move<0x141>(v);     // row_half_mirror: the other quad of each 8
+    return v;
+}
+// the same for the 64-bit integer sums of the snapped bars (two 32-bit moves per level)
+template <int CTRL> __device__ __forceinline__ uint64_t dpp_move64(uint64_t v) {
+    const uint32_t lo = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) (uint32_t) v, CTRL, 0xF, 0xF, false);
+    const uint32_t hi = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) (uint32_t) (v >> 32), CTRL, 0xF, 0xF, false);
+    return ((uint64_t) hi << 32) | lo;
+}
+template <int GL> __device__ __forceinline__ uint64_t group_sum64(uint64_t v) {
+    static_assert(GL == 2 || GL == 4 || GL == 8, "lanes per group");
+    v = v + dpp_move64<0xB1>(v);
+    if constexpr (GL >= 4) v = v + dpp_move64<0x4E>(v);
+    if constexpr (GL >= 8) v = v + dpp_move64<0x141>(v);
     return v;
 }
 #endif

@@ -333,7 +333,37 @@ glv_frame_kernel(const FrameArgs a) {
             float* lrow = reinterpret_cast<float*>(xslot);
             float* lres = lrow + N;                                       // XREGION has NN/E points (2T floats) of slack: bars + 1 <= 2T (glv_api.cpp bar_fusable)
             static_assert(2 * T >= 64, "the chunk reads of bar_item_load stay inside the slot's region");
-            if (active) {
+            constexpr bool snap = fc_snap(STATEFUL);
+            if (active && snap) {
+                // bars at texels of the pre-smoothing pass (glv_frame.h bar_snap_lane_sum): the same work lists, exact 64-bit integer sums, and
+                // each step's result is already the bar's -- texel or float bits -- so the slack behind the row takes 4 bytes per bar as above
+                const int sub = tid & (GL - 1);
+                const uint32_t g = (uint32_t) tid / GL;
+                const BarItem* items = a.bar_items + g;
+                uint32_t* lout = reinterpret_cast<uint32_t*>(lres);
+                const bool r16 = a.bars_r16 != 0;
+                BarItem it[BB];
+#pragma unroll
+                for (int b = 0; b < BB; ++b) it[b] = items[(size_t) b * G];
+                uint64_t total = 0;
+                for (uint32_t s0 = 0; s0 < a.bar_nsteps; s0 += BB) {
+                    BarTaps tp[BB];
+                    BarItem nx[BB];
+#pragma unroll
+                    for (int b = 0; b < BB; ++b) tp[b] = bar_item_load<false>(lrow, a.bar_w, it[b], sub);
+#pragma unroll
+                    for (int b = 0; b < BB; ++b) nx[b] = items[(size_t) (s0 + BB + b) * G];
+                    if constexpr (BB <= kBarBatch) GLV_SCHED_FENCE();
+#pragma unroll
+                    for (int b = 0; b < BB; ++b) {
+                        const uint64_t chunk_sum = group_sum64<GL>(bar_snap_lane_sum(tp[b]));
+                        total = it[b].keep != 0.0f ? total + chunk_sum : chunk_sum;
+                        if (sub == 0) lout[it[b].res] = r16 ? bar_snap_texel(total) : __builtin_bit_cast(uint32_t, bar_snap_float(total));
+                    }
+#pragma unroll
+                    for (int b = 0; b < BB; ++b) it[b] = nx[b];
+                }
+            } else if (active) {
                 const int sub = tid & (GL - 1);
                 const uint32_t g = (uint32_t) tid / GL;
                 const BarItem* items = a.bar_items + g;
@@ -367,7 +397,11 @@ glv_frame_kernel(const FrameArgs a) {
             }
             sy.sync();
             if (active) {
-                if (GL16 && a.bars_r16) {                  // uniform: the bars as GL_R16 texels (the smooth pass's render target, render.c:2277-2303)
+                if (GL16 && a.bars_r16 && snap) {          // snapped texels: the integer results as they are
+                    uint16_t* bo = reinterpret_cast<uint16_t*>(a.bars_out) + row * a.bars;
+                    const uint32_t* lout = reinterpret_cast<const uint32_t*>(lres);
+                    for (uint32_t k = (uint32_t) tid; k < a.bars; k += T) bo[k] = (uint16_t) lout[k];
+                } else if (GL16 && a.bars_r16) {           // uniform: the bars as GL_R16 texels (the smooth pass's render target, render.c:2277-2303)
                     uint16_t* bo = reinterpret_cast<uint16_t*>(a.bars_out) + row * a.bars;
                     if ((uint32_t) tid < a.bars) bo[tid] = (uint16_t) unorm16(lres[tid] / bar_wsum);
                     for (uint32_t k = (uint32_t) tid + T; k < a.bars; k += T) bo[k] = (uint16_t) unorm16(lres[k] / a.bar_desc[k].weight_sum);
@@ -602,6 +636,8 @@ hipError_t launch_variant(FrameClass cls, const FrameArgs& a, int grid, hipStrea
     };
     switch (cls) {     // (in the order of the kernels in the code object)
         case FC_GL16_LIVE:       return launch_class(std::integral_constant<int, FC_GL16_LIVE>{});
+        case FC_GL16_SNAP_LIVE:  return launch_class(std::integral_constant<int, FC_GL16_SNAP_LIVE>{});
+        case FC_GL16_SNAP:       return launch_class(std::integral_constant<int, FC_GL16_SNAP>{});
         case FC_GL16_BARS_LIVE:  return launch_class(std::integral_constant<int, FC_GL16_BARS_LIVE>{});
         case FC_GL16_BARS:       return launch_class(std::integral_constant<int, FC_GL16_BARS>{});
         case FC_GL16:            return launch_class(std::integral_constant<int, FC_GL16>{});

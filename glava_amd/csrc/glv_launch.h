@@ -62,6 +62,9 @@ struct BarIRowsTables {
 };
 hipError_t launch_bars_i8(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st, bool r16);
 hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt);     // function attributes of the kernels launch_bars_i8 would pick
+// bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels) over texel rows: uint16, or floats c / 65535 (rows_f32); one lane per bar and row
+hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const uint32_t* wi,
+                            hipStream_t st, bool r16);
 hipError_t launch_ring_planar(const void* ring, int is_f32, uint32_t n, uint32_t rot, int mono, size_t streams, float* out, hipStream_t st);
 hipError_t launch_unpack(const int16_t* pcm, size_t frames, int mono, float* l, float* r, hipStream_t st);
 

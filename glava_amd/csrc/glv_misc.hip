@@ -1163,6 +1163,39 @@ hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt) {
     return e;
 }
 
+// GLV_OP_BARS at texels of the pre-smoothing pass as a second launch (glv_batch_set_bar_texels, where the frame kernel does not take them): one
+// lane per (row, bar) over the chain's texel rows -- uint16 (F32IN false) or the floats c / 65535 of the pass-by-pass chain (true) -- with the
+// fused epilogue's exact sum (glv_frame.h bar_snap_*; weights W' of glv_tables.h make_bar_snap_weights, in tap order from desc[k].tap_offset)
+template <bool F32IN, bool R16>
+__global__ void __launch_bounds__(256) glv_bars_snap_kernel(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const uint32_t* wi) {
+    const size_t i = (size_t) blockIdx.x * 256u + threadIdx.x;
+    if (i >= nrows * bars) return;
+    const size_t row = i / bars;
+    const BarDesc d = desc[i % bars];
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < d.count; ++j) {                  // first_bin + count <= n (glv_tables.h bar_chunks_in_row)
+        const size_t at = row * n + d.first_bin + j;
+        const uint32_t c = F32IN ? unorm16(static_cast<const float*>(rows)[at]) : (uint32_t) static_cast<const uint16_t*>(rows)[at];
+        total += (uint64_t) wi[d.tap_offset + j] * c;
+    }
+    if constexpr (R16) static_cast<uint16_t*>(bars_out)[i] = (uint16_t) bar_snap_texel(total);
+    else static_cast<float*>(bars_out)[i] = bar_snap_float(total) / d.weight_sum;
+}
+hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const uint32_t* wi,
+                            hipStream_t st, bool r16) {
+    const size_t total = nrows * bars;
+    if (total == 0) return hipSuccess;
+    const dim3 grid((unsigned) ((total + 255) / 256));
+    if (rows_f32) {
+        if (r16) hipLaunchKernelGGL((glv_bars_snap_kernel<true, true>), grid, dim3(256), 0, st, rows, bars_out, nrows, n, bars, desc, wi);
+        else hipLaunchKernelGGL((glv_bars_snap_kernel<true, false>), grid, dim3(256), 0, st, rows, bars_out, nrows, n, bars, desc, wi);
+    } else {
+        if (r16) hipLaunchKernelGGL((glv_bars_snap_kernel<false, true>), grid, dim3(256), 0, st, rows, bars_out, nrows, n, bars, desc, wi);
+        else hipLaunchKernelGGL((glv_bars_snap_kernel<false, false>), grid, dim3(256), 0, st, rows, bars_out, nrows, n, bars, desc, wi);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_bars(const float* spec, float* bars_out, size_t nrows, uint32_t n, uint32_t bars, uint32_t nsteps,
                        const BarItem* items, const BarDesc* desc, const float* tap_w, hipStream_t st, bool r16, const BarRowsTables* rt) {
     const int r = r16 ? 1 : 0;

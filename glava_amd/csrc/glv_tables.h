@@ -118,14 +118,18 @@ inline float bar_round_formula(uint32_t formula, float x) {                     
     if (formula == 2u) return x;                                                  // linear
     return (0.5f * sinf((3.14159265359f * x) - (3.14159265359f / 2.0f))) + 0.5f;  // sinusoidal
 }
-inline void make_bar_taps(std::vector<BarDesc>& desc, std::vector<float>& tap_w, uint32_t n, uint32_t bars, float smooth_factor, float phase = 0.0f, const BarShape& shape = BarShape{}) {
+// texels != nullptr (glv_batch_set_bar_texels): bar k takes the taps of row texels[k] of the pre-smoothing pass (bars = n, phase 0.5), i.e.
+// idx = (texels[k] + 0.5) / n in exactly that row's float operations; `bars` is then the length of the texel table.
+inline void make_bar_taps(std::vector<BarDesc>& desc, std::vector<float>& tap_w, uint32_t n, uint32_t bars, float smooth_factor, float phase = 0.0f, const BarShape& shape = BarShape{},
+                          const uint32_t* texels = nullptr) {
     const uint32_t chunk = bar_chunk_of(n);
     auto scale = [&](float u) { return -logf((-shape.range * u) + 1.0f) / shape.scale; };
     auto clamp01 = [](float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); };
     desc.resize(bars);
     tap_w.clear();
     for (uint32_t k = 0; k < bars; ++k) {
-        const float idx = phase == 0.0f ? (float) k / (float) bars : ((float) k + phase) / (float) bars;   // gl_FragCoord.x / w
+        const float idx = texels ? ((float) texels[k] + 0.5f) / (float) n                                  // the twin's row texels[k]
+                                 : phase == 0.0f ? (float) k / (float) bars : ((float) k + phase) / (float) bars;   // gl_FragCoord.x / w
         const float smin = scale(clamp01(idx - smooth_factor)) * (float) n;
         const float smax = scale(clamp01(idx + smooth_factor)) * (float) n;
         const float m = (smax - smin) / 2.0f, rm = smin + m;
@@ -420,6 +424,32 @@ inline bool make_bar_itiles(std::vector<BarMTile>& itiles, std::vector<int8_t>& 
             }
     }
     wq.resize(wq.size() + (size_t) kBarILookAhead * 3u * 64u * 16u, 0);         // what the look-ahead reads past the last tile
+    return true;
+}
+
+// ---- bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels) ------------------------------------------------------------------
+// Bar k is texel t[k] of the twin -- the same chain with bars = n, bar_phase 0.5, whose texels make_bar_itiles' integer pass computes: its taps
+// are the twin's row t[k] (make_bar_taps with texels), its weights bar_int_weights of them.  The kernels keep ONE scale for every bar,
+// W' = W << (31 - P), so that (glv_frame.h bar_snap_texel / bar_snap_float)
+//     (sum W' c + 2^30) >> 31                        == (sum W c + 2^(P-1)) >> P                   (the twin's texel)
+//     (float) (ldexp((double) sum W' c, -31) / 65535) == (float) (ldexp((double) sum W c, -P) / 65535)   (its float form)
+// bit for bit: the shift scales the sum and the divisor by the same power of two, and sum W' c <= 2^31 * 65535 < 2^47 is exact in a double.
+// W' <= 2^31 fits a uint32; the products and sums take 64 bits.  A bar whose weights sum to 0 / NaN (P < 0; the twin's texel 0, float NaN) has
+// W' = 0 and weight_sum NaN, every other bar weight_sum 1: the float form is divided by it.  wi has tap_w's layout (chunk padding included).
+// Returns false where a bar's P exceeds 31 or a weight is negative: the twin has no integer tables then.
+inline bool make_bar_snap_weights(std::vector<uint32_t>& wi, std::vector<BarDesc>& desc, const std::vector<float>& tap_w) {
+    wi.assign(tap_w.size(), 0u);
+    std::vector<int32_t> W;
+    for (BarDesc& d : desc) {
+        const int P = bar_int_weights(tap_w.data() + d.tap_offset, d.count, W);
+        if (P == -2) return false;
+        d.weight_sum = P < 0 ? __builtin_nanf("") : 1.0f;
+        if (P < 0) continue;
+        for (uint32_t j = 0; j < d.count; ++j) {
+            if (W[j] < 0) return false;
+            wi[d.tap_offset + j] = (uint32_t) W[j] << (31 - P);
+        }
+    }
     return true;
 }
 

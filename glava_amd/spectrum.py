@@ -14,6 +14,8 @@ import ctypes as C
 import os
 from dataclasses import dataclass
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GLV_SPECTRUM_LIB: an A/B build of the SAME library (glava_amd.build --variant, tools/ab_bench.sh); never a fallback
 LIB_PATH = os.environ.get("GLV_SPECTRUM_LIB") or os.path.join(HERE, "csrc", "libglvspectrum.so")
@@ -92,6 +94,8 @@ def lib() -> C.CDLL:
         L.glv_batch_ring_update_s16.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint, vp]
         L.glv_batch_ring_update_f32.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint, vp]
         L.glv_batch_bars.argtypes = [vp, vp, vp, vp]
+        if hasattr(L, "glv_batch_set_bar_texels"):      # (added within ABI 7: callers detect it by the symbol)
+            L.glv_batch_set_bar_texels.argtypes = [vp, vp, C.c_uint32]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -230,6 +234,19 @@ class Batch:
 
     def bars(self, d_spec, d_bars, stream: int | None = None) -> None:
         _check(lib().glv_batch_bars(self._h, _ptr(d_spec), _ptr(d_bars), _ptr(stream)))
+
+    def set_bar_texels(self, texels) -> None:
+        """GLV_OP_BARS at texels of the pre-smoothed texture (glv_batch_set_bar_texels): bar k = texel texels[k] of the
+        pre-smoothing pass (bars = n, bar_phase 0.5); None / empty turns it off.  glava_amd.bar_positions computes the
+        texels the shipped modules sample."""
+        if texels is None or len(texels) == 0:
+            _check(lib().glv_batch_set_bar_texels(self._h, None, 0))
+            return
+        t = np.ascontiguousarray(np.asarray(texels, dtype=np.int64))
+        if t.ndim != 1 or (t < 0).any() or (t >= 1 << 32).any():
+            raise ValueError("texels: a 1-d list of non-negative 32-bit indices")
+        t = t.astype(np.uint32)
+        _check(lib().glv_batch_set_bar_texels(self._h, t.ctypes.data_as(C.c_void_p), len(t)))
 
     def reset(self) -> None:
         _check(lib().glv_batch_reset(self._h))

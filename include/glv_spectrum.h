@@ -24,7 +24,8 @@ extern "C" {
 #define GLV_ABI_VERSION 7      /* 5 (round 5): + glv_gl_texture; GLV_OP_BARS over texel rows (gl_storage != 0, 256 bars or more) is the exact integer mean
                                   6 (round 6): + GLV_OP_BARS_ONLY, glv_batch_live_bins, glv_batch_bars_arithmetic, glv_batch_tune_placement; GLV_OP_R16 in a creation mask is a hint
                                   7 (round 6): glv_params grew smooth_audio()'s shape -- round_formula, sample_mode, sample_hybrid_weight, sample_scale, sample_range
-                                               (appended; all-zero == the shipped shape, so a caller that zero-fills the tail keeps ABI 6's results); GLV_BARS_F32_SEQ */
+                                               (appended; all-zero == the shipped shape, so a caller that zero-fills the tail keeps ABI 6's results); GLV_BARS_F32_SEQ
+                                  7, added without a version change: glv_batch_set_bar_texels (bars at texels of the pre-smoothing pass; detect it by the symbol) */
 
 /* status codes (0 = ok).  The reference has no error channel: it prints and calls
  * glava_abort() (glava/glava.h:17, glava/render.c passim); the in-tree shim maps any
@@ -59,7 +60,9 @@ enum {
                                    matrix cores compute: glava_amd/csrc/glv_frame.h "GLV_OP_BARS arithmetic";
                                    oracle/glv_oracle.c glvo_bars_chunked restates both) -- within 2e-4 relative of the
                                    shader's tap-by-tap loop, identical bits on every device path.  A bar whose weights
-                                   sum to 0 is 0 / 0 as in the shader.
+                                   sum to 0 is 0 / 0 as in the shader.  These are the `setsmoothpass false` bars (smooth_audio()
+                                   averaging the spectrum at the bar positions); the shipped default's bars are texels of
+                                   the pre-smoothed texture: glv_batch_set_bar_texels.
                                    Inside the GL chains (gl_storage != 0, gravity / average in the chain: the rows the bars sample are
                                    GL_R16 TEXELS, as in the reference's pre-smoothing pass, render.c:2277-2303) 256 bars or more are computed
                                    EXACTLY (ABI 5): per bar the shader's float weights w_j become integers W_j = llrint(w_j 2^P / sum w) with the
@@ -171,7 +174,10 @@ typedef struct glv_params {
                                to 1 on every input; kept as the checker of 1 and for the chains 1 does not fuse.  The storage
                                class (1 vs 0 / 2) is fixed when a batch or state is created. */
     float bar_phase;        /* GLV_OP_BARS evaluates smooth_audio() at idx = (k + bar_phase) / bars, k = 0 .. bars-1.
-                               0 (default): the bar positions of the modules (radial/1.frag:58-70: pos = k / (NBARS / 2)).
+                               0 (default): the bar positions of the modules (radial/1.frag:58-70: pos = k / (NBARS / 2)) with the
+                               `setsmoothpass false` semantics -- smooth_audio() averaging the spectrum at those positions.  With
+                               setsmoothpass true (GLava's default) the shipped modules fetch texels of the pre-smoothed texture
+                               instead: those bars come from glv_batch_set_bar_texels (bar_phase is then ignored).
                                0.5 with bars == n: the texel centres of the reference's pre-smoothing pass
                                (util/smooth_pass.frag: smooth_audio(tex, sz, gl_FragCoord.x / w), render.c:2277-2303) -- the
                                texture every stock module samples when setsmoothpass is on (the default) */
@@ -339,6 +345,25 @@ int glv_batch_ring_planar(glv_batch* b, int f32_ring, float* d_planar, void* hip
  * d_bars float [streams][2][bars]; what GLV_OP_BARS runs after the transform. */
 int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_stream);
 
+/* GLV_OP_BARS at texels of the pre-smoothed texture: bar k = texel t[k] of the pre-smoothing pass (bars = n, bar_phase 0.5), which is what the
+ * shipped modules sample with setsmoothpass true -- smooth_audio(tex, sz, p) is then one texelFetch(tex, int(round(p * sz)), 0) (util/smooth.glsl:61-63;
+ * radial/1.frag:69-71, bars/1.frag:64-90; glava_amd.bar_positions computes the t[k] of both modules).  Contract: with the table set,
+ *     bars_out[row][k] == twin_out[row][t[k]]   bit for bit, as GL_R16 texels (GLV_OP_R16) and as floats,
+ * where the twin is the same batch created with bars = n and bar_phase = 0.5, in its arithmetic (glv_batch_bars_arithmetic, which reports it):
+ * GLV_BARS_I8_EXACT -- texel floor(sum W_j c_j / 2^P + 1/2), float (float) (ldexp((double) sum W_j c_j, -P) / 65535), the integer weights of the twin's
+ * row t[k] (oracle glvo_bars_int_at) -- for sample_mode average, GLV_BARS_F32_SEQ for maximum / hybrid.  In one launch where the transform kernel
+ * takes the bars (the GL_R16 chain, gl_storage 1, sample_mode average, whenever the unsnapped bars of the configuration fuse), else as a second launch.
+ *   texels == NULL or count == 0: off -- the unsnapped bars again, bit for bit.  Synchronous, may allocate (like glv_batch_set_params).
+ *   Refused: count != bars or any t[k] >= n (GLV_ERR_INVALID); a batch created without GLV_OP_BARS or with gl_storage 0 (GLV_ERR_STATE: a float chain
+ *   has no pre-smoothed texture); a twin whose arithmetic would be GLV_BARS_F32_MATRIX (GLV_ERR_INVALID, glv_last_error says why).
+ *   While a table is set: glv_batch_set_params that changes bars or sets gl_storage 0, glv_batch_bars, and GLV_OP_BARS calls that are not a GL chain
+ *   (GLV_OP_FFT with gravity / average, no GLV_OP_SMOOTH) are refused with GLV_ERR_STATE; a change of smooth_factor or of the shape rebuilds the
+ *   table's taps.  glv_batch_reset keeps the table, glv_batch_destroy frees it.
+ * glv_batch_live_bins: every snapped position lies in [0, 1), which the live bins already cover whenever smooth_factor >= 1 / bars (the unsnapped
+ * last bar then reaches smooth_audio()'s last bin); a smaller factor grows them to the snapped taps' reach -- refused on a GLV_OP_BARS_ONLY batch
+ * that has already run its live class (glv_batch_reset first). */
+int glv_batch_set_bar_texels(glv_batch* b, const uint32_t* texels, uint32_t count);
+
 /* Kernel-time accounting for the roofline report: HIP events recorded on the caller's
  * stream around every launch between begin/end; returns accumulated milliseconds and the
  * number of launches of the dominant (FFT) kernel. */
@@ -412,6 +437,7 @@ const char* glv_batch_kernel_name(const glv_batch* b);
  *                          the f32 matrix cores (bit-equal to smooth_audio()'s float order, NOT to glvo_bars_int_at)
  *   GLV_BARS_F32_SEQ       (ABI 7) sample_mode maximum / hybrid: one lane per bar and row, the shader's loop in float as glv_params.sample_mode documents
  *                          (oracle glvo_bars_mode_at), float and texel rows alike
+ * With bar texels set (glv_batch_set_bar_texels) it reports the twin's arithmetic: GLV_BARS_I8_EXACT or GLV_BARS_F32_SEQ.
  * Float rows (gl_storage 0) always take the float forms.  Callers and parity tests that depend on the exact form check this. */
 enum { GLV_BARS_NONE = 0, GLV_BARS_F32_CHAIN = 1, GLV_BARS_F32_MATRIX = 2, GLV_BARS_I8_EXACT = 3, GLV_BARS_F32_SEQ = 4 };
 int glv_batch_bars_arithmetic(const glv_batch* b);
