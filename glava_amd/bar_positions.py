@@ -48,3 +48,51 @@ def bars_module_bar_texels(n: int, area_width: float, bar_width: float = 5, bar_
     p = (p + F(F(F(0.5) + center) / W)).astype(F)                          # p += sign(p) * ((0.5 + center) / AREA_WIDTH), p > 0
     p = p[p <= F(1.0)]
     return _snap(p, n)
+
+
+def _snap_beyond(p: np.ndarray, n: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """_snap plus, per entry, whether the fetch lands on texel n or beyond (a position of 1.0 or more): GLSL leaves such a
+    texelFetch undefined; the entry is clipped to n - 1 as _snap clips"""
+    x = (p.astype(F) * F(n)).astype(F)
+    t, ties = _snap(p, n)
+    return t, ties, np.rint(x).astype(np.int64) >= n
+
+
+def graph_column_texels(n: int, screen_w: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """graph/1.frag:87-88 (gl_FragCoord at integer pixel centres, graph/1.frag:2): a column's height starts from
+    smooth_audio_adj(tex, sz, idx / half_w, pixel) -- util/smooth.glsl:67-73, three fetches at max(p - pixel, 0), p and
+    min(p + pixel, 1), averaged as (al + am + ar) / 3.0F -- with half_w = screen.x / 2 (integer division) and
+    pixel = 1.0F / float(screen.x).  Returns ``(texels[count, 3], ties[count, 3], beyond[count, 3])`` (left, middle, right)
+    for idx = 0 .. screen_w - screen_w // 2 inclusive: the table ``Batch.set_column_texels`` takes.  Every index the module
+    uses is a row of it: DIRECTION >= 0 draws x < half_w from the left channel at idx = half_w - x and the other pixels
+    from the right channel at idx = x - half_w; DIRECTION < 0 at idx = x and idx = screen_w - x (which reaches half_w + 1
+    for an odd width); `middle` reads positions 1 and 0, rows half_w and 0.  idx >= half_w is a position of 1.0 or more --
+    texel n or beyond, which GLSL leaves undefined (the shipped shader multiplies the outermost column by 0): such entries
+    are flagged in ``beyond`` and clipped to n - 1."""
+    half_w = screen_w // 2
+    if half_w < 1:
+        raise ValueError("screen_w must be at least 2")
+    pixel = F(F(1.0) / F(screen_w))
+    idx = np.arange(screen_w - half_w + 1, dtype=np.int64).astype(F)
+    p = (idx / F(half_w)).astype(F)
+    pos = np.stack([np.maximum((p - pixel).astype(F), F(0.0)), p, np.minimum((p + pixel).astype(F), F(1.0))], axis=1)
+    t, ties, beyond = _snap_beyond(pos.reshape(-1), n)
+    return t.reshape(-1, 3), ties.reshape(-1, 3), beyond.reshape(-1, 3)
+
+
+def circle_texels(n: int, theta, rotate: float = 3.14159265359 / 2, invert: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """circle/1.frag:34-46 for the angles ``theta`` (radians: what atan(dy, dx) hands the shader's apply_smooth):
+    idx = theta + ROTATE (circle.glsl: PI / 2), folded at PI through mod(abs(idx), TWOPI), negated when INVERT > 0,
+    pos = abs(idx) / (PI + 0.001F).  Returns ``(texels, is_left, ties)``: the texel of each angle, whether the shader
+    fetches it from the left channel (idx > 0; the right one otherwise) and the ties of _snap -- a table for
+    ``Batch.set_bar_texels``."""
+    TWOPI, PI = F(6.28318530718), F(3.14159265359)
+    idx = (np.asarray(theta, dtype=np.float64).astype(F).reshape(-1) + F(rotate)).astype(F)
+    a = np.abs(idx)
+    d = (a - (TWOPI * np.floor((a / TWOPI).astype(F))).astype(F)).astype(F)            # mod(x, y) = x - y * floor(x / y)
+    idx = np.where(d > PI, (-np.sign(idx) * (TWOPI - d).astype(F)).astype(F), idx).astype(F)
+    if invert > 0:
+        idx = (-idx).astype(F)
+    pos = (np.abs(idx) / F(PI + F(0.001))).astype(F)
+    t, ties = _snap(pos, n)
+    return t, idx > 0, ties

@@ -6,6 +6,7 @@
 // there is no CPU compute path here and none is ever substituted.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -376,6 +377,13 @@ struct glv_batch {
     uint32_t snap_bins = 0;                  // bins of a row the snapped bars sample (whole 64s)
     glv_params snap_of{};                    // the parameters the snapped tables were made for (smooth_factor, the shape, bars)
     bool snapped() const { return !snap_tex.empty(); }
+    // glv_batch_set_column_texels: column x is the mean of texels col_tex[x][0..2] of the same pass.  snap_tex then holds the DISTINCT texels (sorted)
+    // and the snapped tables above are made over those; col_map says where a column's three sit among them.  The second launch (glv_columns_kernel)
+    // has work lists of its own (256 / bar_lanes_of(n) groups), and for maximum / hybrid d_snap_w holds the float weights in tap order.
+    std::vector<uint32_t> col_tex;           // [bars][3] as the caller gave them; empty = off
+    glv::ColumnMap* d_col_map = nullptr;
+    glv::BarItem* d_col_items = nullptr; uint32_t col_nsteps = 0;
+    bool columns() const { return !col_tex.empty(); }
     glv::BarRowsTables snap_rows_tables() const {
         glv::BarRowsTables t = rows_tables();
         t.mblocks = d_snap_mblocks; t.nmblocks = snap_nmblocks; t.mw = d_snap_mw; t.mode_bins = snap_bins < p.n ? snap_bins : p.n;
@@ -755,15 +763,21 @@ int ensure_bar_tables(glv_batch* b) {
 
 void drop_snap_tables(glv_batch* b) {
     auto drop = [](auto*& ptr) { if (ptr) { (void) hipFree(ptr); ptr = nullptr; } };
-    drop(b->d_snap_desc); drop(b->d_snap_w); drop(b->d_snap_mblocks); drop(b->d_snap_mw);
+    drop(b->d_snap_desc); drop(b->d_snap_w); drop(b->d_snap_mblocks); drop(b->d_snap_mw); drop(b->d_col_items); b->col_nsteps = 0;
     for (int v = 0; v < glv_batch::kMaxVariants; ++v) { drop(b->d_snap_fitems[v]); b->snap_fusable[v] = false; b->snap_fnsteps[v] = 0; }
     b->snap_nmblocks = 0; b->snap_bins = 0;
 }
 bool bars_fusable(const glv_batch* b, unsigned ops);
+// glv_batch_set_column_texels: the most distinct texels the frame kernel's epilogue takes; more go to the second launch (glv_columns_kernel).
+// Measured at N = 4096, 64 K streams (profiles/r08/column_texels.txt): 321 texels fused 1.61 ms, the second launch 2.10 ms, the twin plus a gather 2.09 ms --
+// and the second launch loses to the twin from there up (801 texels 4.08 against 3.23 ms), so whatever fits behind the row is fused: the bound is the room
+// of the widest configuration (4 x 256 lanes), not a crossover.  801 texels fused (N = 16384, 256 lanes) is tested but not timed.
+constexpr uint32_t kColumnsFuseMax = 1023;
 
 // The tables of bars at texels `tex` of the pre-smoothing pass (glv_batch_set_bar_texels; glv_tables.h make_bar_snap_weights): every check first,
 // then the device tables are replaced -- a refused table leaves the batch as it was.  Synchronous; creation / set calls only.
-int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex) {
+// columns (glv_batch_set_column_texels): `tex` are the distinct texels the columns read -- bars = their number, not glv_params.bars.
+int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex, bool columns) {
     const uint32_t n = b->p.n, bars = (uint32_t) tex.size();
     const bool averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;
     const glv::BarShape shape = bar_shape(b->p);
@@ -794,6 +808,8 @@ int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex) {
     bool fusable[glv_batch::kMaxVariants] = {};
     std::vector<glv::BarModeBlock> blocks;
     std::vector<float> mw;
+    std::vector<glv::BarItem> citems;
+    uint32_t cnsteps = 0;
     const int nv = glv::frame_variants(b->log_nn);
     if (averaging) {
         if (!glv::make_bar_snap_weights(wi, desc, w)) return fail(GLV_ERR_INVALID, "bar texels: a bar's integer weights do not exist for these parameters");
@@ -802,9 +818,15 @@ int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex) {
         for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) {
             const glv::FrameGeometry geo = glv::frame_geometry(b->log_nn, v);
             // every result is 4 bytes behind the row, as the unsnapped totals: bars + the dump slot in the 2 * lanes floats of slack
-            fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && bars + 1 <= 2 * (uint32_t) geo.lanes;
+            // (columns keep 16-bit texels there: twice as many.  kColumnsFuseMax: beyond it the second launch is the quicker route)
+            fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && (columns ? bars + 1 <= 4 * (uint32_t) geo.lanes && bars <= kColumnsFuseMax : bars + 1 <= 2 * (uint32_t) geo.lanes);
             if (fusable[v]) fnsteps[v] = glv::make_bar_items(fitems[v], desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
         }
+        if (columns) cnsteps = glv::make_bar_items(citems, desc, 256u / gl, zero_off, chunk, (uint32_t) glv::kBarBatch);
+    } else if (columns) {
+        wi.resize(w.size());                                  // glv_columns_kernel MODE 1 / 2: the float weights in tap order, as bits
+        std::memcpy(wi.data(), w.data(), sizeof(float) * w.size());
+        if (wi.empty()) wi.push_back(0u);
     } else {
         glv::make_bar_mode_blocks(blocks, mw, desc, w);
         if (mw.empty()) mw.push_back(0.0f);
@@ -816,16 +838,23 @@ int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex) {
     drop_snap_tables(b);
     HIP_TRY(hipMalloc(&b->d_snap_desc, sizeof(glv::BarDesc) * desc.size()));
     HIP_TRY(hipMemcpy(b->d_snap_desc, desc.data(), sizeof(glv::BarDesc) * desc.size(), hipMemcpyHostToDevice));
-    if (averaging) {
+    if (averaging || columns) {
         HIP_TRY(hipMalloc(&b->d_snap_w, sizeof(uint32_t) * wi.size()));
         HIP_TRY(hipMemcpy(b->d_snap_w, wi.data(), sizeof(uint32_t) * wi.size(), hipMemcpyHostToDevice));
+    }
+    if (averaging && columns) {
+        HIP_TRY(hipMalloc(&b->d_col_items, sizeof(glv::BarItem) * citems.size()));
+        HIP_TRY(hipMemcpy(b->d_col_items, citems.data(), sizeof(glv::BarItem) * citems.size(), hipMemcpyHostToDevice));
+        b->col_nsteps = cnsteps;
+    }
+    if (averaging) {
         for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) {
             if (!fusable[v]) continue;
             HIP_TRY(hipMalloc(&b->d_snap_fitems[v], sizeof(glv::BarItem) * fitems[v].size()));
             HIP_TRY(hipMemcpy(b->d_snap_fitems[v], fitems[v].data(), sizeof(glv::BarItem) * fitems[v].size(), hipMemcpyHostToDevice));
             b->snap_fusable[v] = true; b->snap_fnsteps[v] = fnsteps[v];
         }
-    } else {
+    } else if (!columns) {
         HIP_TRY(hipMalloc(&b->d_snap_mblocks, sizeof(glv::BarModeBlock) * blocks.size()));
         HIP_TRY(hipMemcpy(b->d_snap_mblocks, blocks.data(), sizeof(glv::BarModeBlock) * blocks.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMalloc(&b->d_snap_mw, sizeof(float) * mw.size()));
@@ -843,7 +872,7 @@ bool snap_current(const glv_batch* b) {
 }
 int ensure_snap_tables(glv_batch* b) {
     if (!b->snapped() || snap_current(b)) return GLV_OK;
-    return build_snap_tables(b, b->snap_tex);
+    return build_snap_tables(b, b->snap_tex, b->columns());
 }
 
 // the gravity step on texels (only the GL_R16 state needs it: 65 536 evaluations on the host whenever g changes -- for the
@@ -960,6 +989,8 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
             return fail(GLV_ERR_STATE, "GLV_OP_BARS with bar texels set (glv_batch_set_bar_texels) needs a GL chain's texel rows: GLV_OP_FFT with gravity / average on "
                                        "gl_storage 1 or 2, without GLV_OP_SMOOTH (ops 0x%x)", ops);
         if (!snap_current(b)) return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
+        if (b->columns() && (ops & GLV_OP_R16))
+            return fail(GLV_ERR_STATE, "GLV_OP_R16 with column texels set (glv_batch_set_column_texels): a mean of three texels is not a texel, the columns are floats");
     }
     if ((ops & GLV_OP_SMOOTH) && (!b->d_smin || b->smooth_d != b->p.smooth_distance || b->smooth_r != b->p.smooth_ratio))
         return fail(GLV_ERR_STATE, "GLV_OP_SMOOTH: the batch has no window bounds for these parameters (unusable smooth_ratio at creation, or changed without glv_batch_set_params)");
@@ -977,8 +1008,9 @@ struct ChainPlan {
     } route = FRAME;
     enum Bars { NO_BARS, BARS_F32, BARS_I8, BARS_I8_FLOATS,                    // the second bars launch: over f32 rows, over texel rows (the
                                                                                // integer matrix-core pass), over texel values as floats c / 65535;
-                BARS_SNAP, BARS_SNAP_FLOATS, BARS_SNAP_MODE } bars = NO_BARS;   // bars at texels of the pre-smoothing pass: over texel rows, over
+                BARS_SNAP, BARS_SNAP_FLOATS, BARS_SNAP_MODE,                    // bars at texels of the pre-smoothing pass: over texel rows, over
                                                                                // c / 65535, and sample_mode maximum / hybrid (glv_bars_mode_kernel)
+                BARS_COLUMNS } bars = NO_BARS;                                  // means of three such texels (glv_columns_kernel; rows c / 65535)
     int variant = 0, grid = 0;                  // the frame kernel's configuration and workgroups (FFT chains)
     glv::FrameClass cls = glv::FC_PLAIN;        // ... and its class
     unsigned ops = 0;                           // what the first kernel runs (FrameArgs::ops)
@@ -1019,6 +1051,7 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, float* d
     } else pl.rows = pl.out ? pl.out : b->d_grav;           // no rows out: a chain that ends in gravity, whose state is its output
     // many bars of texel rows: the integer matrix-core pass -- on the GL_R16 chain's texels, or on the texel values of the GL passes
     if (!(ops & GLV_OP_BARS) || pl.fused_bars) pl.bars = ChainPlan::NO_BARS;
+    else if (snap && b->columns()) pl.bars = ChainPlan::BARS_COLUMNS;
     else if (snap) pl.bars = b->p.sample_mode != GLV_SAMPLE_AVERAGE ? ChainPlan::BARS_SNAP_MODE : pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_FLOATS;
     else if (b->p.bars >= glv::kBarSeqMin && b->bars_i8() && (pl.route == ChainPlan::GL_FUSED || (gl_passes && !(ops & GLV_OP_SMOOTH))))
         pl.bars = pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_I8 : ChainPlan::BARS_I8_FLOATS;
@@ -1036,7 +1069,7 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, float* d
     // GLV_OP_BARS_ONLY: ... and what they do not sample is not computed, nor is its state kept -- the GL_R16 chain, and a float chain with
     // the bars fused (check_ops vetted the call)
     if (b->live_bins() != 0 && (pl.route == ChainPlan::GL_FUSED || pl.fused_bars)) pl.live_points = b->live_bins() / 2u;
-    pl.cls = glv::frame_class(pl.route == ChainPlan::GL_FUSED, pl.fused_bars, pl.live_points != 0, pl.ops, snap);
+    pl.cls = glv::frame_class(pl.route == ChainPlan::GL_FUSED, pl.fused_bars, pl.live_points != 0, pl.ops, snap, snap && b->columns());
     return GLV_OK;
 }
 
@@ -1049,6 +1082,9 @@ int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, uint32_t 
         e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w, st, r16, &rt);
     } else if (pl.bars == ChainPlan::BARS_SNAP || pl.bars == ChainPlan::BARS_SNAP_FLOATS) {
         e = glv::launch_bars_snap(pl.rows, pl.bars == ChainPlan::BARS_SNAP_FLOATS, d_bars, units, b->p.n, b->p.bars, b->d_snap_desc, b->d_snap_w, st, r16);
+    } else if (pl.bars == ChainPlan::BARS_COLUMNS) {
+        e = glv::launch_columns(pl.rows, d_bars, units, b->p.n, (uint32_t) b->snap_tex.size(), b->p.bars, b->col_nsteps, b->d_col_items, b->d_snap_desc,
+                                reinterpret_cast<const float*>(b->d_snap_w), b->d_col_map, b->p.sample_mode, shape_hybrid(b->p), st);
     } else if (pl.bars == ChainPlan::BARS_SNAP_MODE) {
         const glv::BarRowsTables rt = b->snap_rows_tables();
         e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, 0, nullptr, b->d_snap_desc, nullptr, st, r16, &rt);
@@ -1084,7 +1120,7 @@ int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, 
     if (pl.fused_bars && (ops & GLV_OP_BARS) && b->snapped()) {
         a.bar_desc = b->d_snap_desc; a.bar_items = b->d_snap_fitems[pl.variant]; a.bar_nsteps = b->snap_fnsteps[pl.variant];
         a.bar_w = reinterpret_cast<const float*>(b->d_snap_w);     // (the uint32 weights W' travel as the bits of the float weights; kernel class FC_GL16_SNAP*)
-        a.bars = b->p.bars; a.bars_out = d_out;
+        a.bars = b->p.bars; a.bars_out = d_out; a.col_map = b->d_col_map;
     } else if (pl.fused_bars) {
         a.bar_desc = b->d_bar_desc; a.bar_items = b->d_bar_fitems[pl.variant]; a.bar_nsteps = b->bar_fnsteps[pl.variant]; a.bar_w = b->d_bar_w;
         a.bars = b->p.bars; a.bars_out = d_out;
@@ -1301,6 +1337,7 @@ int glv_batch_destroy(glv_batch* b) {
     if (b->d_bar_mblocks) (void) hipFree(b->d_bar_mblocks);
     if (b->d_bar_mw) (void) hipFree(b->d_bar_mw);
     drop_snap_tables(b);
+    if (b->d_col_map) (void) hipFree(b->d_col_map);
     for (hipEvent_t e : b->ev) (void) hipEventDestroy(e);
     delete b;
     return GLV_OK;
@@ -1429,7 +1466,7 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
     if (b->p.bars == 0 || b->p.bars > b->p.n) return fail(GLV_ERR_INVALID, "bars=%u out of range", b->p.bars);
     HIP_TRY(hipSetDevice(b->device));
     if (!b->d_bar_desc) return fail(GLV_ERR_STATE, "the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created)");
-    if (b->snapped()) return fail(GLV_ERR_STATE, "glv_batch_bars takes float spectra, not a GL chain's texels: refused while bar texels are set (glv_batch_set_bar_texels)");
+    if (b->snapped()) return fail(GLV_ERR_STATE, "glv_batch_bars takes float spectra, not a GL chain's texels: refused while bar texels or column texels are set (glv_batch_set_bar_texels / glv_batch_set_column_texels)");
     const glv::BarRowsTables rt = b->rows_tables();
     hipError_t e = glv::launch_bars(d_spec, d_bars, (size_t) b->streams * 2, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w,
                                     (hipStream_t) hip_stream, false, &rt);
@@ -1437,35 +1474,66 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
     return GLV_OK;
 }
 
-int glv_batch_set_bar_texels(glv_batch* b, const uint32_t* texels, uint32_t count) {
+// glv_batch_set_bar_texels (width 1) and glv_batch_set_column_texels (width 3: left, middle, right) share everything but the table's shape
+static int set_snap_texels(glv_batch* b, const uint32_t* texels, uint32_t count, uint32_t width) {
+    const bool cols = width == 3;
+    const char* what = cols ? "column texels" : "bar texels";
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     HIP_TRY(hipSetDevice(b->device));
     // the tables are replaced in place: every kernel already queued on the device must have read them first (as glv_batch_set_params)
     HIP_TRY(hipDeviceSynchronize());
     if (texels == nullptr || count == 0) {                 // off: the unsnapped tables, untouched meanwhile, serve again
+        if (b->snapped() && b->columns() != cols) return GLV_OK;      // (the other kind of table is set: this kind is off already)
         drop_snap_tables(b);
-        b->snap_tex.clear();
+        b->snap_tex.clear(); b->col_tex.clear();
+        if (b->d_col_map) { (void) hipFree(b->d_col_map); b->d_col_map = nullptr; }
         b->update_live_bins();
         return GLV_OK;
     }
+    if (b->snapped() && b->columns() != cols)
+        return fail(GLV_ERR_STATE, "%s: %s are set on this batch -- the two tables exclude each other, clear the other one first", what, cols ? "bar texels" : "column texels");
     if (!(b->ops_mask & GLV_OP_BARS) || !b->d_bar_desc)
-        return fail(GLV_ERR_STATE, "bar texels: the batch was created without GLV_OP_BARS (or has no bar tables)");
+        return fail(GLV_ERR_STATE, "%s: the batch was created without GLV_OP_BARS (or has no bar tables)", what);
     if (b->p.gl_storage == 0)
-        return fail(GLV_ERR_STATE, "bar texels: gl_storage 0 -- a float chain has no pre-smoothed texture to sample");
-    if (count != b->p.bars) return fail(GLV_ERR_INVALID, "bar texels: %u entries for bars=%u", count, b->p.bars);
-    for (uint32_t k = 0; k < count; ++k)
-        if (texels[k] >= b->p.n) return fail(GLV_ERR_INVALID, "bar texels: t[%u] = %u is not a texel of the n=%u pass", k, texels[k], b->p.n);
+        return fail(GLV_ERR_STATE, "%s: gl_storage 0 -- a float chain has no pre-smoothed texture to sample", what);
+    if (count != b->p.bars) return fail(GLV_ERR_INVALID, "%s: %u entries for bars=%u", what, count, b->p.bars);
+    for (uint32_t k = 0; k < count * width; ++k)
+        if (texels[k] >= b->p.n) return fail(GLV_ERR_INVALID, "%s: t[%u] = %u is not a texel of the n=%u pass", what, k, texels[k], b->p.n);
+    std::vector<uint32_t> tex(texels, texels + (size_t) count * width);
+    std::vector<glv::ColumnMap> map;
+    if (cols) {                                            // the distinct texels, sorted, and where each column's three sit among them
+        std::sort(tex.begin(), tex.end());
+        tex.erase(std::unique(tex.begin(), tex.end()), tex.end());
+        // glv_columns_kernel keeps them (and a dump slot) as 16-bit values in the 64 KiB of LDS a launch may ask for without an attribute
+        if (tex.size() > 32766u) return fail(GLV_ERR_INVALID, "column texels: %zu distinct texels, at most 32766", tex.size());
+        map.resize(count);
+        for (uint32_t x = 0; x < count; ++x) {
+            auto at = [&](uint32_t t) { return (uint16_t) (std::lower_bound(tex.begin(), tex.end(), t) - tex.begin()); };
+            map[x] = glv::ColumnMap{at(texels[3 * x]), at(texels[3 * x + 1]), at(texels[3 * x + 2]), 0};
+        }
+    }
     const uint32_t live_before = b->live_bins();
     const std::vector<uint32_t> before = b->snap_tex;
-    int rc = build_snap_tables(b, std::vector<uint32_t>(texels, texels + count));
+    int rc = build_snap_tables(b, tex, cols);
     // (as glv_batch_set_params: a GLV_OP_BARS_ONLY batch that ran its live class cannot start sampling beyond the bins it kept)
     if (rc == GLV_OK && b->ran_live && b->live_bins() != live_before) {
         if (before.empty()) { drop_snap_tables(b); b->snap_tex.clear(); b->update_live_bins(); }
-        else (void) build_snap_tables(b, before);
-        rc = fail(GLV_ERR_STATE, "bar texels: these taps reach beyond the live bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first");
+        else (void) build_snap_tables(b, before, cols);
+        rc = fail(GLV_ERR_STATE, "%s: these taps reach beyond the live bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first", what);
+    }
+    if (rc == GLV_OK && cols) {
+        glv::ColumnMap* d_map = nullptr;
+        HIP_TRY(hipMalloc(&d_map, sizeof(glv::ColumnMap) * map.size()));
+        hipError_t e = hipMemcpy(d_map, map.data(), sizeof(glv::ColumnMap) * map.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void) hipFree(d_map); HIP_TRY(e); }
+        if (b->d_col_map) (void) hipFree(b->d_col_map);
+        b->d_col_map = d_map;
+        b->col_tex.assign(texels, texels + (size_t) count * 3);
     }
     return rc;
 }
+int glv_batch_set_bar_texels(glv_batch* b, const uint32_t* texels, uint32_t count) { return set_snap_texels(b, texels, count, 1); }
+int glv_batch_set_column_texels(glv_batch* b, const uint32_t* texels, uint32_t count) { return set_snap_texels(b, texels, count, 3); }
 
 int glv_prelude_bufscale(int device, const float* d_in, float* d_out, size_t rows, uint32_t n_out, uint32_t k, void* hip_stream) {
     if (!d_in || !d_out) return fail(GLV_ERR_INVALID, "NULL device pointer");

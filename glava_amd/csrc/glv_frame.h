@@ -39,6 +39,8 @@ constexpr uint32_t kBarModeUnroll = 4;
 // completes, or `bars` (a dump slot) when it does not, keep = 0.0f when the chunk opens a bar (the running total
 // restarts), 1.0f otherwise.
 struct alignas(16) BarItem { uint32_t w_byte, tex_byte, res; float keep; };
+// One column of glv_batch_set_column_texels: where its left, middle and right texel sit in the list of distinct texels (one 8-byte load)
+struct alignas(8) ColumnMap { uint16_t l, m, r, pad; };
 // Many bars (>= 256; glv_tables.h make_bar_mtiles): one tile of 32 consecutive bars -- first bin, pairs of bins, where its 64
 // weights per pair start -- and one round of glv_bars_rows_kernel: tiles [k0, k1) whose bins [origin, end) sit in the LDS ring.
 struct alignas(16) BarTile { uint32_t k0, k1, origin, end; };
@@ -71,17 +73,21 @@ enum FrameClass : int {
     FC_GL16_SNAP = 10,       // FC_GL16_BARS / FC_GL16_BARS_LIVE with the bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels: exact
     FC_GL16_SNAP_LIVE = 11,  //   integer sums, glv_frame.h bar_snap_*).  Own classes, not a run-time flag: the flag cost the unsnapped live class
                              //   1.3 % (68.2 vs 69.1 M frames/s, N = 4096, 64 K streams, same box alternating: profiles/r07/snapped_bars.txt)
+    FC_GL16_COLS = 12,       // FC_GL16_SNAP / FC_GL16_SNAP_LIVE whose snapped texels stay in LDS, as 16-bit values; lane x then stores the mean of three
+    FC_GL16_COLS_LIVE = 13,  //   of them: column x of the graph module (glv_batch_set_column_texels, column_mean).  Own classes for the same reason
 };
-constexpr int kFrameClasses = 12;
-GLV_HD constexpr bool fc_snap(int c) { return c == FC_GL16_SNAP || c == FC_GL16_SNAP_LIVE; }
+constexpr int kFrameClasses = 14;
+GLV_HD constexpr bool fc_cols(int c) { return c == FC_GL16_COLS || c == FC_GL16_COLS_LIVE; }
+GLV_HD constexpr bool fc_snap(int c) { return c == FC_GL16_SNAP || c == FC_GL16_SNAP_LIVE || fc_cols(c); }
 GLV_HD constexpr bool fc_fused_bars(int c) { return c == FC_STATE_BARS || c == FC_GL16_BARS || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE || fc_snap(c); }
 GLV_HD constexpr bool fc_gl16(int c) { return c == FC_GL16 || c == FC_GL16_BARS || c == FC_GL16_LIVE || c == FC_GL16_BARS_LIVE || fc_snap(c); }
-GLV_HD constexpr bool fc_live(int c) { return c == FC_GL16_LIVE || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE || c == FC_GL16_SNAP_LIVE; }
+GLV_HD constexpr bool fc_live(int c) { return c == FC_GL16_LIVE || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE || c == FC_GL16_SNAP_LIVE || c == FC_GL16_COLS_LIVE; }
 GLV_HD constexpr bool fc_has_state(int c) { return c != FC_PLAIN && c != FC_R16; }
 GLV_HD constexpr bool fc_texel_out(int c) { return c == FC_R16 || c == FC_STATE_R16; }     // rows out as uint16 texels, always
 // the class of a launch: the GL_R16 chain (gl_storage 1), the bars fused, the live blocks only (the float chains have a live class with the
 // bars fused only), else the ops the kernel sees (state: OP_GRAVITY / OP_AVERAGE; texel rows: OP_R16)
-GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, uint32_t ops, bool snap = false) {
+GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, uint32_t ops, bool snap = false, bool cols = false) {
+    if (gl16 && fused_bars && snap && cols) return live ? FC_GL16_COLS_LIVE : FC_GL16_COLS;
     if (gl16 && fused_bars && snap) return live ? FC_GL16_SNAP_LIVE : FC_GL16_SNAP;
     if (gl16) return fused_bars ? (live ? FC_GL16_BARS_LIVE : FC_GL16_BARS) : (live ? FC_GL16_LIVE : FC_GL16);
     if (fused_bars) return live ? FC_STATE_BARS_LIVE : FC_STATE_BARS;
@@ -136,6 +142,8 @@ struct FrameArgs {
     uint32_t bars;
     uint32_t bar_nsteps;        // multiple of bar_batch_of(log2 nn)
                                 // (kernel classes FC_GL16_SNAP*: bar_w holds the uint32 weights W' of bar_snap_lane_sum as float bits)
+    const ColumnMap* col_map;   // kernel classes FC_GL16_COLS* (glv_batch_set_column_texels): [bars] columns, bars_out float [units][bars]; the work
+                                // lists cover the DISTINCT texels the columns read and BarItem::res indexes those
 };
 
 // ---- GLV_OP_BARS arithmetic (smooth.glsl:25-40; tex clamped to [0,1] like the GL_R16 texture the
@@ -259,6 +267,15 @@ GLV_HD uint64_t bar_snap_lane_sum(const BarTaps& s) {
 // form ldexp((double) T, -31) / 65535 (which the caller divides by the bar's weight_sum, 1 -- or NaN for a bar whose weights sum to 0)
 GLV_HD uint32_t bar_snap_texel(uint64_t total) { return (uint32_t) ((total + (1ull << 30)) >> 31); }
 GLV_HD float bar_snap_float(uint64_t total) { return (float) (__builtin_ldexp((double) total, -31) / 65535.0); }
+// ---- columns: means of three texels of the pre-smoothing pass (glv_batch_set_column_texels) --------------------------------------------------
+// The graph module's smooth_audio_adj with setsmoothpass true (util/smooth.glsl:67-73): three texelFetch results -- GL_R16 texels c read back
+// as c / 65535 (unorm16_to_float) -- added left to right and divided by 3.0F: two IEEE additions and a true division, each rounded on its own
+// (every translation unit is compiled with -ffp-contract=off; no reciprocal).  The texels are the snapped bars' integer results.
+GLV_HD float column_mean(uint32_t cl, uint32_t cm, uint32_t cr) {
+    const float lm = unorm16_to_float(cl) + unorm16_to_float(cm);
+    const float lmr = lm + unorm16_to_float(cr);
+    return lmr / 3.0f;
+}
 
 #if defined(__HIPCC__)
 // sum over each group of GL = 2 / 4 / 8 lanes (aligned inside a DPP row), result in every lane of the group: VALU-speed cross-lane

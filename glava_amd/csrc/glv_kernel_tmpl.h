@@ -313,7 +313,7 @@ glv_frame_kernel(const FrameArgs a) {
     };
     // FUSED_BARS: lane k of a slot stores bar k (and k + T, ... when bars > T): the first one's weight sum stays in a register
     float bar_wsum = 1.0f;
-    if constexpr (FUSED_BARS) { if ((uint32_t) tid < a.bars) bar_wsum = a.bar_desc[tid].weight_sum; }
+    if constexpr (FUSED_BARS && !fc_cols(STATEFUL)) { if ((uint32_t) tid < a.bars) bar_wsum = a.bar_desc[tid].weight_sum; }
     // the epilogue of one row; every lane of the workgroup calls it (barriers inside when FUSED_BARS)
     auto finish_row = [&](const cf (&v)[E], size_t row, int tid, bool active) {
         if constexpr (FUSED_BARS) {
@@ -334,6 +334,9 @@ glv_frame_kernel(const FrameArgs a) {
             float* lres = lrow + N;                                       // XREGION has NN/E points (2T floats) of slack: bars + 1 <= 2T (glv_api.cpp bar_fusable)
             static_assert(2 * T >= 64, "the chunk reads of bar_item_load stay inside the slot's region");
             constexpr bool snap = fc_snap(STATEFUL);
+            // columns (glv_batch_set_column_texels): the snapped loop over the DISTINCT texels the columns read, kept as 16-bit texels -- 2 bytes
+            // each in the same slack, (texels + 1) <= 4T -- and after the barrier lane x stores the mean of column x's three (column_mean)
+            constexpr bool cols = fc_cols(STATEFUL);
             if (active && snap) {
                 // bars at texels of the pre-smoothing pass (glv_frame.h bar_snap_lane_sum): the same work lists, exact 64-bit integer sums, and
                 // each step's result is already the bar's -- texel or float bits -- so the slack behind the row takes 4 bytes per bar as above
@@ -358,7 +361,8 @@ glv_frame_kernel(const FrameArgs a) {
                     for (int b = 0; b < BB; ++b) {
                         const uint64_t chunk_sum = group_sum64<GL>(bar_snap_lane_sum(tp[b]));
                         total = it[b].keep != 0.0f ? total + chunk_sum : chunk_sum;
-                        if (sub == 0) lout[it[b].res] = r16 ? bar_snap_texel(total) : __builtin_bit_cast(uint32_t, bar_snap_float(total));
+                        if constexpr (cols) { if (sub == 0) reinterpret_cast<uint16_t*>(lres)[it[b].res] = (uint16_t) bar_snap_texel(total); }
+                        else if (sub == 0) lout[it[b].res] = r16 ? bar_snap_texel(total) : __builtin_bit_cast(uint32_t, bar_snap_float(total));
                     }
 #pragma unroll
                     for (int b = 0; b < BB; ++b) it[b] = nx[b];
@@ -396,6 +400,16 @@ glv_frame_kernel(const FrameArgs a) {
                 }
             }
             sy.sync();
+            if constexpr (cols) {
+                if (active) {
+                    const uint16_t* ltex = reinterpret_cast<const uint16_t*>(lres);
+                    float* co = a.bars_out + row * a.bars;
+                    for (uint32_t x = (uint32_t) tid; x < a.bars; x += T) {
+                        const ColumnMap m = a.col_map[x];
+                        co[x] = column_mean(ltex[m.l], ltex[m.m], ltex[m.r]);
+                    }
+                }
+            } else
             if (active) {
                 if (GL16 && a.bars_r16 && snap) {          // snapped texels: the integer results as they are
                     uint16_t* bo = reinterpret_cast<uint16_t*>(a.bars_out) + row * a.bars;
@@ -636,6 +650,8 @@ hipError_t launch_variant(FrameClass cls, const FrameArgs& a, int grid, hipStrea
     };
     switch (cls) {     // (in the order of the kernels in the code object)
         case FC_GL16_LIVE:       return launch_class(std::integral_constant<int, FC_GL16_LIVE>{});
+        case FC_GL16_COLS_LIVE:  return launch_class(std::integral_constant<int, FC_GL16_COLS_LIVE>{});
+        case FC_GL16_COLS:       return launch_class(std::integral_constant<int, FC_GL16_COLS>{});
         case FC_GL16_SNAP_LIVE:  return launch_class(std::integral_constant<int, FC_GL16_SNAP_LIVE>{});
         case FC_GL16_SNAP:       return launch_class(std::integral_constant<int, FC_GL16_SNAP>{});
         case FC_GL16_BARS_LIVE:  return launch_class(std::integral_constant<int, FC_GL16_BARS_LIVE>{});

@@ -65,6 +65,10 @@ hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt);     // functio
 // bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels) over texel rows: uint16, or floats c / 65535 (rows_f32); one lane per bar and row
 hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const uint32_t* wi,
                             hipStream_t st, bool r16);
+// columns = means of three texels of the pre-smoothing pass (glv_batch_set_column_texels) over a GL chain's rows as floats c / 65535: ntex distinct texels
+// (desc, tap_w: W' as float bits for mode 0 with work lists `items` for 256 / bar_lanes_of(n) groups; float weights in tap order for modes 1 / 2), cols columns
+hipError_t launch_columns(const float* rows, float* cols_out, size_t nrows, uint32_t n, uint32_t ntex, uint32_t cols, uint32_t nsteps, const BarItem* items,
+                          const BarDesc* desc, const float* tap_w, const ColumnMap* map, uint32_t mode, float hybrid_weight, hipStream_t st);
 hipError_t launch_ring_planar(const void* ring, int is_f32, uint32_t n, uint32_t rot, int mono, size_t streams, float* out, hipStream_t st);
 hipError_t launch_unpack(const int16_t* pcm, size_t frames, int mono, float* l, float* r, hipStream_t st);
 

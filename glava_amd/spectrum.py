@@ -96,6 +96,8 @@ def lib() -> C.CDLL:
         L.glv_batch_bars.argtypes = [vp, vp, vp, vp]
         if hasattr(L, "glv_batch_set_bar_texels"):      # (added within ABI 7: callers detect it by the symbol)
             L.glv_batch_set_bar_texels.argtypes = [vp, vp, C.c_uint32]
+        if hasattr(L, "glv_batch_set_column_texels"):   # (likewise)
+            L.glv_batch_set_column_texels.argtypes = [vp, vp, C.c_uint32]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -247,6 +249,19 @@ class Batch:
             raise ValueError("texels: a 1-d list of non-negative 32-bit indices")
         t = t.astype(np.uint32)
         _check(lib().glv_batch_set_bar_texels(self._h, t.ctypes.data_as(C.c_void_p), len(t)))
+
+    def set_column_texels(self, table) -> None:
+        """GLV_OP_BARS as the graph module's columns (glv_batch_set_column_texels): column x = the float mean of texels
+        table[x] = (left, middle, right) of the pre-smoothing pass, (T(l) + T(m) + T(r)) / 3 in the shader's float order;
+        None / empty turns it off.  glava_amd.bar_positions.graph_column_texels computes the table of a window width."""
+        if table is None or len(table) == 0:
+            _check(lib().glv_batch_set_column_texels(self._h, None, 0))
+            return
+        t = np.ascontiguousarray(np.asarray(table, dtype=np.int64))
+        if t.ndim != 2 or t.shape[1] != 3 or (t < 0).any() or (t >= 1 << 32).any():
+            raise ValueError("table: [count][3] non-negative 32-bit indices (left, middle, right)")
+        t = np.ascontiguousarray(t.astype(np.uint32))
+        _check(lib().glv_batch_set_column_texels(self._h, t.ctypes.data_as(C.c_void_p), t.shape[0]))
 
     def reset(self) -> None:
         _check(lib().glv_batch_reset(self._h))

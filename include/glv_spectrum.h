@@ -25,7 +25,8 @@ extern "C" {
                                   6 (round 6): + GLV_OP_BARS_ONLY, glv_batch_live_bins, glv_batch_bars_arithmetic, glv_batch_tune_placement; GLV_OP_R16 in a creation mask is a hint
                                   7 (round 6): glv_params grew smooth_audio()'s shape -- round_formula, sample_mode, sample_hybrid_weight, sample_scale, sample_range
                                                (appended; all-zero == the shipped shape, so a caller that zero-fills the tail keeps ABI 6's results); GLV_BARS_F32_SEQ
-                                  7, added without a version change: glv_batch_set_bar_texels (bars at texels of the pre-smoothing pass; detect it by the symbol) */
+                                  7, added without a version change: glv_batch_set_bar_texels (bars at texels of the pre-smoothing pass; detect it by the symbol),
+                                               glv_batch_set_column_texels (the graph module's columns: means of three such texels; likewise) */
 
 /* status codes (0 = ok).  The reference has no error channel: it prints and calls
  * glava_abort() (glava/glava.h:17, glava/render.c passim); the in-tree shim maps any
@@ -363,6 +364,29 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
  * last bar then reaches smooth_audio()'s last bin); a smaller factor grows them to the snapped taps' reach -- refused on a GLV_OP_BARS_ONLY batch
  * that has already run its live class (glv_batch_reset first). */
 int glv_batch_set_bar_texels(glv_batch* b, const uint32_t* texels, uint32_t count);
+
+/* GLV_OP_BARS as the columns of the graph module: the float mean of THREE texels of the pre-smoothed texture per column, which is what graph/1.frag:87-88
+ * draws from with setsmoothpass true -- smooth_audio_adj (util/smooth.glsl:67-73) fetches at idx - pixel, idx, idx + pixel and returns (al + am + ar) / 3.0F.
+ * texels is [count][3]: left, middle, right (glava_amd.bar_positions.graph_column_texels computes the table of a window width).  Contract: with the table
+ * set, a GLV_OP_BARS call on a GL chain writes, for every row and column x,
+ *     out[row][x] == fdiv(fadd(fadd(T(l), T(m)), T(r)), 3.0f)   bit for bit, as floats,
+ * where T(t) is the float of GL_R16 texel c = the twin's texel t of that row: c / 65535 correctly rounded, what texelFetch returns.  The twin is the same
+ * batch with bars = n, bar_phase 0.5, GLV_OP_R16, in the arithmetic glv_batch_bars_arithmetic reports (GLV_BARS_I8_EXACT for sample_mode average,
+ * GLV_BARS_F32_SEQ for maximum / hybrid).  Plain IEEE float additions in that order and a true division by 3: no fused multiply-add, no reciprocal.
+ * Internally the table is a bar-texel table over the DISTINCT texels (neighbouring columns share them: 401 columns read 801 texels, not 1203) plus an
+ * index map.  In one launch where the transform kernel takes the bars (as glv_batch_set_bar_texels) and the distinct texels fit behind its row in LDS as
+ * 16-bit values -- (distinct + 1) <= 4 x the configuration's lanes per row, 511 texels at N = 4096 and 1023 at N = 16384 as shipped; else a second launch (glv_columns_kernel) over the
+ * chain's rows, which keeps a row's texels in LDS: no texel array in HBM either way.
+ *   texels == NULL or count == 0: off -- the batch behaves as before, bit for bit.  Synchronous, may allocate (like glv_batch_set_params).
+ *   Refused: count != bars, any entry >= n, more than 32766 distinct texels (GLV_ERR_INVALID); setting this table while bar texels are set, or bar texels
+ *   while this one is set (GLV_ERR_STATE: clear the other first); GLV_OP_R16 in a call while columns are set (GLV_ERR_STATE: a mean of three texels is not
+ *   a texel).  Every other refusal, the glv_batch_set_params / glv_batch_reset / glv_batch_destroy rules and the glv_batch_live_bins rule are those of
+ *   glv_batch_set_bar_texels.  Added within ABI 7 without a version change: detect it by the symbol.
+ * Measured (64 K streams, N = 4096, GLV_OP_BARS_ONLY, log_mode 1, one MI355X; profiles/r08/column_texels.txt) against the twin plus a gather-and-average of
+ * its texels: a 320-pixel window (321 texels, one launch) 1.61 ms against 2.09 ms; an 800-pixel window (801 texels, second launch) 4.08 ms against 3.23 ms;
+ * 1920 pixels (1921 texels) 8.23 ms against 5.95 ms.  So at N = 4096 the call pays where the columns fuse -- windows up to 510 pixels wide -- and from
+ * there on a caller is better served by the twin and its own gather; the second launch is kept for the contract (every table works), not for speed. */
+int glv_batch_set_column_texels(glv_batch* b, const uint32_t* texels /* [count][3]: left, middle, right */, uint32_t count);
 
 /* Kernel-time accounting for the roofline report: HIP events recorded on the caller's
  * stream around every launch between begin/end; returns accumulated milliseconds and the
