@@ -80,6 +80,35 @@ def graph_column_texels(n: int, screen_w: int) -> tuple[np.ndarray, np.ndarray, 
     return t.reshape(-1, 3), ties.reshape(-1, 3), beyond.reshape(-1, 3)
 
 
+def wave_column_texels(n: int, screen_w: int) -> tuple[np.ndarray, np.ndarray]:
+    """wave/1.frag:17-23 (gl_FragCoord at integer pixel centres, wave/1.frag:2): pixel x draws from
+    texture(audio_l, (gl_FragCoord.x + o) / screen.x), o in {-1, 0, 1}, on a GL_NEAREST / GL_REPEAT texture
+    (render.c:1714-1717; :514-517 for the upload texture when the pre-smoothing pass is off).  Returns ``(texels, edge)``
+    for x + o = -1 .. screen_w -- ``screen_w + 2`` entries, pixel x uses entries x, x + 1, x + 2 -- the table
+    ``Batch.set_bar_texels`` takes for GLV_OP_WAVE | GLV_OP_BARS.
+
+    The mapping is the one OpenGL 4.5 section 8.14 prescribes for NEAREST with REPEAT, in float32 as the shader computes
+    its coordinate: u = float(x + o) / float(screen_w), u' = u * n, texel = floor(u') mod n (Euclidean: -1 wraps to the top
+    end, screen_w to texel 0).  It is taken from the specification and is NOT checked against llvmpipe: the reference
+    harness under oracle/ only reads `optimize_fft` binds, so the wave module cannot be run through it.
+
+    ``edge`` flags the entries where an implementation's coordinate precision may legitimately pick the neighbouring
+    texel: u' within one float32 ulp of an integer.  One case is exempt: when (x + o) * n / screen_w IS that integer in
+    exact arithmetic, then (n a power of two) the odd part of screen_w divides x + o, the quotient u is a dyadic rational
+    that float32 -- and any binary fixed-point coordinate -- holds exactly, and scaling by n is exact too: every
+    implementation lands on the same texel boundary and floor() picks the same texel.  So screen_w == n (u' = x + o)
+    has no edges; a width with a large odd part (4097 against n = 4096) has."""
+    if screen_w < 1:
+        raise ValueError("screen_w must be at least 1")
+    xi = np.arange(-1, screen_w + 1, dtype=np.int64)
+    u = (xi.astype(F) / F(screen_w)).astype(F)
+    up = (u * F(n)).astype(F)
+    texels = np.mod(np.floor(up).astype(np.int64), n).astype(np.uint32)
+    near = np.abs(up - np.rint(up)) <= np.spacing(np.abs(up))
+    exact = (xi * n) % screen_w == 0
+    return texels, near & ~exact
+
+
 def circle_texels(n: int, theta, rotate: float = 3.14159265359 / 2, invert: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """circle/1.frag:34-46 for the angles ``theta`` (radians: what atan(dy, dx) hands the shader's apply_smooth):
     idx = theta + ROTATE (circle.glsl: PI / 2), folded at PI through mod(abs(idx), TWOPI), negated when INVERT > 0,

@@ -304,6 +304,7 @@ struct glv_batch {
     uint32_t rows = 0;           // channel rows the state arrays and the scratch rows were sized for (streams * 2; 1 for the single-stream drop-ins)
     bool single_row = false;
     bool unfused_bars = false;   // GLV_UNFUSED_BARS in the environment at creation (diagnostics: bars always as a second launch)
+    bool unfused_wave = false;   // GLV_UNFUSED_WAVE likewise: GLV_OP_WAVE | GLV_OP_BARS always as the waveform kernel + the bars kernel
     bool state16 = false;        // gl_storage == 1 at creation: d_grav / d_hist hold uint16 texels (2 bytes per value)
     float grav_g = 0.f; uint32_t grav_sub = 0; bool grav_int = false, grav_known = false;   // the gravity step on texels (glv_tables.h gravity_r16_integer_step)
     float* d_scratch = nullptr;  // [streams*2][n] spectra feeding GLV_OP_BARS
@@ -934,6 +935,8 @@ int batch_prepare(glv_batch* b) {
         bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
         for (int v = 0; v < glv::frame_variants(b->log_nn) && v < glv_batch::kMaxVariants; ++v) all_fused = all_fused && b->bar_fusable[v];
         if (!all_fused && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * b->p.n));
+        // GLV_OP_WAVE | GLV_OP_BARS in two launches: the waveform kernel's texels (or their floats) wait for the bars kernel in the same rows
+        if ((b->ops_mask & GLV_OP_WAVE) && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * b->p.n));
         if (int rc = ensure_snap_tables(b)) return rc;
         b->update_live_bins();
     }
@@ -964,6 +967,20 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
     const bool state_is_output = (ops & GLV_OP_GRAVITY) && !(ops & (GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_RAW));
     if (!d_out && !(state_is_output && !(ops & GLV_OP_BARS) && !b->state16))
         return fail(GLV_ERR_INVALID, "NULL output pointer (allowed only for f32-state chains ending in gravity, see glv_batch_gravity_state)");
+    if (ops & GLV_OP_WAVE) {
+        // the wave module's bind is the unpack, wrange and the upload and nothing else (wave/1.frag:7-9); with GLV_OP_BARS the pre-smoothing pass over it
+        if (ops & (GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_RAW | GLV_OP_WRANGE | GLV_OP_MAGNITUDE | GLV_OP_SMOOTH | GLV_OP_OUTPUT_IS_STATE))
+            return fail(GLV_ERR_INVALID, "GLV_OP_WAVE combines with GLV_OP_BARS and GLV_OP_R16 only (it includes wrange and is stateless; ops 0x%x)", ops);
+        if (ops & GLV_OP_BARS) {
+            if (b->p.gl_storage == 0)
+                return fail(GLV_ERR_STATE, "GLV_OP_WAVE | GLV_OP_BARS: gl_storage 0 -- a float chain has no texel rows for the pre-smoothing pass to sample");
+            if ((b->ops_mask & (GLV_OP_WAVE | GLV_OP_BARS)) != (unsigned) (GLV_OP_WAVE | GLV_OP_BARS))
+                return fail(GLV_ERR_STATE, "GLV_OP_WAVE | GLV_OP_BARS needs both bits in glv_batch_create's ops_mask (0x%x): the rows between its two launches are made at creation", b->ops_mask);
+        }
+        // (with or without bars: a batch whose bars are the graph module's columns is not the wave module's)
+        if (b->columns())
+            return fail(GLV_ERR_STATE, "GLV_OP_WAVE with column texels set (glv_batch_set_column_texels): the wave shader does not average three texels (wave/1.frag:17-23)");
+    }
     const unsigned stateful = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE);
     if (stateful & ~b->ops_mask)
         return fail(GLV_ERR_STATE, "ops 0x%x need state the batch was not created with (ops_mask 0x%x)", ops, b->ops_mask);
@@ -974,7 +991,7 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
     if ((ops & GLV_OP_WRANGE) && (ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "GLV_OP_WRANGE excludes GLV_OP_FFT");
     if ((ops & GLV_OP_RAW) && !(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "GLV_OP_RAW needs GLV_OP_FFT");
     if ((ops & GLV_OP_MAGNITUDE) && (ops & (GLV_OP_FFT | GLV_OP_WRANGE))) return fail(GLV_ERR_INVALID, "GLV_OP_MAGNITUDE excludes GLV_OP_FFT and GLV_OP_WRANGE");
-    if (!(ops & (GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_WRANGE | GLV_OP_SMOOTH | GLV_OP_MAGNITUDE | GLV_OP_R16))) return fail(GLV_ERR_INVALID, "empty ops");
+    if (!(ops & (GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_WRANGE | GLV_OP_SMOOTH | GLV_OP_MAGNITUDE | GLV_OP_R16 | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "empty ops");
     if ((ops & GLV_OP_R16) && (ops & (GLV_OP_RAW | GLV_OP_SMOOTH))) return fail(GLV_ERR_INVALID, "GLV_OP_R16 excludes GLV_OP_RAW and GLV_OP_SMOOTH");
     if ((ops & GLV_OP_R16) && !d_out) return fail(GLV_ERR_INVALID, "GLV_OP_R16 needs an output buffer");
     if ((ops & GLV_OP_OUTPUT_IS_STATE) && (!state_is_output || !d_out || (ops & (GLV_OP_BARS | GLV_OP_R16)) || b->p.gl_storage))
@@ -985,7 +1002,8 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
         return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
     if ((ops & GLV_OP_BARS) && b->snapped()) {
         // bars at texels of the pre-smoothing pass: the chain's rows must be what that pass samples -- a GL chain's texels, not smoothed
-        if (!(ops & GLV_OP_FFT) || !(gl_fused_chain(b, ops) || gl_passes_chain(b, ops)) || (ops & GLV_OP_SMOOTH))
+        // (... or the wave texture's: GLV_OP_WAVE | GLV_OP_BARS, vetted above)
+        if (!(ops & GLV_OP_WAVE) && (!(ops & GLV_OP_FFT) || !(gl_fused_chain(b, ops) || gl_passes_chain(b, ops)) || (ops & GLV_OP_SMOOTH)))
             return fail(GLV_ERR_STATE, "GLV_OP_BARS with bar texels set (glv_batch_set_bar_texels) needs a GL chain's texel rows: GLV_OP_FFT with gravity / average on "
                                        "gl_storage 1 or 2, without GLV_OP_SMOOTH (ops 0x%x)", ops);
         if (!snap_current(b)) return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
@@ -1005,6 +1023,7 @@ struct ChainPlan {
         FRAME,          // the frame kernel
         POST,           // operators on planar rows (no GLV_OP_FFT)
         COPY,           // smooth / bars only: on a copy of the input rows
+        WAVE,           // GLV_OP_WAVE: unpack, wrange, upload (glv_wave_kernel) -- with bars the integer pass straight from the frames, or two launches
     } route = FRAME;
     enum Bars { NO_BARS, BARS_F32, BARS_I8, BARS_I8_FLOATS,                    // the second bars launch: over f32 rows, over texel rows (the
                                                                                // integer matrix-core pass), over texel values as floats c / 65535;
@@ -1018,9 +1037,37 @@ struct ChainPlan {
     float* out = nullptr;                       // where the first kernel writes its rows (NULL: the state is the output, or only bars leave)
     float* rows = nullptr;                      // the finished rows: what the smooth pass and the second bars launch work on
     uint32_t out_limit = 0, live_points = 0;    // FrameArgs::out_limit / live_points
+    bool wave_fused = false;                    // WAVE: the bars in ONE launch (glv_bars_rows_i8_kernel parks texels made from the s16 frames)
+    bool wave_r16 = false;                      // WAVE: the waveform kernel writes texels (else their floats c / 65535)
+    uint32_t wave_limit = 0;                    // WAVE: samples of a row the waveform kernel produces (what the bars sample, or n)
 };
 
-int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, float* d_out, ChainPlan& pl) {
+// GLV_OP_WAVE (check_ops vetted the call).  Without bars: the waveform kernel into the caller's buffer.  With bars the pre-smoothing pass runs over the
+// upload's texels in the arithmetic of the GL_R16 chain's second launch: GLV_BARS_I8_EXACT straight from s16 frames / the s16 ring in one launch; every
+// other form -- f32 inputs, a ring rotated by a number of frames that is not a multiple of 8, maximum / hybrid, fewer than 256 bars, bar texels, no integer tables, the single-stream drop-in, GLV_UNFUSED_WAVE -- as
+// the waveform kernel into the scratch rows (texels where the bars kernel takes texels, their floats else; only what the bars sample), then the bars kernel.
+int plan_wave(glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float* d_out, ChainPlan& pl) {
+    pl.route = ChainPlan::WAVE; pl.ops = ops; pl.out = d_out; pl.bars = ChainPlan::NO_BARS;
+    pl.wave_r16 = (ops & GLV_OP_R16) != 0; pl.wave_limit = b->p.n;
+    if (!(ops & GLV_OP_BARS)) return GLV_OK;
+    const bool averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;
+    if (b->snapped()) pl.bars = averaging ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_MODE;
+    else if (averaging && b->p.bars >= glv::kBarSeqMin && b->bars_i8()) pl.bars = ChainPlan::BARS_I8;
+    else pl.bars = ChainPlan::BARS_F32;
+    // (the integer pass parks groups of 8 frames: a ring whose oldest frame is not at a multiple of 8 -- an update of a sample_sz / 4 that is not one -- would wrap inside a group)
+    pl.wave_fused = pl.bars == ChainPlan::BARS_I8 && (in_mode == glv::IN_S16_STEREO || in_mode == glv::IN_S16_RING) && (rot & 7u) == 0u && !b->unfused_wave && !b->single_row;
+    if (pl.wave_fused) return GLV_OK;
+    if (!b->d_scratch) return fail(GLV_ERR_STATE, "GLV_OP_WAVE | GLV_OP_BARS needs the internal rows: announce both bits in glv_batch_create's ops_mask");
+    pl.out = pl.rows = b->d_scratch;
+    pl.wave_r16 = pl.bars == ChainPlan::BARS_I8 || pl.bars == ChainPlan::BARS_SNAP;
+    // what the bars do not sample is not produced -- where the bars kernel never multiplies what lies beyond (integer weights of 0, taps, staged bins)
+    const uint32_t bins = b->snapped() ? b->snap_bins : b->bar_bins_needed;
+    if ((pl.bars != ChainPlan::BARS_F32 || !averaging) && bins != 0 && bins < b->p.n) pl.wave_limit = bins;
+    return GLV_OK;
+}
+
+int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t rot, float* d_out, ChainPlan& pl) {
+    if (ops & GLV_OP_WAVE) return plan_wave(b, in_mode, ops, rot, d_out, pl);
     const bool gl_passes = gl_passes_chain(b, ops);
     if (gl_fused_chain(b, ops)) pl.route = ChainPlan::GL_FUSED;
     else if (ops & GLV_OP_FFT) pl.route = gl_passes ? ChainPlan::GL_PASSES : ChainPlan::FRAME;
@@ -1094,6 +1141,25 @@ int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, uint32_t 
     }
     ++b->last_launches;
     return e == hipSuccess ? GLV_OK : fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
+}
+
+// Carries out a WAVE plan: one HIP-event window around its one or two launches; stream-ordered, nothing is allocated.
+int run_wave(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units, uint32_t rot, hipStream_t st) {
+    const bool mono = b->p.channels == 1;
+    if (int rc = timed_launch_begin(b, st)) return rc;
+    hipError_t e;
+    if (pl.wave_fused) {
+        const glv::BarIRowsTables irt = b->irows_tables();
+        e = glv::launch_bars_i8_pcm(d_in, rot, mono, d_out, units, b->p.n, b->p.bars, &irt, st, (ops & GLV_OP_R16) != 0);
+        b->kernel_name = "glv_bars_rows_i8_kernel";
+    } else {
+        e = glv::launch_wave(d_in, in_mode, mono, b->p.n, rot, units, pl.out, pl.wave_r16, pl.wave_limit, st);
+        b->kernel_name = "glv_wave_kernel";
+    }
+    ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    if (!pl.wave_fused) if (int rc = launch_bars_pass(b, pl, d_out, units, (ops & GLV_OP_R16) != 0, st)) return rc;
+    return timed_launch_end(b, st);
 }
 
 // Carries out a plan: the first kernel (and the GL passes), the batch's state bookkeeping, the smooth pass, the second bars launch --
@@ -1182,10 +1248,11 @@ int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned 
     b->last_launches = 0;
     HIP_TRY(hipSetDevice(b->device));
     ChainPlan pl;
-    if (int rc = plan_chain(b, in_mode, ops, units, d_out, pl)) return rc;
+    if (int rc = plan_chain(b, in_mode, ops, units, rot, d_out, pl)) return rc;
     if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
         return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
     if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+    if (pl.route == ChainPlan::WAVE) return run_wave(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
     return run_chain(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
 }
 
@@ -1213,6 +1280,7 @@ int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, 
     b->p = *p; b->streams = streams; b->ops_mask = ops_mask; b->device = device;
     b->rows = single_row ? 1u : streams * 2u; b->single_row = single_row;
     b->unfused_bars = std::getenv("GLV_UNFUSED_BARS") != nullptr;
+    b->unfused_wave = std::getenv("GLV_UNFUSED_WAVE") != nullptr;
     b->bar_i8_off = std::getenv("GLV_NO_BARS_I8") != nullptr;
     b->log_nn = log2_exact(p->n) - 1;
     hipDeviceProp_t prop;
@@ -1345,7 +1413,7 @@ int glv_batch_destroy(glv_batch* b) {
 
 int glv_batch_process_s16(glv_batch* b, const int16_t* d_pcm, float* d_out, unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "s16 input requires GLV_OP_FFT");
+    if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "s16 input requires GLV_OP_FFT or GLV_OP_WAVE");
     return process(b, d_pcm, glv::IN_S16_STEREO, d_out, ops, b->streams * 2, 0, (hipStream_t) hip_stream);
 }
 
@@ -1356,7 +1424,7 @@ int glv_batch_process_f32(glv_batch* b, const float* d_f32, float* d_out, unsign
 
 int glv_batch_process_f32_stereo(glv_batch* b, const float* d_pcm, float* d_out, unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "interleaved input requires GLV_OP_FFT");
+    if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "interleaved input requires GLV_OP_FFT or GLV_OP_WAVE");
     return process(b, d_pcm, glv::IN_F32_STEREO, d_out, ops, b->streams * 2, 0, (hipStream_t) hip_stream);
 }
 
@@ -1396,7 +1464,7 @@ static int ring_push(glv_batch* b, bool f32, const void* d_new, uint32_t new_fra
 int glv_batch_ring_update_s16(glv_batch* b, const int16_t* d_new, uint32_t new_frames, float* d_out, unsigned ops,
                               void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "ring mode requires GLV_OP_FFT (glv_batch_ring_append_s16 appends without transforming)");
+    if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "ring mode requires GLV_OP_FFT or GLV_OP_WAVE (glv_batch_ring_append_s16 appends without transforming)");
     hipStream_t st = (hipStream_t) hip_stream;
     HIP_TRY(hipSetDevice(b->device));
     if (int rc = check_ops(b, ops, d_out)) return rc;            // nothing is appended when the call cannot be processed
@@ -1409,7 +1477,7 @@ int glv_batch_ring_update_s16(glv_batch* b, const int16_t* d_new, uint32_t new_f
 
 int glv_batch_ring_update_f32(glv_batch* b, const float* d_new, uint32_t new_frames, float* d_out, unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "ring mode requires GLV_OP_FFT (glv_batch_ring_append_f32 appends without transforming)");
+    if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "ring mode requires GLV_OP_FFT or GLV_OP_WAVE (glv_batch_ring_append_f32 appends without transforming)");
     if (!d_new) return fail(GLV_ERR_INVALID, "d_new is NULL (the PulseAudio backend has no zero-fill path)");
     hipStream_t st = (hipStream_t) hip_stream;
     HIP_TRY(hipSetDevice(b->device));
@@ -1587,6 +1655,16 @@ uint64_t glv_batch_algorithmic_bytes(const glv_batch* b, unsigned ops, int input
     //     4N + 16N + 4N + 4N = 28N
     //   gl_storage 2 (pass by pass): the transform's f32 spectra are written and read back by the gravity / average pass (+16N)
     const uint64_t N = b->p.n, F = b->p.avg_frames;
+    if (ops & GLV_OP_WAVE) {
+        // GLV_OP_WAVE: the input bytes the result depends on + the output bytes.  Without bars every frame of the window (4N / 8N) and 4N texels or 8N
+        // floats; with bars the frames below the last tap of any bar, in whole 64s (the reach the bars kernels are handed: 0.288 N as shipped), and the
+        // bars.  The texel rows between the two launches of the unfused forms are traffic of the organisation and are not counted.
+        const uint64_t in_b = input_is_s16 ? 4 : 8, out_b = (ops & GLV_OP_R16) ? 4 : 8;
+        if (!(ops & GLV_OP_BARS)) return (in_b * N + out_b * N) * b->streams;
+        uint64_t reach = b->snapped() ? b->snap_bins : b->bar_bins_sampled;
+        if (reach == 0 || reach > N) reach = N;
+        return (in_b * reach + out_b * b->p.bars) * b->streams;
+    }
     const bool stateful = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
     //   GLV_OP_BARS_ONLY: state traffic is counted for the live bins L only -- the bins the bars sample, NOT the (larger) share of the row the kernel
     //   class keeps (FrameGeometry::live_points: an implementation granularity, its extra bytes are traffic above the algorithmic figure)
@@ -1814,7 +1892,7 @@ int glv_state_create(const glv_params* p, int device, glv_state** out) {
     glv_state* s = new (std::nothrow) glv_state();
     if (!s) return fail(GLV_ERR_NOMEM, "out of host memory");
     // (GL_R16 state -- the accel path of handle_audio, glv_gl_texture -- also announces the pre-smoothing pass: one scratch row)
-    const unsigned mask = GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_SMOOTH | (p && p->gl_storage == 1 && p->bars >= 1 && p->bars <= p->n ? (unsigned) GLV_OP_BARS : 0u);
+    const unsigned mask = GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_WAVE | (p && p->gl_storage == 1 && p->bars >= 1 && p->bars <= p->n ? (unsigned) GLV_OP_BARS : 0u);
     int rc = batch_create_rows(p, 1, mask, device, true, &s->b);
     if (rc == GLV_OK) {
         const char* mode = std::getenv("GLV_STAGING");
@@ -1958,6 +2036,46 @@ int glv_gl_texture(const glv_params* p, glv_state* s, const float* buf, int smoo
     HIP_TRY(hipSetDevice(b->device));
     // render.c:2230: no averaging pass with a single frame; the chain then ends in the gravity store
     const unsigned ops = GLV_OP_FFT | GLV_OP_GRAVITY | (p->avg_frames > 1 ? (unsigned) GLV_OP_AVERAGE : 0u) | (smooth_pass ? (unsigned) GLV_OP_BARS : 0u) | GLV_OP_R16;
+    const size_t in_bytes = sizeof(float) * p->n, out_bytes = sizeof(uint16_t) * p->n;
+    if (s->mapped) {
+        if (!s->h_tex) {
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_tex), out_bytes, hipHostMallocMapped));
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->d_tex), s->h_tex, 0));
+        }
+        std::memcpy(s->h_io, buf, in_bytes);
+        const int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), ops, 1, 0, nullptr);
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if (rc) return rc;
+        std::memcpy(texels, s->h_tex, out_bytes);
+        return GLV_OK;
+    }
+    if (!s->d_tex) HIP_TRY(hipMalloc(&s->d_tex, out_bytes));
+    HIP_TRY(hipMemcpyAsync(s->d_io, buf, in_bytes, hipMemcpyHostToDevice, nullptr));
+    if (int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), ops, 1, 0, nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(texels, s->d_tex, out_bytes, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return GLV_OK;
+}
+
+int glv_wave_texture(const glv_params* p, glv_state* s, const float* buf, int smooth_pass, uint16_t* texels) {
+    if (!s || !s->b) return fail(GLV_ERR_INVALID, "state is NULL");
+    if (!buf || !texels) return fail(GLV_ERR_INVALID, "NULL buffer");
+    if (int rc = validate(p)) return rc;
+    glv_batch* b = s->b;
+    if (p->n != b->p.n || p->avg_frames != b->p.avg_frames)
+        return fail(GLV_ERR_STATE, "params (n=%u, F=%u) do not match the state (n=%u, F=%u)", p->n, p->avg_frames, b->p.n, b->p.avg_frames);
+    if (smooth_pass && (p->gl_storage != 1 || !b->state16 || !(b->ops_mask & GLV_OP_BARS)))
+        return fail(GLV_ERR_STATE, "glv_wave_texture with the pre-smoothing pass needs a state created with gl_storage = 1 and bars = n (the pass samples GL_R16 texels)");
+    if (smooth_pass && p->bars != p->n)
+        return fail(GLV_ERR_INVALID, "glv_wave_texture with the pre-smoothing pass: bars must equal n (bar_phase 0.5: the pass's texel centres)");
+    if (!same_params(b->p, *p)) {
+        glv_params rest = *p;
+        rest.ur = b->p.ur; rest.gravity_step = b->p.gravity_step;
+        if (same_params(b->p, rest)) { b->p.ur = p->ur; b->p.gravity_step = p->gravity_step; update_gravity_step(b); }
+        else if (int rc = glv_batch_set_params(b, p)) return rc;
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    const unsigned ops = GLV_OP_WAVE | (smooth_pass ? (unsigned) GLV_OP_BARS : 0u) | GLV_OP_R16;
     const size_t in_bytes = sizeof(float) * p->n, out_bytes = sizeof(uint16_t) * p->n;
     if (s->mapped) {
         if (!s->h_tex) {

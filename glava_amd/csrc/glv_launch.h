@@ -61,7 +61,13 @@ struct BarIRowsTables {
     const BarTile* rounds; uint32_t nrounds, ring_bins;
 };
 hipError_t launch_bars_i8(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st, bool r16);
-hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt);     // function attributes of the kernels launch_bars_i8 would pick
+hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt);     // function attributes of the kernels launch_bars_i8 / launch_bars_i8_pcm would pick
+// the same pass straight from interleaved s16 frames (GLV_OP_WAVE | GLV_OP_BARS in one launch): pcm int16 [nrows / 2][n][2], row 2 s + c is channel c of
+// stream s; the kernel unpacks, applies wrange and quantises the frames it parks.  rot: index of the oldest frame (the device ring; 0 for frames)
+hipError_t launch_bars_i8_pcm(const void* pcm, uint32_t rot, bool mono, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st, bool r16);
+// GLV_OP_WAVE without bars / the first of its two launches (glv_wave_kernel): unpack -> wrange -> GL_R16 texels (r16) or their floats c / 65535, for the
+// first `limit` samples (a multiple of 8) of every row; out rows keep a pitch of n.  in_mode: glv_frame.h InMode; units: channel rows
+hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint32_t rot, size_t units, void* out, bool r16, uint32_t limit, hipStream_t st);
 // bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels) over texel rows: uint16, or floats c / 65535 (rows_f32); one lane per bar and row
 hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const uint32_t* wi,
                             hipStream_t st, bool r16);

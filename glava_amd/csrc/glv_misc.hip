@@ -79,6 +79,90 @@ __global__ void __launch_bounds__(256) glv_ring_planar_kernel(const void* __rest
     }
 }
 
+// ---- GLV_OP_WAVE: the wave module's bind (shaders/glava/wave/1.frag:7-9: window, wrange) ---------------
+// Per channel row: the backend's unpack (fifo.c:94-110 / pulse_input.c:155-178; mono: the mix into both rows), transform_wrange (render.c:773-781:
+// b += 1.0F; b /= 2.0F) and the GL_R16 upload (render.c:521-524), written as the texels c (R16) or as the floats c / 65535 texelFetch returns.
+// KIND 0 / 1: interleaved s16 / f32 frames -- one lane takes 8 frames of a stream (two 16-byte loads of s16, four of f32) and stores both channel
+// rows' 8 values (one 16-byte store of texels per row, two of floats): 4 n bytes in and 4 n (8 n) out per s16 stereo frame.  `rot` is the index of
+// the oldest frame of a device ring (0 for frames); a rotation that is not a multiple of 8 frames can wrap inside a group and takes the frames one
+// by one.  KIND 2: planar f32 rows, taken as they are (the lb / rb snapshot is already unpacked), 8 samples per lane.  Only the first `limit` samples
+// of a row (a multiple of 8) are produced -- in front of the bars kernel that is what the bars sample; out rows keep their pitch of n.
+typedef unsigned int glv_wave_u4 __attribute__((ext_vector_type(4)));
+template <int KIND, bool R16>
+__global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ in, void* __restrict__ out, size_t groups_total, uint32_t n, uint32_t limit,
+                                                       uint32_t rot, int mono) {
+    const uint32_t gpr = limit / 8u;                                     // groups of 8 samples per row (KIND 2) / per stream
+    auto emit = [&](size_t row, uint32_t t, const float (&x)[8]) {
+        uint32_t c[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float p0 = x[2 * q] + 1.0f, p1 = x[2 * q + 1] + 1.0f;  // render.c:777-778
+            c[q] = pack_unorm16(p0 / 2.0f, p1 / 2.0f);                   // render.c:521-524
+        }
+        if constexpr (R16) {
+            st<glv_wave_u4>(static_cast<uint16_t*>(out) + row * n, t * 2u, glv_wave_u4{c[0], c[1], c[2], c[3]});
+        } else {
+            BarW4 lo, hi;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                lo.w[2 * q] = unorm16_to_float(c[q] & 0xffffu); lo.w[2 * q + 1] = unorm16_to_float(c[q] >> 16);
+                hi.w[2 * q] = unorm16_to_float(c[2 + q] & 0xffffu); hi.w[2 * q + 1] = unorm16_to_float(c[2 + q] >> 16);
+            }
+            st<BarW4>(static_cast<float*>(out) + row * n, t * 4u, lo);
+            st<BarW4>(static_cast<float*>(out) + row * n, t * 4u + 16u, hi);
+        }
+    };
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < groups_total; i += (size_t) gridDim.x * blockDim.x) {
+        const size_t s = i / gpr;                                        // stream (KIND 0 / 1) or row (KIND 2)
+        const uint32_t t = (uint32_t) (i % gpr) * 8u;
+        if constexpr (KIND == 2) {
+            const float* src = static_cast<const float*>(in) + s * n;
+            const BarW4 a = ld<BarW4>(src, t * 4u), b = ld<BarW4>(src, t * 4u + 16u);
+            const float x[8] = {a.w[0], a.w[1], a.w[2], a.w[3], b.w[0], b.w[1], b.w[2], b.w[3]};
+            emit(s, t, x);
+        } else {
+            float l[8], r[8];
+            const bool whole = (rot & 7u) == 0u;                         // (uniform) bin and rot multiples of 8: the group does not wrap
+            const uint32_t pos = (t + rot) & (n - 1u);
+            if constexpr (KIND == 0) {
+                const uint32_t* src = static_cast<const uint32_t*>(in) + s * n;
+                uint32_t f[8];
+                if (whole) {
+                    const glv_wave_u4 a = ld<glv_wave_u4>(src, pos * 4u), b = ld<glv_wave_u4>(src, pos * 4u + 16u);
+                    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+                } else {
+#pragma unroll
+                    for (uint32_t q = 0; q < 8; ++q) f[q] = src[(t + q + rot) & (n - 1u)];
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int a = (int16_t) (f[q] & 0xffffu), b = (int16_t) (f[q] >> 16);
+                    if (mono) { l[q] = unpack_s16_mono(a, b); r[q] = l[q]; } else { l[q] = unpack_s16(a); r[q] = unpack_s16(b); }
+                }
+            } else {
+                const cf* src = static_cast<const cf*>(in) + s * n;
+                cf f[8];
+                if (whole) {
+#pragma unroll
+                    for (uint32_t q = 0; q < 4; ++q) {
+                        const BarW4 a = ld<BarW4>(src, pos * 8u + q * 16u);
+                        f[2 * q] = cf{a.w[0], a.w[1]}; f[2 * q + 1] = cf{a.w[2], a.w[3]};
+                    }
+                } else {
+#pragma unroll
+                    for (uint32_t q = 0; q < 8; ++q) f[q] = src[(t + q + rot) & (n - 1u)];
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    if (mono) { l[q] = (f[q].x + f[q].y) / 2; r[q] = l[q]; } else { l[q] = f[q].x; r[q] = f[q].y; }     // pulse_input.c:167
+                }
+            }
+            emit(2 * s, t, l);
+            emit(2 * s + 1, t, r);
+        }
+    }
+}
+
 // ---- rd_update prelude (glava/render.c:1765-1809) ------------------------------------------------
 // bufscale: mean of k consecutive samples, float accumulation in index order, one float division
 __global__ void __launch_bounds__(256) glv_bufscale_kernel(const float* __restrict__ in, float* __restrict__ out,
@@ -709,12 +793,22 @@ static hipError_t launch_bars_mode(const float* spec, void* bars_out, size_t nro
 typedef int glv_i4v __attribute__((ext_vector_type(4)));
 typedef int glv_i2v __attribute__((ext_vector_type(2)));
 typedef int glv_i16v __attribute__((ext_vector_type(16)));
-template <int S, int RB, bool F32IN, bool R16>
+// SRC: where a row's texels come from.  I8_TEXELS / I8_FLOATS: rows of a GL chain in HBM (uint16 texels / the floats c / 65535 of the pass-by-pass
+// chain).  I8_PCM_S16 (GLV_OP_WAVE | GLV_OP_BARS in one launch): interleaved s16 frames -- rows_in is int16 [nrows / 2][n][2], row 2 s + c is channel c
+// of stream s, `rot` the index of the oldest frame (the device ring; 0 for frames), `mono` the backend's mix (fifo.c:98-102) -- and fetch() makes the
+// wave module's upload texels on the way into LDS: unpack (fifo.c:94-110), wrange (render.c:773-781), GL_R16 quantisation (render.c:521-524).  No texel
+// array of the upload reaches HBM, and only the frames the ring windows cover are read.  An s16 fetch is two 16-byte loads like I8_FLOATS' (rot must
+// be a multiple of 8 frames, so that a group of 8 never wraps: launch_bars_i8_pcm refuses others); they are compiler-visible loads converted where they are fetched, so
+// the compiler's own wait for them sits in fetch() and the hand-counted vmcnt(6) of the weight stream stays correct (loads retire in order: more
+// loads behind a bank's requests only make that wait stricter).
+enum I8Source { I8_TEXELS = 0, I8_FLOATS = 1, I8_PCM_S16 = 2 };
+template <int S, int RB, int SRC, bool R16>
 __global__ void __launch_bounds__(64 * kRowsWaves, 2) glv_bars_rows_i8_kernel(const void* __restrict__ rows_in, void* __restrict__ bars_out, size_t nrows, uint32_t n,
                                                                               uint32_t bars, const BarTile* __restrict__ rounds, uint32_t nrounds, uint32_t rounds_per_wg,
                                                                               const BarMTile* __restrict__ tiles, const glv_i4v* __restrict__ wq,
-                                                                              const BarIFin* __restrict__ fin) {
+                                                                              const BarIFin* __restrict__ fin, uint32_t rot, uint32_t mono) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool F32IN = SRC == I8_FLOATS, PCM = SRC == I8_PCM_S16;
     static_assert(S % 32 == 0 && (RB == 64 || RB == 32), "16-bin chunks never straddle the ring's end and (S + 16) / 16 is odd; one or two row groups");
     extern __shared__ __attribute__((aligned(16))) char i8_lds[];       // [2 planes][RB rows][S + 16 bytes]
     constexpr uint32_t PITCH = S + 16, S16 = S / 16, G = RB / 32, CPI = 64 * kRowsWaves / RB;       // CPI: columns of 8 bins one sweep of the workgroup fetches
@@ -729,12 +823,28 @@ __global__ void __launch_bounds__(64 * kRowsWaves, 2) glv_bars_rows_i8_kernel(co
     if (t_begin >= t_end) return;
     const uint32_t frow = threadIdx.x % (uint32_t) RB, fcol = threadIdx.x / (uint32_t) RB;
     const size_t srow = row0 + (frow < R ? frow : R - 1);                 // (a partial row block repeats its last row; its stores are masked)
-    const char* src = static_cast<const char*>(rows_in) + srow * (size_t) n * (F32IN ? 4u : 2u);
+    const char* src = static_cast<const char*>(rows_in) + (PCM ? srow >> 1 : srow) * (size_t) n * (F32IN || PCM ? 4u : 2u);
+    const uint32_t ch_shift = PCM ? ((uint32_t) srow & 1u) * 16u : 0u;   // (PCM: the row's channel sits in this half of a frame's dword)
     struct Tex8 { uint32_t d[4]; };                                     // 8 texels, two per dword
     auto fetch = [&](uint32_t bin) -> Tex8 {
         Tex8 v;
         bin = bin + 8u <= n ? bin : n - 8u;                             // (a dummy request -- nothing new to park -- at the row's very end stays inside the row)
-        if constexpr (F32IN) {                                          // rows of floats c / 65535 (the pass-by-pass chain): back to the texels, exactly
+        if constexpr (PCM) {                                            // 8 stereo s16 frames from `rot` on: this row's channel (or the mix) -> (x + 1) / 2 -> texels
+            // (rot is a multiple of 8 frames, as bin is -- the host sends other rotations through the waveform kernel: a group never wraps)
+            uint32_t pos = (bin + rot) & (n - 1u);
+            pos = pos + 8u <= n ? pos : n - 8u;                         // defensive: bin and rot are multiples of 8, so this never fires -- but a request never leaves the row
+            const glv_i4v a = ld<glv_i4v>(src, pos * 4u), b = ld<glv_i4v>(src, pos * 4u + 16u);
+            const uint32_t f[8] = {(uint32_t) a.x, (uint32_t) a.y, (uint32_t) a.z, (uint32_t) a.w, (uint32_t) b.x, (uint32_t) b.y, (uint32_t) b.z, (uint32_t) b.w};
+            float y[8];
+#pragma unroll
+            for (uint32_t q = 0; q < 8; ++q) {
+                const float x = mono ? unpack_s16_mono((int) (int16_t) (f[q] & 0xffffu), (int) (int16_t) (f[q] >> 16)) : unpack_s16((int) (int16_t) ((f[q] >> ch_shift) & 0xffffu));
+                const float p = x + 1.0f;                               // render.c:777-778
+                y[q] = p / 2.0f;
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) v.d[q] = pack_unorm16(y[2 * q], y[2 * q + 1]);
+        } else if constexpr (F32IN) {                                   // rows of floats c / 65535 (the pass-by-pass chain): back to the texels, exactly
             const BarW4 a = ld<BarW4>(src, bin * 4u), b = ld<BarW4>(src, bin * 4u + 16u);
             v.d[0] = pack_unorm16(a.w[0], a.w[1]); v.d[1] = pack_unorm16(a.w[2], a.w[3]);
             v.d[2] = pack_unorm16(b.w[0], b.w[1]); v.d[3] = pack_unorm16(b.w[2], b.w[3]);
@@ -1013,6 +1123,23 @@ hipError_t launch_ring_planar(const void* ring, int is_f32, uint32_t n, uint32_t
     return hipGetLastError();
 }
 
+hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint32_t rot, size_t units, void* out, bool r16, uint32_t limit, hipStream_t st) {
+    if (limit == 0 || limit > n || (limit & 7u) || rot >= n) return hipErrorInvalidValue;
+    const bool planar = in_mode == IN_F32_PLANAR;
+    if (!planar && (units & 1u)) return hipErrorInvalidValue;           // interleaved frames: whole streams
+    const size_t total = (planar ? units : units / 2) * (limit / 8u);
+    if (total == 0) return hipSuccess;
+    const int grid = capped_grid(total, 256);
+    const int m = mono ? 1 : 0;
+#define GLV_WAVE_LAUNCH(KIND) \
+    do { if (r16) hipLaunchKernelGGL((glv_wave_kernel<KIND, true>), dim3(grid), dim3(256), 0, st, in, out, total, n, limit, rot, m); \
+         else hipLaunchKernelGGL((glv_wave_kernel<KIND, false>), dim3(grid), dim3(256), 0, st, in, out, total, n, limit, rot, m); } while (0)
+    if (planar) GLV_WAVE_LAUNCH(2);
+    else if (in_mode == IN_S16_STEREO || in_mode == IN_S16_RING) GLV_WAVE_LAUNCH(0);
+    else GLV_WAVE_LAUNCH(1);
+#undef GLV_WAVE_LAUNCH
+    return hipGetLastError();
+}
 hipError_t launch_bufscale(const float* in, float* out, size_t total_out, uint32_t k, hipStream_t st) {
     hipLaunchKernelGGL(glv_bufscale_kernel, dim3(capped_grid(total_out, 256)), dim3(256), 0, st, in, out, total_out, k);
     return hipGetLastError();
@@ -1110,15 +1237,15 @@ hipError_t prepare_bars_rows(uint32_t n, const BarRowsTables* rt) {
 
 // the i8 kernel for ring_bins in {160, 288, 448, 832} (64 rows per workgroup) or 1600 (32 rows: the bars of n = 32768); nrows == 0: the
 // dynamic-LDS attribute only
-template <int S, int RB, bool F32IN, bool R16>
-static hipError_t launch_bars_i8_one(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st) {
+template <int S, int RB, int SRC, bool R16>
+static hipError_t launch_bars_i8_one(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st, uint32_t rot = 0, uint32_t mono = 0) {
     const size_t lds = (size_t) 2 * RB * (S + 16);
     static std::atomic<bool> done[64] = {};
     if (lds > 64 * 1024) {
         int dev = 0;
         (void) hipGetDevice(&dev);
         if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(glv_bars_rows_i8_kernel<S, RB, F32IN, R16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(glv_bars_rows_i8_kernel<S, RB, SRC, R16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
             if (e != hipSuccess) return e;
             if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
         }
@@ -1133,33 +1260,40 @@ static hipError_t launch_bars_i8_one(const void* rows, void* bars_out, size_t nr
     if (yb > rt.nrounds) yb = rt.nrounds;
     const uint32_t rpw = (rt.nrounds + yb - 1) / yb;
     yb = (rt.nrounds + rpw - 1) / rpw;
-    hipLaunchKernelGGL((glv_bars_rows_i8_kernel<S, RB, F32IN, R16>), dim3(xb, yb), dim3(64 * kRowsWaves), lds, st, rows, bars_out, nrows, n, bars, rt.rounds, rt.nrounds, rpw,
-                       rt.tiles, reinterpret_cast<const glv_i4v*>(rt.wq), rt.fin);
+    hipLaunchKernelGGL((glv_bars_rows_i8_kernel<S, RB, SRC, R16>), dim3(xb, yb), dim3(64 * kRowsWaves), lds, st, rows, bars_out, nrows, n, bars, rt.rounds, rt.nrounds, rpw,
+                       rt.tiles, reinterpret_cast<const glv_i4v*>(rt.wq), rt.fin, rot, mono);
     return hipGetLastError();
 }
-template <bool F32IN, bool R16>
-static hipError_t launch_bars_i8_in(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st) {
+template <int SRC, bool R16>
+static hipError_t launch_bars_i8_in(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st, uint32_t rot = 0, uint32_t mono = 0) {
     switch (rt.ring_bins) {
-        case 160: return launch_bars_i8_one<160, 64, F32IN, R16>(rows, bars_out, nrows, n, bars, rt, st);
-        case 288: return launch_bars_i8_one<288, 64, F32IN, R16>(rows, bars_out, nrows, n, bars, rt, st);
-        case 448: return launch_bars_i8_one<448, 64, F32IN, R16>(rows, bars_out, nrows, n, bars, rt, st);
-        case 832: return launch_bars_i8_one<832, 64, F32IN, R16>(rows, bars_out, nrows, n, bars, rt, st);
-        case 1600: return launch_bars_i8_one<1600, 32, F32IN, R16>(rows, bars_out, nrows, n, bars, rt, st);
+        case 160: return launch_bars_i8_one<160, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
+        case 288: return launch_bars_i8_one<288, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
+        case 448: return launch_bars_i8_one<448, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
+        case 832: return launch_bars_i8_one<832, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
+        case 1600: return launch_bars_i8_one<1600, 32, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
     }
     return hipErrorInvalidValue;
 }
 // rows: uint16 [nrows][n] texels (rows_f32 false) or float [nrows][n] holding texel values c / 65535 (true)
 hipError_t launch_bars_i8(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st, bool r16) {
     if (rt == nullptr || rt->tiles == nullptr || rt->rounds == nullptr || rt->nrounds == 0) return hipErrorInvalidValue;
-    if (rows_f32) return r16 ? launch_bars_i8_in<true, true>(rows, bars_out, nrows, n, bars, *rt, st) : launch_bars_i8_in<true, false>(rows, bars_out, nrows, n, bars, *rt, st);
-    return r16 ? launch_bars_i8_in<false, true>(rows, bars_out, nrows, n, bars, *rt, st) : launch_bars_i8_in<false, false>(rows, bars_out, nrows, n, bars, *rt, st);
+    if (rows_f32) return r16 ? launch_bars_i8_in<I8_FLOATS, true>(rows, bars_out, nrows, n, bars, *rt, st) : launch_bars_i8_in<I8_FLOATS, false>(rows, bars_out, nrows, n, bars, *rt, st);
+    return r16 ? launch_bars_i8_in<I8_TEXELS, true>(rows, bars_out, nrows, n, bars, *rt, st) : launch_bars_i8_in<I8_TEXELS, false>(rows, bars_out, nrows, n, bars, *rt, st);
+}
+hipError_t launch_bars_i8_pcm(const void* pcm, uint32_t rot, bool mono, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st, bool r16) {
+    if (rt == nullptr || rt->tiles == nullptr || rt->rounds == nullptr || rt->nrounds == 0 || (nrows & 1u) || rot >= n || (rot & 7u)) return hipErrorInvalidValue;
+    return r16 ? launch_bars_i8_in<I8_PCM_S16, true>(pcm, bars_out, nrows, n, bars, *rt, st, rot, mono ? 1u : 0u)
+               : launch_bars_i8_in<I8_PCM_S16, false>(pcm, bars_out, nrows, n, bars, *rt, st, rot, mono ? 1u : 0u);
 }
 hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt) {
     if (rt == nullptr || rt->rounds == nullptr || rt->nrounds == 0) return hipSuccess;
-    hipError_t e = launch_bars_i8_in<false, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
-    if (e == hipSuccess) e = launch_bars_i8_in<false, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
-    if (e == hipSuccess) e = launch_bars_i8_in<true, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
-    if (e == hipSuccess) e = launch_bars_i8_in<true, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    hipError_t e = launch_bars_i8_in<I8_TEXELS, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    if (e == hipSuccess) e = launch_bars_i8_in<I8_TEXELS, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    if (e == hipSuccess) e = launch_bars_i8_in<I8_FLOATS, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    if (e == hipSuccess) e = launch_bars_i8_in<I8_FLOATS, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    if (e == hipSuccess) e = launch_bars_i8_in<I8_PCM_S16, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    if (e == hipSuccess) e = launch_bars_i8_in<I8_PCM_S16, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
     return e;
 }
 

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("GLV_SPECTRUM_LIB") or os.path.join(HERE, "csrc", "lib
 
 OP_FFT, OP_GRAVITY, OP_AVERAGE, OP_RAW, OP_WRANGE, OP_BARS, OP_SMOOTH, OP_MAGNITUDE, OP_R16 = 1, 2, 4, 8, 16, 32, 64, 128, 256
 OP_PRIVATE_STATE, OP_RING_S16, OP_RING_F32, OP_OUTPUT_IS_STATE, OP_BARS_ONLY = 512, 1024, 2048, 4096, 8192
+OP_WAVE = 1 << 14                  # the wave module's bind: unpack -> wrange -> GL_R16 upload (with OP_BARS: + the pre-smoothing pass)
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_STATE = 0, 1, 2, 3, 4, 5
 BARS_NONE, BARS_F32_CHAIN, BARS_F32_MATRIX, BARS_I8_EXACT, BARS_F32_SEQ = 0, 1, 2, 3, 4
 ROUND_SINUSOIDAL, ROUND_CIRCULAR, ROUND_LINEAR = 0, 1, 2          # glv_params.round_formula
@@ -83,6 +84,8 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, vp, vp]
         L.glv_texels_r16.argtypes = [P, vp, vp, vp]
         L.glv_gl_texture.argtypes = [P, vp, vp, C.c_int, vp]
+        if hasattr(L, "glv_wave_texture"):              # (added within ABI 7: callers detect it by the symbol)
+            L.glv_wave_texture.argtypes = [P, vp, vp, C.c_int, vp]
         L.glv_unpack_s16.argtypes = [C.c_int, vp, C.c_size_t, C.c_int, vp, vp]
         L.glv_batch_create.argtypes = [P, C.c_uint32, C.c_uint, C.c_int, C.POINTER(vp)]
         L.glv_batch_reset.argtypes = [vp]
@@ -422,6 +425,13 @@ class State:
         host buffers: n float samples in (not modified), n GL_R16 texels out; the state must have gl_storage = 1"""
         cp = self.params.c()
         _check(lib().glv_gl_texture(C.byref(cp), self._h, _ptr(buf), 1 if smooth_pass else 0, _ptr(texels)))
+
+    def wave_texture(self, buf, texels, smooth_pass: bool = True) -> None:
+        """handle_audio for the wave module's bind (transforms window, wrange): transform_wrange, the GL_R16 upload and -- smooth_pass --
+        the pre-smoothing pass (render.c:773-781, :521-524, :2276-2303); host buffers: n floats of lb / rb in (not modified), n GL_R16
+        texels out; the pass needs a state with gl_storage = 1, bars = n, bar_phase = 0.5"""
+        cp = self.params.c()
+        _check(lib().glv_wave_texture(C.byref(cp), self._h, _ptr(buf), 1 if smooth_pass else 0, _ptr(texels)))
 
     def reset(self) -> None:
         _check(lib().glv_state_reset(self._h))

@@ -26,7 +26,8 @@ extern "C" {
                                   7 (round 6): glv_params grew smooth_audio()'s shape -- round_formula, sample_mode, sample_hybrid_weight, sample_scale, sample_range
                                                (appended; all-zero == the shipped shape, so a caller that zero-fills the tail keeps ABI 6's results); GLV_BARS_F32_SEQ
                                   7, added without a version change: glv_batch_set_bar_texels (bars at texels of the pre-smoothing pass; detect it by the symbol),
-                                               glv_batch_set_column_texels (the graph module's columns: means of three such texels; likewise) */
+                                               glv_batch_set_column_texels (the graph module's columns: means of three such texels; likewise),
+                                               GLV_OP_WAVE and glv_wave_texture (the wave module's bind on the device; likewise) */
 
 /* status codes (0 = ok).  The reference has no error channel: it prints and calls
  * glava_abort() (glava/glava.h:17, glava/render.c passim); the in-tree shim maps any
@@ -111,6 +112,35 @@ enum {
                                    bar sample further: smooth_audio() clamps its positions to [0, 1]).  A stateful call without GLV_OP_BARS and glv_batch_gravity_state are refused
                                    (GLV_ERR_STATE); so is a glv_batch_set_params that would take a batch which has run its live class to the
                                    full chain (the state beyond the live bins was never kept) -- until glv_batch_reset */
+    GLV_OP_WAVE     = 1u << 14, /* the wave module's bind (shaders/glava/wave/1.frag:7-9 requests `window`, `wrange`; `window` has no CPU stage,
+                                   render.c:850): per channel row the backend's unpack (fifo.c:94-110 / pulse_input.c:155-178; channels == 1: the mono mix
+                                   into both rows; planar f32 rows are taken as they are), transform_wrange (render.c:773-781: b += 1.0F; b /= 2.0F) and
+                                   the GL_R16 upload (render.c:521-524, :2185) -- from EVERY input entry point (s16 / f32 interleaved frames, planar f32,
+                                   both device rings, oldest frame first), stateless.  Outputs:
+                                     GLV_OP_WAVE | GLV_OP_R16     uint16 [streams][2][n]: the upload's texels c
+                                     GLV_OP_WAVE                  float  [streams][2][n]: c / 65535 correctly rounded -- what texelFetch returns, the texture the
+                                                                  module samples with `setsmoothpass false`
+                                     GLV_OP_WAVE | GLV_OP_BARS [| GLV_OP_R16]   the pre-smoothing pass over those texels (audio is true for SRC_AUDIO_L/R,
+                                                                  render.c:2325-2326, so handle_audio runs it on the waveform too: render.c:2276-2303,
+                                                                  util/smooth_pass.frag): arithmetic and outputs exactly what GLV_OP_BARS documents for the
+                                                                  GL_R16 chain -- GLV_BARS_I8_EXACT for sample_mode average at 256 bars or more,
+                                                                  GLV_BARS_F32_SEQ for maximum / hybrid (glv_batch_bars_arithmetic reports it).  With bars = n,
+                                                                  bar_phase = 0.5 and GLV_OP_R16 that is the texture the shipped wave module samples
+                                                                  (wave/1.frag:17-23).  From s16 frames and the s16 ring (its oldest frame at a multiple of 8), GLV_BARS_I8_EXACT runs as ONE launch:
+                                                                  the integer pass unpacks, applies wrange and quantises the frames as it parks them in LDS,
+                                                                  reading only the frames its bars sample; every other form is the waveform kernel into rows
+                                                                  made at creation, then the bars kernel (glv_batch_last_launches reports which;
+                                                                  GLV_UNFUSED_WAVE in the environment at creation forces two launches: diagnostics).
+                                                                  NOT MEASURED YET: which of the two forms is faster on an MI355X has not been timed (no
+                                                                  device was available when this was written); the one-launch form is the default because it
+                                                                  moves fewer bytes (no texel rows between launches), not on evidence.  tools/wave_texture_bench.py
+                                                                  times both forms in one process and is to be run, its output kept as
+                                                                  profiles/r09/wave_texture.txt, and the default set from it.
+                                   A new bit: every call without it is what it was.  Refused: with GLV_OP_FFT / GRAVITY / AVERAGE / RAW / WRANGE / MAGNITUDE /
+                                   SMOOTH / OUTPUT_IS_STATE (GLV_ERR_INVALID); GLV_OP_WAVE | GLV_OP_BARS on a gl_storage 0 batch (GLV_ERR_STATE: a float chain has
+                                   no texel rows), on a batch whose ops_mask lacked either bit (GLV_ERR_STATE: the rows between the two launches are made at
+                                   creation); any GLV_OP_WAVE call, with or without bars, while column texels are set (GLV_ERR_STATE: the wave shader does not average three texels).  With bar texels set
+                                   (glv_batch_set_bar_texels) GLV_OP_WAVE | GLV_OP_BARS gives the texels of the pass at the table's positions */
     GLV_OP_OUTPUT_IS_STATE = 1u << 12 /* opt-in, with a chain that ENDS in gravity (GLV_OP_GRAVITY without AVERAGE / SMOOTH / RAW, f32
                                    rows out, no gl_storage): transform_gravity stores every value twice, to its `applied` array and to
                                    the buffer (render.c:733-734) -- with this flag ONE array is kept: the call writes the spectra
@@ -256,6 +286,15 @@ int glv_texels_r16(const glv_params* p, glv_state* s, const float* buf, uint16_t
  * (normally avg_window_kind = 1; for the pre-smoothing pass bars = n and bar_phase = 0.5); it holds the gravity store and the ring like
  * the reference's gr_store / gr.out textures do.  integration/render_hip.patch binds this into handle_audio. */
 int glv_gl_texture(const glv_params* p, glv_state* s, const float* buf, int smooth_pass, uint16_t* texels);
+/* == handle_audio for a bind whose transforms are `window`, `wrange` -- the wave module's (shaders/glava/wave/1.frag:7-9) --, from the CPU transform
+ * to the texture the module samples (glava/render.c:2113-2309): transform_wrange of the n floats in buf (lb / rb; not modified; render.c:773-781),
+ * the GL_R16 upload (:521-524, :2185) and -- smooth_pass != 0, the shipped default (smooth_parameters.glsl:78) -- the pre-smoothing pass
+ * (:2276-2303) in its exact integer form (GLV_OP_BARS, GLV_BARS_I8_EXACT).  texels: the n GL_R16 texels of the upload or of the pass; the module
+ * reads them with texture(audio_l, (gl_FragCoord.x + o) / screen.x), o in {-1, 0, 1}, GL_NEAREST / GL_REPEAT (wave/1.frag:17-23, render.c:1714-1717;
+ * glava_amd.bar_positions.wave_column_texels restates the mapping).  GLV_OP_WAVE [| GLV_OP_BARS] | GLV_OP_R16 on one row.  The pass needs a state
+ * created with gl_storage = 1, bars = n and bar_phase = 0.5 (GLV_ERR_STATE / GLV_ERR_INVALID otherwise); smooth_pass == 0 works on any state.
+ * Added within ABI 7 without a version change: detect it by the symbol.  integration/render_hip.patch does not bind it yet. */
+int glv_wave_texture(const glv_params* p, glv_state* s, const float* buf, int smooth_pass, uint16_t* texels);
 
 /* == the unpack loop of the FIFO backend, glava/fifo.c:94-110 (and :67-79 when pcm == NULL):
  * `frames` interleaved stereo s16 frames -> planar f32.  Runs on the device (the bit-exactness
@@ -307,6 +346,8 @@ int glv_batch_destroy(glv_batch* b);
  * d_out receives a copy (28 n bytes per frame); d_out may be NULL -- the spectra are then left in the state buffer only, read
  * them through glv_batch_gravity_state (20 n).  With GLV_OP_OUTPUT_IS_STATE d_out itself becomes the state (20 n; see the flag
  * for what the caller promises).  (With GLV_OP_BARS a chain ending in gravity keeps the spectra in the state internally.) */
+/* (every input entry point -- this one, _f32, _f32_stereo and the two ring updates -- takes GLV_OP_FFT chains or GLV_OP_WAVE; planar f32 also the operators
+ * without a transform) */
 int glv_batch_process_s16(glv_batch* b, const int16_t* d_pcm, float* d_out, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
@@ -358,7 +399,8 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
  *   Refused: count != bars or any t[k] >= n (GLV_ERR_INVALID); a batch created without GLV_OP_BARS or with gl_storage 0 (GLV_ERR_STATE: a float chain
  *   has no pre-smoothed texture); a twin whose arithmetic would be GLV_BARS_F32_MATRIX (GLV_ERR_INVALID, glv_last_error says why).
  *   While a table is set: glv_batch_set_params that changes bars or sets gl_storage 0, glv_batch_bars, and GLV_OP_BARS calls that are not a GL chain
- *   (GLV_OP_FFT with gravity / average, no GLV_OP_SMOOTH) are refused with GLV_ERR_STATE; a change of smooth_factor or of the shape rebuilds the
+ *   (GLV_OP_FFT with gravity / average, no GLV_OP_SMOOTH) or GLV_OP_WAVE | GLV_OP_BARS (the same contract over the wave texture: the twin is the same
+ *   GLV_OP_WAVE | GLV_OP_BARS call with bars = n, bar_phase 0.5; always a second launch) are refused with GLV_ERR_STATE; a change of smooth_factor or of the shape rebuilds the
  *   table's taps.  glv_batch_reset keeps the table, glv_batch_destroy frees it.
  * glv_batch_live_bins: every snapped position lies in [0, 1), which the live bins already cover whenever smooth_factor >= 1 / bars (the unsnapped
  * last bar then reaches smooth_audio()'s last bin); a smaller factor grows them to the snapped taps' reach -- refused on a GLV_OP_BARS_ONLY batch
@@ -398,7 +440,10 @@ int glv_batch_timing_end(glv_batch* b, double* kernel_ms, uint64_t* launches);
  * read and written, output.  Rows that one launch of a multi-launch chain hands to the next (the uint16 `av` rows in front of the
  * pre-smoothing pass, bars that are not computed inside the transform's launch) are traffic of the organisation, not of the problem, and
  * are not counted -- except gl_storage 2, whose pass-by-pass f32 round trip (+16 n) is its definition.  A chain that ends in gravity is
- * counted with its output copy (28 n) unless GLV_OP_OUTPUT_IS_STATE is in `ops` (20 n; a NULL d_out moves those 20 n too). */
+ * counted with its output copy (28 n) unless GLV_OP_OUTPUT_IS_STATE is in `ops` (20 n; a NULL d_out moves those 20 n too).
+ * GLV_OP_WAVE: the input bytes the result depends on plus the output bytes, per stereo frame -- without GLV_OP_BARS the whole window (4 n for s16, 8 n
+ * for f32) and 4 n texels or 8 n floats out; with GLV_OP_BARS the frames the bars sample (4 or 8 bytes x the sampled reach: the bins below the last tap of
+ * any bar, in whole 64s -- 0.288 n with the shipped shape) and 4 or 8 bytes x bars out.  The texel rows between two launches are not counted. */
 uint64_t glv_batch_algorithmic_bytes(const glv_batch* b, unsigned ops, int input_is_s16);
 
 /* GLV_OP_BARS_ONLY batches: the bins of a row the chain keeps alive, [0, glv_batch_live_bins) (what the bars sample, in whole store
