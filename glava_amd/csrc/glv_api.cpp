@@ -155,6 +155,35 @@ int wisdom_load_file(const char* path, int* skipped = nullptr, int* v1 = nullptr
     return n_loaded;
 }
 
+// One array in device memory and its only owner: freed when the owner goes, so no table has a free list to be kept in step with.
+// upload() / alloc() make the new array completely before the held one is replaced and freed: after a failure the owner holds what
+// it held.  Synchronous (hipMalloc, hipMemcpy from pageable memory): creation and the set calls only, never the process path
+// (tests/test_stream_order.py forbids these names there).
+template <class T> class DeviceArray {
+    T* p_ = nullptr;
+    hipError_t renew(const T* src, size_t count, bool zeroed) {
+        T* q = nullptr;
+        hipError_t e = hipMalloc(&q, sizeof(T) * count);
+        if (e == hipSuccess && src) e = hipMemcpy(q, src, sizeof(T) * count, hipMemcpyHostToDevice);
+        if (e == hipSuccess && zeroed) e = hipMemset(q, 0, sizeof(T) * count);
+        if (e != hipSuccess) { if (q) (void) hipFree(q); return e; }
+        reset();
+        p_ = q;
+        return hipSuccess;
+    }
+public:
+    DeviceArray() = default;
+    DeviceArray(DeviceArray&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DeviceArray& operator=(DeviceArray&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~DeviceArray() { reset(); }
+    hipError_t upload(const T* src, size_t count) { return renew(src, count, false); }       // exactly `count` elements, copied from the host
+    hipError_t upload(const std::vector<T>& v) { return renew(v.data(), v.size(), false); }
+    hipError_t alloc(size_t count, bool zeroed) { return renew(nullptr, count, zeroed); }     // no host data: as hipMalloc left them, or zeros
+    void reset() { if (p_) (void) hipFree(p_); p_ = nullptr; }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
+
 // Device-resident constants of one transform size.  The size-only tables -- twiddles, the window in both forms (the float-pair
 // form is SEARCHED on the device: n workgroups trying 65 536 sample values per position), the log table -- are made once per
 // (device, n) and shared by every batch of that size with a reference count (glv_multi shards, the five configs[4]
@@ -162,7 +191,7 @@ int wisdom_load_file(const char* path, int* skipped = nullptr, int* v1 = nullptr
 // parameters and stay per batch.
 struct SharedTables {
     int device = 0; uint32_t n = 0; int refs = 0;
-    glv::cf* d_tw = nullptr; double* d_win = nullptr; float* d_win_split = nullptr; glv::LogEntry* d_log = nullptr;
+    DeviceArray<glv::cf> d_tw; DeviceArray<double> d_win; DeviceArray<float> d_win_split; DeviceArray<glv::LogEntry> d_log;
     int win_shifted = 0;
 };
 std::mutex g_tab_mu;
@@ -175,7 +204,7 @@ struct Tables {
     float* d_win_split = nullptr;      // the same window as float pairs, for s16 samples (glv_core.h WinSplit; made on the device)
     int win_shifted = 0;               // positions whose low part was moved by an ulp or more (diagnostics)
     glv::LogEntry* d_log = nullptr;
-    float* d_tilt = nullptr;
+    DeviceArray<float> d_tilt;
     float tilt_scale = 0.f, tilt_cutoff = 0.f;
     bool tilt_fold = false;
     uint32_t n_ = 0;
@@ -185,17 +214,11 @@ struct Tables {
         std::vector<float> t(n_);
         glv::make_tilt(t.data(), n_, fft_scale, fft_cutoff, fold);
         tilt_fold = fold;
-        if (!d_tilt) HIP_TRY(hipMalloc(&d_tilt, sizeof(float) * n_));
-        HIP_TRY(hipMemcpy(d_tilt, t.data(), sizeof(float) * n_, hipMemcpyHostToDevice));
+        // (rewritten where they are once they exist: the array a captured launch points at stays the one the next call reads)
+        if (!d_tilt) HIP_TRY(d_tilt.upload(t));
+        else HIP_TRY(hipMemcpy(d_tilt, t.data(), sizeof(float) * n_, hipMemcpyHostToDevice));
         tilt_scale = fft_scale; tilt_cutoff = fft_cutoff;
         return GLV_OK;
-    }
-    static void free_shared(SharedTables* t) {
-        if (t->d_tw) (void) hipFree(t->d_tw);
-        if (t->d_win) (void) hipFree(t->d_win);
-        if (t->d_win_split) (void) hipFree(t->d_win_split);
-        if (t->d_log) (void) hipFree(t->d_log);
-        delete t;
     }
     static int make_shared(SharedTables* t) {
         const uint32_t n = t->n, nn = n / 2;
@@ -203,13 +226,11 @@ struct Tables {
         std::vector<double> win(n);
         glv::make_twiddles(tw.data(), nn);
         glv::make_window(win.data(), n);
-        HIP_TRY(hipMalloc(&t->d_tw, sizeof(glv::cf) * nn));
-        HIP_TRY(hipMalloc(&t->d_win, sizeof(double) * n));
-        HIP_TRY(hipMemcpy(t->d_tw, tw.data(), sizeof(glv::cf) * nn, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t->d_win, win.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_TRY(t->d_tw.upload(tw));
+        HIP_TRY(t->d_win.upload(win));
         {   // the split window: searched and proven on the device for every s16 sample value (glv_misc.hip)
             int* d_fs = nullptr;
-            HIP_TRY(hipMalloc(&t->d_win_split, sizeof(float) * 2 * n));
+            HIP_TRY(t->d_win_split.alloc(2 * (size_t) n, false));
             HIP_TRY(hipMalloc(&d_fs, 2 * sizeof(int)));
             HIP_TRY(hipMemset(d_fs, 0, 2 * sizeof(int)));
             hipError_t e = glv::launch_window_split(t->d_win, t->d_win_split, n, d_fs, nullptr);
@@ -222,8 +243,7 @@ struct Tables {
         }
         glv::LogEntry lt[glv::kLogTabMaxSize];
         glv::make_log_table(lt);
-        HIP_TRY(hipMalloc(&t->d_log, sizeof(lt)));
-        HIP_TRY(hipMemcpy(t->d_log, lt, sizeof(lt), hipMemcpyHostToDevice));
+        HIP_TRY(t->d_log.upload(lt, glv::kLogTabMaxSize));
         return GLV_OK;
     }
     int create(uint32_t n, int device) {
@@ -234,7 +254,7 @@ struct Tables {
             SharedTables* t = new (std::nothrow) SharedTables();
             if (!t) return fail(GLV_ERR_NOMEM, "out of host memory");
             t->device = device; t->n = n;
-            if (int rc = make_shared(t)) { free_shared(t); return rc; }
+            if (int rc = make_shared(t)) { delete t; return rc; }
             g_tabs.push_back(t);
             shared = t;
         }
@@ -243,13 +263,12 @@ struct Tables {
         return GLV_OK;
     }
     void destroy() {
-        if (d_tilt) (void) hipFree(d_tilt);
-        d_tilt = nullptr;
+        d_tilt.reset();
         if (shared) {
             std::lock_guard<std::mutex> lock(g_tab_mu);
             if (--shared->refs == 0) {
                 for (size_t i = 0; i < g_tabs.size(); ++i) if (g_tabs[i] == shared) { g_tabs.erase(g_tabs.begin() + (long) i); break; }
-                free_shared(shared);
+                delete shared;
             }
             shared = nullptr;
         }
@@ -271,6 +290,63 @@ void fill_common(glv::FrameArgs& a, const glv_params& p, const Tables& t) {
     for (uint32_t f = 0; f < p.avg_frames; ++f) a.wts32[f] = (float) a.wts[f];
 }
 
+// bins of a row a tap table reaches: the largest first_bin + count, in whole 64s (whole store instructions, the ring fill's 16-byte loads); 0: no taps
+uint32_t bins_reached(const std::vector<glv::BarDesc>& desc) {
+    uint32_t reach = 0;
+    for (const glv::BarDesc& d : desc) reach = d.first_bin + d.count > reach ? d.first_bin + d.count : reach;
+    return (reach + 63u) & ~63u;
+}
+
+constexpr int kMaxVariants = 4;
+// One set of GLV_OP_BARS tables (host generated).  A batch holds two: the bars of glv_params (glv_batch::bar) and, while glv_batch_set_bar_texels /
+// glv_batch_set_column_texels has a table set, the bars at texels of the pre-smoothing pass (glv_batch::snap).
+struct BarTableSet {
+    DeviceArray<glv::BarDesc> desc;          // taps
+    DeviceArray<float> w;                    // their weights, + one chunk of zeros for padding items (snapped: the uint32 weights W' as float bits; columns
+                                             // under maximum / hybrid: the float weights in tap order)
+    // work lists for the fused epilogue (lanes / GL groups per row), one per kernel configuration of the size (their lanes per row differ)
+    DeviceArray<glv::BarItem> fitems[kMaxVariants];
+    uint32_t fnsteps[kMaxVariants] = {}; bool fusable[kMaxVariants] = {};
+    DeviceArray<glv::BarModeBlock> mblocks; DeviceArray<float> mw; uint32_t nmblocks = 0;   // sample_mode maximum / hybrid (glv_tables.h make_bar_mode_blocks)
+    uint32_t bins = 0;                       // bins of a row the bars sample (bins_reached; 0: no tap, every bin counts as sampled)
+};
+// ... and what only the bars of glv_params have
+struct BarExtras {
+    DeviceArray<glv::BarItem> items; uint32_t nsteps = 0;   // work lists for glv_bars_kernel (32 groups per row)
+    // >= 256 bars (glv_tables.h make_bar_mtiles): tiles of 32 bars, their weights in MFMA operand layout, the bars' {weight sum, reciprocal}, and -- when
+    // they could be cut -- the rounds of glv_bars_rows_kernel for its LDS ring
+    DeviceArray<glv::BarMTile> mtiles; DeviceArray<float> wt, wsum; DeviceArray<glv::BarTile> rounds;
+    uint32_t ntiles = 0, nrounds = 0, ring_bins = 0, bins_needed = 0;      // bins_needed: bins of a row the many-bars kernels sample (0: all)
+    // the same pass over TEXEL rows (the GL chains, gl_storage != 0): exact integer arithmetic on the i8 matrix cores (glv_tables.h make_bar_itiles)
+    DeviceArray<glv::BarMTile> itiles; DeviceArray<int8_t> wq; DeviceArray<glv::BarIFin> fin; DeviceArray<glv::BarTile> irounds;
+    uint32_t intiles = 0, inrounds = 0, iring_bins = 0;
+    bool i8_none = false;        // the integer tables could not be made for these parameters (a bar wider than any ring / P > 31): the f32 chain serves
+    uint32_t count = 0; float factor = -1.f, phase = 0.f;
+    glv_params shape_of{};       // made for: bars, smooth_factor, bar_phase and the shape fields (round_formula ... sample_range)
+    glv::BarIRowsTables irows_tables() const { return glv::BarIRowsTables{itiles, intiles, wq, fin, irounds, inrounds, iring_bins}; }
+    bool i8() const { return irounds.get() != nullptr && inrounds != 0; }
+};
+// ... and the bars at texels of the pre-smoothing pass.  glv_batch_set_bar_texels: bar k is texel tex[k] (the twin: bars = n, bar_phase 0.5); empty = off.
+// The set follows the snapped taps: average -- snapped desc (weight_sum 1, NaN where the weights sum to 0), W' in tap_w's layout plus a zero chunk, one fused
+// work list per kernel configuration; maximum / hybrid -- the snapped desc and glv_bars_mode_kernel's blocks.
+// glv_batch_set_column_texels: column x is the mean of texels col_tex[x][0..2] of the same pass.  tex then holds the DISTINCT texels (sorted) and the set
+// is made over those; col_map says where a column's three sit among them.  The second launch (glv_columns_kernel) has work lists of its own
+// (256 / bar_lanes_of(n) groups).
+struct SnapExtras {
+    std::vector<uint32_t> tex;
+    std::vector<uint32_t> col_tex;           // [bars][3] as the caller gave them; empty = off
+    DeviceArray<glv::ColumnMap> col_map;
+    DeviceArray<glv::BarItem> col_items; uint32_t col_nsteps = 0;
+    glv_params of{};                         // the parameters the set was made for (smooth_factor, the shape, bars)
+};
+// what launch_bars takes besides the taps: the many-bars tiles (the bars of glv_params only) and the maximum / hybrid blocks of the set `s`
+glv::BarRowsTables rows_tables(const glv_params& p, const BarExtras& x, const BarTableSet& s) {
+    glv::BarRowsTables t{x.mtiles, x.ntiles, x.wt, x.wsum, x.rounds, x.nrounds, x.ring_bins};
+    t.mode = p.sample_mode; t.hybrid_weight = shape_hybrid(p);
+    t.mblocks = s.mblocks; t.nmblocks = s.nmblocks; t.mw = s.mw; t.mode_bins = s.bins < p.n ? s.bins : p.n;
+    return t;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -286,7 +362,7 @@ struct glv_batch {
     const float* grav_cur = nullptr;   // where the latest gravity output lives: d_grav, or the caller's output buffer of the previous
                                  // call when the output doubles as the state (render.c:733-734; see GLV_OP_PRIVATE_STATE)
     float* d_hist = nullptr;     // [streams*2][F][n]   ring (average; doubles as gravity state)
-    int16_t* d_ring = nullptr;   // [streams][n][2]     FIFO ring mode
+    DeviceArray<int16_t> d_ring;     // [streams][n][2]     FIFO ring mode
     int grav_mode = 0;           // which buffer holds gravity's `applied`: 0 not used yet, 1 d_grav (gravity without average
                                  // in the same call), 2 the newest ring slot (gravity + average fused)
     uint32_t head = 0;           // history slot receiving the next frame
@@ -307,89 +383,41 @@ struct glv_batch {
     bool unfused_wave = false;   // GLV_UNFUSED_WAVE likewise: GLV_OP_WAVE | GLV_OP_BARS always as the waveform kernel + the bars kernel
     bool state16 = false;        // gl_storage == 1 at creation: d_grav / d_hist hold uint16 texels (2 bytes per value)
     float grav_g = 0.f; uint32_t grav_sub = 0; bool grav_int = false, grav_known = false;   // the gravity step on texels (glv_tables.h gravity_r16_integer_step)
-    float* d_scratch = nullptr;  // [streams*2][n] spectra feeding GLV_OP_BARS
-    float* d_ring_f32 = nullptr; // [streams][n][2] interleaved f32 ring (glv_batch_ring_update_f32)
+    DeviceArray<float> d_scratch;    // [streams*2][n] spectra feeding GLV_OP_BARS
+    DeviceArray<float> d_ring_f32;   // [streams][n][2] interleaved f32 ring (glv_batch_ring_update_f32)
     uint32_t ring_pos_f32 = 0;
-    int* d_smin = nullptr;       // transform_smooth window bounds (host generated)
-    int* d_smax = nullptr;
+    DeviceArray<int> d_smin, d_smax; // transform_smooth window bounds (host generated)
     uint32_t smooth_asz = 0;
     uint32_t smooth_reach = 0;   // floats of a row the walk touches: max smax + 1 (>= asz)
     uint32_t smooth_window = 0;  // largest smax - smin + 1; also covers smax - t and t - smin (the ring kernel's slot reuse)
     float smooth_d = -1.f, smooth_r = -1.f;
-    glv::BarDesc* d_bar_desc = nullptr;   // GLV_OP_BARS tap tables (host generated)
-    float* d_bar_w = nullptr;
-    glv::BarItem* d_bar_items = nullptr;    // work lists for glv_bars_kernel (32 groups per row)
-    // work lists for the fused epilogue (lanes / GL groups per row), one per kernel configuration of the size (their lanes per row differ)
-    static constexpr int kMaxVariants = 4;
-    glv::BarItem* d_bar_fitems[kMaxVariants] = {};
-    uint32_t bar_fnsteps[kMaxVariants] = {}; bool bar_fusable[kMaxVariants] = {};
-    uint32_t bar_nsteps = 0;
-    uint32_t bar_count = 0; float bar_factor = -1.f, bar_phase = 0.f;
-    glv_params bar_shape_of{};               // the shape fields (round_formula ... sample_range) the tables were made for
-    glv::BarModeBlock* d_bar_mblocks = nullptr; float* d_bar_mw = nullptr; uint32_t bar_nmblocks = 0;   // sample_mode maximum / hybrid (glv_tables.h make_bar_mode_blocks)
-    glv::BarMTile* d_bar_mtiles = nullptr;  // >= 256 bars (glv_tables.h make_bar_mtiles): tiles of 32 bars, their weights in MFMA operand layout, the bars'
-    float* d_bar_wt = nullptr;              // {weight sum, reciprocal}, and -- when they could be cut -- the rounds of glv_bars_rows_kernel for its LDS ring
-    float* d_bar_wsum = nullptr;
-    glv::BarTile* d_bar_rounds = nullptr;
-    uint32_t bar_ntiles = 0, bar_nrounds = 0, bar_ring_bins = 0, bar_bins_needed = 0;      // bar_bins_needed: bins of a row the many-bars kernels sample (0: all)
-    // GLV_OP_BARS_ONLY: the chain lives below bar_bins_sampled (the last bin any bar has a tap on, rounded up to 64) -- when EVERY kernel configuration
+    BarTableSet bar; BarExtras bar_x;        // GLV_OP_BARS: the bars of glv_params (ensure_bar_tables)
+    BarTableSet snap; SnapExtras snap_x;     // ... and at texels of the pre-smoothing pass (build_snap_tables; snap.bins: never 0 while a table is set)
+    bool bar_i8_off = false;     // GLV_NO_BARS_I8 in the environment at creation (diagnostics: the f32 matrix-core kernel on texel rows too)
+    bool snapped() const { return !snap_x.tex.empty(); }
+    bool columns() const { return !snap_x.col_tex.empty(); }
+    // GLV_OP_BARS_ONLY: the chain lives below the bins the bars sample (the last bin any bar has a tap on, rounded up to 64) -- when EVERY kernel configuration
     // of the size keeps those bins alive in its live class (a compile-time share of the row, FrameGeometry::live_points; whichever configuration a
     // call runs, the bins the bars sample are maintained) and a live class exists for the chain: the GL_R16 chains have one with the bars in a second
     // launch (7) and one with the bars fused (9); the float chains only the fused one (8).
     // 0: every bin is live (no flag, or one of the conditions fails: the full chain, the same results)
-    uint32_t bar_bins_sampled = 0;
     uint32_t live_bins_now = 0;                     // refreshed with the bar tables and when the batch is prepared (update_live_bins)
     uint32_t live_bins() const { return live_bins_now; }
     bool ran_live = false;                          // a live kernel class has run since creation / the last reset: the state beyond the live bins is stale
-    void update_live_bins() {
-        live_bins_now = 0u;
+    // the live bins with snapped bars that sample `snap_bins` bins of a row (0: none set)
+    uint32_t live_bins_with(uint32_t snap_bins) const {
         // (snapped bars sample positions in [0, 1) -- the unsnapped bars' last taps reach scale_audio(1) n once smooth_factor >= 1 / bars; a smaller
         // factor can leave the last snapped taps beyond them, and the live bins then grow to cover them)
-        const uint32_t sampled = snapped() && snap_bins > bar_bins_sampled ? snap_bins : bar_bins_sampled;
-        if (!(ops_mask & GLV_OP_BARS_ONLY) || sampled == 0 || sampled >= p.n || p.gl_storage > 1u || p.log_mode == 2u) return;
+        const uint32_t sampled = snap_bins > bar.bins ? snap_bins : bar.bins;
+        if (!(ops_mask & GLV_OP_BARS_ONLY) || sampled == 0 || sampled >= p.n || p.gl_storage > 1u || p.log_mode == 2u) return 0u;
         for (int v = 0; v < glv::frame_variants(log_nn); ++v)
-            if ((uint32_t) glv::frame_geometry(log_nn, v).live_points * 2u < sampled) return;
+            if ((uint32_t) glv::frame_geometry(log_nn, v).live_points * 2u < sampled) return 0u;
         // (a float chain's live class is the fused one: the production configuration must take the bars; a call that runs a configuration which cannot
         // -- forced, or from the wisdom -- takes the full chain for that call: it maintains every bin, the live calls the sampled ones, the bars see no difference)
-        if (p.gl_storage == 0u && (!bar_fusable[0] || unfused_bars)) return;
-        live_bins_now = sampled;
+        if (p.gl_storage == 0u && (!bar.fusable[0] || unfused_bars)) return 0u;
+        return sampled;
     }
-    glv::BarRowsTables rows_tables() const {
-        glv::BarRowsTables t{d_bar_mtiles, bar_ntiles, d_bar_wt, d_bar_wsum, d_bar_rounds, bar_nrounds, bar_ring_bins};
-        t.mode = p.sample_mode; t.hybrid_weight = p.sample_hybrid_weight != 0.0f ? p.sample_hybrid_weight : 0.65f;
-        t.mblocks = d_bar_mblocks; t.nmblocks = bar_nmblocks; t.mw = d_bar_mw; t.mode_bins = bar_bins_sampled < p.n ? bar_bins_sampled : p.n;
-        return t;
-    }
-    // the same pass over TEXEL rows (the GL chains, gl_storage != 0): exact integer arithmetic on the i8 matrix cores (glv_tables.h make_bar_itiles)
-    glv::BarMTile* d_bar_itiles = nullptr; int8_t* d_bar_wq = nullptr; glv::BarIFin* d_bar_fin = nullptr; glv::BarTile* d_bar_irounds = nullptr;
-    uint32_t bar_intiles = 0, bar_inrounds = 0, bar_iring_bins = 0;
-    bool bar_i8_none = false;    // the integer tables could not be made for these parameters (a bar wider than any ring / P > 31): the f32 chain serves
-    bool bar_i8_off = false;     // GLV_NO_BARS_I8 in the environment at creation (diagnostics: the f32 matrix-core kernel on texel rows too)
-    glv::BarIRowsTables irows_tables() const { return glv::BarIRowsTables{d_bar_itiles, bar_intiles, d_bar_wq, d_bar_fin, d_bar_irounds, bar_inrounds, bar_iring_bins}; }
-    bool bars_i8() const { return d_bar_irounds != nullptr && bar_inrounds != 0; }
-    // glv_batch_set_bar_texels: bar k is texel snap_tex[k] of the pre-smoothing pass (the twin: bars = n, bar_phase 0.5); empty = off.  The tables
-    // follow the snapped taps: average -- snapped desc (weight_sum 1, NaN where the weights sum to 0), W' in tap_w's layout plus a zero chunk, one
-    // fused work list per kernel configuration; maximum / hybrid -- the snapped desc and glv_bars_mode_kernel's blocks
-    std::vector<uint32_t> snap_tex;
-    glv::BarDesc* d_snap_desc = nullptr; uint32_t* d_snap_w = nullptr;
-    glv::BarItem* d_snap_fitems[kMaxVariants] = {};
-    uint32_t snap_fnsteps[kMaxVariants] = {}; bool snap_fusable[kMaxVariants] = {};
-    glv::BarModeBlock* d_snap_mblocks = nullptr; float* d_snap_mw = nullptr; uint32_t snap_nmblocks = 0;
-    uint32_t snap_bins = 0;                  // bins of a row the snapped bars sample (whole 64s)
-    glv_params snap_of{};                    // the parameters the snapped tables were made for (smooth_factor, the shape, bars)
-    bool snapped() const { return !snap_tex.empty(); }
-    // glv_batch_set_column_texels: column x is the mean of texels col_tex[x][0..2] of the same pass.  snap_tex then holds the DISTINCT texels (sorted)
-    // and the snapped tables above are made over those; col_map says where a column's three sit among them.  The second launch (glv_columns_kernel)
-    // has work lists of its own (256 / bar_lanes_of(n) groups), and for maximum / hybrid d_snap_w holds the float weights in tap order.
-    std::vector<uint32_t> col_tex;           // [bars][3] as the caller gave them; empty = off
-    glv::ColumnMap* d_col_map = nullptr;
-    glv::BarItem* d_col_items = nullptr; uint32_t col_nsteps = 0;
-    bool columns() const { return !col_tex.empty(); }
-    glv::BarRowsTables snap_rows_tables() const {
-        glv::BarRowsTables t = rows_tables();
-        t.mblocks = d_snap_mblocks; t.nmblocks = snap_nmblocks; t.mw = d_snap_mw; t.mode_bins = snap_bins < p.n ? snap_bins : p.n;
-        return t;
-    }
+    void update_live_bins() { live_bins_now = live_bins_with(snapped() ? snap.bins : 0u); }
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;  // start/stop pairs
@@ -407,9 +435,10 @@ struct glv_state {
     // buffer + two hipMemcpyAsync of round 1 (kept for A/B in tests/test_gpu_parity.py::test_single_stream_dropin_latency).
     float* h_io = nullptr;       // host view
     float* d_io = nullptr;       // device view of h_io (mapped), or a device buffer when copy staging is selected
-    uint16_t* h_tex = nullptr;
-    uint16_t* d_tex = nullptr;
-    float* d_seq = nullptr;      // device buffer for GLV_OP_SMOOTH: its kernel walks a row element by element, which must not happen over PCIe
+    uint16_t* h_tex = nullptr;   // the texel outputs' staging, made by the first call that needs it (round_trip)
+    uint16_t* d_tex = nullptr;   // device view of h_tex (mapped), or tex_copy's array
+    DeviceArray<uint16_t> tex_copy;
+    DeviceArray<float> seq;      // device buffer for GLV_OP_SMOOTH: its kernel walks a row element by element, which must not happen over PCIe
     bool mapped = true;
 };
 
@@ -495,16 +524,8 @@ int batch_alloc(glv_batch* b, uint32_t rows) {
         b->grav_cur = b->d_grav;
     }
     // the device rings of the FIFO / PulseAudio modes, when the creation mask announces them
-    if (b->ops_mask & GLV_OP_RING_S16) {
-        const size_t bytes = sizeof(int16_t) * 2 * n * b->streams;
-        HIP_TRY(hipMalloc(&b->d_ring, bytes));
-        HIP_TRY(hipMemset(b->d_ring, 0, bytes));          // == the calloc'd rings of glava.c:487-494
-    }
-    if (b->ops_mask & GLV_OP_RING_F32) {
-        const size_t bytes = sizeof(float) * 2 * n * b->streams;
-        HIP_TRY(hipMalloc(&b->d_ring_f32, bytes));
-        HIP_TRY(hipMemset(b->d_ring_f32, 0, bytes));
-    }
+    if (b->ops_mask & GLV_OP_RING_S16) HIP_TRY(b->d_ring.alloc(2 * n * b->streams, true));          // == the calloc'd rings of glava.c:487-494
+    if (b->ops_mask & GLV_OP_RING_F32) HIP_TRY(b->d_ring_f32.alloc(2 * n * b->streams, true));
     return GLV_OK;
 }
 
@@ -520,7 +541,7 @@ bool gl_passes_chain(const glv_batch* b, unsigned ops) {
 // run on the raw values)
 unsigned frame_ops(const glv_batch* b, unsigned ops) { return gl_passes_chain(b, ops) ? GLV_OP_FFT | (ops & GLV_OP_RAW) : ops; }
 // The launch wisdom's class of an FFT chain: its frame kernel's class with the bars fused and every bin live.  The key is chosen before the
-// configuration, and whether the bars fuse depends on the configuration (bar_fusable[variant]): a chain with GLV_OP_BARS is class 2 or 6
+// configuration, and whether the bars fuse depends on the configuration (BarTableSet::fusable[variant]): a chain with GLV_OP_BARS is class 2 or 6
 // even where its bars run as a second launch.  The values are part of the wisdom file format (0..6).
 uint32_t wisdom_class(const glv_batch* b, unsigned ops) {
     const unsigned f = frame_ops(b, ops);
@@ -606,9 +627,15 @@ int ensure_smooth_tables(glv_batch* b) {
     const size_t n = b->p.n;
     std::vector<int> lo(n), hi(n);
     const size_t asz = glv::make_smooth_bounds(lo.data(), hi.data(), n, b->p.smooth_distance, b->p.smooth_ratio);
-    if (!b->d_smin) { HIP_TRY(hipMalloc(&b->d_smin, sizeof(int) * n)); HIP_TRY(hipMalloc(&b->d_smax, sizeof(int) * n)); }
-    HIP_TRY(hipMemcpy(b->d_smin, lo.data(), sizeof(int) * asz, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_smax, hi.data(), sizeof(int) * asz, hipMemcpyHostToDevice));
+    if (!b->d_smin) {                          // n entries each, of which asz are read; both or neither
+        DeviceArray<int> smin, smax;
+        HIP_TRY(smin.upload(lo));
+        HIP_TRY(smax.upload(hi));
+        b->d_smin = std::move(smin); b->d_smax = std::move(smax);
+    } else {                                   // (rewritten where they are, as the tilt factors)
+        HIP_TRY(hipMemcpy(b->d_smin, lo.data(), sizeof(int) * asz, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b->d_smax, hi.data(), sizeof(int) * asz, hipMemcpyHostToDevice));
+    }
     size_t reach = asz;
     long window = 1;
     for (size_t t = 0; t < asz; ++t) {
@@ -637,11 +664,13 @@ uint32_t make_itiles_any_ring(std::vector<glv::BarMTile>& itiles, std::vector<in
 
 // GLV_OP_BARS tables: taps, weights, the work lists of glv_bars_kernel and one fused work list per kernel configuration of the
 // size (their lanes per row differ).  Host generation + synchronous upload: creation / glv_batch_set_params only.
+// Built in a local set that replaces the batch's as the last step: a refused or failed call leaves the batch exactly as it was.  For the length of
+// the call the old and the new tables exist together (kilobytes to a few megabytes, beside state arrays of the streams' size).
 int ensure_bar_tables(glv_batch* b) {
     const bool averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;                                       // maximum / hybrid: glv_bars_mode_kernel, no matrix-core / fused form
     const bool want_i8 = b->p.gl_storage != 0 && b->p.bars >= glv::kBarSeqMin && !b->bar_i8_off && averaging;      // chains whose rows are texels
-    if (b->d_bar_desc && b->bar_count == b->p.bars && b->bar_factor == b->p.smooth_factor && b->bar_phase == b->p.bar_phase && same_shape(b->bar_shape_of, b->p)
-        && (want_i8 == (b->d_bar_itiles != nullptr) || b->bar_i8_none)) return GLV_OK;
+    if (b->bar.desc && b->bar_x.count == b->p.bars && b->bar_x.factor == b->p.smooth_factor && b->bar_x.phase == b->p.bar_phase && same_shape(b->bar_x.shape_of, b->p)
+        && (want_i8 == (b->bar_x.itiles.get() != nullptr) || b->bar_x.i8_none)) return GLV_OK;
     if (b->p.bars == 0 || b->p.bars > b->p.n) return fail(GLV_ERR_INVALID, "bars=%u out of range", b->p.bars);
     {   // the shape: scale_audio(1) = -log(1 - SAMPLE_RANGE) / SAMPLE_SCALE is the last position smooth_audio() samples (a share of the row)
         const float sc = shape_scale(b->p), rg = shape_range(b->p), hw = shape_hybrid(b->p);
@@ -656,84 +685,61 @@ int ensure_bar_tables(glv_batch* b) {
     std::vector<float> w;
     glv::make_bar_taps(desc, w, b->p.n, b->p.bars, b->p.smooth_factor, b->p.bar_phase, bar_shape(b->p));
     if (!glv::bar_chunks_in_row(desc, b->p.n)) return fail(GLV_ERR_INVALID, "bars: a tap chunk would leave the row (n=%u smooth_factor=%g)", b->p.n, (double) b->p.smooth_factor);
-    auto drop = [](auto*& ptr) { if (ptr) { (void) hipFree(ptr); ptr = nullptr; } };
-    drop(b->d_bar_desc); drop(b->d_bar_w); drop(b->d_bar_items); drop(b->d_bar_mtiles); drop(b->d_bar_wt); drop(b->d_bar_wsum); drop(b->d_bar_rounds);
-    drop(b->d_bar_itiles); drop(b->d_bar_wq); drop(b->d_bar_fin); drop(b->d_bar_irounds); drop(b->d_bar_mblocks); drop(b->d_bar_mw);
-    b->bar_nmblocks = 0;
-    b->bar_intiles = 0; b->bar_inrounds = 0; b->bar_iring_bins = 0; b->bar_i8_none = false;
-    for (int v = 0; v < glv_batch::kMaxVariants; ++v) { drop(b->d_bar_fitems[v]); b->bar_fusable[v] = false; b->bar_fnsteps[v] = 0; }
-    b->bar_count = 0;
+    BarTableSet s;
+    BarExtras x;
     // work lists: 256 / GL groups per row for glv_bars_kernel; T / GL groups for the frame kernel (GL = bar_lanes_of(n); fused bars:
     // whole waves per row, fewer than 2 * lanes bars).  one chunk of zero weights appended for padding items.
     const uint32_t zero_off = (uint32_t) w.size();
     const uint32_t chunk = glv::bar_chunk_of(b->p.n), gl = (uint32_t) glv::bar_lanes_of(b->p.n);
     w.resize(w.size() + chunk, 0.0f);
     std::vector<glv::BarItem> items;
-    b->bar_nsteps = glv::make_bar_items(items, desc, 256 / gl, zero_off, chunk);
-    HIP_TRY(hipMalloc(&b->d_bar_items, sizeof(glv::BarItem) * items.size()));
-    HIP_TRY(hipMemcpy(b->d_bar_items, items.data(), sizeof(glv::BarItem) * items.size(), hipMemcpyHostToDevice));
+    x.nsteps = glv::make_bar_items(items, desc, 256 / gl, zero_off, chunk);
+    HIP_TRY(x.items.upload(items));
     const int nv = glv::frame_variants(b->log_nn);
-    for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) {
+    for (int v = 0; v < nv && v < kMaxVariants; ++v) {
         const glv::FrameGeometry geo = glv::frame_geometry(b->log_nn, v);
         // bar totals + the dump slot fit the 2 * lanes floats of slack behind the row in LDS
         // (from 256 bars up a bar is one fma chain, glv_tables.h make_bar_mtiles: the chunked loop of the epilogue does not apply)
-        b->bar_fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && b->p.bars + 1 <= 2 * (uint32_t) geo.lanes && b->p.bars < glv::kBarSeqMin && averaging;
-        if (!b->bar_fusable[v]) continue;
+        s.fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && b->p.bars + 1 <= 2 * (uint32_t) geo.lanes && b->p.bars < glv::kBarSeqMin && averaging;
+        if (!s.fusable[v]) continue;
         std::vector<glv::BarItem> fitems;
-        b->bar_fnsteps[v] = glv::make_bar_items(fitems, desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
-        HIP_TRY(hipMalloc(&b->d_bar_fitems[v], sizeof(glv::BarItem) * fitems.size()));
-        HIP_TRY(hipMemcpy(b->d_bar_fitems[v], fitems.data(), sizeof(glv::BarItem) * fitems.size(), hipMemcpyHostToDevice));
+        s.fnsteps[v] = glv::make_bar_items(fitems, desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
+        HIP_TRY(s.fitems[v].upload(fitems));
     }
-    HIP_TRY(hipMalloc(&b->d_bar_desc, sizeof(glv::BarDesc) * desc.size()));
-    HIP_TRY(hipMalloc(&b->d_bar_w, sizeof(float) * w.size()));
-    HIP_TRY(hipMemcpy(b->d_bar_desc, desc.data(), sizeof(glv::BarDesc) * desc.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_bar_w, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
-    b->bar_count = b->p.bars; b->bar_factor = b->p.smooth_factor; b->bar_phase = b->p.bar_phase; b->bar_shape_of = b->p;
-    b->bar_bins_sampled = 0;
-    for (const glv::BarDesc& d : desc) b->bar_bins_sampled = d.first_bin + d.count > b->bar_bins_sampled ? d.first_bin + d.count : b->bar_bins_sampled;
-    b->bar_bins_sampled = (b->bar_bins_sampled + 63u) & ~63u;                      // whole store instructions (the ring fill's 16-byte loads)
-    // many bars (the pre-smoothing pass): tiles of 32 bars for the chain kernels; rounds for the smallest LDS ring that takes them
-    b->bar_ntiles = 0; b->bar_nrounds = 0; b->bar_ring_bins = 0; b->bar_bins_needed = 0;
-    b->update_live_bins();
+    HIP_TRY(s.desc.upload(desc));
+    HIP_TRY(s.w.upload(w));
+    x.count = b->p.bars; x.factor = b->p.smooth_factor; x.phase = b->p.bar_phase; x.shape_of = b->p;
+    s.bins = bins_reached(desc);
     if (!averaging) {                          // sample_mode maximum / hybrid: one lane per bar and row off block-transposed weights, any number of bars
         std::vector<glv::BarModeBlock> blocks;
         std::vector<float> mw;
         glv::make_bar_mode_blocks(blocks, mw, desc, w);
         if (mw.empty()) mw.push_back(0.0f);
-        HIP_TRY(hipMalloc(&b->d_bar_mblocks, sizeof(glv::BarModeBlock) * blocks.size()));
-        HIP_TRY(hipMemcpy(b->d_bar_mblocks, blocks.data(), sizeof(glv::BarModeBlock) * blocks.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&b->d_bar_mw, sizeof(float) * mw.size()));
-        HIP_TRY(hipMemcpy(b->d_bar_mw, mw.data(), sizeof(float) * mw.size(), hipMemcpyHostToDevice));
-        b->bar_nmblocks = (uint32_t) blocks.size();
-        if (b->bar_bins_sampled == 0) b->bar_bins_sampled = 64u;                   // (no bar has a tap: every bar is 0, or 0 / 0 in the hybrid)
-        b->bar_bins_needed = b->bar_bins_sampled;                                  // what a transform in front of the bars has to store of a row
-        return GLV_OK;
-    }
-    if (b->p.bars >= glv::kBarSeqMin) {
+        HIP_TRY(s.mblocks.upload(blocks));
+        HIP_TRY(s.mw.upload(mw));
+        s.nmblocks = (uint32_t) blocks.size();
+        if (s.bins == 0) s.bins = 64u;                                             // (no bar has a tap: every bar is 0, or 0 / 0 in the hybrid)
+        x.bins_needed = s.bins;                                                    // what a transform in front of the bars has to store of a row
+    } else if (b->p.bars >= glv::kBarSeqMin) {
+        // many bars (the pre-smoothing pass): tiles of 32 bars for the chain kernels; rounds for the smallest LDS ring that takes them
         std::vector<glv::BarMTile> mtiles;
         std::vector<glv::BarTile> rounds;
         std::vector<float> wt, wsum;
         for (uint32_t bins : {160u, 288u, 448u, 832u}) {                          // glv_misc.hip launch_bars: the ring sizes the kernel is built for
             if (!glv::make_bar_mtiles(mtiles, wt, wsum, rounds, desc, w, b->p.n, bins, 4u))       // 4 = glv_misc.hip kRowsWaves
                 return fail(GLV_ERR_INVALID, "bars: no tile table (bars=%u)", b->p.bars);
-            if (!rounds.empty()) { b->bar_ring_bins = bins; break; }
+            if (!rounds.empty()) { x.ring_bins = bins; break; }
         }
         if (std::getenv("GLV_NO_BARS_ROWS")) rounds.clear();                        // (diagnostics: the one-lane-per-bar kernel for every row count)
-        HIP_TRY(hipMalloc(&b->d_bar_mtiles, sizeof(glv::BarMTile) * mtiles.size()));
-        HIP_TRY(hipMemcpy(b->d_bar_mtiles, mtiles.data(), sizeof(glv::BarMTile) * mtiles.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&b->d_bar_wt, sizeof(float) * wt.size()));
-        HIP_TRY(hipMemcpy(b->d_bar_wt, wt.data(), sizeof(float) * wt.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&b->d_bar_wsum, sizeof(float) * wsum.size()));
-        HIP_TRY(hipMemcpy(b->d_bar_wsum, wsum.data(), sizeof(float) * wsum.size(), hipMemcpyHostToDevice));
-        b->bar_ntiles = (uint32_t) mtiles.size();
-        b->bar_bins_needed = 0;
-        for (const glv::BarDesc& d : desc) b->bar_bins_needed = d.first_bin + d.count > b->bar_bins_needed ? d.first_bin + d.count : b->bar_bins_needed;
-        b->bar_bins_needed = (b->bar_bins_needed + 63u) & ~63u;                     // whole store instructions (and slack for the fill's 16-byte loads)
+        HIP_TRY(x.mtiles.upload(mtiles));
+        HIP_TRY(x.wt.upload(wt));
+        HIP_TRY(x.wsum.upload(wsum));
+        x.ntiles = (uint32_t) mtiles.size();
+        x.bins_needed = bins_reached(desc);
         if (!rounds.empty()) {
-            HIP_TRY(hipMalloc(&b->d_bar_rounds, sizeof(glv::BarTile) * rounds.size()));
-            HIP_TRY(hipMemcpy(b->d_bar_rounds, rounds.data(), sizeof(glv::BarTile) * rounds.size(), hipMemcpyHostToDevice));
-            b->bar_nrounds = (uint32_t) rounds.size();
-            const glv::BarRowsTables rt = b->rows_tables();
+            HIP_TRY(x.rounds.upload(rounds));
+            x.nrounds = (uint32_t) rounds.size();
+            const glv::BarRowsTables rt = rows_tables(b->p, x, s);
             HIP_TRY(glv::prepare_bars_rows(b->p.n, &rt));
         }
         // texel rows: the integer tables, for the smallest ring that takes them (glv_misc.hip launch_bars_i8: the rings the kernel is built for)
@@ -742,32 +748,30 @@ int ensure_bar_tables(glv_batch* b) {
             std::vector<glv::BarTile> irounds;
             std::vector<int8_t> wq;
             std::vector<glv::BarIFin> fin;
-            b->bar_iring_bins = make_itiles_any_ring(itiles, wq, fin, irounds, desc, w, b->p.n);
-            if (irounds.empty()) b->bar_i8_none = true;
+            x.iring_bins = make_itiles_any_ring(itiles, wq, fin, irounds, desc, w, b->p.n);
+            if (irounds.empty()) x.i8_none = true;
             else {
-                HIP_TRY(hipMalloc(&b->d_bar_itiles, sizeof(glv::BarMTile) * itiles.size()));
-                HIP_TRY(hipMemcpy(b->d_bar_itiles, itiles.data(), sizeof(glv::BarMTile) * itiles.size(), hipMemcpyHostToDevice));
-                HIP_TRY(hipMalloc(&b->d_bar_wq, wq.size()));
-                HIP_TRY(hipMemcpy(b->d_bar_wq, wq.data(), wq.size(), hipMemcpyHostToDevice));
-                HIP_TRY(hipMalloc(&b->d_bar_fin, sizeof(glv::BarIFin) * fin.size()));
-                HIP_TRY(hipMemcpy(b->d_bar_fin, fin.data(), sizeof(glv::BarIFin) * fin.size(), hipMemcpyHostToDevice));
-                HIP_TRY(hipMalloc(&b->d_bar_irounds, sizeof(glv::BarTile) * irounds.size()));
-                HIP_TRY(hipMemcpy(b->d_bar_irounds, irounds.data(), sizeof(glv::BarTile) * irounds.size(), hipMemcpyHostToDevice));
-                b->bar_intiles = (uint32_t) itiles.size(); b->bar_inrounds = (uint32_t) irounds.size();
-                const glv::BarIRowsTables irt = b->irows_tables();
+                HIP_TRY(x.itiles.upload(itiles));
+                HIP_TRY(x.wq.upload(wq));
+                HIP_TRY(x.fin.upload(fin));
+                HIP_TRY(x.irounds.upload(irounds));
+                x.intiles = (uint32_t) itiles.size(); x.inrounds = (uint32_t) irounds.size();
+                const glv::BarIRowsTables irt = x.irows_tables();
                 HIP_TRY(glv::prepare_bars_i8(b->p.n, &irt));
             }
         }
     }
+    b->bar = std::move(s); b->bar_x = std::move(x);
+    b->update_live_bins();
     return GLV_OK;
 }
 
-void drop_snap_tables(glv_batch* b) {
-    auto drop = [](auto*& ptr) { if (ptr) { (void) hipFree(ptr); ptr = nullptr; } };
-    drop(b->d_snap_desc); drop(b->d_snap_w); drop(b->d_snap_mblocks); drop(b->d_snap_mw); drop(b->d_col_items); b->col_nsteps = 0;
-    for (int v = 0; v < glv_batch::kMaxVariants; ++v) { drop(b->d_snap_fitems[v]); b->snap_fusable[v] = false; b->snap_fnsteps[v] = 0; }
-    b->snap_nmblocks = 0; b->snap_bins = 0;
+// the internal rows ([rows][n] floats): whatever of a chain does not stay inside one launch waits there for the next
+int ensure_scratch(glv_batch* b) {
+    if (!b->d_scratch) HIP_TRY(b->d_scratch.alloc((size_t) b->rows * b->p.n, false));
+    return GLV_OK;
 }
+
 bool bars_fusable(const glv_batch* b, unsigned ops);
 // glv_batch_set_column_texels: the most distinct texels the frame kernel's epilogue takes; more go to the second launch (glv_columns_kernel).
 // Measured at N = 4096, 64 K streams (profiles/r08/column_texels.txt): 321 texels fused 1.61 ms, the second launch 2.10 ms, the twin plus a gather 2.09 ms --
@@ -775,10 +779,12 @@ bool bars_fusable(const glv_batch* b, unsigned ops);
 // of the widest configuration (4 x 256 lanes), not a crossover.  801 texels fused (N = 16384, 256 lanes) is tested but not timed.
 constexpr uint32_t kColumnsFuseMax = 1023;
 
-// The tables of bars at texels `tex` of the pre-smoothing pass (glv_batch_set_bar_texels; glv_tables.h make_bar_snap_weights): every check first,
-// then the device tables are replaced -- a refused table leaves the batch as it was.  Synchronous; creation / set calls only.
+// The tables of bars at texels `tex` of the pre-smoothing pass (glv_batch_set_bar_texels; glv_tables.h make_bar_snap_weights), made in `s` / `x`:
+// every check, then the uploads, and the batch's own tables are not touched -- the caller commits them (commit_snap_tables) or, by returning, does
+// not: a refused or failed table leaves the batch as it was.  (The internal rows a second launch needs are the one thing made in the batch, after
+// everything else went through; a batch may always hold them.)  Synchronous; creation / set calls only.
 // columns (glv_batch_set_column_texels): `tex` are the distinct texels the columns read -- bars = their number, not glv_params.bars.
-int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex, bool columns) {
+int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex, bool columns, BarTableSet& s, SnapExtras& x) {
     const uint32_t n = b->p.n, bars = (uint32_t) tex.size();
     const bool averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;
     const glv::BarShape shape = bar_shape(b->p);
@@ -800,80 +806,65 @@ int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex, bool colum
     std::vector<float> w;
     glv::make_bar_taps(desc, w, n, bars, b->p.smooth_factor, 0.5f, shape, tex.data());
     if (!glv::bar_chunks_in_row(desc, n)) return fail(GLV_ERR_INVALID, "bar texels: a tap chunk would leave the row (n=%u smooth_factor=%g)", n, (double) b->p.smooth_factor);
-    uint32_t sampled = 0;
-    for (const glv::BarDesc& d : desc) sampled = d.first_bin + d.count > sampled ? d.first_bin + d.count : sampled;
-    sampled = sampled == 0 ? 64u : (sampled + 63u) & ~63u;
-    std::vector<uint32_t> wi;
-    std::vector<std::vector<glv::BarItem>> fitems(glv_batch::kMaxVariants);
-    uint32_t fnsteps[glv_batch::kMaxVariants] = {};
-    bool fusable[glv_batch::kMaxVariants] = {};
-    std::vector<glv::BarModeBlock> blocks;
-    std::vector<float> mw;
-    std::vector<glv::BarItem> citems;
-    uint32_t cnsteps = 0;
+    s.bins = bins_reached(desc);
+    if (s.bins == 0) s.bins = 64u;
     const int nv = glv::frame_variants(b->log_nn);
     if (averaging) {
+        std::vector<uint32_t> wi;
         if (!glv::make_bar_snap_weights(wi, desc, w)) return fail(GLV_ERR_INVALID, "bar texels: a bar's integer weights do not exist for these parameters");
         const uint32_t zero_off = (uint32_t) wi.size(), chunk = glv::bar_chunk_of(n), gl = (uint32_t) glv::bar_lanes_of(n);
         wi.resize(wi.size() + chunk, 0u);
-        for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) {
+        HIP_TRY(s.w.upload(reinterpret_cast<const float*>(wi.data()), wi.size()));      // (the uint32 weights W' travel as the bits of float weights)
+        for (int v = 0; v < nv && v < kMaxVariants; ++v) {
             const glv::FrameGeometry geo = glv::frame_geometry(b->log_nn, v);
             // every result is 4 bytes behind the row, as the unsnapped totals: bars + the dump slot in the 2 * lanes floats of slack
             // (columns keep 16-bit texels there: twice as many.  kColumnsFuseMax: beyond it the second launch is the quicker route)
-            fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && (columns ? bars + 1 <= 4 * (uint32_t) geo.lanes && bars <= kColumnsFuseMax : bars + 1 <= 2 * (uint32_t) geo.lanes);
-            if (fusable[v]) fnsteps[v] = glv::make_bar_items(fitems[v], desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
+            s.fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && (columns ? bars + 1 <= 4 * (uint32_t) geo.lanes && bars <= kColumnsFuseMax : bars + 1 <= 2 * (uint32_t) geo.lanes);
+            if (!s.fusable[v]) continue;
+            std::vector<glv::BarItem> fitems;
+            s.fnsteps[v] = glv::make_bar_items(fitems, desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
+            HIP_TRY(s.fitems[v].upload(fitems));
         }
-        if (columns) cnsteps = glv::make_bar_items(citems, desc, 256u / gl, zero_off, chunk, (uint32_t) glv::kBarBatch);
+        if (columns) {
+            std::vector<glv::BarItem> citems;
+            x.col_nsteps = glv::make_bar_items(citems, desc, 256u / gl, zero_off, chunk, (uint32_t) glv::kBarBatch);
+            HIP_TRY(x.col_items.upload(citems));
+        }
     } else if (columns) {
-        wi.resize(w.size());                                  // glv_columns_kernel MODE 1 / 2: the float weights in tap order, as bits
-        std::memcpy(wi.data(), w.data(), sizeof(float) * w.size());
-        if (wi.empty()) wi.push_back(0u);
+        if (w.empty()) w.push_back(0.0f);
+        HIP_TRY(s.w.upload(w));                                  // glv_columns_kernel MODE 1 / 2: the float weights in tap order
     } else {
+        std::vector<glv::BarModeBlock> blocks;
+        std::vector<float> mw;
         glv::make_bar_mode_blocks(blocks, mw, desc, w);
         if (mw.empty()) mw.push_back(0.0f);
+        HIP_TRY(s.mblocks.upload(blocks));
+        HIP_TRY(s.mw.upload(mw));
+        s.nmblocks = (uint32_t) blocks.size();
     }
+    HIP_TRY(s.desc.upload(desc));
+    x.tex = tex; x.of = b->p;
     // a second launch needs the chain's rows: the internal rows, unless every chain the creation mask announces fuses in every configuration
     bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
-    for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) all_fused = all_fused && fusable[v];
-    if (!all_fused && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * n));
-    drop_snap_tables(b);
-    HIP_TRY(hipMalloc(&b->d_snap_desc, sizeof(glv::BarDesc) * desc.size()));
-    HIP_TRY(hipMemcpy(b->d_snap_desc, desc.data(), sizeof(glv::BarDesc) * desc.size(), hipMemcpyHostToDevice));
-    if (averaging || columns) {
-        HIP_TRY(hipMalloc(&b->d_snap_w, sizeof(uint32_t) * wi.size()));
-        HIP_TRY(hipMemcpy(b->d_snap_w, wi.data(), sizeof(uint32_t) * wi.size(), hipMemcpyHostToDevice));
-    }
-    if (averaging && columns) {
-        HIP_TRY(hipMalloc(&b->d_col_items, sizeof(glv::BarItem) * citems.size()));
-        HIP_TRY(hipMemcpy(b->d_col_items, citems.data(), sizeof(glv::BarItem) * citems.size(), hipMemcpyHostToDevice));
-        b->col_nsteps = cnsteps;
-    }
-    if (averaging) {
-        for (int v = 0; v < nv && v < glv_batch::kMaxVariants; ++v) {
-            if (!fusable[v]) continue;
-            HIP_TRY(hipMalloc(&b->d_snap_fitems[v], sizeof(glv::BarItem) * fitems[v].size()));
-            HIP_TRY(hipMemcpy(b->d_snap_fitems[v], fitems[v].data(), sizeof(glv::BarItem) * fitems[v].size(), hipMemcpyHostToDevice));
-            b->snap_fusable[v] = true; b->snap_fnsteps[v] = fnsteps[v];
-        }
-    } else if (!columns) {
-        HIP_TRY(hipMalloc(&b->d_snap_mblocks, sizeof(glv::BarModeBlock) * blocks.size()));
-        HIP_TRY(hipMemcpy(b->d_snap_mblocks, blocks.data(), sizeof(glv::BarModeBlock) * blocks.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&b->d_snap_mw, sizeof(float) * mw.size()));
-        HIP_TRY(hipMemcpy(b->d_snap_mw, mw.data(), sizeof(float) * mw.size(), hipMemcpyHostToDevice));
-        b->snap_nmblocks = (uint32_t) blocks.size();
-    }
-    if (&b->snap_tex != &tex) b->snap_tex = tex;
-    b->snap_of = b->p; b->snap_bins = sampled;
+    for (int v = 0; v < nv && v < kMaxVariants; ++v) all_fused = all_fused && s.fusable[v];
+    return all_fused ? GLV_OK : ensure_scratch(b);
+}
+void commit_snap_tables(glv_batch* b, BarTableSet& s, SnapExtras& x) {
+    b->snap = std::move(s); b->snap_x = std::move(x);
     b->update_live_bins();
-    return GLV_OK;
 }
 // the snapped tables follow smooth_factor and the shape (glv_batch_set_params; bar_phase does not enter them)
 bool snap_current(const glv_batch* b) {
-    return b->d_snap_desc && b->snap_of.bars == b->p.bars && same_bits(b->snap_of.smooth_factor, b->p.smooth_factor) && same_shape(b->snap_of, b->p);
+    return b->snap.desc && b->snap_x.of.bars == b->p.bars && same_bits(b->snap_x.of.smooth_factor, b->p.smooth_factor) && same_shape(b->snap_x.of, b->p);
 }
 int ensure_snap_tables(glv_batch* b) {
     if (!b->snapped() || snap_current(b)) return GLV_OK;
-    return build_snap_tables(b, b->snap_tex, b->columns());
+    BarTableSet s;
+    SnapExtras x;
+    if (int rc = build_snap_tables(b, b->snap_x.tex, b->columns(), s, x)) return rc;
+    x.col_tex = std::move(b->snap_x.col_tex); x.col_map = std::move(b->snap_x.col_map);       // the columns' map follows the texels, not the parameters
+    commit_snap_tables(b, s, x);
+    return GLV_OK;
 }
 
 // the gravity step on texels (only the GL_R16 state needs it: 65 536 evaluations on the host whenever g changes -- for the
@@ -895,7 +886,7 @@ bool same_params(const glv_params& a, const glv_params& b) {
 }
 
 // Can the bars of a chain -- or of every chain a creation mask announces -- be computed inside the frame kernel, from the finished row in LDS?
-// The part that does not depend on the kernel configuration (bar_fusable[variant]: whole-wave rows, the bars fit the slack behind the row):
+// The part that does not depend on the kernel configuration (BarTableSet::fusable[variant]: whole-wave rows, the bars fit the slack behind the row):
 // a chain with state and no smoothing pass, whose kernel class takes them -- the float chain's bars as GL_R16 texels leave through
 // glv_bars_kernel, the GL_R16 chain stores them itself, the GL passes one by one (gl_storage 2, the audit log) never fuse; GLV_UNFUSED_BARS
 // (diagnostics) forces two launches.  process() adds that the chain transforms (GLV_OP_FFT) and is not run pass by pass (GLV_OP_RAW).
@@ -933,10 +924,9 @@ int batch_prepare(glv_batch* b) {
         // state.  One difference from process(): under the audit log (log_mode 2) a float chain fuses its bars and gets the rows all the
         // same -- which batches hold them is kept as it was.
         bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
-        for (int v = 0; v < glv::frame_variants(b->log_nn) && v < glv_batch::kMaxVariants; ++v) all_fused = all_fused && b->bar_fusable[v];
-        if (!all_fused && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * b->p.n));
+        for (int v = 0; v < glv::frame_variants(b->log_nn) && v < kMaxVariants; ++v) all_fused = all_fused && b->bar.fusable[v];
         // GLV_OP_WAVE | GLV_OP_BARS in two launches: the waveform kernel's texels (or their floats) wait for the bars kernel in the same rows
-        if ((b->ops_mask & GLV_OP_WAVE) && !b->d_scratch) HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * b->p.n));
+        if (!all_fused || (b->ops_mask & GLV_OP_WAVE)) if (int rc = ensure_scratch(b)) return rc;
         if (int rc = ensure_snap_tables(b)) return rc;
         b->update_live_bins();
     }
@@ -954,8 +944,7 @@ int batch_prepare(glv_batch* b) {
         (void) hipGetLastError();
     }
     // the pass-by-pass GL chain parks the transform's f32 spectra when the caller's buffer cannot take them (texel / bar outputs)
-    if (b->p.gl_storage == 2 && (b->ops_mask & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !b->d_scratch && !b->single_row)
-        HIP_TRY(hipMalloc(&b->d_scratch, sizeof(float) * (size_t) b->rows * b->p.n));
+    if (b->p.gl_storage == 2 && (b->ops_mask & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !b->single_row) return ensure_scratch(b);
     return GLV_OK;
 }
 
@@ -996,9 +985,9 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
     if ((ops & GLV_OP_R16) && !d_out) return fail(GLV_ERR_INVALID, "GLV_OP_R16 needs an output buffer");
     if ((ops & GLV_OP_OUTPUT_IS_STATE) && (!state_is_output || !d_out || (ops & (GLV_OP_BARS | GLV_OP_R16)) || b->p.gl_storage))
         return fail(GLV_ERR_INVALID, "GLV_OP_OUTPUT_IS_STATE needs a chain that ends in gravity with f32 rows out (no AVERAGE / SMOOTH / RAW / BARS / R16, gl_storage 0)");
-    if ((ops & GLV_OP_BARS) && !b->d_bar_desc)
+    if ((ops & GLV_OP_BARS) && !b->bar.desc)
         return fail(GLV_ERR_STATE, "GLV_OP_BARS: the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created; tables are built at creation and by glv_batch_set_params, process calls never allocate)");
-    if ((ops & GLV_OP_BARS) && (b->bar_count != b->p.bars || b->bar_factor != b->p.smooth_factor || b->bar_phase != b->p.bar_phase || !same_shape(b->bar_shape_of, b->p)))
+    if ((ops & GLV_OP_BARS) && (b->bar_x.count != b->p.bars || b->bar_x.factor != b->p.smooth_factor || b->bar_x.phase != b->p.bar_phase || !same_shape(b->bar_x.shape_of, b->p)))
         return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
     if ((ops & GLV_OP_BARS) && b->snapped()) {
         // bars at texels of the pre-smoothing pass: the chain's rows must be what that pass samples -- a GL chain's texels, not smoothed
@@ -1052,7 +1041,7 @@ int plan_wave(glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float* d_ou
     if (!(ops & GLV_OP_BARS)) return GLV_OK;
     const bool averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;
     if (b->snapped()) pl.bars = averaging ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_MODE;
-    else if (averaging && b->p.bars >= glv::kBarSeqMin && b->bars_i8()) pl.bars = ChainPlan::BARS_I8;
+    else if (averaging && b->p.bars >= glv::kBarSeqMin && b->bar_x.i8()) pl.bars = ChainPlan::BARS_I8;
     else pl.bars = ChainPlan::BARS_F32;
     // (the integer pass parks groups of 8 frames: a ring whose oldest frame is not at a multiple of 8 -- an update of a sample_sz / 4 that is not one -- would wrap inside a group)
     pl.wave_fused = pl.bars == ChainPlan::BARS_I8 && (in_mode == glv::IN_S16_STEREO || in_mode == glv::IN_S16_RING) && (rot & 7u) == 0u && !b->unfused_wave && !b->single_row;
@@ -1061,7 +1050,7 @@ int plan_wave(glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float* d_ou
     pl.out = pl.rows = b->d_scratch;
     pl.wave_r16 = pl.bars == ChainPlan::BARS_I8 || pl.bars == ChainPlan::BARS_SNAP;
     // what the bars do not sample is not produced -- where the bars kernel never multiplies what lies beyond (integer weights of 0, taps, staged bins)
-    const uint32_t bins = b->snapped() ? b->snap_bins : b->bar_bins_needed;
+    const uint32_t bins = b->snapped() ? b->snap.bins : b->bar_x.bins_needed;
     if ((pl.bars != ChainPlan::BARS_F32 || !averaging) && bins != 0 && bins < b->p.n) pl.wave_limit = bins;
     return GLV_OK;
 }
@@ -1079,8 +1068,8 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t
     // the state the operators keep anyway); otherwise the spectra stay internal -- in the gravity state
     // when the chain ends in gravity, in the scratch rows else -- and a bars kernel runs after.
     const bool snap = (ops & GLV_OP_BARS) && b->snapped();      // (check_ops: a GL chain's texel rows)
-    pl.fused_bars = (ops & GLV_OP_BARS) && (ops & GLV_OP_FFT) && !gl_passes && bars_fusable(b, ops) && pl.variant < glv_batch::kMaxVariants
-                    && (snap ? b->snap_fusable[pl.variant] : b->bar_fusable[pl.variant]);
+    pl.fused_bars = (ops & GLV_OP_BARS) && (ops & GLV_OP_FFT) && !gl_passes && bars_fusable(b, ops) && pl.variant < kMaxVariants
+                    && (snap ? b->snap : b->bar).fusable[pl.variant];
     pl.out = d_out;
     if (ops & GLV_OP_BARS) {
         const bool state_is_output = (ops & GLV_OP_GRAVITY) && !(ops & (GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_RAW));
@@ -1100,7 +1089,7 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t
     if (!(ops & GLV_OP_BARS) || pl.fused_bars) pl.bars = ChainPlan::NO_BARS;
     else if (snap && b->columns()) pl.bars = ChainPlan::BARS_COLUMNS;
     else if (snap) pl.bars = b->p.sample_mode != GLV_SAMPLE_AVERAGE ? ChainPlan::BARS_SNAP_MODE : pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_FLOATS;
-    else if (b->p.bars >= glv::kBarSeqMin && b->bars_i8() && (pl.route == ChainPlan::GL_FUSED || (gl_passes && !(ops & GLV_OP_SMOOTH))))
+    else if (b->p.bars >= glv::kBarSeqMin && b->bar_x.i8() && (pl.route == ChainPlan::GL_FUSED || (gl_passes && !(ops & GLV_OP_SMOOTH))))
         pl.bars = pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_I8 : ChainPlan::BARS_I8_FLOATS;
     else pl.bars = ChainPlan::BARS_F32;
     if (pl.route == ChainPlan::GL_PASSES) pl.ops = frame_ops(b, ops);
@@ -1110,7 +1099,7 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t
         if (pl.bars == ChainPlan::BARS_I8 || pl.bars == ChainPlan::BARS_SNAP) pl.ops |= glv::OP_R16;   // ... but the GL_R16 chain hands the integer pass its rows as 16-bit texels
     }
     // the GL_R16 chain's rows go to the bars of a second launch and nowhere else (the scratch rows): what those bars do not sample is not stored
-    const uint32_t bins_needed = snap ? b->snap_bins : b->bar_bins_needed;
+    const uint32_t bins_needed = snap ? b->snap.bins : b->bar_x.bins_needed;
     if (pl.route == ChainPlan::GL_FUSED && pl.bars != ChainPlan::NO_BARS && bins_needed != 0 && bins_needed < b->p.n)
         pl.out_limit = bins_needed * 4u;
     // GLV_OP_BARS_ONLY: ... and what they do not sample is not computed, nor is its state kept -- the GL_R16 chain, and a float chain with
@@ -1125,18 +1114,18 @@ int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, uint32_t 
     hipError_t e;
     if (pl.bars == ChainPlan::NO_BARS) return GLV_OK;
     if (pl.bars == ChainPlan::BARS_F32) {
-        const glv::BarRowsTables rt = b->rows_tables();
-        e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w, st, r16, &rt);
+        const glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->bar);
+        e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, b->bar_x.nsteps, b->bar_x.items, b->bar.desc, b->bar.w, st, r16, &rt);
     } else if (pl.bars == ChainPlan::BARS_SNAP || pl.bars == ChainPlan::BARS_SNAP_FLOATS) {
-        e = glv::launch_bars_snap(pl.rows, pl.bars == ChainPlan::BARS_SNAP_FLOATS, d_bars, units, b->p.n, b->p.bars, b->d_snap_desc, b->d_snap_w, st, r16);
+        e = glv::launch_bars_snap(pl.rows, pl.bars == ChainPlan::BARS_SNAP_FLOATS, d_bars, units, b->p.n, b->p.bars, b->snap.desc, reinterpret_cast<const uint32_t*>(b->snap.w.get()), st, r16);
     } else if (pl.bars == ChainPlan::BARS_COLUMNS) {
-        e = glv::launch_columns(pl.rows, d_bars, units, b->p.n, (uint32_t) b->snap_tex.size(), b->p.bars, b->col_nsteps, b->d_col_items, b->d_snap_desc,
-                                reinterpret_cast<const float*>(b->d_snap_w), b->d_col_map, b->p.sample_mode, shape_hybrid(b->p), st);
+        e = glv::launch_columns(pl.rows, d_bars, units, b->p.n, (uint32_t) b->snap_x.tex.size(), b->p.bars, b->snap_x.col_nsteps, b->snap_x.col_items, b->snap.desc,
+                                b->snap.w, b->snap_x.col_map, b->p.sample_mode, shape_hybrid(b->p), st);
     } else if (pl.bars == ChainPlan::BARS_SNAP_MODE) {
-        const glv::BarRowsTables rt = b->snap_rows_tables();
-        e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, 0, nullptr, b->d_snap_desc, nullptr, st, r16, &rt);
+        const glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->snap);
+        e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, 0, nullptr, b->snap.desc, nullptr, st, r16, &rt);
     } else {
-        const glv::BarIRowsTables irt = b->irows_tables();
+        const glv::BarIRowsTables irt = b->bar_x.irows_tables();
         e = glv::launch_bars_i8(pl.rows, pl.bars == ChainPlan::BARS_I8_FLOATS, d_bars, units, b->p.n, b->p.bars, &irt, st, r16);
     }
     ++b->last_launches;
@@ -1149,7 +1138,7 @@ int run_wave(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, f
     if (int rc = timed_launch_begin(b, st)) return rc;
     hipError_t e;
     if (pl.wave_fused) {
-        const glv::BarIRowsTables irt = b->irows_tables();
+        const glv::BarIRowsTables irt = b->bar_x.irows_tables();
         e = glv::launch_bars_i8_pcm(d_in, rot, mono, d_out, units, b->p.n, b->p.bars, &irt, st, (ops & GLV_OP_R16) != 0);
         b->kernel_name = "glv_bars_rows_i8_kernel";
     } else {
@@ -1183,13 +1172,10 @@ int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, 
         a.grav_w = d_out; a.out = nullptr;
     }
     const float* grav_next = gravity_only ? (out_is_state ? d_out : b->d_grav) : b->grav_cur;
-    if (pl.fused_bars && (ops & GLV_OP_BARS) && b->snapped()) {
-        a.bar_desc = b->d_snap_desc; a.bar_items = b->d_snap_fitems[pl.variant]; a.bar_nsteps = b->snap_fnsteps[pl.variant];
-        a.bar_w = reinterpret_cast<const float*>(b->d_snap_w);     // (the uint32 weights W' travel as the bits of the float weights; kernel class FC_GL16_SNAP*)
-        a.bars = b->p.bars; a.bars_out = d_out; a.col_map = b->d_col_map;
-    } else if (pl.fused_bars) {
-        a.bar_desc = b->d_bar_desc; a.bar_items = b->d_bar_fitems[pl.variant]; a.bar_nsteps = b->bar_fnsteps[pl.variant]; a.bar_w = b->d_bar_w;
-        a.bars = b->p.bars; a.bars_out = d_out;
+    if (pl.fused_bars) {
+        const BarTableSet& t = b->snapped() ? b->snap : b->bar;   // (snapped: the uint32 weights W' travel as the bits of float weights; kernel class FC_GL16_SNAP*)
+        a.bar_desc = t.desc; a.bar_items = t.fitems[pl.variant]; a.bar_nsteps = t.fnsteps[pl.variant]; a.bar_w = t.w;
+        a.bars = b->p.bars; a.bars_out = d_out; a.col_map = b->snap_x.col_map;      // (NULL unless column texels are set)
     }
     if (pl.route == ChainPlan::GL_FUSED) a.gl_storage = 1;
     if (pl.route == ChainPlan::POST && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) a.gl_storage = b->p.gl_storage;   // the post kernel models it directly
@@ -1297,6 +1283,55 @@ int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, 
     return GLV_OK;
 }
 
+// ---- the single-stream drop-ins' two steps ----------------------------------------------------------
+// Scalar knobs may change between calls, exactly like gl_data fields: what depends on them is regenerated when they do (compared
+// field by field: padding bytes of a caller's struct mean nothing).  GLava's measured `ur` changes every frame (render.c:2387):
+// that touches nothing but the gravity step -- no table, no launch plan.
+int sync_params(glv_batch* b, const glv_params* p) {
+    if (same_params(b->p, *p)) return GLV_OK;
+    glv_params rest = *p;
+    rest.ur = b->p.ur; rest.gravity_step = b->p.gravity_step;
+    if (!same_params(b->p, rest)) return glv_batch_set_params(b, p);
+    b->p.ur = p->ur; b->p.gravity_step = p->gravity_step;
+    update_gravity_step(b);
+    return GLV_OK;
+}
+
+// One update of the state's row from host memory and back: in_bytes of `in` through the staging, `ops`, out_bytes into `out` -- floats
+// through the same staging, or GL_R16 texels (`texels`) through a staging of their own, made by the first call that asks for it.
+// Mapped staging: memcpy in, one launch, one synchronisation, memcpy out.  Copy staging (GLV_STAGING=copy), and GLV_OP_SMOOTH under
+// either (its row goes to the device buffer `seq`): two asynchronous copies around the launch.
+int round_trip(glv_state* s, const void* in, size_t in_bytes, void* out, size_t out_bytes, unsigned ops, bool texels) {
+    glv_batch* b = s->b;
+    HIP_TRY(hipSetDevice(b->device));
+    const bool via_seq = s->mapped && (ops & GLV_OP_SMOOTH);
+    if (via_seq && !s->seq) HIP_TRY(s->seq.alloc(b->p.n, false));
+    if (texels && !s->d_tex) {
+        if (s->mapped) {
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_tex), out_bytes, hipHostMallocMapped));
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->d_tex), s->h_tex, 0));
+        } else {
+            HIP_TRY(s->tex_copy.alloc(b->p.n, false));
+            s->d_tex = s->tex_copy;
+        }
+    }
+    float* d_in = via_seq ? s->seq.get() : s->d_io;
+    float* d_out = texels ? reinterpret_cast<float*>(s->d_tex) : d_in;
+    if (s->mapped && !via_seq) {
+        std::memcpy(s->h_io, in, in_bytes);
+        const int rc = process(b, d_in, glv::IN_F32_PLANAR, d_out, ops, 1, 0, nullptr);
+        HIP_TRY(hipStreamSynchronize(nullptr));        // also after a failed launch: nothing may still be reading h_io
+        if (rc) return rc;
+        std::memcpy(out, texels ? static_cast<const void*>(s->h_tex) : s->h_io, out_bytes);
+        return GLV_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, nullptr));
+    if (int rc = process(b, d_in, glv::IN_F32_PLANAR, d_out, ops, 1, 0, nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return GLV_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -1385,29 +1420,8 @@ int glv_batch_destroy(glv_batch* b) {
     b->tab.destroy();
     state_free(b->d_grav);
     state_free(b->d_hist);
-    if (b->d_ring) (void) hipFree(b->d_ring);
-    if (b->d_scratch) (void) hipFree(b->d_scratch);
-    if (b->d_ring_f32) (void) hipFree(b->d_ring_f32);
-    if (b->d_smin) (void) hipFree(b->d_smin);
-    if (b->d_smax) (void) hipFree(b->d_smax);
-    if (b->d_bar_desc) (void) hipFree(b->d_bar_desc);
-    if (b->d_bar_w) (void) hipFree(b->d_bar_w);
-    if (b->d_bar_items) (void) hipFree(b->d_bar_items);
-    for (glv::BarItem* f : b->d_bar_fitems) if (f) (void) hipFree(f);
-    if (b->d_bar_mtiles) (void) hipFree(b->d_bar_mtiles);
-    if (b->d_bar_wt) (void) hipFree(b->d_bar_wt);
-    if (b->d_bar_wsum) (void) hipFree(b->d_bar_wsum);
-    if (b->d_bar_rounds) (void) hipFree(b->d_bar_rounds);
-    if (b->d_bar_itiles) (void) hipFree(b->d_bar_itiles);
-    if (b->d_bar_wq) (void) hipFree(b->d_bar_wq);
-    if (b->d_bar_fin) (void) hipFree(b->d_bar_fin);
-    if (b->d_bar_irounds) (void) hipFree(b->d_bar_irounds);
-    if (b->d_bar_mblocks) (void) hipFree(b->d_bar_mblocks);
-    if (b->d_bar_mw) (void) hipFree(b->d_bar_mw);
-    drop_snap_tables(b);
-    if (b->d_col_map) (void) hipFree(b->d_col_map);
     for (hipEvent_t e : b->ev) (void) hipEventDestroy(e);
-    delete b;
+    delete b;                    // every table and ring frees itself (DeviceArray)
     return GLV_OK;
 }
 
@@ -1451,11 +1465,11 @@ static int ring_push(glv_batch* b, bool f32, const void* d_new, uint32_t new_fra
     if (new_frames == 0 || new_frames > n)
         return fail(GLV_ERR_INVALID, "new_frames=%u: must be in [1, n=%u] (sample_sz/4 of %s)", new_frames, n, f32 ? "pulse_input.c:155-178" : "fifo.c:38,91");
     const size_t fb = f32 ? 8 : 4;
-    void** ring = f32 ? reinterpret_cast<void**>(&b->d_ring_f32) : reinterpret_cast<void**>(&b->d_ring);
+    char* ring = f32 ? reinterpret_cast<char*>(b->d_ring_f32.get()) : reinterpret_cast<char*>(b->d_ring.get());
     uint32_t* pos = f32 ? &b->ring_pos_f32 : &b->ring_pos;
-    if (!*ring)
+    if (!ring)
         return fail(GLV_ERR_STATE, "the batch was created without GLV_OP_RING_%s in its ops_mask (rings are allocated at creation, ring updates never allocate)", f32 ? "F32" : "S16");
-    if (int rc = ring_append(static_cast<char*>(*ring), static_cast<const char*>(d_new), *pos, new_frames, n, fb, b->streams, st)) return rc;
+    if (int rc = ring_append(ring, static_cast<const char*>(d_new), *pos, new_frames, n, fb, b->streams, st)) return rc;
     *old_pos = *pos;
     *pos = (*pos + new_frames) % n;                              // the oldest frame now sits here: the window starts there
     return GLV_OK;
@@ -1507,7 +1521,7 @@ int glv_batch_ring_append_f32(glv_batch* b, const float* d_new, uint32_t new_fra
 int glv_batch_ring_planar(glv_batch* b, int f32_ring, float* d_planar, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_planar) return fail(GLV_ERR_INVALID, "NULL device pointer");
-    const void* ring = f32_ring ? static_cast<const void*>(b->d_ring_f32) : static_cast<const void*>(b->d_ring);
+    const void* ring = f32_ring ? static_cast<const void*>(b->d_ring_f32.get()) : static_cast<const void*>(b->d_ring.get());
     if (!ring) return fail(GLV_ERR_STATE, "the batch has no %s ring yet (create it with GLV_OP_RING_%s or append to it first)", f32_ring ? "f32" : "s16", f32_ring ? "F32" : "S16");
     HIP_TRY(hipSetDevice(b->device));
     hipError_t e = glv::launch_ring_planar(ring, f32_ring ? 1 : 0, b->p.n, f32_ring ? b->ring_pos_f32 : b->ring_pos, b->p.channels == 1, b->streams,
@@ -1533,10 +1547,10 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
     if (!d_spec || !d_bars) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (b->p.bars == 0 || b->p.bars > b->p.n) return fail(GLV_ERR_INVALID, "bars=%u out of range", b->p.bars);
     HIP_TRY(hipSetDevice(b->device));
-    if (!b->d_bar_desc) return fail(GLV_ERR_STATE, "the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created)");
+    if (!b->bar.desc) return fail(GLV_ERR_STATE, "the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created)");
     if (b->snapped()) return fail(GLV_ERR_STATE, "glv_batch_bars takes float spectra, not a GL chain's texels: refused while bar texels or column texels are set (glv_batch_set_bar_texels / glv_batch_set_column_texels)");
-    const glv::BarRowsTables rt = b->rows_tables();
-    hipError_t e = glv::launch_bars(d_spec, d_bars, (size_t) b->streams * 2, b->p.n, b->p.bars, b->bar_nsteps, b->d_bar_items, b->d_bar_desc, b->d_bar_w,
+    const glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->bar);
+    hipError_t e = glv::launch_bars(d_spec, d_bars, (size_t) b->streams * 2, b->p.n, b->p.bars, b->bar_x.nsteps, b->bar_x.items, b->bar.desc, b->bar.w,
                                     (hipStream_t) hip_stream, false, &rt);
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "bars launch failed: %s", hipGetErrorString(e));
     return GLV_OK;
@@ -1548,19 +1562,17 @@ static int set_snap_texels(glv_batch* b, const uint32_t* texels, uint32_t count,
     const char* what = cols ? "column texels" : "bar texels";
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     HIP_TRY(hipSetDevice(b->device));
-    // the tables are replaced in place: every kernel already queued on the device must have read them first (as glv_batch_set_params)
+    // the old tables are freed: every kernel already queued on the device must have read them first (as glv_batch_set_params)
     HIP_TRY(hipDeviceSynchronize());
     if (texels == nullptr || count == 0) {                 // off: the unsnapped tables, untouched meanwhile, serve again
         if (b->snapped() && b->columns() != cols) return GLV_OK;      // (the other kind of table is set: this kind is off already)
-        drop_snap_tables(b);
-        b->snap_tex.clear(); b->col_tex.clear();
-        if (b->d_col_map) { (void) hipFree(b->d_col_map); b->d_col_map = nullptr; }
+        b->snap = BarTableSet(); b->snap_x = SnapExtras();
         b->update_live_bins();
         return GLV_OK;
     }
     if (b->snapped() && b->columns() != cols)
         return fail(GLV_ERR_STATE, "%s: %s are set on this batch -- the two tables exclude each other, clear the other one first", what, cols ? "bar texels" : "column texels");
-    if (!(b->ops_mask & GLV_OP_BARS) || !b->d_bar_desc)
+    if (!(b->ops_mask & GLV_OP_BARS) || !b->bar.desc)
         return fail(GLV_ERR_STATE, "%s: the batch was created without GLV_OP_BARS (or has no bar tables)", what);
     if (b->p.gl_storage == 0)
         return fail(GLV_ERR_STATE, "%s: gl_storage 0 -- a float chain has no pre-smoothed texture to sample", what);
@@ -1580,25 +1592,19 @@ static int set_snap_texels(glv_batch* b, const uint32_t* texels, uint32_t count,
             map[x] = glv::ColumnMap{at(texels[3 * x]), at(texels[3 * x + 1]), at(texels[3 * x + 2]), 0};
         }
     }
-    const uint32_t live_before = b->live_bins();
-    const std::vector<uint32_t> before = b->snap_tex;
-    int rc = build_snap_tables(b, tex, cols);
+    // built beside the batch's tables and committed as the last step: whatever refuses or fails before leaves the batch exactly as it was
+    BarTableSet set;
+    SnapExtras extras;
+    if (int rc = build_snap_tables(b, tex, cols, set, extras)) return rc;
     // (as glv_batch_set_params: a GLV_OP_BARS_ONLY batch that ran its live class cannot start sampling beyond the bins it kept)
-    if (rc == GLV_OK && b->ran_live && b->live_bins() != live_before) {
-        if (before.empty()) { drop_snap_tables(b); b->snap_tex.clear(); b->update_live_bins(); }
-        else (void) build_snap_tables(b, before, cols);
-        rc = fail(GLV_ERR_STATE, "%s: these taps reach beyond the live bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first", what);
+    if (b->ran_live && b->live_bins_with(set.bins) != b->live_bins())
+        return fail(GLV_ERR_STATE, "%s: these taps reach beyond the live bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first", what);
+    if (cols) {
+        HIP_TRY(extras.col_map.upload(map));
+        extras.col_tex.assign(texels, texels + (size_t) count * 3);
     }
-    if (rc == GLV_OK && cols) {
-        glv::ColumnMap* d_map = nullptr;
-        HIP_TRY(hipMalloc(&d_map, sizeof(glv::ColumnMap) * map.size()));
-        hipError_t e = hipMemcpy(d_map, map.data(), sizeof(glv::ColumnMap) * map.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void) hipFree(d_map); HIP_TRY(e); }
-        if (b->d_col_map) (void) hipFree(b->d_col_map);
-        b->d_col_map = d_map;
-        b->col_tex.assign(texels, texels + (size_t) count * 3);
-    }
-    return rc;
+    commit_snap_tables(b, set, extras);
+    return GLV_OK;
 }
 int glv_batch_set_bar_texels(glv_batch* b, const uint32_t* texels, uint32_t count) { return set_snap_texels(b, texels, count, 1); }
 int glv_batch_set_column_texels(glv_batch* b, const uint32_t* texels, uint32_t count) { return set_snap_texels(b, texels, count, 3); }
@@ -1661,7 +1667,7 @@ uint64_t glv_batch_algorithmic_bytes(const glv_batch* b, unsigned ops, int input
         // bars.  The texel rows between the two launches of the unfused forms are traffic of the organisation and are not counted.
         const uint64_t in_b = input_is_s16 ? 4 : 8, out_b = (ops & GLV_OP_R16) ? 4 : 8;
         if (!(ops & GLV_OP_BARS)) return (in_b * N + out_b * N) * b->streams;
-        uint64_t reach = b->snapped() ? b->snap_bins : b->bar_bins_sampled;
+        uint64_t reach = b->snapped() ? b->snap.bins : b->bar.bins;
         if (reach == 0 || reach > N) reach = N;
         return (in_b * reach + out_b * b->p.bars) * b->streams;
     }
@@ -1686,11 +1692,11 @@ uint32_t glv_batch_live_bins(const glv_batch* b) { return b ? b->live_bins() : 0
 const char* glv_batch_kernel_name(const glv_batch* b) { return b ? b->kernel_name : ""; }
 
 int glv_batch_bars_arithmetic(const glv_batch* b) {
-    if (!b || b->bar_count == 0 || !b->d_bar_desc) return GLV_BARS_NONE;
+    if (!b || b->bar_x.count == 0 || !b->bar.desc) return GLV_BARS_NONE;
     if (b->snapped()) return b->p.sample_mode != GLV_SAMPLE_AVERAGE ? GLV_BARS_F32_SEQ : GLV_BARS_I8_EXACT;   // the twin's (set_bar_texels made sure)
     if (b->p.sample_mode != GLV_SAMPLE_AVERAGE) return GLV_BARS_F32_SEQ;
     if (b->p.bars < glv::kBarSeqMin) return GLV_BARS_F32_CHAIN;
-    return b->p.gl_storage != 0 && b->bars_i8() ? GLV_BARS_I8_EXACT : GLV_BARS_F32_MATRIX;
+    return b->p.gl_storage != 0 && b->bar_x.i8() ? GLV_BARS_I8_EXACT : GLV_BARS_F32_MATRIX;
 }
 
 int glv_batch_last_grid(const glv_batch* b) { return b ? b->last_grid : 0; }
@@ -1913,27 +1919,16 @@ int glv_state_create(const glv_params* p, int device, glv_state** out) {
 
 int glv_state_reset(glv_state* s) {
     if (!s || !s->b) return fail(GLV_ERR_INVALID, "state is NULL");
-    glv_batch* b = s->b;
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t n = b->p.n;
-    const size_t esz = b->state16 ? sizeof(uint16_t) : sizeof(float);
-    HIP_TRY(hipMemset(b->d_hist, 0, esz * b->p.avg_frames * n));
-    HIP_TRY(hipMemset(b->d_grav, 0, esz * n));
-    b->head = 0; b->grav_mode = 0; b->grav_cur = b->d_grav;
-    return GLV_OK;
+    return glv_batch_reset(s->b);      // one row, no rings: the same two memsets; the positions and flags it clears besides are never set on such a batch
 }
 
 int glv_state_destroy(glv_state* s) {
     if (!s) return GLV_OK;
     if (s->b) { (void) hipSetDevice(s->b->device); glv_batch_destroy(s->b); }
-    if (s->d_seq) (void) hipFree(s->d_seq);
     if (s->mapped) {
         if (s->h_io) (void) hipHostFree(s->h_io);
         if (s->h_tex) (void) hipHostFree(s->h_tex);
-    } else {
-        if (s->d_io) (void) hipFree(s->d_io);
-        if (s->d_tex) (void) hipFree(s->d_tex);
-    }
+    } else if (s->d_io) (void) hipFree(s->d_io);
     delete s;
     return GLV_OK;
 }
@@ -1945,40 +1940,8 @@ static int single(const glv_params* p, glv_state* s, float* buf, unsigned ops) {
     glv_batch* b = s->b;
     if (p->n != b->p.n || p->avg_frames != b->p.avg_frames)
         return fail(GLV_ERR_STATE, "params (n=%u, F=%u) do not match the state (n=%u, F=%u)", p->n, p->avg_frames, b->p.n, b->p.avg_frames);
-    // scalar knobs may change between calls, exactly like gl_data fields: what depends on them is regenerated when they do
-    // (compared field by field: padding bytes of a caller's struct mean nothing.  GLava's measured `ur` changes every frame
-    // (render.c:2387): that touches nothing but the gravity step -- no table, no launch plan)
-    if (!same_params(b->p, *p)) {
-        glv_params rest = *p;
-        rest.ur = b->p.ur; rest.gravity_step = b->p.gravity_step;
-        if (same_params(b->p, rest)) {
-            b->p.ur = p->ur; b->p.gravity_step = p->gravity_step;
-            update_gravity_step(b);
-        } else if (int rc = glv_batch_set_params(b, p)) return rc;
-    }
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t bytes = sizeof(float) * p->n;
-    if (s->mapped && (ops & GLV_OP_SMOOTH)) {
-        if (!s->d_seq) HIP_TRY(hipMalloc(&s->d_seq, bytes));
-        HIP_TRY(hipMemcpyAsync(s->d_seq, buf, bytes, hipMemcpyHostToDevice, nullptr));
-        if (int rc = process(b, s->d_seq, glv::IN_F32_PLANAR, s->d_seq, ops, 1, 0, nullptr)) return rc;
-        HIP_TRY(hipMemcpyAsync(buf, s->d_seq, bytes, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return GLV_OK;
-    }
-    if (s->mapped) {
-        std::memcpy(s->h_io, buf, bytes);
-        const int rc = process(b, s->d_io, glv::IN_F32_PLANAR, s->d_io, ops, 1, 0, nullptr);
-        HIP_TRY(hipStreamSynchronize(nullptr));        // also after a failed launch: nothing may still be reading h_io
-        if (rc) return rc;
-        std::memcpy(buf, s->h_io, bytes);
-        return GLV_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(s->d_io, buf, bytes, hipMemcpyHostToDevice, nullptr));
-    if (int rc = process(b, s->d_io, glv::IN_F32_PLANAR, s->d_io, ops, 1, 0, nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(buf, s->d_io, bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return GLV_OK;
+    if (int rc = sync_params(b, p)) return rc;
+    return round_trip(s, buf, sizeof(float) * p->n, buf, sizeof(float) * p->n, ops, false);
 }
 
 int glv_fft(const glv_params* p, glv_state* s, float* buf) { return single(p, s, buf, GLV_OP_FFT); }
@@ -1994,27 +1957,9 @@ int glv_texels_r16(const glv_params* p, glv_state* s, const float* buf, uint16_t
     if (!s || !s->b) return fail(GLV_ERR_INVALID, "state is NULL");
     if (!buf || !texels) return fail(GLV_ERR_INVALID, "NULL buffer");
     if (int rc = validate(p)) return rc;
-    glv_batch* b = s->b;
-    if (p->n != b->p.n) return fail(GLV_ERR_STATE, "params n=%u does not match the state (n=%u)", p->n, b->p.n);
-    HIP_TRY(hipSetDevice(b->device));
-    if (s->mapped) {
-        if (!s->h_tex) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_tex), sizeof(uint16_t) * p->n, hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->d_tex), s->h_tex, 0));
-        }
-        std::memcpy(s->h_io, buf, sizeof(float) * p->n);
-        const int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), GLV_OP_R16, 1, 0, nullptr);
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if (rc) return rc;
-        std::memcpy(texels, s->h_tex, sizeof(uint16_t) * p->n);
-        return GLV_OK;
-    }
-    if (!s->d_tex) HIP_TRY(hipMalloc(&s->d_tex, sizeof(uint16_t) * p->n));
-    HIP_TRY(hipMemcpyAsync(s->d_io, buf, sizeof(float) * p->n, hipMemcpyHostToDevice, nullptr));
-    if (int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), GLV_OP_R16, 1, 0, nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(texels, s->d_tex, sizeof(uint16_t) * p->n, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return GLV_OK;
+    if (p->n != s->b->p.n) return fail(GLV_ERR_STATE, "params n=%u does not match the state (n=%u)", p->n, s->b->p.n);
+    // (the conversion reads no knob: the state's parameters stay as they are)
+    return round_trip(s, buf, sizeof(float) * p->n, texels, sizeof(uint16_t) * p->n, GLV_OP_R16, true);
 }
 
 int glv_gl_texture(const glv_params* p, glv_state* s, const float* buf, int smooth_pass, uint16_t* texels) {
@@ -2027,34 +1972,10 @@ int glv_gl_texture(const glv_params* p, glv_state* s, const float* buf, int smoo
     if (p->gl_storage != 1 || !b->state16) return fail(GLV_ERR_STATE, "glv_gl_texture needs a state created with gl_storage = 1 (the GL passes' GL_R16 storage)");
     if (smooth_pass && (p->bars != p->n || !(b->ops_mask & GLV_OP_BARS)))
         return fail(GLV_ERR_INVALID, "glv_gl_texture with the pre-smoothing pass: bars must equal n (bar_phase 0.5: the pass's texel centres) when the state is created");
-    if (!same_params(b->p, *p)) {
-        glv_params rest = *p;
-        rest.ur = b->p.ur; rest.gravity_step = b->p.gravity_step;
-        if (same_params(b->p, rest)) { b->p.ur = p->ur; b->p.gravity_step = p->gravity_step; update_gravity_step(b); }
-        else if (int rc = glv_batch_set_params(b, p)) return rc;
-    }
-    HIP_TRY(hipSetDevice(b->device));
+    if (int rc = sync_params(b, p)) return rc;
     // render.c:2230: no averaging pass with a single frame; the chain then ends in the gravity store
     const unsigned ops = GLV_OP_FFT | GLV_OP_GRAVITY | (p->avg_frames > 1 ? (unsigned) GLV_OP_AVERAGE : 0u) | (smooth_pass ? (unsigned) GLV_OP_BARS : 0u) | GLV_OP_R16;
-    const size_t in_bytes = sizeof(float) * p->n, out_bytes = sizeof(uint16_t) * p->n;
-    if (s->mapped) {
-        if (!s->h_tex) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_tex), out_bytes, hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->d_tex), s->h_tex, 0));
-        }
-        std::memcpy(s->h_io, buf, in_bytes);
-        const int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), ops, 1, 0, nullptr);
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if (rc) return rc;
-        std::memcpy(texels, s->h_tex, out_bytes);
-        return GLV_OK;
-    }
-    if (!s->d_tex) HIP_TRY(hipMalloc(&s->d_tex, out_bytes));
-    HIP_TRY(hipMemcpyAsync(s->d_io, buf, in_bytes, hipMemcpyHostToDevice, nullptr));
-    if (int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), ops, 1, 0, nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(texels, s->d_tex, out_bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return GLV_OK;
+    return round_trip(s, buf, sizeof(float) * p->n, texels, sizeof(uint16_t) * p->n, ops, true);
 }
 
 int glv_wave_texture(const glv_params* p, glv_state* s, const float* buf, int smooth_pass, uint16_t* texels) {
@@ -2068,33 +1989,9 @@ int glv_wave_texture(const glv_params* p, glv_state* s, const float* buf, int sm
         return fail(GLV_ERR_STATE, "glv_wave_texture with the pre-smoothing pass needs a state created with gl_storage = 1 and bars = n (the pass samples GL_R16 texels)");
     if (smooth_pass && p->bars != p->n)
         return fail(GLV_ERR_INVALID, "glv_wave_texture with the pre-smoothing pass: bars must equal n (bar_phase 0.5: the pass's texel centres)");
-    if (!same_params(b->p, *p)) {
-        glv_params rest = *p;
-        rest.ur = b->p.ur; rest.gravity_step = b->p.gravity_step;
-        if (same_params(b->p, rest)) { b->p.ur = p->ur; b->p.gravity_step = p->gravity_step; update_gravity_step(b); }
-        else if (int rc = glv_batch_set_params(b, p)) return rc;
-    }
-    HIP_TRY(hipSetDevice(b->device));
+    if (int rc = sync_params(b, p)) return rc;
     const unsigned ops = GLV_OP_WAVE | (smooth_pass ? (unsigned) GLV_OP_BARS : 0u) | GLV_OP_R16;
-    const size_t in_bytes = sizeof(float) * p->n, out_bytes = sizeof(uint16_t) * p->n;
-    if (s->mapped) {
-        if (!s->h_tex) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_tex), out_bytes, hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->d_tex), s->h_tex, 0));
-        }
-        std::memcpy(s->h_io, buf, in_bytes);
-        const int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), ops, 1, 0, nullptr);
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if (rc) return rc;
-        std::memcpy(texels, s->h_tex, out_bytes);
-        return GLV_OK;
-    }
-    if (!s->d_tex) HIP_TRY(hipMalloc(&s->d_tex, out_bytes));
-    HIP_TRY(hipMemcpyAsync(s->d_io, buf, in_bytes, hipMemcpyHostToDevice, nullptr));
-    if (int rc = process(b, s->d_io, glv::IN_F32_PLANAR, reinterpret_cast<float*>(s->d_tex), ops, 1, 0, nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(texels, s->d_tex, out_bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return GLV_OK;
+    return round_trip(s, buf, sizeof(float) * p->n, texels, sizeof(uint16_t) * p->n, ops, true);
 }
 
 int glv_device_malloc(int device, size_t bytes, void** d_ptr) {
@@ -2133,20 +2030,15 @@ int glv_unpack_s16(int device, const int16_t* pcm, size_t frames, int channels, 
     if (channels != 1 && channels != 2) return fail(GLV_ERR_INVALID, "channels=%d: must be 1 or 2", channels);
     if (frames == 0) return GLV_OK;
     if (int rc = ensure_device(device)) return rc;
-    int16_t* d_pcm = nullptr; float* d_l = nullptr; float* d_r = nullptr;
-    int rc = GLV_OK;
-    auto cleanup = [&]() { if (d_pcm) (void) hipFree(d_pcm); if (d_l) (void) hipFree(d_l); if (d_r) (void) hipFree(d_r); };
-#define TRY_C(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(GLV_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
-    TRY_C(hipMalloc(&d_pcm, frames * 4));
-    TRY_C(hipMalloc(&d_l, frames * 4));
-    TRY_C(hipMalloc(&d_r, frames * 4));
-    if (pcm) TRY_C(hipMemcpy(d_pcm, pcm, frames * 4, hipMemcpyHostToDevice));
-    else     TRY_C(hipMemset(d_pcm, 0, frames * 4));            // fifo.c:67-79
-    TRY_C(glv::launch_unpack(d_pcm, frames, channels == 1, d_l, d_r, nullptr));
-    TRY_C(hipMemcpy(l, d_l, frames * 4, hipMemcpyDeviceToHost));
-    TRY_C(hipMemcpy(r, d_r, frames * 4, hipMemcpyDeviceToHost));
-#undef TRY_C
-    cleanup();
+    DeviceArray<int16_t> d_pcm;
+    DeviceArray<float> d_l, d_r;
+    if (pcm) HIP_TRY(d_pcm.upload(pcm, frames * 2));
+    else     HIP_TRY(d_pcm.alloc(frames * 2, true));            // fifo.c:67-79
+    HIP_TRY(d_l.alloc(frames, false));
+    HIP_TRY(d_r.alloc(frames, false));
+    HIP_TRY(glv::launch_unpack(d_pcm, frames, channels == 1, d_l, d_r, nullptr));
+    HIP_TRY(hipMemcpy(l, d_l, frames * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(r, d_r, frames * 4, hipMemcpyDeviceToHost));
     return GLV_OK;
 }
 
