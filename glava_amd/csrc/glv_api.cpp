@@ -1110,7 +1110,7 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t
 }
 
 // the second bars launch of a chain (ChainPlan::bars) over its finished rows
-int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, uint32_t units, bool r16, hipStream_t st) {
+int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, size_t units, bool r16, hipStream_t st) {
     hipError_t e;
     if (pl.bars == ChainPlan::NO_BARS) return GLV_OK;
     if (pl.bars == ChainPlan::BARS_F32) {
@@ -1240,6 +1240,128 @@ int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned 
     if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
     if (pl.route == ChainPlan::WAVE) return run_wave(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
     return run_chain(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
+}
+
+// ---- track mode: `steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16) ----------------------
+// Three stages, kernels only.  (1) The transform, with the stateless frame kernels as they are: the whole [streams * pitch] frame sequence is
+// cut into back-to-back windows of n frames q = n / hop times, launch r starting r * hop frames in -- window t of stream s, which starts at
+// a multiple h of hop, is row h / q of launch h % q.  The rows (texels where the chain's first act is the GL_R16 upload) go to the caller's
+// workspace.  (2) glv_track_scan_kernel walks the steps per bin with the state on chip and writes every step's result -- into d_out, or
+// with GLV_OP_BARS into the workspace's second region in the row format the bars kernel takes.  (3) The bars of a second launch over
+// steps * streams * 2 finished rows.
+struct TrackPlan {
+    uint32_t q = 0, log_q = 0;          // residue launches
+    uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
+    uint64_t k0 = 0;                    // windows of launch 0 (launch r: (frames - r * hop) / n, k0 or k0 - 1)
+    bool state = false;                 // the chain keeps gravity / average state
+    bool in16 = false;                  // the transform's rows are GL_R16 texels (kernel class FC_R16), else floats (FC_PLAIN)
+    bool out16 = false;                 // the scan's results are texels
+    ChainPlan::Bars bars = ChainPlan::NO_BARS;
+    uint64_t rows_bytes = 0, work_bytes = 0;   // the transform's region of the workspace (a multiple of 256 bytes), and all of it
+};
+// Everything about a track call that does not depend on its pointers or on what the batch did before: refusals, geometry, workspace.
+int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by glv_batch_track_s16)
+    const uint32_t n = b->p.n;
+    if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "a track call transforms: GLV_OP_FFT is required (ops 0x%x)", ops);
+    const unsigned allowed = GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_BARS | GLV_OP_R16 | GLV_OP_PRIVATE_STATE;
+    if (ops & ~allowed)
+        return fail(GLV_ERR_INVALID, "a track call takes GLV_OP_FFT with GLV_OP_GRAVITY / AVERAGE / BARS / R16 only (no RAW, SMOOTH, WAVE, WRANGE, MAGNITUDE, OUTPUT_IS_STATE; ops 0x%x)", ops);
+    if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
+    const int lh = log2_exact(hop);
+    if (lh < 2 || hop > n) return fail(GLV_ERR_INVALID, "hop=%u: must be a power of two in [4, n=%u]", hop, n);
+    if (pitch_frames % hop != 0) return fail(GLV_ERR_INVALID, "pitch_frames=%u is not a multiple of hop=%u", pitch_frames, hop);
+    if ((uint64_t) pitch_frames < (uint64_t) n + (uint64_t) (steps - 1) * hop)
+        return fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%u frames every hop=%u", pitch_frames, steps, n, hop);
+    if (b->p.gl_storage == 2) return fail(GLV_ERR_STATE, "gl_storage 2 is the pass-by-pass checker form: a track call runs on gl_storage 0 and 1");
+    if (b->ops_mask & GLV_OP_BARS_ONLY)
+        return fail(GLV_ERR_STATE, "the batch was created with GLV_OP_BARS_ONLY: its state beyond the live bins does not exist, which the scan over time would read");
+    if (b->columns()) return fail(GLV_ERR_STATE, "column texels are set (glv_batch_set_column_texels): a track call has no columns form");
+    if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
+    if (int rc = check_ops(b, ops, &some_output)) return rc;
+    tp.q = n / hop; tp.log_q = (uint32_t) log2_exact(tp.q);
+    tp.frames = (uint64_t) (b->streams - 1) * pitch_frames + (uint64_t) (steps - 1) * hop + n;
+    tp.k0 = tp.frames / n;
+    const uint64_t out_rows = (uint64_t) steps * b->streams * 2u;
+    if (2u * tp.k0 > 0xffffffffull || out_rows > 0xffffffffull || (uint64_t) b->streams * (pitch_frames / hop) + steps > 0xffffffffull)
+        return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
+    tp.state = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
+    const bool gl = tp.state && b->state16;                       // the GL_R16 chain, texel state (log_mode 2: its passes one by one -- the same texels)
+    const bool snap = (ops & GLV_OP_BARS) && b->snapped();        // (check_ops: a GL chain's texel rows)
+    // the bars of a second launch, as plan_chain picks them for a chain whose transform kernel does not take them
+    if (!(ops & GLV_OP_BARS)) tp.bars = ChainPlan::NO_BARS;
+    else if (snap) tp.bars = b->p.sample_mode != GLV_SAMPLE_AVERAGE ? ChainPlan::BARS_SNAP_MODE : b->p.log_mode != 2 ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_FLOATS;
+    else if (gl && b->p.bars >= glv::kBarSeqMin && b->bar_x.i8()) tp.bars = b->p.log_mode != 2 ? ChainPlan::BARS_I8 : ChainPlan::BARS_I8_FLOATS;
+    else tp.bars = ChainPlan::BARS_F32;
+    tp.in16 = tp.state ? gl : ((ops & GLV_OP_R16) && !(ops & GLV_OP_BARS));
+    // with bars the texel conversion applies to the bars: the rows stay floats, unless the bars kernel takes texel rows
+    tp.out16 = (ops & GLV_OP_BARS) ? (tp.bars == ChainPlan::BARS_I8 || tp.bars == ChainPlan::BARS_SNAP) : (ops & GLV_OP_R16) != 0;
+    auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t) 255u; };
+    tp.rows_bytes = up256((uint64_t) tp.q * 2u * tp.k0 * n * (tp.in16 ? 2u : 4u));
+    tp.work_bytes = tp.rows_bytes + ((ops & GLV_OP_BARS) ? up256(out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+    return GLV_OK;
+}
+
+int track(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
+    TrackPlan tp;
+    if (int rc = plan_track(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    if (ops & GLV_OP_GRAVITY) {                                   // (as process: one `applied` buffer per form)
+        const int mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+        if (b->grav_mode != 0 && b->grav_mode != mode)
+            return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
+                                       "their state in different buffers (glv_batch_reset, or one batch per chain)",
+                        b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
+    }
+    if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
+        return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
+    b->last_launches = 0;
+    HIP_TRY(hipSetDevice(b->device));
+    if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+    const uint32_t n = b->p.n, units = b->streams * 2u;
+    char* const work = static_cast<char*>(d_work);
+    if (int rc = timed_launch_begin(b, st)) return rc;
+    // (1) the transform: q launches of the stateless kernel class, each over back-to-back windows
+    const unsigned t_ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u);
+    const glv::FrameClass cls = glv::frame_class(false, false, false, t_ops);
+    glv::FrameArgs a;
+    fill_common(a, b->p, b->tab);
+    a.ops = t_ops; a.log_mode = b->p.log_mode;
+    for (uint32_t r = 0; r < tp.q; ++r) {
+        const uint64_t k_r = (tp.frames - (uint64_t) r * hop) / n;            // k0 or k0 - 1; never past the last window any step reads
+        if (k_r == 0) continue;                                                // (counted all the same: the launch count is n / hop)
+        a.in = d_pcm + (size_t) r * hop * 2u;
+        a.out = reinterpret_cast<float*>(work + (size_t) r * 2u * tp.k0 * n * (tp.in16 ? 2u : 4u));
+        a.units = (uint32_t) (2u * k_r);
+        int variant = 0, grid = 0;
+        launch_plan(b, a.units, glv::IN_S16_STEREO, t_ops, &variant, &grid);
+        b->last_grid = grid; b->last_variant = variant;
+        const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_STEREO, (int) b->p.log_mode, variant, cls, a, grid, st);
+        if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    }
+    b->last_launches += (int) tp.q;
+    // (2) the scan over time
+    ChainPlan pl;
+    pl.bars = tp.bars;
+    pl.rows = reinterpret_cast<float*>(work + tp.rows_bytes);
+    a.in = work; a.out = (ops & GLV_OP_BARS) ? pl.rows : static_cast<float*>(d_out);
+    a.units = units; a.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE);
+    a.grav = b->grav_cur; a.grav_w = b->d_grav; a.hist = b->d_hist; a.head = b->head;
+    a.grav_sub = b->grav_sub; a.grav_int = b->grav_int ? 1u : 0u; a.gl_storage = tp.in16 && tp.state ? 1u : 0u;
+    glv::TrackGeometry g;
+    g.n = n; g.steps = steps; g.hops_per_pitch = pitch_frames / hop; g.log_q = tp.log_q; g.residue_rows = (uint32_t) (2u * tp.k0); g.out_texels = tp.out16 ? 1u : 0u;
+    {
+        const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
+        if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
+    }
+    b->kernel_name = "glv_track_scan_kernel";
+    // the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
+    if (ops & GLV_OP_AVERAGE) b->head = (uint32_t) (((uint64_t) b->head + steps) % b->p.avg_frames);
+    if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
+    // (3) the bars of every step's rows
+    if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) steps * units, (ops & GLV_OP_R16) != 0, st)) return rc;
+    return timed_launch_end(b, st);
 }
 
 int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, int device, bool single_row, glv_batch** out) {
@@ -1440,6 +1562,22 @@ int glv_batch_process_f32_stereo(glv_batch* b, const float* d_pcm, float* d_out,
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "interleaved input requires GLV_OP_FFT or GLV_OP_WAVE");
     return process(b, d_pcm, glv::IN_F32_STEREO, d_out, ops, b->streams * 2, 0, (hipStream_t) hip_stream);
+}
+
+uint64_t glv_batch_track_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    TrackPlan tp;
+    if (const int rc = plan_track(b, pitch_frames, hop, steps, ops, tp)) {     // no return code to carry it: the message names the code
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return tp.work_bytes;
+}
+
+int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                        unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    return track(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 // append `new_frames` frames of `fb` bytes each per stream at ring position `pos` (frames) of rings with a pitch of n frames:

@@ -378,6 +378,17 @@ GLV_HD uint32_t apply_state_r16(uint32_t tex, uint32_t off, size_t row, uint32_t
     return tex;
 }
 
+// One term of transform_average's sum on the float chain (render.c:757-760): product and sum in double, rounded to float per term
+// (render.c:759); without a window the plain float sum.  Shared by apply_state and the scan over time (glv_misc.hip glv_track_scan_kernel).
+GLV_HD void average_add(cf& acc, cf v, double w, bool windowed) {
+    if (windowed) {
+        acc.x = (float) ((double) acc.x + w * (double) v.x);
+        acc.y = (float) ((double) acc.y + w * (double) v.y);
+    } else { acc.x = acc.x + v.x; acc.y = acc.y + v.y; }
+}
+// ... and its end: the division by the frame count (render.c:761)
+GLV_HD cf average_end(cf acc, float frames) { return cf{acc.x / frames, acc.y / frames}; }
+
 GLV_HD cf apply_state(cf val, uint32_t off, size_t row, uint32_t n, const FrameArgs& a) {
     if (a.gl_storage == 1) return texels_to_float(apply_state_r16(pack_unorm16(val.x, val.y), off, row, n, a));
     if (a.gl_storage) {
@@ -410,21 +421,14 @@ GLV_HD cf apply_state(cf val, uint32_t off, size_t row, uint32_t n, const FrameA
         if (F == 1) prev = ld<cf>(h + (size_t) a.head * n, off);
         for (uint32_t f = 0; f + 1 < F; ++f) {                               // oldest .. second newest
             prev = ld<cf>(h + (size_t) ring_slot(a.head, f, F) * n, off);
-            if (a.avg_window) {                                              // render.c:759, double product
-                acc.x = (float) ((double) acc.x + a.wts[f] * (double) prev.x);
-                acc.y = (float) ((double) acc.y + a.wts[f] * (double) prev.y);
-            } else { acc.x = acc.x + prev.x; acc.y = acc.y + prev.y; }
+            average_add(acc, prev, a.wts[f], a.avg_window != 0);
         }
         if (a.ops & OP_GRAVITY) {
             val.x = gravity(val.x, prev.x, a.g); val.y = gravity(val.y, prev.y, a.g);
         }
         st<cf>(h + (size_t) a.head * n, off, val);
-        if (a.avg_window) {
-            acc.x = (float) ((double) acc.x + a.wts[F - 1] * (double) val.x);
-            acc.y = (float) ((double) acc.y + a.wts[F - 1] * (double) val.y);
-        } else { acc.x = acc.x + val.x; acc.y = acc.y + val.y; }
-        val.x = acc.x / a.F_as_float;                                        // render.c:761
-        val.y = acc.y / a.F_as_float;
+        average_add(acc, val, a.wts[F - 1], a.avg_window != 0);
+        val = average_end(acc, a.F_as_float);
     } else if (a.ops & OP_GRAVITY) {
         const cf st0 = ld<cf>(a.grav + row * (size_t) n, off);               // uniform base
         val.x = gravity(val.x, st0.x, a.g); val.y = gravity(val.y, st0.y, a.g);

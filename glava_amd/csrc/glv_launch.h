@@ -35,6 +35,16 @@ int frame_variants(int log_nn);                                        // kernel
 bool frame_variant_ok(int log_nn, int in_mode, int log_mode, int variant);   // is `variant` built for this input / log mode
 FrameGeometry frame_geometry(int log_nn, int variant);
 hipError_t launch_post(const FrameArgs& a, uint32_t n, hipStream_t st);
+// the scan over time of a track call (glv_track_scan_kernel): a.in = the residue launches' rows, a.units = channel rows of one update, a.out = the
+// results step-major ([steps][units][n]), state pointers / head / weights as for launch_post.  Where window t of stream s lies among the rows:
+struct TrackGeometry {
+    uint32_t n, steps;
+    uint32_t hops_per_pitch;   // pitch_frames / hop: window t of stream s starts at hop (s * hops_per_pitch + t) frames = h hops
+    uint32_t log_q;            // log2(n / hop): the window is row h >> log_q of residue launch h & (n / hop - 1)
+    uint32_t residue_rows;     // channel rows between the first rows of two residue launches
+    uint32_t out_texels;       // results as GL_R16 texels (uint16 rows) instead of floats
+};
+hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool rows_texels, hipStream_t st);
 hipError_t launch_bufscale(const float* in, float* out, size_t total_out, uint32_t k, hipStream_t st);
 hipError_t launch_lerp(const float* s0, const float* e0, float* out, size_t total, float mod, hipStream_t st);
 hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin, const int* smax, uint32_t asz, uint32_t reach,

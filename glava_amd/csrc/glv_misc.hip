@@ -44,6 +44,115 @@ __global__ void __launch_bounds__(256) glv_post_kernel(const FrameArgs a, const 
     }
 }
 
+// ---- the scan over time of a track call (glv_batch_track_s16) ---------------------------------------------------------------------
+// The transform launches left every window of every stream as one finished row (texels where the chain's first act is the GL_R16 upload,
+// IN16; floats else).  gravity and the average are a recurrence over time per bin: one lane owns one float pair / texel pair of one channel
+// row, like glv_post_kernel, and walks the `steps` updates with the gravity value in a register and the F-slot ring in LDS -- [F][lanes],
+// lane-contiguous: every access of a wave is 64 consecutive words.  The batch's state arrays are read once before the first step and
+// written once after the last, in the layout `steps` sequential calls would have left (the ring by slot: the host advances the head).
+// A lane touches its own column of the ring only: no barrier anywhere.  The step is apply_state's / apply_state_r16's, helper by helper.
+// The row of a step does not depend on the state: kTrackDepth steps' loads are in flight ahead of the one being computed (a register ring,
+// indices compile-time) -- at few streams the loop is a chain of HBM round trips otherwise.
+// Window t of stream s starts at frame s * pitch + t * hop = (s * hops_per_pitch + t) * hop of the whole sequence: with q = n / hop it is row
+// k = h >> log_q of the residue launch r = h & (q - 1), whose rows start at r * residue_rows.
+constexpr int kTrackLanes = 64;          // one wave per workgroup: with few streams the lanes of a row spread over n / 128 CUs
+constexpr int kTrackDepth = 8;
+template <bool IN16>
+__global__ void __launch_bounds__(kTrackLanes) glv_track_scan_kernel(const FrameArgs a, const TrackGeometry t) {
+    using V = typename std::conditional<IN16, uint32_t, cf>::type;         // one lane's element of a row: a texel pair / a float pair
+    extern __shared__ __attribute__((aligned(8))) unsigned char track_lds[];
+    V* const ring = reinterpret_cast<V*>(track_lds) + threadIdx.x;          // slot f of this lane: ring[f * kTrackLanes]
+    const uint32_t blocks_per_row = t.n / (2u * (uint32_t) kTrackLanes);
+    const uint32_t row = blockIdx.x / blocks_per_row;                       // uniform: a workgroup lies inside one channel row
+    const uint32_t pair = (blockIdx.x % blocks_per_row) * (uint32_t) kTrackLanes + threadIdx.x;
+    const uint32_t off = pair * (uint32_t) sizeof(V);                       // byte offset in an input / state row
+    const size_t row_bytes = (size_t) t.n * (sizeof(V) / 2u);
+    const uint32_t F = a.F;
+    const bool grav = (a.ops & OP_GRAVITY) != 0, avg = (a.ops & OP_AVERAGE) != 0, windowed = a.avg_window != 0;
+    const bool out16 = t.out_texels != 0;
+    // ---- the lane's slice of the state, once
+    V gs = V();
+    if (avg) {
+        const char* h = reinterpret_cast<const char*>(a.hist) + (size_t) row * F * row_bytes;
+        for (uint32_t f = 0; f < F; ++f) ring[f * kTrackLanes] = ld<V>(h + (size_t) f * row_bytes, off);
+    } else if (grav) gs = ld<V>(reinterpret_cast<const char*>(a.grav) + (size_t) row * row_bytes, off);
+    uint32_t head = a.head;
+    // ---- where step tt's row lies, and where its result goes (uniform arithmetic)
+    const uint64_t h0 = (uint64_t) (row >> 1) * t.hops_per_pitch;
+    const uint32_t q_mask = (1u << t.log_q) - 1u;
+    const char* const in = static_cast<const char*>(a.in);
+    auto fetch = [&](uint32_t tt) -> V {
+        const uint64_t h = h0 + tt;
+        const uint64_t in_row = (uint64_t) ((uint32_t) h & q_mask) * t.residue_rows + 2u * (h >> t.log_q) + (row & 1u);
+        return ld<V>(in + in_row * row_bytes, off);
+    };
+    char* const out = reinterpret_cast<char*>(a.out);
+    const size_t out_row_bytes = (size_t) t.n * (out16 ? 2u : 4u);
+    const uint32_t out_off = pair * (out16 ? 4u : 8u);
+    auto step = [&](V x, uint32_t tt) {
+        char* const o = out + ((size_t) tt * a.units + row) * out_row_bytes;
+        if constexpr (IN16) {
+            uint32_t tex = x;                                               // apply_state_r16
+            if (grav) {
+                const uint32_t store = avg ? ring[(F == 1 ? head : ring_slot(head, F - 2, F)) * kTrackLanes] : gs;
+                tex = gravity_r16(tex, store, a.g, a.grav_sub, a.grav_int);
+                if (!avg) gs = tex;
+            }
+            if (avg) {
+                cf acc = { 0.0f, 0.0f };
+                for (uint32_t f = 0; f + 1 < F; ++f) weighted_texels(acc, ring[ring_slot(head, f, F) * kTrackLanes], a.wts32[f], windowed);
+                ring[head * kTrackLanes] = tex;
+                if (F > 1) {
+                    weighted_texels(acc, tex, a.wts32[F - 1], windowed);
+                    tex = pack_unorm16(div_frames(acc.x, a.F_as_float, a.F_rcp), div_frames(acc.y, a.F_as_float, a.F_rcp));
+                }
+                head = head + 1u == F ? 0u : head + 1u;
+            }
+            if (out16) st<uint32_t>(o, out_off, tex);
+            else st<cf>(o, out_off, texels_to_float(tex));
+        } else {
+            cf val = x;                                                     // apply_state, the float chain
+            if (avg) {
+                cf acc = { 0.0f, 0.0f }, prev = { 0.0f, 0.0f };
+                if (F == 1) prev = ring[head * kTrackLanes];
+                for (uint32_t f = 0; f + 1 < F; ++f) {
+                    prev = ring[ring_slot(head, f, F) * kTrackLanes];
+                    average_add(acc, prev, a.wts[f], windowed);
+                }
+                if (grav) { val.x = gravity(val.x, prev.x, a.g); val.y = gravity(val.y, prev.y, a.g); }
+                ring[head * kTrackLanes] = val;
+                average_add(acc, val, a.wts[F - 1], windowed);
+                val = average_end(acc, a.F_as_float);
+                head = head + 1u == F ? 0u : head + 1u;
+            } else if (grav) {
+                val.x = gravity(val.x, gs.x, a.g); val.y = gravity(val.y, gs.y, a.g);
+                gs = val;
+            }
+            if (out16) st<uint32_t>(o, out_off, pack_unorm16(val.x, val.y));    // render.c:521-524
+            else st<cf>(o, out_off, val);
+        }
+    };
+    // ---- the walk
+    V ahead[kTrackDepth];
+#pragma unroll
+    for (int j = 0; j < kTrackDepth; ++j) ahead[j] = (uint32_t) j < t.steps ? fetch((uint32_t) j) : V();
+    for (uint32_t t0 = 0; t0 < t.steps; t0 += (uint32_t) kTrackDepth) {
+#pragma unroll
+        for (int j = 0; j < kTrackDepth; ++j) {
+            const uint32_t tt = t0 + (uint32_t) j;
+            if (tt >= t.steps) break;
+            const V x = ahead[j];
+            if (tt + (uint32_t) kTrackDepth < t.steps) ahead[j] = fetch(tt + (uint32_t) kTrackDepth);
+            step(x, tt);
+        }
+    }
+    // ---- the state the sequential calls would have left
+    if (avg) {
+        char* h = reinterpret_cast<char*>(a.hist) + (size_t) row * F * row_bytes;
+        for (uint32_t f = 0; f < F; ++f) st<V>(h + (size_t) f * row_bytes, off, ring[f * kTrackLanes]);
+    } else if (grav) st<V>(reinterpret_cast<char*>(a.grav_w) + (size_t) row * row_bytes, off, gs);
+}
+
 __global__ void __launch_bounds__(256) glv_unpack_kernel(const int16_t* __restrict__ pcm, size_t frames, int mono,
                                                          float* __restrict__ l, float* __restrict__ r) {
     for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < frames; i += (size_t) gridDim.x * blockDim.x) {
@@ -1110,6 +1219,15 @@ static int capped_grid(size_t items, int block) {
 
 hipError_t launch_post(const FrameArgs& a, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(glv_post_kernel, dim3(capped_grid((size_t) a.units * (n / 2), 256)), dim3(256), 0, st, a, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool rows_texels, hipStream_t st) {
+    const uint64_t blocks = (uint64_t) a.units * (t.n / (2u * (uint32_t) kTrackLanes));
+    if (t.n < 2u * (uint32_t) kTrackLanes || t.steps == 0 || blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const size_t lds = (a.ops & OP_AVERAGE) ? (size_t) a.F * kTrackLanes * (rows_texels ? sizeof(uint32_t) : sizeof(cf)) : 0;   // <= 32 KiB (F <= 64)
+    if (rows_texels) hipLaunchKernelGGL((glv_track_scan_kernel<true>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);
+    else hipLaunchKernelGGL((glv_track_scan_kernel<false>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);
     return hipGetLastError();
 }
 

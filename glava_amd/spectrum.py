@@ -101,6 +101,10 @@ def lib() -> C.CDLL:
             L.glv_batch_set_bar_texels.argtypes = [vp, vp, C.c_uint32]
         if hasattr(L, "glv_batch_set_column_texels"):   # (likewise)
             L.glv_batch_set_column_texels.argtypes = [vp, vp, C.c_uint32]
+        if hasattr(L, "glv_batch_track_s16"):           # (likewise)
+            L.glv_batch_track_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
+            L.glv_batch_track_work_bytes.restype = C.c_uint64
+            L.glv_batch_track_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -214,6 +218,20 @@ class Batch:
 
     def process_f32_stereo(self, d_in, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         _check(lib().glv_batch_process_f32_stereo(self._h, _ptr(d_in), _ptr(d_out), ops, _ptr(stream)))
+
+    def track_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
+        """bytes of device workspace track_s16 needs for these arguments (glv_batch_track_work_bytes); raises on arguments the call refuses"""
+        nbytes = int(lib().glv_batch_track_work_bytes(self._h, pitch_frames, hop, steps, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)      # (the message names the code)
+        return nbytes
+
+    def track_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """`steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16): d_pcm int16 [streams][pitch_frames][2], window t of
+        stream s = its frames [t * hop, t * hop + n); d_out step-major, step t exactly what process_s16 call t would have written; d_work at least
+        track_work_bytes(...) bytes, 256-byte aligned.  Output and state bit for bit those of the sequential calls; stream-ordered, kernels only."""
+        _check(lib().glv_batch_track_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
 
     def ring_update_s16(self, d_new, new_frames: int, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         _check(lib().glv_batch_ring_update_s16(self._h, _ptr(d_new), new_frames, _ptr(d_out), ops, _ptr(stream)))
@@ -345,6 +363,19 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def track_residues(n: int, hop: int, pitch_frames: int, streams: int, steps: int) -> list[int]:
+    """Windows K_r of the n / hop transform launches of a track call (include/glv_spectrum.h glv_batch_track_s16): launch r transforms the
+    back-to-back windows that start at frame r * hop + k * n, k < K_r, of the sequence that ends with the last window of the last stream."""
+    frames = (streams - 1) * pitch_frames + (steps - 1) * hop + n
+    return [(frames - r * hop) // n for r in range(n // hop)]
+
+
+def track_window(n: int, hop: int, pitch_frames: int, s: int, t: int) -> tuple[int, int]:
+    """(r, k): window t of stream s of a track call is row k of transform launch r"""
+    start = s * pitch_frames + t * hop
+    return (start % n) // hop, start // n
 
 
 def multi_shard_range(total_streams: int, rank: int, world: int) -> tuple[int, int]:

@@ -349,6 +349,40 @@ int glv_batch_destroy(glv_batch* b);
 /* (every input entry point -- this one, _f32, _f32_stereo and the two ring updates -- takes GLV_OP_FFT chains or GLV_OP_WAVE; planar f32 also the operators
  * without a transform) */
 int glv_batch_process_s16(glv_batch* b, const int16_t* d_pcm, float* d_out, unsigned ops, void* hip_stream);
+/* Track mode: `steps` consecutive updates of every stream in ONE call, from a recording whose every hop is already in HBM -- the time axis as the
+ * parallel one.  Added within ABI 7 without a version change: detect it by the symbol.
+ *   d_pcm   int16 [streams][pitch_frames][2]; window t of stream s = its frames [t * hop, t * hop + n)
+ *   d_out   step-major: d_out + t * (bytes one glv_batch_process_s16 call with these ops writes) is EXACTLY what call t would have written
+ *   d_work  caller-owned workspace of at least glv_batch_track_work_bytes(...) bytes, 256-byte aligned; its contents mean nothing between calls
+ * Contract: the output of step t and the batch's state afterwards -- gravity store, history ring, ring head, which gravity form the batch is in -- are
+ * bit for bit what `steps` consecutive glv_batch_process_s16(b, window_t, out_t, ops, st) calls produce and leave behind.  So a track may be cut into
+ * chunks (track(4) then track(7) == track(11)), track calls mix with process / ring calls on the same batch, and the state a call starts from is
+ * whatever the batch holds.
+ * Accepted: GLV_OP_FFT (required; alone it is a spectrogram) with GLV_OP_GRAVITY / AVERAGE / BARS / R16 in the combinations glv_batch_process_s16 takes,
+ * on gl_storage 0 and 1, channels 1 and 2, every log_mode, GLV_OP_BARS with and without a bar-texel table (glv_batch_set_bar_texels).
+ * Refused: GLV_ERR_INVALID -- GLV_OP_RAW / SMOOTH / WAVE / WRANGE / MAGNITUDE / OUTPUT_IS_STATE, steps == 0, hop not a power of two in [4, n],
+ * pitch_frames % hop != 0, pitch_frames < n + (steps - 1) * hop, a NULL pointer, a workspace that is not 256-byte aligned, more than 2^32 rows in one
+ * call; GLV_ERR_STATE -- gl_storage 2 (the checker form), a batch created with GLV_OP_BARS_ONLY (its state beyond the live bins does not exist),
+ * column texels set, and everything glv_batch_process_s16 refuses (the gravity form mix, unannounced state, parameters changed without
+ * glv_batch_set_params).  A refused call leaves the batch untouched.
+ * Stream-ordered: kernels and nothing else -- nothing is allocated or synchronised, the first call can be captured into a hipGraph.  Three stages:
+ *   1. n / hop launches of the stateless transform kernel.  The frame sequence [0, (streams - 1) * pitch_frames + (steps - 1) * hop + n) is taken as one:
+ *      launch r transforms the back-to-back windows that start at r * hop + k * n, so window (s, t), which starts at s * pitch_frames + t * hop, is row
+ *      k = start / n of launch r = (start % n) / hop.  Windows that straddle two streams, and those between a stream's last step and the next stream, are
+ *      computed and never read: the transform's work follows streams * pitch_frames, not streams * steps -- give a multi-stream recording a pitch close
+ *      to what the call consumes.  No launch reads past the last window of the last stream.
+ *   2. glv_track_scan_kernel (glv_batch_kernel_name): one lane per bin pair walks the steps with the gravity value in a register and the F-slot ring
+ *      in LDS; the batch's state arrays are read once before the first step and written once after the last.
+ *   3. with GLV_OP_BARS the bars kernel of a second launch over steps * streams * 2 finished rows (identical bits on every device path).
+ * glv_batch_last_launches: n / hop + 1, + 1 with GLV_OP_BARS.
+ * Measured against the same updates issued one by one (tools/track_bench.py; profiles/r10/track.txt: one MI355X, N = 4096, hop 256, the GL chain with
+ * F = 5 and the pre-smoothing pass, texels out, 2048 steps; a host clock around the calls and the synchronise that ends them): 1 stream 2.10 ms against
+ * 41.3 ms (19.7 x), 8 streams 2.60 against 44.6 ms (17.1 x), 64 streams 6.00 against 46.1 ms (7.7 x); 1024 streams, 256 steps, 8.42 against 10.7 ms
+ * (1.27 x).  The one-by-one form costs ~20 us per update whatever it carries until the chip fills; the two forms had not crossed at 1024 streams, the
+ * largest count measured -- beyond it nothing is known, and the workspace (8 GiB there) grows with streams * steps. */
+uint64_t glv_batch_track_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0 on arguments the call refuses: glv_last_error then starts with the code's name, "GLV_ERR_INVALID: " or "GLV_ERR_STATE: " */
+int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                        unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
