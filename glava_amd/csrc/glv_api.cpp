@@ -298,6 +298,11 @@ uint32_t bins_reached(const std::vector<glv::BarDesc>& desc) {
 }
 
 constexpr int kMaxVariants = 4;
+// glv_batch_track_wave_s16, bars in one launch: a workgroup's rows are consecutive output rows (false) or consecutive steps of one channel row (true).
+// profiles/r11/track_wave.txt (N = 4096, hop 256, ms by rows / by steps): 1 stream x 2048 steps 0.066 / 0.048, 8 streams 0.207 / 0.178, 64 streams 1.38 / 1.43,
+// 1024 streams x 256 steps 2.47 / 2.65 -- apart by about the round-to-round spread either way (the two-launch point, where the order plays no part, shows the
+// same 0.064 / 0.044 between the two batches); by rows is the plain order and wastes no partial block per channel row when steps are few.
+constexpr bool kTrackWaveBySteps = false;
 // One set of GLV_OP_BARS tables (host generated).  A batch holds two: the bars of glv_params (glv_batch::bar) and, while glv_batch_set_bar_texels /
 // glv_batch_set_column_texels has a table set, the bars at texels of the pre-smoothing pass (glv_batch::snap).
 struct BarTableSet {
@@ -381,6 +386,7 @@ struct glv_batch {
     bool single_row = false;
     bool unfused_bars = false;   // GLV_UNFUSED_BARS in the environment at creation (diagnostics: bars always as a second launch)
     bool unfused_wave = false;   // GLV_UNFUSED_WAVE likewise: GLV_OP_WAVE | GLV_OP_BARS always as the waveform kernel + the bars kernel
+    bool track_wave_by_steps = kTrackWaveBySteps;   // row order of glv_batch_track_wave_s16's one-launch form (GLV_TRACK_WAVE_ORDER=rows|steps at creation: diagnostics)
     bool state16 = false;        // gl_storage == 1 at creation: d_grav / d_hist hold uint16 texels (2 bytes per value)
     float grav_g = 0.f; uint32_t grav_sub = 0; bool grav_int = false, grav_known = false;   // the gravity step on texels (glv_tables.h gravity_r16_integer_step)
     DeviceArray<float> d_scratch;    // [streams*2][n] spectra feeding GLV_OP_BARS
@@ -1035,7 +1041,8 @@ struct ChainPlan {
 // upload's texels in the arithmetic of the GL_R16 chain's second launch: GLV_BARS_I8_EXACT straight from s16 frames / the s16 ring in one launch; every
 // other form -- f32 inputs, a ring rotated by a number of frames that is not a multiple of 8, maximum / hybrid, fewer than 256 bars, bar texels, no integer tables, the single-stream drop-in, GLV_UNFUSED_WAVE -- as
 // the waveform kernel into the scratch rows (texels where the bars kernel takes texels, their floats else; only what the bars sample), then the bars kernel.
-int plan_wave(glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float* d_out, ChainPlan& pl) {
+// whole_groups: every window the call reads starts on a group of 8 frames of a 32-byte aligned buffer (a process call's windows do; a track call says)
+int plan_wave(const glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float* d_out, ChainPlan& pl, bool whole_groups = true) {
     pl.route = ChainPlan::WAVE; pl.ops = ops; pl.out = d_out; pl.bars = ChainPlan::NO_BARS;
     pl.wave_r16 = (ops & GLV_OP_R16) != 0; pl.wave_limit = b->p.n;
     if (!(ops & GLV_OP_BARS)) return GLV_OK;
@@ -1044,7 +1051,7 @@ int plan_wave(glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float* d_ou
     else if (averaging && b->p.bars >= glv::kBarSeqMin && b->bar_x.i8()) pl.bars = ChainPlan::BARS_I8;
     else pl.bars = ChainPlan::BARS_F32;
     // (the integer pass parks groups of 8 frames: a ring whose oldest frame is not at a multiple of 8 -- an update of a sample_sz / 4 that is not one -- would wrap inside a group)
-    pl.wave_fused = pl.bars == ChainPlan::BARS_I8 && (in_mode == glv::IN_S16_STEREO || in_mode == glv::IN_S16_RING) && (rot & 7u) == 0u && !b->unfused_wave && !b->single_row;
+    pl.wave_fused = pl.bars == ChainPlan::BARS_I8 && (in_mode == glv::IN_S16_STEREO || in_mode == glv::IN_S16_RING) && (rot & 7u) == 0u && whole_groups && !b->unfused_wave && !b->single_row;
     if (pl.wave_fused) return GLV_OK;
     if (!b->d_scratch) return fail(GLV_ERR_STATE, "GLV_OP_WAVE | GLV_OP_BARS needs the internal rows: announce both bits in glv_batch_create's ops_mask");
     pl.out = pl.rows = b->d_scratch;
@@ -1364,6 +1371,77 @@ int track(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t ho
     return timed_launch_end(b, st);
 }
 
+// ---- track mode for the wave module: the texture of every update of a recording in one call (glv_batch_track_wave_s16) -------------
+// GLV_OP_WAVE is stateless and transforms nothing: a call is plan_wave's one or two launches over steps * streams * 2 rows instead of streams * 2,
+// the kernels' windows cut out of the recordings by glv::WaveWindows.  The bars arithmetic, what the waveform kernel writes and how much of a row are
+// plan_wave's own choices (track and process cannot disagree); the rows between two launches live in the caller's workspace, not in the scratch rows
+// (sized for one update).
+struct TrackWavePlan {
+    ChainPlan pl;                   // the one or two launches of windows that start at any frame
+    bool one_launch = false;        // with bars: plan_wave fuses where hop and pitch keep every window on a group of 8 frames -- of a 32-byte aligned d_pcm, which
+                                    // only the call sees: on any other it runs `pl`
+    uint64_t rows = 0;              // steps * streams * 2
+    uint64_t work_bytes = 256;      // (without bars there is no second launch and nothing to park: the convention keeps 0 for "refused")
+};
+int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackWavePlan& tp) {
+    static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by track_wave)
+    const uint32_t n = b->p.n;
+    if (!(ops & GLV_OP_WAVE)) return fail(GLV_ERR_INVALID, "a wave track call needs GLV_OP_WAVE (ops 0x%x; GLV_OP_FFT chains: glv_batch_track_s16)", ops);
+    if (ops & ~(unsigned) (GLV_OP_WAVE | GLV_OP_BARS | GLV_OP_R16))
+        return fail(GLV_ERR_INVALID, "a wave track call takes GLV_OP_WAVE with GLV_OP_BARS / GLV_OP_R16 only (ops 0x%x)", ops);
+    if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
+    if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
+    if ((uint64_t) pitch_frames < (uint64_t) n + (uint64_t) (steps - 1) * hop)
+        return fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%u frames every hop=%u", pitch_frames, steps, n, hop);
+    if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
+    tp.rows = (uint64_t) steps * b->streams * 2u;
+    if (tp.rows > 0x100000000ull)
+        return fail(GLV_ERR_INVALID, "steps=%u of %u streams: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams);
+    if (int rc = check_ops(b, ops, &some_output)) return rc;
+    // The sizing query does not see d_pcm, so with bars the workspace is always what the two launches need: plan_wave is asked twice, for windows that
+    // start anywhere (the plan every call can fall back on) and for this call's hop and pitch.
+    if (int rc = plan_wave(b, glv::IN_S16_STEREO, ops, 0, nullptr, tp.pl, false)) return rc;
+    if (ops & GLV_OP_BARS) {
+        ChainPlan grouped;
+        if (int rc = plan_wave(b, glv::IN_S16_STEREO, ops, 0, nullptr, grouped, hop % 8u == 0u && pitch_frames % 8u == 0u)) return rc;
+        tp.one_launch = grouped.wave_fused;
+        tp.work_bytes = (tp.rows * n * (tp.pl.wave_r16 ? 2u : 4u) + 255u) & ~(uint64_t) 255u;
+    }
+    return GLV_OK;
+}
+
+int track_wave(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
+    TrackWavePlan tp;
+    if (int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    ChainPlan& pl = tp.pl;
+    const bool fused = tp.one_launch && (reinterpret_cast<uintptr_t>(d_pcm) & 31u) == 0u;
+    b->last_launches = 0;
+    HIP_TRY(hipSetDevice(b->device));
+    const bool mono = b->p.channels == 1, r16 = (ops & GLV_OP_R16) != 0;
+    glv::WaveWindows w;
+    w.units = b->streams * 2u; w.steps = steps; w.hop = hop; w.pitch_frames = pitch_frames;
+    // (a store's 32-bit lane offset spans 4 rows of the workgroup: `units` rows apart by steps)
+    w.by_steps = b->track_wave_by_steps && (4ull * w.units + 2u) * b->p.bars * 4u <= 0xffffffffull ? 1u : 0u;
+    if (int rc = timed_launch_begin(b, st)) return rc;
+    hipError_t e;
+    if (fused) {
+        const glv::BarIRowsTables irt = b->bar_x.irows_tables();
+        e = glv::launch_bars_i8_pcm_track(d_pcm, w, mono, d_out, b->p.n, b->p.bars, &irt, st, r16);
+        b->kernel_name = "glv_bars_rows_i8_kernel";
+    } else {
+        if (ops & GLV_OP_BARS) pl.out = pl.rows = static_cast<float*>(d_work);
+        else pl.out = static_cast<float*>(d_out);
+        e = glv::launch_wave_track(d_pcm, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
+        b->kernel_name = "glv_wave_kernel";
+    }
+    ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    if (!fused) if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) tp.rows, r16, st)) return rc;
+    return timed_launch_end(b, st);
+}
+
 int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, int device, bool single_row, glv_batch** out) {
     if (!out) return fail(GLV_ERR_INVALID, "out is NULL");
     *out = nullptr;
@@ -1389,6 +1467,7 @@ int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, 
     b->rows = single_row ? 1u : streams * 2u; b->single_row = single_row;
     b->unfused_bars = std::getenv("GLV_UNFUSED_BARS") != nullptr;
     b->unfused_wave = std::getenv("GLV_UNFUSED_WAVE") != nullptr;
+    if (const char* o = std::getenv("GLV_TRACK_WAVE_ORDER")) b->track_wave_by_steps = std::strcmp(o, "steps") == 0;
     b->bar_i8_off = std::getenv("GLV_NO_BARS_I8") != nullptr;
     b->log_nn = log2_exact(p->n) - 1;
     hipDeviceProp_t prop;
@@ -1578,6 +1657,22 @@ int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frame
                         unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     return track(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    TrackWavePlan tp;
+    if (const int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) {     // no return code to carry it: the message names the code
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return tp.work_bytes;
+}
+
+int glv_batch_track_wave_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    return track_wave(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 // append `new_frames` frames of `fb` bytes each per stream at ring position `pos` (frames) of rings with a pitch of n frames:

@@ -197,10 +197,13 @@ __global__ void __launch_bounds__(256) glv_ring_planar_kernel(const void* __rest
 // by one.  KIND 2: planar f32 rows, taken as they are (the lb / rb snapshot is already unpacked), 8 samples per lane.  Only the first `limit` samples
 // of a row (a multiple of 8) are produced -- in front of the bars kernel that is what the bars sample; out rows keep their pitch of n.
 typedef unsigned int glv_wave_u4 __attribute__((ext_vector_type(4)));
+// KIND 3 (glv_batch_track_wave_s16): KIND 0's arithmetic over every window of a track call -- `s` counts windows, step-major (window t * streams + stream),
+// whose frames start at stream * pitch_frames + t * hop of the recordings (WaveWindows; the other kinds never read it).  A window starts at any frame:
+// frames are dwords, so a group whose first frame is not 16-byte aligned takes its 8 frames one naturally aligned dword at a time.
 template <int KIND, bool R16>
 __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ in, void* __restrict__ out, size_t groups_total, uint32_t n, uint32_t limit,
-                                                       uint32_t rot, int mono) {
-    const uint32_t gpr = limit / 8u;                                     // groups of 8 samples per row (KIND 2) / per stream
+                                                       uint32_t rot, int mono, const WaveWindows w) {
+    const uint32_t gpr = limit / 8u;                                     // groups of 8 samples per row (KIND 2) / per stream (window)
     auto emit = [&](size_t row, uint32_t t, const float (&x)[8]) {
         uint32_t c[4];
 #pragma unroll
@@ -229,6 +232,26 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
             const BarW4 a = ld<BarW4>(src, t * 4u), b = ld<BarW4>(src, t * 4u + 16u);
             const float x[8] = {a.w[0], a.w[1], a.w[2], a.w[3], b.w[0], b.w[1], b.w[2], b.w[3]};
             emit(s, t, x);
+        } else if constexpr (KIND == 3) {
+            const uint32_t streams = w.units / 2u;
+            const uint64_t first = (uint64_t) (s % streams) * w.pitch_frames + (uint64_t) (s / streams) * w.hop + t;      // the group's first frame
+            const uint32_t* src = static_cast<const uint32_t*>(in) + first;
+            uint32_t f[8];
+            if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+                const glv_wave_u4 a = ld<glv_wave_u4>(src, 0u), b = ld<glv_wave_u4>(src, 16u);
+                f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+            } else {
+#pragma unroll
+                for (uint32_t q = 0; q < 8; ++q) f[q] = src[q];
+            }
+            float l[8], r[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int a = (int16_t) (f[q] & 0xffffu), b = (int16_t) (f[q] >> 16);
+                if (mono) { l[q] = unpack_s16_mono(a, b); r[q] = l[q]; } else { l[q] = unpack_s16(a); r[q] = unpack_s16(b); }
+            }
+            emit(2 * s, t, l);                                           // (row t' * units + 2 stream + c = 2 s + c)
+            emit(2 * s + 1, t, r);
         } else {
             float l[8], r[8];
             const bool whole = (rot & 7u) == 0u;                         // (uniform) bin and rot multiples of 8: the group does not wrap
@@ -909,15 +932,19 @@ typedef int glv_i16v __attribute__((ext_vector_type(16)));
 // array of the upload reaches HBM, and only the frames the ring windows cover are read.  An s16 fetch is two 16-byte loads like I8_FLOATS' (rot must
 // be a multiple of 8 frames, so that a group of 8 never wraps: launch_bars_i8_pcm refuses others); they are compiler-visible loads converted where they are fetched, so
 // the compiler's own wait for them sits in fetch() and the hand-counted vmcnt(6) of the weight stream stays correct (loads retire in order: more
-// loads behind a bank's requests only make that wait stricter).
-enum I8Source { I8_TEXELS = 0, I8_FLOATS = 1, I8_PCM_S16 = 2 };
+// loads behind a bank's requests only make that wait stricter).  I8_PCM_TRACK (glv_batch_track_wave_s16): I8_PCM_S16's fetch() over the windows of a
+// track call -- the row's frames start at WaveWindows' stream * pitch_frames + step * hop of the recordings (a multiple of 8 frames of a 32-byte aligned
+// buffer: the host sends other geometries through the waveform kernel), no rotation: the same two compiler-visible 16-byte loads.  Its rows are the call's
+// steps * units output rows, step-major; a workgroup takes RB consecutive ones, or (by_steps) RB consecutive steps of one channel row -- blockIdx.x =
+// channel row * ceil(steps / RB) + block of steps -- whose output rows lie `units` rows apart.  The other sources never read WaveWindows.
+enum I8Source { I8_TEXELS = 0, I8_FLOATS = 1, I8_PCM_S16 = 2, I8_PCM_TRACK = 3 };
 template <int S, int RB, int SRC, bool R16>
 __global__ void __launch_bounds__(64 * kRowsWaves, 2) glv_bars_rows_i8_kernel(const void* __restrict__ rows_in, void* __restrict__ bars_out, size_t nrows, uint32_t n,
                                                                               uint32_t bars, const BarTile* __restrict__ rounds, uint32_t nrounds, uint32_t rounds_per_wg,
                                                                               const BarMTile* __restrict__ tiles, const glv_i4v* __restrict__ wq,
-                                                                              const BarIFin* __restrict__ fin, uint32_t rot, uint32_t mono) {
+                                                                              const BarIFin* __restrict__ fin, uint32_t rot, uint32_t mono, const WaveWindows ww) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr bool F32IN = SRC == I8_FLOATS, PCM = SRC == I8_PCM_S16;
+    constexpr bool F32IN = SRC == I8_FLOATS, TRACK = SRC == I8_PCM_TRACK, PCM = SRC == I8_PCM_S16 || TRACK;
     static_assert(S % 32 == 0 && (RB == 64 || RB == 32), "16-bin chunks never straddle the ring's end and (S + 16) / 16 is odd; one or two row groups");
     extern __shared__ __attribute__((aligned(16))) char i8_lds[];       // [2 planes][RB rows][S + 16 bytes]
     constexpr uint32_t PITCH = S + 16, S16 = S / 16, G = RB / 32, CPI = 64 * kRowsWaves / RB;       // CPI: columns of 8 bins one sweep of the workgroup fetches
@@ -925,22 +952,43 @@ __global__ void __launch_bounds__(64 * kRowsWaves, 2) glv_bars_rows_i8_kernel(co
     char* plane_l = i8_lds + (size_t) RB * PITCH;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    const size_t row0 = (size_t) blockIdx.x * RB;
-    if (row0 >= nrows) return;
-    const uint32_t R = (uint32_t) (nrows - row0 < RB ? nrows - row0 : RB);
+    // row0: the workgroup's first output row; its R rows lie row_step rows apart (TRACK by steps: R steps from step0 on of channel row `unit`)
+    size_t row0 = (size_t) blockIdx.x * RB;
+    uint32_t R, row_step = 1u, step0 = 0u, unit = 0u;
+    if (TRACK && ww.by_steps) {
+        const uint32_t blocks_per_unit = (ww.steps + RB - 1u) / RB;
+        unit = blockIdx.x / blocks_per_unit;
+        step0 = (blockIdx.x % blocks_per_unit) * RB;
+        if (unit >= ww.units) return;
+        R = ww.steps - step0 < RB ? ww.steps - step0 : RB;
+        row0 = (size_t) step0 * ww.units + unit;
+        row_step = ww.units;
+    } else {
+        if (row0 >= nrows) return;
+        R = (uint32_t) (nrows - row0 < RB ? nrows - row0 : RB);
+    }
     const uint32_t t_begin = blockIdx.y * rounds_per_wg, t_end = t_begin + rounds_per_wg < nrounds ? t_begin + rounds_per_wg : nrounds;
     if (t_begin >= t_end) return;
     const uint32_t frow = threadIdx.x % (uint32_t) RB, fcol = threadIdx.x / (uint32_t) RB;
-    const size_t srow = row0 + (frow < R ? frow : R - 1);                 // (a partial row block repeats its last row; its stores are masked)
-    const char* src = static_cast<const char*>(rows_in) + (PCM ? srow >> 1 : srow) * (size_t) n * (F32IN || PCM ? 4u : 2u);
-    const uint32_t ch_shift = PCM ? ((uint32_t) srow & 1u) * 16u : 0u;   // (PCM: the row's channel sits in this half of a frame's dword)
+    const size_t srow = row0 + (size_t) (frow < R ? frow : R - 1) * row_step;   // (a partial row block repeats its last row; its stores are masked)
+    const char* src;
+    uint32_t ch_shift = 0u;                                             // (PCM: the row's channel sits in this half of a frame's dword)
+    if constexpr (TRACK) {                                              // the row's window: 64-bit frame arithmetic, nothing wraps
+        const uint64_t step = srow / ww.units;
+        const uint32_t u = (uint32_t) (srow % ww.units);
+        src = static_cast<const char*>(rows_in) + ((uint64_t) (u >> 1) * ww.pitch_frames + step * ww.hop) * 4u;
+        ch_shift = (u & 1u) * 16u;
+    } else {
+        src = static_cast<const char*>(rows_in) + (PCM ? srow >> 1 : srow) * (size_t) n * (F32IN || PCM ? 4u : 2u);
+        if constexpr (PCM) ch_shift = ((uint32_t) srow & 1u) * 16u;
+    }
     struct Tex8 { uint32_t d[4]; };                                     // 8 texels, two per dword
     auto fetch = [&](uint32_t bin) -> Tex8 {
         Tex8 v;
         bin = bin + 8u <= n ? bin : n - 8u;                             // (a dummy request -- nothing new to park -- at the row's very end stays inside the row)
         if constexpr (PCM) {                                            // 8 stereo s16 frames from `rot` on: this row's channel (or the mix) -> (x + 1) / 2 -> texels
             // (rot is a multiple of 8 frames, as bin is -- the host sends other rotations through the waveform kernel: a group never wraps)
-            uint32_t pos = (bin + rot) & (n - 1u);
+            uint32_t pos = TRACK ? bin : (bin + rot) & (n - 1u);         // (a track call's windows are frames, not rings)
             pos = pos + 8u <= n ? pos : n - 8u;                         // defensive: bin and rot are multiples of 8, so this never fires -- but a request never leaves the row
             const glv_i4v a = ld<glv_i4v>(src, pos * 4u), b = ld<glv_i4v>(src, pos * 4u + 16u);
             const uint32_t f[8] = {(uint32_t) a.x, (uint32_t) a.y, (uint32_t) a.z, (uint32_t) a.w, (uint32_t) b.x, (uint32_t) b.y, (uint32_t) b.z, (uint32_t) b.w};
@@ -1107,9 +1155,10 @@ __global__ void __launch_bounds__(64 * kRowsWaves, 2) glv_bars_rows_i8_kernel(co
         // address space and the stores become FLAT ones -- and the lane offset is re-defined opaquely in every basic block that stores: its
         // zero-extension must sit next to the store for the addressing mode to be matched.)
         // register r of a group is row 8 (r / 4) + r % 4 (+ 4 for the upper lanes: in the lane offset) of its 32
-        uint32_t loff = (4u * (lane >> 5) * bars + kb) * (uint32_t) sizeof(OutT);
-        const size_t one_row = (size_t) bars * sizeof(OutT);
-        size_t ro = row0 * one_row;                                             // uniform: offset of the row the next store goes to
+        // (TRACK by steps: the group's rows lie row_step rows apart -- the host keeps 4 row_step bars within the 32-bit lane offset; else row_step is 1)
+        uint32_t loff = (4u * (lane >> 5) * (TRACK ? row_step : 1u) * bars + kb) * (uint32_t) sizeof(OutT);
+        const size_t one_row = (size_t) bars * sizeof(OutT) * (TRACK ? row_step : 1u);
+        size_t ro = row0 * ((size_t) bars * sizeof(OutT));                                             // uniform: offset of the row the next store goes to
         // a partial last block: rows of the group this lane may store
         uint32_t rlim = R > 4u * (lane >> 5) ? R - 4u * (lane >> 5) : 0u;
         asm volatile("" : "+v"(rlim));
@@ -1250,12 +1299,20 @@ hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint3
     const int grid = capped_grid(total, 256);
     const int m = mono ? 1 : 0;
 #define GLV_WAVE_LAUNCH(KIND) \
-    do { if (r16) hipLaunchKernelGGL((glv_wave_kernel<KIND, true>), dim3(grid), dim3(256), 0, st, in, out, total, n, limit, rot, m); \
-         else hipLaunchKernelGGL((glv_wave_kernel<KIND, false>), dim3(grid), dim3(256), 0, st, in, out, total, n, limit, rot, m); } while (0)
+    do { if (r16) hipLaunchKernelGGL((glv_wave_kernel<KIND, true>), dim3(grid), dim3(256), 0, st, in, out, total, n, limit, rot, m, WaveWindows()); \
+         else hipLaunchKernelGGL((glv_wave_kernel<KIND, false>), dim3(grid), dim3(256), 0, st, in, out, total, n, limit, rot, m, WaveWindows()); } while (0)
     if (planar) GLV_WAVE_LAUNCH(2);
     else if (in_mode == IN_S16_STEREO || in_mode == IN_S16_RING) GLV_WAVE_LAUNCH(0);
     else GLV_WAVE_LAUNCH(1);
 #undef GLV_WAVE_LAUNCH
+    return hipGetLastError();
+}
+hipError_t launch_wave_track(const void* pcm, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st) {
+    if (limit == 0 || limit > n || (limit & 7u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || w.hop == 0) return hipErrorInvalidValue;
+    const size_t total = (size_t) w.steps * (w.units / 2u) * (limit / 8u);
+    const int grid = capped_grid(total, 256);
+    if (r16) hipLaunchKernelGGL((glv_wave_kernel<3, true>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);
+    else hipLaunchKernelGGL((glv_wave_kernel<3, false>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);
     return hipGetLastError();
 }
 hipError_t launch_bufscale(const float* in, float* out, size_t total_out, uint32_t k, hipStream_t st) {
@@ -1356,7 +1413,8 @@ hipError_t prepare_bars_rows(uint32_t n, const BarRowsTables* rt) {
 // the i8 kernel for ring_bins in {160, 288, 448, 832} (64 rows per workgroup) or 1600 (32 rows: the bars of n = 32768); nrows == 0: the
 // dynamic-LDS attribute only
 template <int S, int RB, int SRC, bool R16>
-static hipError_t launch_bars_i8_one(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st, uint32_t rot = 0, uint32_t mono = 0) {
+static hipError_t launch_bars_i8_one(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st, uint32_t rot = 0, uint32_t mono = 0,
+                                     const WaveWindows& ww = WaveWindows()) {
     const size_t lds = (size_t) 2 * RB * (S + 16);
     static std::atomic<bool> done[64] = {};
     if (lds > 64 * 1024) {
@@ -1370,7 +1428,13 @@ static hipError_t launch_bars_i8_one(const void* rows, void* bars_out, size_t nr
     }
     if (nrows == 0) return hipSuccess;
     // RB rows per workgroup in x, ranges of rounds in y (512 workgroups, as glv_bars_rows_kernel)
-    const uint32_t xb = (uint32_t) ((nrows + RB - 1) / RB);
+    uint32_t xb = (uint32_t) ((nrows + RB - 1) / RB);
+    if (SRC == I8_PCM_TRACK && ww.by_steps) {                                   // RB steps of one channel row per workgroup: a partial block per channel row
+        if ((4ull * ww.units + 2u) * bars * 4u > 0xffffffffull) return hipErrorInvalidValue;     // (the lane offset of a store spans 4 rows `units` apart)
+        const uint64_t blocks = (uint64_t) ww.units * ((ww.steps + RB - 1u) / RB);
+        if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+        xb = (uint32_t) blocks;
+    }
     uint32_t yb = xb >= 512 ? 1 : (512 + xb - 1) / xb;
 #if defined(GLV_TUNE_BUILD)
     if (const char* o = std::getenv("GLV_ROWS_YB")) yb = (uint32_t) atoi(o);
@@ -1379,17 +1443,18 @@ static hipError_t launch_bars_i8_one(const void* rows, void* bars_out, size_t nr
     const uint32_t rpw = (rt.nrounds + yb - 1) / yb;
     yb = (rt.nrounds + rpw - 1) / rpw;
     hipLaunchKernelGGL((glv_bars_rows_i8_kernel<S, RB, SRC, R16>), dim3(xb, yb), dim3(64 * kRowsWaves), lds, st, rows, bars_out, nrows, n, bars, rt.rounds, rt.nrounds, rpw,
-                       rt.tiles, reinterpret_cast<const glv_i4v*>(rt.wq), rt.fin, rot, mono);
+                       rt.tiles, reinterpret_cast<const glv_i4v*>(rt.wq), rt.fin, rot, mono, ww);
     return hipGetLastError();
 }
 template <int SRC, bool R16>
-static hipError_t launch_bars_i8_in(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st, uint32_t rot = 0, uint32_t mono = 0) {
+static hipError_t launch_bars_i8_in(const void* rows, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarIRowsTables& rt, hipStream_t st, uint32_t rot = 0, uint32_t mono = 0,
+                                    const WaveWindows& ww = WaveWindows()) {
     switch (rt.ring_bins) {
-        case 160: return launch_bars_i8_one<160, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
-        case 288: return launch_bars_i8_one<288, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
-        case 448: return launch_bars_i8_one<448, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
-        case 832: return launch_bars_i8_one<832, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
-        case 1600: return launch_bars_i8_one<1600, 32, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono);
+        case 160: return launch_bars_i8_one<160, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono, ww);
+        case 288: return launch_bars_i8_one<288, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono, ww);
+        case 448: return launch_bars_i8_one<448, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono, ww);
+        case 832: return launch_bars_i8_one<832, 64, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono, ww);
+        case 1600: return launch_bars_i8_one<1600, 32, SRC, R16>(rows, bars_out, nrows, n, bars, rt, st, rot, mono, ww);
     }
     return hipErrorInvalidValue;
 }
@@ -1404,6 +1469,15 @@ hipError_t launch_bars_i8_pcm(const void* pcm, uint32_t rot, bool mono, void* ba
     return r16 ? launch_bars_i8_in<I8_PCM_S16, true>(pcm, bars_out, nrows, n, bars, *rt, st, rot, mono ? 1u : 0u)
                : launch_bars_i8_in<I8_PCM_S16, false>(pcm, bars_out, nrows, n, bars, *rt, st, rot, mono ? 1u : 0u);
 }
+hipError_t launch_bars_i8_pcm_track(const void* pcm, const WaveWindows& w, bool mono, void* bars_out, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st,
+                                    bool r16) {
+    if (rt == nullptr || rt->tiles == nullptr || rt->rounds == nullptr || rt->nrounds == 0 || w.units == 0 || (w.units & 1u) || w.steps == 0) return hipErrorInvalidValue;
+    // a group of 8 frames is two 16-byte loads: every window starts on one
+    if ((reinterpret_cast<uintptr_t>(pcm) & 31u) || (w.hop & 7u) || (w.pitch_frames & 7u)) return hipErrorInvalidValue;
+    const size_t nrows = (size_t) w.steps * w.units;
+    return r16 ? launch_bars_i8_in<I8_PCM_TRACK, true>(pcm, bars_out, nrows, n, bars, *rt, st, 0u, mono ? 1u : 0u, w)
+               : launch_bars_i8_in<I8_PCM_TRACK, false>(pcm, bars_out, nrows, n, bars, *rt, st, 0u, mono ? 1u : 0u, w);
+}
 hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt) {
     if (rt == nullptr || rt->rounds == nullptr || rt->nrounds == 0) return hipSuccess;
     hipError_t e = launch_bars_i8_in<I8_TEXELS, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
@@ -1412,6 +1486,8 @@ hipError_t prepare_bars_i8(uint32_t n, const BarIRowsTables* rt) {
     if (e == hipSuccess) e = launch_bars_i8_in<I8_FLOATS, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
     if (e == hipSuccess) e = launch_bars_i8_in<I8_PCM_S16, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
     if (e == hipSuccess) e = launch_bars_i8_in<I8_PCM_S16, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    if (e == hipSuccess) e = launch_bars_i8_in<I8_PCM_TRACK, true>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
+    if (e == hipSuccess) e = launch_bars_i8_in<I8_PCM_TRACK, false>(nullptr, nullptr, 0, n, 0, *rt, nullptr);
     return e;
 }
 

@@ -105,6 +105,10 @@ def lib() -> C.CDLL:
             L.glv_batch_track_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
             L.glv_batch_track_work_bytes.restype = C.c_uint64
             L.glv_batch_track_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_wave_s16"):      # (likewise)
+            L.glv_batch_track_wave_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
+            L.glv_batch_track_wave_work_bytes.restype = C.c_uint64
+            L.glv_batch_track_wave_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -232,6 +236,22 @@ class Batch:
         stream s = its frames [t * hop, t * hop + n); d_out step-major, step t exactly what process_s16 call t would have written; d_work at least
         track_work_bytes(...) bytes, 256-byte aligned.  Output and state bit for bit those of the sequential calls; stream-ordered, kernels only."""
         _check(lib().glv_batch_track_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
+        """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on
+        arguments the call refuses"""
+        nbytes = int(lib().glv_batch_track_wave_work_bytes(self._h, pitch_frames, hop, steps, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)      # (the message names the code)
+        return nbytes
+
+    def track_wave_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """the wave module's texture of `steps` consecutive updates of every stream from one long buffer (glv_batch_track_wave_s16): d_pcm int16
+        [streams][pitch_frames][2], window t of stream s = its frames [t * hop, t * hop + n), any hop >= 1; ops OP_WAVE [| OP_BARS] [| OP_R16]; d_out
+        step-major, step t bit for bit what process_s16 on window t would have written; d_work at least track_wave_work_bytes(...) bytes, 256-byte
+        aligned.  Stateless; stream-ordered, kernels only."""
+        _check(lib().glv_batch_track_wave_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
 
     def ring_update_s16(self, d_new, new_frames: int, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         _check(lib().glv_batch_ring_update_s16(self._h, _ptr(d_new), new_frames, _ptr(d_out), ops, _ptr(stream)))
@@ -376,6 +396,14 @@ def track_window(n: int, hop: int, pitch_frames: int, s: int, t: int) -> tuple[i
     """(r, k): window t of stream s of a track call is row k of transform launch r"""
     start = s * pitch_frames + t * hop
     return (start % n) // hop, start // n
+
+
+def track_wave_rows(n: int, hop: int, pitch_frames: int, streams: int, steps: int) -> list[int]:
+    """First frame (of the whole [streams][pitch_frames] buffer) of every output row of a wave track call (include/glv_spectrum.h
+    glv_batch_track_wave_s16): row t * streams * 2 + 2 s + c is channel c of the n frames from s * pitch_frames + t * hop on."""
+    if hop < 1 or steps < 1 or pitch_frames < n + (steps - 1) * hop:
+        raise ValueError("hop >= 1, steps >= 1 and pitch_frames >= n + (steps - 1) * hop")
+    return [s * pitch_frames + t * hop for t in range(steps) for s in range(streams) for _ in range(2)]
 
 
 def multi_shard_range(total_streams: int, rank: int, world: int) -> tuple[int, int]:

@@ -131,11 +131,12 @@ enum {
                                                                   reading only the frames its bars sample; every other form is the waveform kernel into rows
                                                                   made at creation, then the bars kernel (glv_batch_last_launches reports which;
                                                                   GLV_UNFUSED_WAVE in the environment at creation forces two launches: diagnostics).
-                                                                  NOT MEASURED YET: which of the two forms is faster on an MI355X has not been timed (no
-                                                                  device was available when this was written); the one-launch form is the default because it
-                                                                  moves fewer bytes (no texel rows between launches), not on evidence.  tools/wave_texture_bench.py
-                                                                  times both forms in one process and is to be run, its output kept as
-                                                                  profiles/r09/wave_texture.txt, and the default set from it.
+                                                                  Measured (tools/wave_texture_bench.py, profiles/r09/wave_texture.txt: one MI355X, 65536
+                                                                  streams, N = 4096, HIP events around every launch, medians of 7 rounds of 20 calls): one
+                                                                  launch 0.724 ms per call, two launches 0.723 ms (90.5 / 90.6 M frames/s) -- no difference
+                                                                  beyond the spread (0.046 / 0.003 ms); for orientation the GL chain's pre-smoothing launch over
+                                                                  the same 131072 rows is 0.48 ms.  The one-launch form stays the default: it is no slower and
+                                                                  needs no rows between launches.  glv_batch_track_wave_s16 inherits it.
                                    A new bit: every call without it is what it was.  Refused: with GLV_OP_FFT / GRAVITY / AVERAGE / RAW / WRANGE / MAGNITUDE /
                                    SMOOTH / OUTPUT_IS_STATE (GLV_ERR_INVALID); GLV_OP_WAVE | GLV_OP_BARS on a gl_storage 0 batch (GLV_ERR_STATE: a float chain has
                                    no texel rows), on a batch whose ops_mask lacked either bit (GLV_ERR_STATE: the rows between the two launches are made at
@@ -383,6 +384,42 @@ int glv_batch_process_s16(glv_batch* b, const int16_t* d_pcm, float* d_out, unsi
 uint64_t glv_batch_track_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0 on arguments the call refuses: glv_last_error then starts with the code's name, "GLV_ERR_INVALID: " or "GLV_ERR_STATE: " */
 int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                         unsigned ops, void* hip_stream);
+/* Track mode for the wave module: the texture of every update of a recording in ONE call (glv_batch_track_s16 refuses GLV_OP_WAVE; these are the entry
+ * points that take it).  Added within ABI 7 without a version change: detect them by the symbol.
+ *   d_pcm   int16 [streams][pitch_frames][2]; window t of stream s = its frames [t * hop, t * hop + n).  hop is ANY value >= 1 (a renderer's is
+ *           rate / fps, e.g. 735), hop > n included; pitch_frames >= n + (steps - 1) * hop and nothing else is asked of it.
+ *   ops     GLV_OP_WAVE [| GLV_OP_BARS] [| GLV_OP_R16], the combinations glv_batch_process_s16 takes for GLV_OP_WAVE; channels 1 and 2; a bar-texel
+ *           table (glv_batch_set_bar_texels) is honoured as there.
+ *   d_out   step-major: d_out + t * (bytes one glv_batch_process_s16 call with these ops writes) is bit for bit what that call on window t would have
+ *           written -- texels, floats c / 65535, pass texels, pass floats.
+ *   d_work  caller-owned, 256-byte aligned, at least glv_batch_track_wave_work_bytes(...) bytes (0: refused, glv_last_error starts with the code's
+ *           name).  Without GLV_OP_BARS none is needed: the query reports 256, the pointer must still be non-NULL and aligned and is never touched.
+ *           With GLV_OP_BARS the query reports what the two launches need -- steps * streams * 2 rows of n texels or floats -- for every hop and pitch:
+ *           it does not see d_pcm, whose alignment decides between one launch and two.  A call that runs in one launch never touches d_work.
+ * Stateless: the batch's state, rings and heads are untouched.  Stream-ordered: kernels and nothing else -- nothing is allocated or synchronised, the
+ * first call can be captured into a hipGraph, glv_batch_timing_* covers it.
+ * Refused: GLV_ERR_INVALID -- any bit besides the three, no GLV_OP_WAVE, steps == 0, hop == 0, pitch_frames too short, a NULL pointer, an unaligned
+ * workspace, steps * streams * 2 > 2^32 rows; GLV_ERR_STATE -- what a GLV_OP_WAVE process call is refused for (gl_storage 0 with bars, a creation mask
+ * without both bits, column texels set, bar parameters changed without glv_batch_set_params) and a single-row (drop-in) batch.  A refused call
+ * launches nothing.
+ * Launches (glv_batch_last_launches; glv_batch_kernel_name as for the process call): 1 without bars (glv_wave_kernel over every window).  With bars 1
+ * (glv_bars_rows_i8_kernel straight from the frames) where the process call fuses -- GLV_BARS_I8_EXACT, averaging sample mode, no bar-texel table, no
+ * GLV_UNFUSED_WAVE -- AND every window starts on a group of 8 frames: d_pcm 32-byte aligned, hop % 8 == 0, pitch_frames % 8 == 0.  With bars in every
+ * other case 2 -- a d_pcm that is not 32-byte aligned (a seek to any frame of a recording) included: the waveform kernel writes the samples the bars
+ * read into the workspace, the bars kernel of the process call's second launch runs over all of them.
+ * Which rows share a workgroup of the one-launch form -- 64 consecutive output rows, or 64 consecutive steps of one channel row, whose windows overlap --
+ * changes no bit; the first is the default (GLV_TRACK_WAVE_ORDER=rows|steps in the environment at creation: diagnostics).
+ * Measured against the same windows through glv_batch_process_s16 one by one, timed with a library built from the commit before these entry points (this
+ * one's build: the same times), the window cutting and upload that form needs NOT counted (tools/track_wave_bench.py; profiles/r11/track_wave.txt: one
+ * MI355X, N = 4096, gl_storage 1, bars = n, bar_phase 0.5, GLV_OP_WAVE | GLV_OP_BARS | GLV_OP_R16; a host clock around the calls and the synchronise that ends
+ * them, medians of 7): hop 256, 2048 steps -- 1 stream 0.066 ms against 22.3 ms (338 x), 8 streams 0.207 against 23.2 ms (112 x), 64 streams 1.38 against
+ * 23.5 ms (17.0 x); 1024 streams, 256 steps, 2.47 against 5.98 ms (2.4 x); hop 735 (two launches, 32 MiB of workspace), 1 stream, 2048 steps, 0.064 against
+ * 22.4 ms (349 x).  The one-by-one form costs ~11 us per update until the chip fills; the track call was the faster at every point measured.  By steps
+ * instead of by rows: 0.048 / 0.178 / 1.43 / 2.65 ms at 1 / 8 / 64 / 1024 streams -- ahead at few streams, behind at many, by about the round-to-round
+ * spread either way (the hop-735 point, where the order plays no part, shows the same 0.064 / 0.044 between the two batches). */
+uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);
+int glv_batch_track_wave_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
