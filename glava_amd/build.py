@@ -24,7 +24,7 @@ ARCH = "gfx950"
 HIPFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
             "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 SIZES = (7, 8, 9, 10, 11, 12, 13, 14)
-PARTS = (0, 1, 2)        # glv_inst.hip is compiled per (size, part): s16 inputs / f32 inputs / the runner-up configuration
+PARTS = (0, 1, 2, 3)     # glv_inst.hip is compiled per (size, part): s16 inputs / f32 inputs / the runner-up configuration / a track call's windows
 
 
 def _inst_jobs(obj_dir: str, sizes, extra: list[str]):

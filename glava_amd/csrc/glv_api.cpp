@@ -103,7 +103,7 @@ std::vector<WisdomEntry> g_wisdom;
 std::atomic<uint64_t> g_wisdom_gen{1};      // bumped by every change of the table: invalidates the per-batch caches
 bool g_wisdom_env_loaded = false;
 
-constexpr int kOpsClasses = 7, kInKinds = 5;     // wisdom classes (wisdom_class): glv::FrameClass 0..6
+constexpr int kOpsClasses = 7, kInKinds = 6;     // wisdom classes (wisdom_class): glv::FrameClass 0..6
 uint32_t log2_round(uint32_t v) { uint32_t l = 0; while ((2u << l) <= v) ++l; return ((v >> l << l) * 3 / 2 <= v && l < 31) ? l + 1 : l; }
 bool same_key(const WisdomKey& a, const WisdomKey& b) {
     return a.n == b.n && a.in_kind == b.in_kind && a.ops_class == b.ops_class && a.log_mode == b.log_mode && a.streams_log2 == b.streams_log2
@@ -592,7 +592,8 @@ void launch_plan(glv_batch* b, uint32_t units, int in_mode, unsigned ops, int* v
             pc.hit = wisdom_lookup(wisdom_key(b, in_mode, ops), &pc.variant, &pc.grid);
             // the ring mode runs the frame mode's kernel with a rotated read position: what was tuned for frames (the input
             // glv_batch_autotune measures) serves it until an entry of its own exists
-            if (!pc.hit && in_mode == glv::IN_S16_RING) pc.hit = wisdom_lookup(wisdom_key(b, glv::IN_S16_STEREO, ops), &pc.variant, &pc.grid);
+            // (... and a track call's windows run it with another address per frame: glv::IN_S16_TRACK)
+            if (!pc.hit && (in_mode == glv::IN_S16_RING || in_mode == glv::IN_S16_TRACK)) pc.hit = wisdom_lookup(wisdom_key(b, glv::IN_S16_STEREO, ops), &pc.variant, &pc.grid);
             pc.gen = gen;
         }
         if (pc.hit) { v = pc.variant; g = pc.grid; }
@@ -1265,32 +1266,29 @@ struct TrackPlan {
     bool out16 = false;                 // the scan's results are texels
     ChainPlan::Bars bars = ChainPlan::NO_BARS;
     uint64_t rows_bytes = 0, work_bytes = 0;   // the transform's region of the workspace (a multiple of 256 bytes), and all of it
+    uint64_t out_rows = 0;              // steps * streams * 2
 };
-// Everything about a track call that does not depend on its pointers or on what the batch did before: refusals, geometry, workspace.
-int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
-    static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by glv_batch_track_s16)
-    const uint32_t n = b->p.n;
+// What the two track entries (glv_batch_track_s16, glv_batch_track_windows_s16) share, written once so that they cannot disagree: the refusals that are
+// not about hop or pitch, and what the chain's stages carry.  In the order the checks have always run: (1) the arguments ...
+int track_args(unsigned ops, uint32_t steps) {
     if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "a track call transforms: GLV_OP_FFT is required (ops 0x%x)", ops);
     const unsigned allowed = GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_BARS | GLV_OP_R16 | GLV_OP_PRIVATE_STATE;
     if (ops & ~allowed)
         return fail(GLV_ERR_INVALID, "a track call takes GLV_OP_FFT with GLV_OP_GRAVITY / AVERAGE / BARS / R16 only (no RAW, SMOOTH, WAVE, WRANGE, MAGNITUDE, OUTPUT_IS_STATE; ops 0x%x)", ops);
     if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
-    const int lh = log2_exact(hop);
-    if (lh < 2 || hop > n) return fail(GLV_ERR_INVALID, "hop=%u: must be a power of two in [4, n=%u]", hop, n);
-    if (pitch_frames % hop != 0) return fail(GLV_ERR_INVALID, "pitch_frames=%u is not a multiple of hop=%u", pitch_frames, hop);
-    if ((uint64_t) pitch_frames < (uint64_t) n + (uint64_t) (steps - 1) * hop)
-        return fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%u frames every hop=%u", pitch_frames, steps, n, hop);
+    return GLV_OK;
+}
+// ... (2) each entry's own hop and pitch rules, then (3) the batch, the rows of the output, and the decisions
+int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by the entry)
     if (b->p.gl_storage == 2) return fail(GLV_ERR_STATE, "gl_storage 2 is the pass-by-pass checker form: a track call runs on gl_storage 0 and 1");
     if (b->ops_mask & GLV_OP_BARS_ONLY)
         return fail(GLV_ERR_STATE, "the batch was created with GLV_OP_BARS_ONLY: its state beyond the live bins does not exist, which the scan over time would read");
     if (b->columns()) return fail(GLV_ERR_STATE, "column texels are set (glv_batch_set_column_texels): a track call has no columns form");
     if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
     if (int rc = check_ops(b, ops, &some_output)) return rc;
-    tp.q = n / hop; tp.log_q = (uint32_t) log2_exact(tp.q);
-    tp.frames = (uint64_t) (b->streams - 1) * pitch_frames + (uint64_t) (steps - 1) * hop + n;
-    tp.k0 = tp.frames / n;
-    const uint64_t out_rows = (uint64_t) steps * b->streams * 2u;
-    if (2u * tp.k0 > 0xffffffffull || out_rows > 0xffffffffull || (uint64_t) b->streams * (pitch_frames / hop) + steps > 0xffffffffull)
+    tp.out_rows = (uint64_t) steps * b->streams * 2u;
+    if (tp.out_rows > 0xffffffffull)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
     tp.state = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
     const bool gl = tp.state && b->state16;                       // the GL_R16 chain, texel state (log_mode 2: its passes one by one -- the same texels)
@@ -1303,9 +1301,44 @@ int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t
     tp.in16 = tp.state ? gl : ((ops & GLV_OP_R16) && !(ops & GLV_OP_BARS));
     // with bars the texel conversion applies to the bars: the rows stay floats, unless the bars kernel takes texel rows
     tp.out16 = (ops & GLV_OP_BARS) ? (tp.bars == ChainPlan::BARS_I8 || tp.bars == ChainPlan::BARS_SNAP) : (ops & GLV_OP_R16) != 0;
-    auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t) 255u; };
+    return GLV_OK;
+}
+uint64_t up256(uint64_t v) { return (v + 255u) & ~(uint64_t) 255u; }
+bool pitch_too_short(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps) {
+    if ((uint64_t) pitch_frames >= (uint64_t) n + (uint64_t) (steps - 1) * hop) return false;
+    (void) fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%u frames every hop=%u", pitch_frames, steps, n, hop);
+    return true;
+}
+// Everything about a track call that does not depend on its pointers or on what the batch did before: refusals, geometry, workspace.
+int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    const uint32_t n = b->p.n;
+    if (int rc = track_args(ops, steps)) return rc;
+    const int lh = log2_exact(hop);
+    if (lh < 2 || hop > n) return fail(GLV_ERR_INVALID, "hop=%u: must be a power of two in [4, n=%u]", hop, n);
+    if (pitch_frames % hop != 0) return fail(GLV_ERR_INVALID, "pitch_frames=%u is not a multiple of hop=%u", pitch_frames, hop);
+    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
+    if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
+    tp.q = n / hop; tp.log_q = (uint32_t) log2_exact(tp.q);
+    tp.frames = (uint64_t) (b->streams - 1) * pitch_frames + (uint64_t) (steps - 1) * hop + n;
+    tp.k0 = tp.frames / n;
+    if (2u * tp.k0 > 0xffffffffull || (uint64_t) b->streams * (pitch_frames / hop) + steps > 0xffffffffull)
+        return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
     tp.rows_bytes = up256((uint64_t) tp.q * 2u * tp.k0 * n * (tp.in16 ? 2u : 4u));
-    tp.work_bytes = tp.rows_bytes + ((ops & GLV_OP_BARS) ? up256(out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+    tp.work_bytes = tp.rows_bytes + ((ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+    return GLV_OK;
+}
+// glv_batch_track_windows_s16: any hop >= 1, any pitch that holds the windows.  One transform launch over exactly the windows asked for, so its region of the
+// workspace is steps * streams * 2 rows; a stateless chain without bars writes d_out directly and needs none (256: 0 stays "refused").  The scan's region
+// exists where a scan runs AND bars follow it.
+int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    const uint32_t n = b->p.n;
+    if (int rc = track_args(ops, steps)) return rc;
+    if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
+    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
+    if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
+    if (!tp.state && !(ops & GLV_OP_BARS)) { tp.rows_bytes = 0; tp.work_bytes = 256; return GLV_OK; }
+    tp.rows_bytes = up256(tp.out_rows * n * (tp.in16 ? 2u : 4u));
+    tp.work_bytes = tp.rows_bytes + (tp.state && (ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
     return GLV_OK;
 }
 
@@ -1366,6 +1399,73 @@ int track(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t ho
     // the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
     if (ops & GLV_OP_AVERAGE) b->head = (uint32_t) (((uint64_t) b->head + steps) % b->p.avg_frames);
     if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
+    // (3) the bars of every step's rows
+    if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) steps * units, (ops & GLV_OP_R16) != 0, st)) return rc;
+    return timed_launch_end(b, st);
+}
+
+// ---- track mode at any hop (glv_batch_track_windows_s16): the transform reads each window where it lies ------------------------------
+// (1) ONE launch of the stateless frame kernel in its IN_S16_TRACK mode over the steps * streams windows the call names (glv_frame.h TrackWindows): rows
+// step-major straight into d_out (a stateless chain without bars: nothing else runs), step-major into the workspace (stateless with bars), or
+// stream-major into the workspace for (2) the scan as `track` runs it, whose geometry with one residue (log_q = 0) and hops_per_pitch = steps IS
+// [stream][step][channel].  (3) The bars pass as in `track`.  State bookkeeping as in `track`.
+int track_windows(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
+    TrackPlan tp;
+    if (int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    if (ops & GLV_OP_GRAVITY) {                                   // (as process: one `applied` buffer per form)
+        const int mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+        if (b->grav_mode != 0 && b->grav_mode != mode)
+            return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
+                                       "their state in different buffers (glv_batch_reset, or one batch per chain)",
+                        b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
+    }
+    if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
+        return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
+    b->last_launches = 0;
+    HIP_TRY(hipSetDevice(b->device));
+    if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+    const uint32_t n = b->p.n, units = b->streams * 2u;
+    const bool bars = (ops & GLV_OP_BARS) != 0;
+    char* const work = static_cast<char*>(d_work);
+    if (int rc = timed_launch_begin(b, st)) return rc;
+    // (1) the transform: every window of the call, one launch
+    const unsigned t_ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u);
+    const glv::FrameClass cls = glv::frame_class(false, false, false, t_ops);
+    glv::FrameArgs a;
+    fill_common(a, b->p, b->tab);
+    a.ops = t_ops; a.log_mode = b->p.log_mode;
+    a.in = d_pcm; a.units = (uint32_t) tp.out_rows;
+    a.out = (tp.state || bars) ? reinterpret_cast<float*>(work) : static_cast<float*>(d_out);
+    a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
+    {
+        int variant = 0, grid = 0;
+        launch_plan(b, a.units, glv::IN_S16_TRACK, t_ops, &variant, &grid);
+        b->last_grid = grid; b->last_variant = variant;
+        const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_TRACK, (int) b->p.log_mode, variant, cls, a, grid, st); ++b->last_launches;
+        if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    }
+    b->kernel_name = "glv_frame_kernel";
+    ChainPlan pl;
+    pl.bars = tp.bars;
+    pl.rows = reinterpret_cast<float*>(work);                       // (stateless: the bars read the transform's rows)
+    if (tp.state) {
+        // (2) the scan over time
+        pl.rows = reinterpret_cast<float*>(work + tp.rows_bytes);
+        a.in = work; a.out = bars ? pl.rows : static_cast<float*>(d_out);
+        a.units = units; a.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE);
+        a.grav = b->grav_cur; a.grav_w = b->d_grav; a.hist = b->d_hist; a.head = b->head;
+        a.grav_sub = b->grav_sub; a.grav_int = b->grav_int ? 1u : 0u; a.gl_storage = tp.in16 ? 1u : 0u;
+        glv::TrackGeometry g;
+        g.n = n; g.steps = steps; g.hops_per_pitch = steps; g.log_q = 0; g.residue_rows = 0; g.out_texels = tp.out16 ? 1u : 0u;
+        const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
+        if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
+        b->kernel_name = "glv_track_scan_kernel";
+        // the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
+        if (ops & GLV_OP_AVERAGE) b->head = (uint32_t) (((uint64_t) b->head + steps) % b->p.avg_frames);
+        if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
+    }
     // (3) the bars of every step's rows
     if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) steps * units, (ops & GLV_OP_R16) != 0, st)) return rc;
     return timed_launch_end(b, st);
@@ -1657,6 +1757,22 @@ int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frame
                         unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     return track(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+uint64_t glv_batch_track_windows_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    TrackPlan tp;
+    if (const int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) {     // no return code to carry it: the message names the code
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return tp.work_bytes;
+}
+
+int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    return track_windows(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {

@@ -21,7 +21,8 @@
 
 namespace glv {
 
-enum InMode { IN_S16_STEREO = 0, IN_F32_PLANAR = 1, IN_S16_RING = 2, IN_F32_STEREO = 3, IN_F32_RING = 4 };
+enum InMode { IN_S16_STEREO = 0, IN_F32_PLANAR = 1, IN_S16_RING = 2, IN_F32_STEREO = 3, IN_F32_RING = 4,
+              IN_S16_TRACK = 5 };    // s16 windows cut out of [streams][pitch_frames][2] recordings where they lie (TrackWindows; never a ring)
 enum Epi { EPI_RAW = 0, EPI_MAG = 1, EPI_MAG_STATE = 2, EPI_RAW_STATE = 3 };
 
 // ops bits as in include/glv_spectrum.h
@@ -95,6 +96,21 @@ GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, u
     return (ops & OP_R16) ? FC_R16 : FC_PLAIN;
 }
 
+// IN_S16_TRACK (glv_batch_track_windows_s16): where the windows of a launch lie and where their rows go.  The kernel enumerates frames stream-major,
+// f = s * steps + t -- neighbouring slots and workgroups then hold overlapping windows of ONE stream at the same moment and the overlap meets in L1 / L2 --
+// and frame f reads the n stereo frames from s * pitch_frames + t * hop on (64-bit arithmetic).  Its two channel rows go to row 2 f + ch (stream-major:
+// what glv_track_scan_kernel reads with log_q = 0, hops_per_pitch = steps) or to row (t * streams + s) * 2 + ch (step_major: what d_out and the bars pass take).
+struct TrackWindows {
+    uint64_t pitch_frames, hop;
+    uint32_t steps, streams;
+    uint32_t step_major, pad;
+};
+// (the host side of the same map, for the emulator and the tests' mirror)
+GLV_HD constexpr uint64_t track_window_start(const TrackWindows& w, uint32_t s, uint32_t t) { return (uint64_t) s * w.pitch_frames + (uint64_t) t * w.hop; }
+GLV_HD constexpr uint64_t track_window_row(const TrackWindows& w, uint32_t s, uint32_t t) {
+    return w.step_major ? ((uint64_t) t * w.streams + s) * 2u : ((uint64_t) s * w.steps + t) * 2u;
+}
+
 struct FrameArgs {
     const void* in;        // s16: int16 [units/2][n][2] (a unit is one channel row of a frame);  f32 planar: float [units][n];
                            // f32 stereo (PulseAudio layout, pulse_input.c:155-178): float [units/2][n][2]
@@ -144,6 +160,7 @@ struct FrameArgs {
                                 // (kernel classes FC_GL16_SNAP*: bar_w holds the uint32 weights W' of bar_snap_lane_sum as float bits)
     const ColumnMap* col_map;   // kernel classes FC_GL16_COLS* (glv_batch_set_column_texels): [bars] columns, bars_out float [units][bars]; the work
                                 // lists cover the DISTINCT texels the columns read and BarItem::res indexes those
+    TrackWindows trk;           // IN_S16_TRACK kernels only (units = 2 * streams * steps), as `rot` serves the ring kinds; appended: every field above keeps its offset
 };
 
 // ---- GLV_OP_BARS arithmetic (smooth.glsl:25-40; tex clamped to [0,1] like the GL_R16 texture the
@@ -719,6 +736,19 @@ struct Frame {
             else off = (uint32_t) tid * 8u + (uint32_t) (i * T) * 8u;
             const u32x2 u = ld<u32x2>(frame, off);
             p.x[i] = u.x; p.y[i] = u.y;
+        }
+    }
+    // IN_S16_TRACK: a window starts at ANY frame of a recording, so its first byte is 4-byte aligned and no more.  One whose first byte is 8-byte aligned
+    // takes the 8-byte loads of a back-to-back frame; any other takes complex point c as the two naturally aligned dwords (2c, 2c + 1), as the ring's odd
+    // rotation does without the wrap.  The choice is per window: uniform where a wave never straddles two slots (T % 64 == 0), a divergent branch at
+    // N = 256 / 512.  Either way the lane reads bytes [8 c, 8 c + 8) of the window, c < NN: exactly the window's n frames.
+    GLV_HD static void load_pcm_at(Raw& p, const void* window, int tid) {
+        if ((reinterpret_cast<uintptr_t>(window) & 7u) == 0u) { load_pcm<false>(p, window, tid, 0u); return; }
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const uint32_t off = (uint32_t) tid * 8u + (uint32_t) (i * T) * 8u;
+            p.x[i] = ld<uint32_t>(window, off);
+            p.y[i] = ld<uint32_t>(window, off + 4u);
         }
     }
     // one sample of channel `ch` (0 = left/low half, 1 = right/high half) -- fifo.c:105-106;

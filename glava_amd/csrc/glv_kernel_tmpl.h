@@ -204,7 +204,8 @@ glv_frame_kernel(const FrameArgs a) {
     constexpr int E = FR::E;
     constexpr int T = FR::T, N = FR::N;
     constexpr bool RING = IN_MODE == IN_S16_RING;
-    constexpr bool S16 = IN_MODE == IN_S16_STEREO || RING;
+    constexpr bool TRACK = IN_MODE == IN_S16_TRACK;    // windows where they lie in a recording (a.trk): never a ring, stateless classes only (launch_variant)
+    constexpr bool S16 = IN_MODE == IN_S16_STEREO || RING || TRACK;
     constexpr bool WSPLIT = S16 && win_split_of(LOG_NN, STATEFUL);     // s16 samples: the window product without fp64 (glv_core.h apply_window_split)
     // f32 rows may hold -0.0, Inf and NaN: no unit-twiddle shortcut, non-finite values through the bit-faithful log
     constexpr bool NF = !S16;
@@ -438,6 +439,19 @@ glv_frame_kernel(const FrameArgs a) {
         return r < a.units ? r : a.units - 1;
     };
 
+    // IN_S16_TRACK: where frame f = s * steps + t of the launch begins and where its channel-0 row goes (glv_frame.h TrackWindows).  One 32-bit division per
+    // call, on a value that is wave-uniform wherever `slot` is (WAVE_SLOT); the window's start in 64-bit arithmetic.
+    // Bounded reads: every caller passes f < units / 2 = streams * steps (frame_of / row_of clamp an idle slot and the look-ahead of a slot's last frame to
+    // the LAST frame, as they do for back-to-back frames), so s < streams and t < steps: the address is the start of a window the call names, and
+    // load_pcm_at reads that window's n frames and not a byte more.  No launch reads outside the windows [s * pitch + t * hop, + n) of the call.
+    struct TrackAt { const void* win; size_t row0; };
+    auto track_at = [&](uint32_t f) -> TrackAt {
+        const uint32_t s = f / a.trk.steps, t = f - s * a.trk.steps;
+        const uint64_t start = (uint64_t) s * a.trk.pitch_frames + (uint64_t) t * a.trk.hop;
+        return { static_cast<const char*>(a.in) + start * 4u, a.trk.step_major ? ((size_t) t * a.trk.streams + s) * 2u : (size_t) f * 2u };
+    };
+    (void) track_at;
+
     unsigned xcount = 0;
     // A workgroup with a single slot takes both channel rows of a frame back to back (SEQ = 2), so
     // the frame's PCM is still fetched from HBM once and re-read from this CU's L1/L2.
@@ -471,9 +485,13 @@ glv_frame_kernel(const FrameArgs a) {
         auto frame_ptr = [&](uint32_t f) -> const void* { return static_cast<const char*>(a.in) + (size_t) f * ((size_t) N * 4); };
         cf v[E];
         typename FR::Raw raw;
+        size_t trow = 0, trow_next = 0;      // TRACK: channel-0 row of the slot's current frame / of the frame whose samples `raw` holds
+        (void) trow; (void) trow_next; (void) frame_ptr;
         if (blockIdx.x * SLOTS < nframes) {
             int tid = tid_outer;
             asm volatile("" : "+v"(tid));
+            if constexpr (TRACK) { const TrackAt w = track_at(frame_of(0)); FR::load_pcm_at(raw, w.win, tid); trow = w.row0; }
+            else
             FR::template load_pcm<RING>(raw, frame_ptr(frame_of(0)), tid, a.rot);
             FR::template unpack_window<0, WSPLIT>(v, raw, win, tid, 0u, a.mono != 0);
         }
@@ -486,6 +504,8 @@ glv_frame_kernel(const FrameArgs a) {
             const uint32_t fraw = blockIdx.x * SLOTS + m * fstride + slot;
             const bool active = fraw < nframes;
             const uint32_t f = frame_of(m);
+            if constexpr (TRACK) { if (ch) { const TrackAt w = track_at(frame_of(m + 1)); FR::load_pcm_at(raw, w.win, tid); trow_next = w.row0; } }   // A
+            else
             if (ch) FR::template load_pcm<RING>(raw, frame_ptr(frame_of(m + 1)), tid, a.rot);   // A
             if constexpr (LIVE_PRE) { FR::live_prefetch(live_pre, (size_t) f * 2 + ch, tid, a); live_pre_ptr = &live_pre; }   // A': the row's old state (W awaits it)
             GLV_SCHED_FENCE();
@@ -495,6 +515,8 @@ glv_frame_kernel(const FrameArgs a) {
             // WPRE: the first window values of row r+1 are requested ahead of D's stores (glv_frame.h window_prefetch)
             typename FR::template WinPre<WPRE> wp;
             if constexpr (WPRE > 0) { FR::template window_prefetch<WPRE>(wp, win, tid); GLV_SCHED_FENCE(); }
+            if constexpr (TRACK) { finish_row(v, trow + ch, tid, active); if (ch) trow = trow_next; }   // D
+            else
             finish_row(v, (size_t) f * 2 + ch, tid, active);                                     // D
             GLV_SCHED_FENCE();
             FR::template unpack_window<WPRE, WSPLIT>(v, raw, win, tid, ch ^ 1u, a.mono != 0, wp.w);      // C
@@ -588,6 +610,17 @@ glv_frame_kernel(const FrameArgs a) {
         const bool active = base + slot < a.units;
         const uint32_t row = row_of(base);
         cf v[E];
+        if constexpr (TRACK) {
+            // not pipelined (no production configuration): one slot = one channel row of the window its frame names, one division per row
+            typename FR::Raw raw;
+            const TrackAt w = track_at(row >> 1);
+            FR::load_pcm_at(raw, w.win, tid);
+            GLV_SCHED_FENCE();
+            FR::template unpack_window<0, WSPLIT>(v, raw, win, tid, row & 1u, a.mono != 0);
+            BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
+            finish_row(v, w.row0 + (row & 1u), tid, active);
+            continue;
+        } else
         if constexpr (S16) {
             // not pipelined: one slot = one channel row; the two channels of a frame sit in neighbouring
             // slots (the second reader of the frame's PCM hits L1/L2).  Measured faster than keeping the
@@ -643,7 +676,8 @@ hipError_t launch_variant(FrameClass cls, const FrameArgs& a, int grid, hipStrea
     // region (NBUF 1); the GL_R16 chain is built for log modes 0 and 1
     auto launch_class = [&](auto c) -> hipError_t {
         constexpr int C = decltype(c)::value;
-        if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2)) return hipErrorInvalidValue;
+        // (IN_S16_TRACK: a track call's transform is always stateless -- the other twelve classes are not instantiated for it)
+        if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2) || (IN_MODE == IN_S16_TRACK && fc_has_state(C))) return hipErrorInvalidValue;
         else if constexpr (fc_has_state(C))
             return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE_S>, done[C]);
         else return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TWREG, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE>, done[C]);

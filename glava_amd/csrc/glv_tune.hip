@@ -11,6 +11,9 @@
 #ifndef GLV_TUNE_LOG_NN
 #define GLV_TUNE_LOG_NN 11
 #endif
+#ifndef GLV_TUNE_IN_MODE          // -DGLV_TUNE_IN_MODE=IN_S16_TRACK: the variants' kernels for a track call's windows (tools/isa_compile.sh: registers, scratch)
+#define GLV_TUNE_IN_MODE IN_S16_STEREO
+#endif
 
 namespace glv {
 namespace {
@@ -27,9 +30,9 @@ hipError_t launch_v(int in_mode, int log_mode, const FrameArgs& a, int grid, hip
     if (in_mode != IN_S16_STEREO) return hipErrorInvalidValue;
     const FrameClass cls = frame_class(false, false, false, a.ops);      // the plain and float-state classes: extra_ops of glv_tune_run*
 #if !defined(GLV_TUNE_NO_LOG0)
-    if (log_mode == 0) return launch_variant<K, IN_S16_STEREO, 0, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(cls, a, grid, st);
+    if (log_mode == 0) return launch_variant<K, GLV_TUNE_IN_MODE, 0, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(cls, a, grid, st);
 #endif
-    return launch_variant<K, IN_S16_STEREO, 1, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(cls, a, grid, st);
+    return launch_variant<K, GLV_TUNE_IN_MODE, 1, SLOTS, NBUF, TWREG, WINLDS, OCC, PF, TL, LE, WP, WPS>(cls, a, grid, st);
 }
 
 #define V(S, NB, TR, WL, OC) { "slots=" #S " nbuf=" #NB " twreg=" #TR " winlds=" #WL " occ=" #OC, launch_v<S, NB, TR, WL, OC>, S }

@@ -105,6 +105,10 @@ def lib() -> C.CDLL:
             L.glv_batch_track_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
             L.glv_batch_track_work_bytes.restype = C.c_uint64
             L.glv_batch_track_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_windows_s16"):   # (likewise)
+            L.glv_batch_track_windows_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
+            L.glv_batch_track_windows_work_bytes.restype = C.c_uint64
+            L.glv_batch_track_windows_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
         if hasattr(L, "glv_batch_track_wave_s16"):      # (likewise)
             L.glv_batch_track_wave_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
             L.glv_batch_track_wave_work_bytes.restype = C.c_uint64
@@ -236,6 +240,21 @@ class Batch:
         stream s = its frames [t * hop, t * hop + n); d_out step-major, step t exactly what process_s16 call t would have written; d_work at least
         track_work_bytes(...) bytes, 256-byte aligned.  Output and state bit for bit those of the sequential calls; stream-ordered, kernels only."""
         _check(lib().glv_batch_track_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_windows_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
+        """bytes of device workspace track_windows_s16 needs for these arguments (glv_batch_track_windows_work_bytes; 256 where the call needs none); raises
+        on arguments the call refuses"""
+        nbytes = int(lib().glv_batch_track_windows_work_bytes(self._h, pitch_frames, hop, steps, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)      # (the message names the code)
+        return nbytes
+
+    def track_windows_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_s16 at ANY hop >= 1 and any pitch_frames >= n + (steps - 1) * hop (glv_batch_track_windows_s16): one transform launch reads each window
+        where it lies; d_pcm 4-byte aligned; d_work at least track_windows_work_bytes(...) bytes, 256-byte aligned.  Output and state bit for bit those of
+        the sequential calls; stream-ordered, kernels only."""
+        _check(lib().glv_batch_track_windows_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on
@@ -396,6 +415,18 @@ def track_window(n: int, hop: int, pitch_frames: int, s: int, t: int) -> tuple[i
     """(r, k): window t of stream s of a track call is row k of transform launch r"""
     start = s * pitch_frames + t * hop
     return (start % n) // hop, start // n
+
+
+def track_window_start(pitch_frames: int, hop: int, s: int, t: int) -> int:
+    """first frame (of the whole [streams][pitch_frames] buffer) of window t of stream s of a track call"""
+    return s * pitch_frames + t * hop
+
+
+def track_windows_rows(streams: int, steps: int, step_major: bool) -> list[int]:
+    """The transform launch of glv_batch_track_windows_s16 (glava_amd/csrc/glv_frame.h TrackWindows): the kernel enumerates frames stream-major,
+    f = s * steps + t; entry f is the channel-0 row frame f writes (channel 1: the next row) -- 2 f (stream-major: what the scan over time reads) or
+    (t * streams + s) * 2 (step_major: what d_out and the bars pass take)."""
+    return [(t * streams + s) * 2 if step_major else (s * steps + t) * 2 for s in range(streams) for t in range(steps)]
 
 
 def track_wave_rows(n: int, hop: int, pitch_frames: int, streams: int, steps: int) -> list[int]:

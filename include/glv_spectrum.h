@@ -384,6 +384,49 @@ int glv_batch_process_s16(glv_batch* b, const int16_t* d_pcm, float* d_out, unsi
 uint64_t glv_batch_track_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0 on arguments the call refuses: glv_last_error then starts with the code's name, "GLV_ERR_INVALID: " or "GLV_ERR_STATE: " */
 int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                         unsigned ops, void* hip_stream);
+/* Track mode at ANY hop: the transform reads each window where it lies in the recording.  Added within ABI 7 without a version change: detect them by
+ * the symbol.  glv_batch_track_s16 above is unchanged.
+ *   d_pcm   int16 [streams][pitch_frames][2], aligned like any int16 frame pointer (4 bytes: a seek to an odd frame of a recording is a valid argument);
+ *           window t of stream s = its frames [t * hop, t * hop + n).  hop is ANY value >= 1 (a renderer's is rate / fps: 735 at 44.1 kHz and 60 fps, 1470,
+ *           800), hop > n included; pitch_frames >= n + (steps - 1) * hop and nothing else is asked of it.
+ *   d_out, d_work, ops: as for glv_batch_track_s16.
+ * Contract: glv_batch_track_s16's, word for word -- the output of step t and the batch's state afterwards (gravity store, history ring, ring head, which
+ * gravity form the batch is in) are bit for bit what `steps` consecutive glv_batch_process_s16(b, window_t, out_t, ops, st) calls produce and leave behind.
+ * So chunks compose, calls mix with process / ring / glv_batch_track_s16 calls on the same batch, and at a hop both entries take the two produce identical
+ * output and state.
+ * Accepted: what glv_batch_track_s16 accepts (GLV_OP_FFT required, with GLV_OP_GRAVITY / AVERAGE / BARS / R16 / PRIVATE_STATE; gl_storage 0 and 1, channels
+ * 1 and 2, every log_mode, a bar-texel table honoured).  Refused: what it refuses minus its two hop / pitch rules, plus hop == 0 -- GLV_ERR_INVALID: other
+ * operator bits, steps == 0, hop == 0, pitch_frames < n + (steps - 1) * hop, a NULL pointer, a workspace that is not 256-byte aligned,
+ * steps * streams * 2 > 2^32 - 1 rows; GLV_ERR_STATE: gl_storage 2, a GLV_OP_BARS_ONLY batch, column texels set, a single-row (drop-in) batch, and everything
+ * glv_batch_process_s16 refuses (the gravity form mix, unannounced state, parameters changed without glv_batch_set_params).  A refused call launches
+ * nothing and leaves the batch untouched; the query then returns 0 with the code's name at the front of glv_last_error.
+ * Stream-ordered: kernels and nothing else -- nothing is allocated or synchronised, the first call can be captured, glv_batch_timing_* covers it.
+ * Launches (glv_batch_last_launches):
+ *   1  a stateless chain without bars (GLV_OP_FFT [| GLV_OP_R16], a spectrogram): the transform kernel (glv_batch_kernel_name: glv_frame_kernel) takes every
+ *      window of the call in ONE launch and writes step-major rows straight into d_out.  The workspace is never touched; the query reports 256.
+ *   2  stateless with bars: the transform writes step-major rows into the workspace, the bars kernel follows.
+ *   2  with state: the transform writes rows [stream][step][channel] into the workspace, glv_track_scan_kernel (glv_batch_kernel_name) walks them as in
+ *      glv_batch_track_s16; 3 with bars.
+ * The transform enumerates windows stream by stream, so the overlapping windows of one stream are in flight together and their overlap meets in L1 / L2; a
+ * window whose first byte is 8-byte aligned is read with 8-byte loads, any other as pairs of dwords (all are aligned when d_pcm is 8-byte aligned and hop and
+ * pitch_frames are even).  No launch reads a byte outside the windows the call names.
+ * Workspace (R = steps * streams * 2 rows, sizes rounded up to 256 bytes): 256 for the one-launch form; else R * n * (2 for a GL_R16 chain's texel rows, 4
+ * for floats) for the transform, plus, with state AND bars, R * n * (2 | 4) for the scan's results as glv_batch_track_s16 sizes them.  Never more than
+ * glv_batch_track_s16 needs for the same call (its transform region is (n / hop) * 2 * floor(frames / n) rows, frames = (streams - 1) * pitch_frames +
+ * (steps - 1) * hop + n: at least R, and growing with the pitch).
+ * Measured (tools/track_windows_bench.py; profiles/r12/track_windows.txt: one MI355X, N = 4096, the GL chain with F = 5 and the pre-smoothing pass, texels
+ * out; a host clock around the calls and the synchronise that ends them, medians of 7 alternating rounds; 1 / 8 / 64 streams x 2048 steps, 1024 x 256):
+ *   hop 735 against the same windows through glv_batch_process_s16 one by one: 2.02 against 41.6 ms (20.6 x), 2.54 against 44.7 (17.6 x), 5.55 against 46.2
+ *   (8.3 x), 7.68 against 10.7 (1.40 x).  Hop 736, whose windows are all 8-byte aligned: 2.02 / 2.58 / 5.50 / 7.74 ms, and hop 735 from a d_pcm one frame on:
+ *   2.03 / 2.54 / 5.53 / 7.70 -- inside the round-to-round spread of hop 735 at every point: the dword loads cost nothing measurable.
+ *   hop 256 against glv_batch_track_s16 in the same library (3 launches against 18): tight pitch 1.99 against 2.10 ms, 2.53 against 2.58, 5.20 against 5.78,
+ *   7.63 against 8.32 -- ahead at 1 and at 1024 streams, inside the spread (none) at 8 and 64; pitch of twice what the call consumes 1.98 against 2.10,
+ *   2.54 against 2.75, 5.19 against 6.65 (1.28 x), 7.65 against 10.6 (1.39 x), with 8 against 12.5 GiB of workspace at 1024 streams.
+ * Which entry for a power-of-two hop: this one, at every stream count measured (1 to 1024) -- it was behind at none, its time and workspace do not grow with
+ * the pitch, and from 64 streams on a recording with slack behind its windows runs 1.3-1.4 x faster.  Neither entry delegates to the other. */
+uint64_t glv_batch_track_windows_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0: refused */
+int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream);
 /* Track mode for the wave module: the texture of every update of a recording in ONE call (glv_batch_track_s16 refuses GLV_OP_WAVE; these are the entry
  * points that take it).  Added within ABI 7 without a version change: detect them by the symbol.
  *   d_pcm   int16 [streams][pitch_frames][2]; window t of stream s = its frames [t * hop, t * hop + n).  hop is ANY value >= 1 (a renderer's is
