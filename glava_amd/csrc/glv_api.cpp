@@ -1224,43 +1224,62 @@ int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, 
     return timed_launch_end(b, st);
 }
 
+// What a call asks of the state the batch's earlier calls and glv_batch_set_params left, written once for process and the track executor.
+// transform_gravity keeps ONE `applied` buffer per slot (render.c:724).  Here it lives in d_grav when gravity runs
+// without average and in the newest ring slot when both run fused; a batch that mixed the two forms would silently
+// continue from a stale state, so that is refused (reset the batch, or use one batch per operator chain).
+int gravity_form(unsigned ops) { return !(ops & GLV_OP_GRAVITY) ? 0 : (ops & GLV_OP_AVERAGE) ? 2 : 1; }
+int refuse_gravity_mix(const glv_batch* b, unsigned ops) {
+    const int mode = gravity_form(ops);
+    if (mode == 0 || b->grav_mode == 0 || b->grav_mode == mode) return GLV_OK;
+    return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
+                               "their state in different buffers (glv_batch_reset, or one batch per chain)",
+                b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
+}
+// ... committed once nothing can refuse the call any more
+void commit_gravity_form(glv_batch* b, unsigned ops) {
+    if (ops & GLV_OP_GRAVITY) b->grav_mode = gravity_form(ops);
+}
+int refuse_stale_tilt(const glv_batch* b) {
+    if (b->tab.tilt_scale == b->p.fft_scale && b->tab.tilt_cutoff == b->p.fft_cutoff && b->tab.tilt_fold == (b->p.log_mode == 1)) return GLV_OK;
+    return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
+}
+
 // One update of `units` channel rows through the fused kernel (or the post kernel when no FFT is asked).
 int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units,
             uint32_t rot, hipStream_t st) {
     if (!d_in) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (int rc = check_ops(b, ops, d_out)) return rc;
-    // transform_gravity keeps ONE `applied` buffer per slot (render.c:724).  Here it lives in d_grav when gravity runs
-    // without average and in the newest ring slot when both run fused; a batch that mixed the two forms would silently
-    // continue from a stale state, so that is refused (reset the batch, or use one batch per operator chain).
-    if (ops & GLV_OP_GRAVITY) {
-        const int mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
-        if (b->grav_mode != 0 && b->grav_mode != mode)
-            return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
-                                       "their state in different buffers (glv_batch_reset, or one batch per chain)",
-                        b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
-    }
+    if (int rc = refuse_gravity_mix(b, ops)) return rc;
     b->last_launches = 0;
     HIP_TRY(hipSetDevice(b->device));
     ChainPlan pl;
     if (int rc = plan_chain(b, in_mode, ops, units, rot, d_out, pl)) return rc;
-    if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
-        return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
-    if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
+    if (int rc = refuse_stale_tilt(b)) return rc;
+    commit_gravity_form(b, ops);
     if (pl.route == ChainPlan::WAVE) return run_wave(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
     return run_chain(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
 }
 
-// ---- track mode: `steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16) ----------------------
-// Three stages, kernels only.  (1) The transform, with the stateless frame kernels as they are: the whole [streams * pitch] frame sequence is
-// cut into back-to-back windows of n frames q = n / hop times, launch r starting r * hop frames in -- window t of stream s, which starts at
-// a multiple h of hop, is row h / q of launch h % q.  The rows (texels where the chain's first act is the GL_R16 upload) go to the caller's
-// workspace.  (2) glv_track_scan_kernel walks the steps per bin with the state on chip and writes every step's result -- into d_out, or
-// with GLV_OP_BARS into the workspace's second region in the row format the bars kernel takes.  (3) The bars of a second launch over
-// steps * streams * 2 finished rows.
+// ---- track mode: `steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16, glv_batch_track_windows_s16) ------------
+// One executor (`track`) carries out a TrackPlan in three stages, kernels only.  (1) The transform, with the stateless frame kernels as they are, in
+// one of two forms.  Residues (plan_track: hop a power of two, track_residues): the whole [streams * pitch] frame sequence is cut into
+// back-to-back windows of n frames q = n / hop times, launch r starting r * hop frames in -- window t of stream s, which starts at a multiple h of
+// hop, is row h / q of launch h % q.  Windows (plan_track_windows: any hop, track_windows): ONE launch in the kernel's IN_S16_TRACK mode over
+// the steps * streams windows the call names, each read where it lies (glv_frame.h TrackWindows) -- rows step-major straight into d_out (a stateless
+// chain without bars: nothing else runs), step-major into the workspace (stateless with bars), or stream-major into the workspace for the scan, whose
+// geometry with one residue (log_q = 0) and hops_per_pitch = steps IS [stream][step][channel].  Either way the rows are texels where the chain's
+// first act is the GL_R16 upload.  (2) glv_track_scan_kernel (track_scan) walks the steps per bin with the state on chip and writes every
+// step's result -- into d_out, or with GLV_OP_BARS into the workspace's second region in the row format the bars kernel takes.  (3) The bars of a
+// second launch over steps * streams * 2 finished rows.
 struct TrackPlan {
     uint32_t q = 0, log_q = 0;          // residue launches
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
     uint64_t k0 = 0;                    // windows of launch 0 (launch r: (frames - r * hop) / n, k0 or k0 - 1)
+    bool windows = false;               // stage (1) is the one launch over the windows where they lie, else the q residue launches
+    bool to_out = false;                // stage (1) writes d_out and nothing else runs, else it writes the start of the workspace
+    bool scan = false;                  // stage (2) runs: the chain keeps state, or stage (1) left residues (which only the scan puts in step order)
+    uint32_t hops_per_pitch = 0, residue_rows = 0;   // TrackGeometry, with log_q: where the scan finds window t of stream s among stage (1)'s rows
     bool state = false;                 // the chain keeps gravity / average state
     bool in16 = false;                  // the transform's rows are GL_R16 texels (kernel class FC_R16), else floats (FC_PLAIN)
     bool out16 = false;                 // the scan's results are texels
@@ -1288,7 +1307,7 @@ int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsig
     if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
     if (int rc = check_ops(b, ops, &some_output)) return rc;
     tp.out_rows = (uint64_t) steps * b->streams * 2u;
-    if (tp.out_rows > 0xffffffffull)
+    if (tp.out_rows > 0xffffffffull)                              // (the transform and the scan count their rows in FrameArgs::units, a uint32_t)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
     tp.state = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
     const bool gl = tp.state && b->state16;                       // the GL_R16 chain, texel state (log_mode 2: its passes one by one -- the same texels)
@@ -1323,6 +1342,7 @@ int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t
     tp.k0 = tp.frames / n;
     if (2u * tp.k0 > 0xffffffffull || (uint64_t) b->streams * (pitch_frames / hop) + steps > 0xffffffffull)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
+    tp.scan = true; tp.hops_per_pitch = pitch_frames / hop; tp.residue_rows = (uint32_t) (2u * tp.k0);
     tp.rows_bytes = up256((uint64_t) tp.q * 2u * tp.k0 * n * (tp.in16 ? 2u : 4u));
     tp.work_bytes = tp.rows_bytes + ((ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
     return GLV_OK;
@@ -1336,38 +1356,22 @@ int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, 
     if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
     if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
     if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
-    if (!tp.state && !(ops & GLV_OP_BARS)) { tp.rows_bytes = 0; tp.work_bytes = 256; return GLV_OK; }
+    tp.windows = true; tp.scan = tp.state; tp.hops_per_pitch = steps;      // (one residue: log_q and residue_rows stay 0)
+    tp.to_out = !tp.state && !(ops & GLV_OP_BARS);
+    if (tp.to_out) { tp.rows_bytes = 0; tp.work_bytes = 256; return GLV_OK; }
     tp.rows_bytes = up256(tp.out_rows * n * (tp.in16 ? 2u : 4u));
     tp.work_bytes = tp.rows_bytes + (tp.state && (ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
     return GLV_OK;
 }
 
-int track(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+int refuse_track_pointers(const void* d_pcm, const void* d_out, const void* d_work) {
     if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
-    TrackPlan tp;
-    if (int rc = plan_track(b, pitch_frames, hop, steps, ops, tp)) return rc;
-    if (ops & GLV_OP_GRAVITY) {                                   // (as process: one `applied` buffer per form)
-        const int mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
-        if (b->grav_mode != 0 && b->grav_mode != mode)
-            return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
-                                       "their state in different buffers (glv_batch_reset, or one batch per chain)",
-                        b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
-    }
-    if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
-        return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
-    b->last_launches = 0;
-    HIP_TRY(hipSetDevice(b->device));
-    if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
-    const uint32_t n = b->p.n, units = b->streams * 2u;
-    char* const work = static_cast<char*>(d_work);
-    if (int rc = timed_launch_begin(b, st)) return rc;
-    // (1) the transform: q launches of the stateless kernel class, each over back-to-back windows
-    const unsigned t_ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u);
-    const glv::FrameClass cls = glv::frame_class(false, false, false, t_ops);
-    glv::FrameArgs a;
-    fill_common(a, b->p, b->tab);
-    a.ops = t_ops; a.log_mode = b->p.log_mode;
+    return GLV_OK;
+}
+// (1) as residues: q launches of the stateless kernel class, each over back-to-back windows -- the only loop of launches on the track path
+int track_residues(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::FrameClass cls, const int16_t* d_pcm, uint32_t hop, char* work, hipStream_t st) {
+    const uint32_t n = b->p.n;
     for (uint32_t r = 0; r < tp.q; ++r) {
         const uint64_t k_r = (tp.frames - (uint64_t) r * hop) / n;            // k0 or k0 - 1; never past the last window any step reads
         if (k_r == 0) continue;                                                // (counted all the same: the launch count is n / hop)
@@ -1375,99 +1379,66 @@ int track(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t ho
         a.out = reinterpret_cast<float*>(work + (size_t) r * 2u * tp.k0 * n * (tp.in16 ? 2u : 4u));
         a.units = (uint32_t) (2u * k_r);
         int variant = 0, grid = 0;
-        launch_plan(b, a.units, glv::IN_S16_STEREO, t_ops, &variant, &grid);
+        launch_plan(b, a.units, glv::IN_S16_STEREO, a.ops, &variant, &grid);
         b->last_grid = grid; b->last_variant = variant;
         const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_STEREO, (int) b->p.log_mode, variant, cls, a, grid, st);
         if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     }
     b->last_launches += (int) tp.q;
-    // (2) the scan over time
-    ChainPlan pl;
-    pl.bars = tp.bars;
-    pl.rows = reinterpret_cast<float*>(work + tp.rows_bytes);
-    a.in = work; a.out = (ops & GLV_OP_BARS) ? pl.rows : static_cast<float*>(d_out);
-    a.units = units; a.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE);
+    return GLV_OK;
+}
+// (1) as windows: every window of the call where it lies, one launch, into `rows`
+int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::FrameClass cls, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps,
+                        float* rows, hipStream_t st) {
+    a.in = d_pcm; a.out = rows; a.units = (uint32_t) tp.out_rows;
+    a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
+    int variant = 0, grid = 0;
+    launch_plan(b, a.units, glv::IN_S16_TRACK, a.ops, &variant, &grid);
+    b->last_grid = grid; b->last_variant = variant;
+    const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_TRACK, (int) b->p.log_mode, variant, cls, a, grid, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    b->kernel_name = "glv_frame_kernel";
+    return GLV_OK;
+}
+// (2) the scan over time, from stage (1)'s rows at the start of the workspace into `out`
+int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t steps, const char* work, float* out, unsigned ops, hipStream_t st) {
+    a.in = work; a.out = out;
+    a.units = b->streams * 2u; a.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE);
     a.grav = b->grav_cur; a.grav_w = b->d_grav; a.hist = b->d_hist; a.head = b->head;
     a.grav_sub = b->grav_sub; a.grav_int = b->grav_int ? 1u : 0u; a.gl_storage = tp.in16 && tp.state ? 1u : 0u;
     glv::TrackGeometry g;
-    g.n = n; g.steps = steps; g.hops_per_pitch = pitch_frames / hop; g.log_q = tp.log_q; g.residue_rows = (uint32_t) (2u * tp.k0); g.out_texels = tp.out16 ? 1u : 0u;
-    {
-        const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
-        if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
-    }
+    g.n = b->p.n; g.steps = steps; g.hops_per_pitch = tp.hops_per_pitch; g.log_q = tp.log_q; g.residue_rows = tp.residue_rows; g.out_texels = tp.out16 ? 1u : 0u;
+    const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
     b->kernel_name = "glv_track_scan_kernel";
     // the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
     if (ops & GLV_OP_AVERAGE) b->head = (uint32_t) (((uint64_t) b->head + steps) % b->p.avg_frames);
     if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
-    // (3) the bars of every step's rows
-    if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) steps * units, (ops & GLV_OP_R16) != 0, st)) return rc;
-    return timed_launch_end(b, st);
+    return GLV_OK;
 }
-
-// ---- track mode at any hop (glv_batch_track_windows_s16): the transform reads each window where it lies ------------------------------
-// (1) ONE launch of the stateless frame kernel in its IN_S16_TRACK mode over the steps * streams windows the call names (glv_frame.h TrackWindows): rows
-// step-major straight into d_out (a stateless chain without bars: nothing else runs), step-major into the workspace (stateless with bars), or
-// stream-major into the workspace for (2) the scan as `track` runs it, whose geometry with one residue (log_q = 0) and hops_per_pitch = steps IS
-// [stream][step][channel].  (3) The bars pass as in `track`.  State bookkeeping as in `track`.
-int track_windows(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
-    if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
-    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
-    TrackPlan tp;
-    if (int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) return rc;
-    if (ops & GLV_OP_GRAVITY) {                                   // (as process: one `applied` buffer per form)
-        const int mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
-        if (b->grav_mode != 0 && b->grav_mode != mode)
-            return fail(GLV_ERR_STATE, "gravity was last applied %s average on this batch and is now requested %s it: the two forms keep "
-                                       "their state in different buffers (glv_batch_reset, or one batch per chain)",
-                        b->grav_mode == 2 ? "fused with" : "without", mode == 2 ? "fused with" : "without");
-    }
-    if (b->tab.tilt_scale != b->p.fft_scale || b->tab.tilt_cutoff != b->p.fft_cutoff || b->tab.tilt_fold != (b->p.log_mode == 1))
-        return fail(GLV_ERR_STATE, "fft_scale / fft_cutoff / log_mode changed without glv_batch_set_params");
+// Carries a plan out: what the plan could not know (the pointers, what the batch did before), then the stages.  A refused call leaves the batch untouched.
+int track(glv_batch* b, const TrackPlan& tp, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (int rc = refuse_track_pointers(d_pcm, d_out, d_work)) return rc;
+    if (int rc = refuse_gravity_mix(b, ops)) return rc;
+    if (int rc = refuse_stale_tilt(b)) return rc;
     b->last_launches = 0;
     HIP_TRY(hipSetDevice(b->device));
-    if (ops & GLV_OP_GRAVITY) b->grav_mode = (ops & GLV_OP_AVERAGE) ? 2 : 1;
-    const uint32_t n = b->p.n, units = b->streams * 2u;
-    const bool bars = (ops & GLV_OP_BARS) != 0;
+    commit_gravity_form(b, ops);
     char* const work = static_cast<char*>(d_work);
+    float* const out = static_cast<float*>(d_out);
     if (int rc = timed_launch_begin(b, st)) return rc;
-    // (1) the transform: every window of the call, one launch
-    const unsigned t_ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u);
-    const glv::FrameClass cls = glv::frame_class(false, false, false, t_ops);
     glv::FrameArgs a;
     fill_common(a, b->p, b->tab);
-    a.ops = t_ops; a.log_mode = b->p.log_mode;
-    a.in = d_pcm; a.units = (uint32_t) tp.out_rows;
-    a.out = (tp.state || bars) ? reinterpret_cast<float*>(work) : static_cast<float*>(d_out);
-    a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
-    {
-        int variant = 0, grid = 0;
-        launch_plan(b, a.units, glv::IN_S16_TRACK, t_ops, &variant, &grid);
-        b->last_grid = grid; b->last_variant = variant;
-        const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_TRACK, (int) b->p.log_mode, variant, cls, a, grid, st); ++b->last_launches;
-        if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    }
-    b->kernel_name = "glv_frame_kernel";
+    a.ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u); a.log_mode = b->p.log_mode;
+    const glv::FrameClass cls = glv::frame_class(false, false, false, a.ops);
+    if (int rc = tp.windows ? track_windows(b, tp, a, cls, d_pcm, pitch_frames, hop, steps, tp.to_out ? out : reinterpret_cast<float*>(work), st)
+                            : track_residues(b, tp, a, cls, d_pcm, hop, work, st)) return rc;
     ChainPlan pl;
     pl.bars = tp.bars;
-    pl.rows = reinterpret_cast<float*>(work);                       // (stateless: the bars read the transform's rows)
-    if (tp.state) {
-        // (2) the scan over time
-        pl.rows = reinterpret_cast<float*>(work + tp.rows_bytes);
-        a.in = work; a.out = bars ? pl.rows : static_cast<float*>(d_out);
-        a.units = units; a.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE);
-        a.grav = b->grav_cur; a.grav_w = b->d_grav; a.hist = b->d_hist; a.head = b->head;
-        a.grav_sub = b->grav_sub; a.grav_int = b->grav_int ? 1u : 0u; a.gl_storage = tp.in16 ? 1u : 0u;
-        glv::TrackGeometry g;
-        g.n = n; g.steps = steps; g.hops_per_pitch = steps; g.log_q = 0; g.residue_rows = 0; g.out_texels = tp.out16 ? 1u : 0u;
-        const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
-        if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
-        b->kernel_name = "glv_track_scan_kernel";
-        // the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
-        if (ops & GLV_OP_AVERAGE) b->head = (uint32_t) (((uint64_t) b->head + steps) % b->p.avg_frames);
-        if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
-    }
+    pl.rows = reinterpret_cast<float*>(work + (tp.scan ? tp.rows_bytes : 0u));       // what the bars read: the scan's results, or a stateless transform's rows
+    if (tp.scan) if (int rc = track_scan(b, tp, a, steps, work, (ops & GLV_OP_BARS) ? pl.rows : out, ops, st)) return rc;
     // (3) the bars of every step's rows
-    if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) steps * units, (ops & GLV_OP_R16) != 0, st)) return rc;
+    if (int rc = launch_bars_pass(b, pl, out, (size_t) steps * b->streams * 2u, (ops & GLV_OP_R16) != 0, st)) return rc;
     return timed_launch_end(b, st);
 }
 
@@ -1491,11 +1462,10 @@ int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uin
         return fail(GLV_ERR_INVALID, "a wave track call takes GLV_OP_WAVE with GLV_OP_BARS / GLV_OP_R16 only (ops 0x%x)", ops);
     if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
     if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
-    if ((uint64_t) pitch_frames < (uint64_t) n + (uint64_t) (steps - 1) * hop)
-        return fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%u frames every hop=%u", pitch_frames, steps, n, hop);
+    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
     if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
     tp.rows = (uint64_t) steps * b->streams * 2u;
-    if (tp.rows > 0x100000000ull)
+    if (tp.rows > 0x100000000ull)                 // (a COUNT of rows, steps * units, which the launchers take as a size_t: exactly 2^32 rows pass)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams);
     if (int rc = check_ops(b, ops, &some_output)) return rc;
     // The sizing query does not see d_pcm, so with bars the workspace is always what the two launches need: plan_wave is asked twice, for windows that
@@ -1505,14 +1475,13 @@ int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uin
         ChainPlan grouped;
         if (int rc = plan_wave(b, glv::IN_S16_STEREO, ops, 0, nullptr, grouped, hop % 8u == 0u && pitch_frames % 8u == 0u)) return rc;
         tp.one_launch = grouped.wave_fused;
-        tp.work_bytes = (tp.rows * n * (tp.pl.wave_r16 ? 2u : 4u) + 255u) & ~(uint64_t) 255u;
+        tp.work_bytes = up256(tp.rows * n * (tp.pl.wave_r16 ? 2u : 4u));
     }
     return GLV_OK;
 }
 
 int track_wave(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
-    if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
-    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
+    if (int rc = refuse_track_pointers(d_pcm, d_out, d_work)) return rc;
     TrackWavePlan tp;
     if (int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) return rc;
     ChainPlan& pl = tp.pl;
@@ -1540,6 +1509,19 @@ int track_wave(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     if (!fused) if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) tp.rows, r16, st)) return rc;
     return timed_launch_end(b, st);
+}
+
+// The sizing query of a track entry: its plan's workspace, or 0 where the plan refuses (no return code to carry it: the message names the code).
+template <class Plan>
+uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, uint32_t, uint32_t, uint32_t, unsigned, Plan&), uint32_t pitch_frames, uint32_t hop, uint32_t steps,
+                            unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    Plan tp;
+    if (const int rc = plan(b, pitch_frames, hop, steps, ops, tp)) {
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return tp.work_bytes;
 }
 
 int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, int device, bool single_row, glv_batch** out) {
@@ -1744,45 +1726,31 @@ int glv_batch_process_f32_stereo(glv_batch* b, const float* d_pcm, float* d_out,
 }
 
 uint64_t glv_batch_track_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
-    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
-    TrackPlan tp;
-    if (const int rc = plan_track(b, pitch_frames, hop, steps, ops, tp)) {     // no return code to carry it: the message names the code
-        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
-        return 0;
-    }
-    return tp.work_bytes;
+    return planned_work_bytes(b, plan_track, pitch_frames, hop, steps, ops);
 }
 
 int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                         unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    return track(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+    TrackPlan tp;
+    if (int rc = plan_track(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 uint64_t glv_batch_track_windows_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
-    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
-    TrackPlan tp;
-    if (const int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) {     // no return code to carry it: the message names the code
-        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
-        return 0;
-    }
-    return tp.work_bytes;
+    return planned_work_bytes(b, plan_track_windows, pitch_frames, hop, steps, ops);
 }
 
 int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                                 unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    return track_windows(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+    TrackPlan tp;
+    if (int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
-    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
-    TrackWavePlan tp;
-    if (const int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) {     // no return code to carry it: the message names the code
-        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
-        return 0;
-    }
-    return tp.work_bytes;
+    return planned_work_bytes(b, plan_track_wave, pitch_frames, hop, steps, ops);
 }
 
 int glv_batch_track_wave_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,

@@ -101,18 +101,8 @@ def lib() -> C.CDLL:
             L.glv_batch_set_bar_texels.argtypes = [vp, vp, C.c_uint32]
         if hasattr(L, "glv_batch_set_column_texels"):   # (likewise)
             L.glv_batch_set_column_texels.argtypes = [vp, vp, C.c_uint32]
-        if hasattr(L, "glv_batch_track_s16"):           # (likewise)
-            L.glv_batch_track_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
-            L.glv_batch_track_work_bytes.restype = C.c_uint64
-            L.glv_batch_track_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
-        if hasattr(L, "glv_batch_track_windows_s16"):   # (likewise)
-            L.glv_batch_track_windows_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
-            L.glv_batch_track_windows_work_bytes.restype = C.c_uint64
-            L.glv_batch_track_windows_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
-        if hasattr(L, "glv_batch_track_wave_s16"):      # (likewise)
-            L.glv_batch_track_wave_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint]
-            L.glv_batch_track_wave_work_bytes.restype = C.c_uint64
-            L.glv_batch_track_wave_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
+        for form in ("track", "track_windows", "track_wave"):   # (likewise, each pair by its call's symbol)
+            _bind_track_pair(L, form)
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -147,6 +137,17 @@ def lib() -> C.CDLL:
         L.glv_multi_run_s16.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_uint, C.c_int, C.c_int, C.POINTER(MultiStats), C.POINTER(C.c_double)]
         _lib = L
     return _lib
+
+
+def _bind_track_pair(L, form: str) -> None:
+    """prototypes of a track entry and its sizing query (glv_batch_<form>_s16, glv_batch_<form>_work_bytes), where the library has them"""
+    if not hasattr(L, f"glv_batch_{form}_s16"):
+        return
+    vp, u32 = C.c_void_p, C.c_uint32
+    query = getattr(L, f"glv_batch_{form}_work_bytes")
+    query.argtypes = [vp, u32, u32, u32, C.c_uint]
+    query.restype = C.c_uint64
+    getattr(L, f"glv_batch_{form}_s16").argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint, vp]
 
 
 def _check(rc: int) -> None:
@@ -227,50 +228,50 @@ class Batch:
     def process_f32_stereo(self, d_in, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         _check(lib().glv_batch_process_f32_stereo(self._h, _ptr(d_in), _ptr(d_out), ops, _ptr(stream)))
 
-    def track_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
-        """bytes of device workspace track_s16 needs for these arguments (glv_batch_track_work_bytes); raises on arguments the call refuses"""
-        nbytes = int(lib().glv_batch_track_work_bytes(self._h, pitch_frames, hop, steps, ops))
+    def _track_work_bytes(self, form: str, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
+        """glv_batch_<form>_work_bytes; 0 is a refusal, whose message names its code"""
+        nbytes = int(getattr(lib(), f"glv_batch_{form}_work_bytes")(self._h, pitch_frames, hop, steps, ops))
         if nbytes == 0:
             msg = lib().glv_last_error().decode()
-            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)      # (the message names the code)
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)
         return nbytes
+
+    def _track_call(self, form: str, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None) -> None:
+        """glv_batch_<form>_s16"""
+        _check(getattr(lib(), f"glv_batch_{form}_s16")(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
+        """bytes of device workspace track_s16 needs for these arguments (glv_batch_track_work_bytes); raises on arguments the call refuses"""
+        return self._track_work_bytes("track", pitch_frames, hop, steps, ops)
 
     def track_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
         """`steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16): d_pcm int16 [streams][pitch_frames][2], window t of
         stream s = its frames [t * hop, t * hop + n); d_out step-major, step t exactly what process_s16 call t would have written; d_work at least
         track_work_bytes(...) bytes, 256-byte aligned.  Output and state bit for bit those of the sequential calls; stream-ordered, kernels only."""
-        _check(lib().glv_batch_track_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+        self._track_call("track", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream)
 
     def track_windows_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_windows_s16 needs for these arguments (glv_batch_track_windows_work_bytes; 256 where the call needs none); raises
         on arguments the call refuses"""
-        nbytes = int(lib().glv_batch_track_windows_work_bytes(self._h, pitch_frames, hop, steps, ops))
-        if nbytes == 0:
-            msg = lib().glv_last_error().decode()
-            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)      # (the message names the code)
-        return nbytes
+        return self._track_work_bytes("track_windows", pitch_frames, hop, steps, ops)
 
     def track_windows_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
         """track_s16 at ANY hop >= 1 and any pitch_frames >= n + (steps - 1) * hop (glv_batch_track_windows_s16): one transform launch reads each window
         where it lies; d_pcm 4-byte aligned; d_work at least track_windows_work_bytes(...) bytes, 256-byte aligned.  Output and state bit for bit those of
         the sequential calls; stream-ordered, kernels only."""
-        _check(lib().glv_batch_track_windows_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+        self._track_call("track_windows", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on
         arguments the call refuses"""
-        nbytes = int(lib().glv_batch_track_wave_work_bytes(self._h, pitch_frames, hop, steps, ops))
-        if nbytes == 0:
-            msg = lib().glv_last_error().decode()
-            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)      # (the message names the code)
-        return nbytes
+        return self._track_work_bytes("track_wave", pitch_frames, hop, steps, ops)
 
     def track_wave_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
         """the wave module's texture of `steps` consecutive updates of every stream from one long buffer (glv_batch_track_wave_s16): d_pcm int16
         [streams][pitch_frames][2], window t of stream s = its frames [t * hop, t * hop + n), any hop >= 1; ops OP_WAVE [| OP_BARS] [| OP_R16]; d_out
         step-major, step t bit for bit what process_s16 on window t would have written; d_work at least track_wave_work_bytes(...) bytes, 256-byte
         aligned.  Stateless; stream-ordered, kernels only."""
-        _check(lib().glv_batch_track_wave_s16(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+        self._track_call("track_wave", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream)
 
     def ring_update_s16(self, d_new, new_frames: int, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         _check(lib().glv_batch_ring_update_s16(self._h, _ptr(d_new), new_frames, _ptr(d_out), ops, _ptr(stream)))

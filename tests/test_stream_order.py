@@ -10,56 +10,22 @@ kernels and asynchronous device-to-device copies, nothing else:
         for BASELINE configs[1] (stateless pass), the F = 5 chain, fused bars, the GL_R16 chain and a ring update.
 """
 import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
 from oracle_lib import lcg_pcm_fast
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FORBIDDEN = ["hipMalloc", "hipFree", "hipMemcpy(", "hipMemset(", "hipMemcpyAsync(", "hipStreamSynchronize", "hipDeviceSynchronize",
-             "hipHostMalloc", "hipEventSynchronize", "hipMemcpyToSymbol", "hipMemcpyFromSymbol",
-             # glv_api.cpp's DeviceArray hides hipMalloc / hipMemcpy / hipMemset / hipFree behind these methods
-             "upload(", "alloc(", "renew(", "reset("]
-
-
-def _function_body(src, signature_re):
-    m = re.search(signature_re, src)
-    assert m, signature_re
-    i = src.index("{", m.end() - 1)
-    depth, j = 0, i
-    while True:
-        if src[j] == "{": depth += 1
-        elif src[j] == "}":
-            depth -= 1
-            if depth == 0: break
-        j += 1
-    return src[i:j + 1]
-
-
-def _strip_comments(s):
-    s = re.sub(r"//[^\n]*", "", s)
-    return re.sub(r"/\*.*?\*/", "", s, flags=re.S)
+from src_scan import STATE_CHECKS, assert_launch_only, read_csrc
 
 
 def test_process_path_has_no_allocating_or_synchronising_call():
-    src = open(os.path.join(ROOT, "glava_amd", "csrc", "glv_api.cpp")).read()
     path = [r"\nint process\(glv_batch\* b, const void\* d_in,", r"\nint check_ops\(", r"\nvoid launch_plan\(", r"\nstatic int ring_append\(",
             r"\nstatic int ring_push\(", r"\nint glv_batch_process_s16\(", r"\nint glv_batch_process_f32\(", r"\nint glv_batch_process_f32_stereo\(",
             r"\nint glv_batch_ring_update_s16\(", r"\nint glv_batch_ring_update_f32\(", r"\nint glv_batch_ring_append_s16\(",
-            r"\nint glv_batch_ring_append_f32\(", r"\nint glv_batch_ring_planar\(", r"\nint glv_batch_bars\(", r"\nint timed_launch_end\("]
-    for sig in path:
-        body = _strip_comments(_function_body(src, sig))
-        # the one copy the path may issue: the asynchronous device-to-device row copy of operator-only chains
-        body = body.replace("hipMemcpyAsync(d_out, d_in, sizeof(float) * (size_t) units * b->p.n, hipMemcpyDeviceToDevice, st)", "")
-        for f in FORBIDDEN:
-            assert f not in body, (sig, f)
-    # and the helpers that DO allocate are reachable from creation / set_params only
-    for helper in ("ensure_bar_tables", "ensure_smooth_tables", "batch_prepare", "set_tilt", "batch_alloc", "ensure_scratch", "build_snap_tables"):
-        for sig in path:
-            assert helper + "(" not in _strip_comments(_function_body(src, sig)), (sig, helper)
+            r"\nint glv_batch_ring_append_f32\(", r"\nint glv_batch_ring_planar\(", r"\nint glv_batch_bars\(", r"\nint timed_launch_end\("] + STATE_CHECKS
+    # the one copy the path may issue: the asynchronous device-to-device row copy of operator-only chains; and the helpers that DO allocate are
+    # reachable from creation / set_params only
+    assert_launch_only(read_csrc("glv_api.cpp"), path,
+                       allowed=["hipMemcpyAsync(d_out, d_in, sizeof(float) * (size_t) units * b->p.n, hipMemcpyDeviceToDevice, st)"])
 
 
 class _Hip:

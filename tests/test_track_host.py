@@ -6,30 +6,7 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# what tests/test_stream_order.py forbids on the process path
-FORBIDDEN = ["hipMalloc", "hipFree", "hipMemcpy(", "hipMemset(", "hipMemcpyAsync(", "hipStreamSynchronize", "hipDeviceSynchronize",
-             "hipHostMalloc", "hipEventSynchronize", "hipMemcpyToSymbol", "hipMemcpyFromSymbol",
-             "upload(", "alloc(", "renew(", "reset("]
-
-
-def _function_body(src, signature_re):
-    m = re.search(signature_re, src)
-    assert m, signature_re
-    i = src.index("{", m.end() - 1)
-    depth, j = 0, i
-    while True:
-        if src[j] == "{": depth += 1
-        elif src[j] == "}":
-            depth -= 1
-            if depth == 0: break
-        j += 1
-    return src[i:j + 1]
-
-
-def _strip_comments(s):
-    s = re.sub(r"//[^\n]*", "", s)
-    return re.sub(r"/\*.*?\*/", "", s, flags=re.S)
+from src_scan import ROOT, TRACK_EXECUTOR, assert_launch_only, function_body, read_csrc, strip_comments
 
 
 def test_track_symbols_are_exported_and_bound(glvlib):
@@ -72,18 +49,15 @@ def test_every_window_is_one_row_of_one_launch(glvlib, n):
 
 
 def test_track_path_has_no_allocating_or_synchronising_call():
-    src = open(os.path.join(ROOT, "glava_amd", "csrc", "glv_api.cpp")).read()
-    path = [r"\nint plan_track\(", r"\nint track\(glv_batch\* b,", r"\nint launch_bars_pass\(", r"\nint glv_batch_track_s16\(", r"\nuint64_t glv_batch_track_work_bytes\(",
-            r"\nint check_ops\(", r"\nvoid launch_plan\(", r"\nint timed_launch_end\("]
-    for sig in path:
-        body = _strip_comments(_function_body(src, sig))
-        for f in FORBIDDEN:
-            assert f not in body, (sig, f)
-        for helper in ("ensure_bar_tables", "ensure_smooth_tables", "batch_prepare", "set_tilt", "batch_alloc", "ensure_scratch", "build_snap_tables"):
-            assert helper + "(" not in body, (sig, helper)
+    src = read_csrc("glv_api.cpp")
+    assert_launch_only(src, [r"\nint plan_track\(", r"\nint glv_batch_track_s16\(", r"\nuint64_t glv_batch_track_work_bytes\("] + TRACK_EXECUTOR)
+    # the residue stage holds the only loop of launches on the path: the executor and the other stages have none
+    assert "for (" in strip_comments(function_body(src, r"\nint track_residues\("))
+    for sig in (r"\nint track\(glv_batch\* b,", r"\nint track_windows\(", r"\nint track_scan\(", r"\nint glv_batch_track_s16\("):
+        body = strip_comments(function_body(src, sig))
+        assert "for (" not in body and "while (" not in body, sig
     # the launchers the path calls launch and nothing else
-    misc = open(os.path.join(ROOT, "glava_amd", "csrc", "glv_misc.hip")).read()
-    body = _strip_comments(_function_body(misc, r"\nhipError_t launch_track_scan\("))
-    for f in FORBIDDEN:
-        assert f not in body, f
+    misc = read_csrc("glv_misc.hip")
+    assert_launch_only(misc, [r"\nhipError_t launch_track_scan\("])
+    body = strip_comments(function_body(misc, r"\nhipError_t launch_track_scan\("))
     assert re.search(r"glv_track_scan_kernel<true>", body) and re.search(r"glv_track_scan_kernel<false>", body)

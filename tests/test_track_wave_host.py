@@ -6,9 +6,7 @@ import re
 
 import pytest
 
-from test_track_host import FORBIDDEN, _function_body, _strip_comments
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from src_scan import ROOT, TRACK_COMMON, assert_launch_only, function_body, read_csrc, strip_comments
 
 
 def test_track_wave_symbols_are_exported_and_bound(glvlib):
@@ -53,24 +51,17 @@ def test_every_output_row_starts_where_its_window_does(glvlib, n):
 
 
 def test_track_wave_path_has_no_allocating_or_synchronising_call():
-    src = open(os.path.join(ROOT, "glava_amd", "csrc", "glv_api.cpp")).read()
-    path = [r"\nint plan_track_wave\(", r"\nint track_wave\(glv_batch\* b,", r"\nint plan_wave\(", r"\nint launch_bars_pass\(", r"\nint glv_batch_track_wave_s16\(",
-            r"\nuint64_t glv_batch_track_wave_work_bytes\(", r"\nint check_ops\(", r"\nint timed_launch_end\("]
-    for sig in path:
-        body = _strip_comments(_function_body(src, sig))
-        for f in FORBIDDEN:
-            assert f not in body, (sig, f)
-        for helper in ("ensure_bar_tables", "ensure_smooth_tables", "batch_prepare", "set_tilt", "batch_alloc", "ensure_scratch", "build_snap_tables"):
-            assert helper + "(" not in body, (sig, helper)
+    src = read_csrc("glv_api.cpp")
+    assert_launch_only(src, [r"\nint plan_track_wave\(", r"\nbool pitch_too_short\(", r"\nint track_wave\(glv_batch\* b,", r"\nint plan_wave\(", r"\nint glv_batch_track_wave_s16\(",
+                             r"\nuint64_t glv_batch_track_wave_work_bytes\("] + TRACK_COMMON)
     # the rows between the two launches live in the caller's workspace, not in the scratch rows of one update
-    body = _strip_comments(_function_body(src, r"\nint track_wave\(glv_batch\* b,"))
+    body = strip_comments(function_body(src, r"\nint track_wave\(glv_batch\* b,"))
     assert "d_scratch" not in body and "d_work" in body
     # the launchers the path calls launch and nothing else
-    misc = open(os.path.join(ROOT, "glava_amd", "csrc", "glv_misc.hip")).read()
+    misc = read_csrc("glv_misc.hip")
     for sig, kernels in ((r"\nhipError_t launch_wave_track\(", (r"glv_wave_kernel<3, true>", r"glv_wave_kernel<3, false>")),
                          (r"\nhipError_t launch_bars_i8_pcm_track\(", (r"launch_bars_i8_in<I8_PCM_TRACK, true>", r"launch_bars_i8_in<I8_PCM_TRACK, false>"))):
-        body = _strip_comments(_function_body(misc, sig))
-        for f in FORBIDDEN:
-            assert f not in body, (sig, f)
+        assert_launch_only(misc, [sig])
+        body = strip_comments(function_body(misc, sig))
         for k in kernels:
             assert re.search(k, body), (sig, k)

@@ -3,32 +3,8 @@ window (stream, step) to where it starts and to the row the transform launch wri
 HIP calls (the method of tests/test_track_host.py)."""
 import ctypes as C
 import os
-import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# what tests/test_stream_order.py forbids on the process path
-FORBIDDEN = ["hipMalloc", "hipFree", "hipMemcpy(", "hipMemset(", "hipMemcpyAsync(", "hipStreamSynchronize", "hipDeviceSynchronize",
-             "hipHostMalloc", "hipEventSynchronize", "hipMemcpyToSymbol", "hipMemcpyFromSymbol",
-             "upload(", "alloc(", "renew(", "reset("]
-
-
-def _function_body(src, signature_re):
-    m = re.search(signature_re, src)
-    assert m, signature_re
-    i = src.index("{", m.end() - 1)
-    depth, j = 0, i
-    while True:
-        if src[j] == "{": depth += 1
-        elif src[j] == "}":
-            depth -= 1
-            if depth == 0: break
-        j += 1
-    return src[i:j + 1]
-
-
-def _strip_comments(s):
-    s = re.sub(r"//[^\n]*", "", s)
-    return re.sub(r"/\*.*?\*/", "", s, flags=re.S)
+from src_scan import ROOT, TRACK_EXECUTOR, assert_launch_only, function_body, read_csrc, strip_comments
 
 
 def test_track_windows_symbols_are_exported_and_bound(glvlib):
@@ -73,33 +49,28 @@ def test_every_window_is_one_row_in_both_orders(glvlib):
 
 
 def test_track_windows_path_has_no_allocating_or_synchronising_call():
-    src = open(os.path.join(ROOT, "glava_amd", "csrc", "glv_api.cpp")).read()
-    path = [r"\nint track_args\(", r"\nint track_chain\(", r"\nbool pitch_too_short\(", r"\nint plan_track_windows\(", r"\nint track_windows\(glv_batch\* b,",
-            r"\nint launch_bars_pass\(", r"\nint glv_batch_track_windows_s16\(", r"\nuint64_t glv_batch_track_windows_work_bytes\(",
-            r"\nint check_ops\(", r"\nvoid launch_plan\(", r"\nint timed_launch_begin\(", r"\nint timed_launch_end\("]
-    for sig in path:
-        body = _strip_comments(_function_body(src, sig))
-        for f in FORBIDDEN:
-            assert f not in body, (sig, f)
-        for helper in ("ensure_bar_tables", "ensure_smooth_tables", "batch_prepare", "set_tilt", "batch_alloc", "ensure_scratch", "build_snap_tables"):
-            assert helper + "(" not in body, (sig, helper)
-    body = _strip_comments(_function_body(src, r"\nint track_windows\(glv_batch\* b,"))
+    src = read_csrc("glv_api.cpp")
+    assert_launch_only(src, [r"\nint plan_track_windows\(", r"\nint glv_batch_track_windows_s16\(", r"\nuint64_t glv_batch_track_windows_work_bytes\("] + TRACK_EXECUTOR)
+    body = strip_comments(function_body(src, r"\nint track_windows\("))
     assert body.count("glv::launch_frame(") == 1 and "IN_S16_TRACK" in body                       # ONE transform launch, in the track input mode
     assert "for (" not in body and "while (" not in body                                          # ... and no loop of launches
+    for sig in (r"\nint track\(glv_batch\* b,", r"\nint track_scan\(", r"\nint glv_batch_track_windows_s16\("):   # ... nor around it, nor after it
+        body = strip_comments(function_body(src, sig))
+        assert "for (" not in body and "while (" not in body and "glv::launch_frame(" not in body, sig
     # the launchers the path calls launch and nothing else
-    misc = open(os.path.join(ROOT, "glava_amd", "csrc", "glv_misc.hip")).read()
-    for sig in (r"\nhipError_t launch_track_scan\(", r"\nhipError_t launch_frame\("):
-        body = _strip_comments(_function_body(misc, sig))
-        for f in FORBIDDEN:
-            assert f not in body, (sig, f)
+    assert_launch_only(read_csrc("glv_misc.hip"), [r"\nhipError_t launch_track_scan\(", r"\nhipError_t launch_frame\("])
 
 
 def test_the_two_track_entries_share_their_decisions():
-    """state / in16 / out16 / bars and every refusal that is not about hop or pitch are written once (track_chain, track_args) and both plans call them"""
-    src = _strip_comments(open(os.path.join(ROOT, "glava_amd", "csrc", "glv_api.cpp")).read())
+    """state / in16 / out16 / bars and every refusal that is not about hop or pitch are written once (track_chain, track_args) and both plans call them;
+    what a call asks of the batch's earlier calls, and the scan, are written once for every entry"""
+    src = strip_comments(read_csrc("glv_api.cpp"))
     for sig in (r"\nint plan_track\(", r"\nint plan_track_windows\("):
-        body = _function_body(src, sig)
+        body = function_body(src, sig)
         assert "track_args(" in body and "track_chain(" in body, sig
         for decided_once in ("tp.state =", "tp.in16 =", "tp.out16 =", "tp.bars =", "check_ops(", "gl_storage == 2", "GLV_OP_BARS_ONLY", "single_row"):
             assert decided_once not in body, (sig, decided_once)
-    assert "log2_exact(hop)" not in _function_body(src, r"\nint plan_track_windows\(")             # any hop
+    assert "log2_exact(hop)" not in function_body(src, r"\nint plan_track_windows\(")             # any hop
+    # (check_ops has "... changed without glv_batch_set_params" messages of its own, about bars and smoothing: the tilt's is the one that ends in log_mode)
+    for once in ('"gravity was last applied', 'log_mode changed without glv_batch_set_params")', "launch_track_scan("):
+        assert src.count(once) == 1, once
