@@ -349,6 +349,7 @@ class Batch:
         return lib().glv_batch_kernel_name(self._h).decode()
 
     def set_grid(self, grid: int) -> None:
+        """workgroups of every frame-kernel launch of this batch (glv_batch_set_grid); grid <= 0: automatic.  The result does not depend on it."""
         _check(lib().glv_batch_set_grid(self._h, grid))
 
     def last_grid(self) -> int:

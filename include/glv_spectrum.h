@@ -564,7 +564,11 @@ uint64_t glv_batch_algorithmic_bytes(const glv_batch* b, unsigned ops, int input
  * instructions); 0 for every other batch (all n bins live).  The kernels round it up to their last pass's block. */
 uint32_t glv_batch_live_bins(const glv_batch* b);
 
-/* Launch-geometry override for tuning (workgroups of the persistent frame kernel; 0 = automatic). */
+/* Launch-geometry override for tuning: the workgroups of every persistent frame-kernel launch of this batch (process, ring-update and track
+ * calls alike).  grid <= 0: automatic (the wisdom's grid, else one workgroup per group of rows until the chip is full).  Any positive grid is
+ * valid: fewer workgroups make more trips each, a grid larger than the work leaves the surplus workgroups idle (they retire at their first
+ * check).  The result does not depend on the grid, bit for bit -- output and state, every input kind, kernel class and configuration
+ * (tests/test_forced_grid.py runs 1, 2 and 3 workgroups, and more than there is work, against the automatic grid and the oracle). */
 int glv_batch_set_grid(glv_batch* b, int grid);
 int glv_batch_last_grid(const glv_batch* b);      /* workgroups the last frame-kernel launch of this batch used */
 int glv_batch_last_launches(const glv_batch* b);  /* kernels the last process / ring-update call of this batch launched (1 for every

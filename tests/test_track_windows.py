@@ -125,8 +125,14 @@ def _chains(G):
 
 CHAIN_NAMES = ["fft", "fft_r16", "gravity", "chain", "chain_plain_sum", "chain_r16", "chain_mono", "average", "gl_gravity", "gl_chain", "gl_chain_r16",
                "gl_chain_F1", "gl_chain_mono", "gl_fft"]
-# (n, kernel configuration): at 256 several slots share a wave (the load form's branch may diverge), 1024 is the smallest size where none does
-SIZES = [(256, 0), (1024, 0), (1024, 1)]
+# (n, kernel configuration): every size and every configuration IN_S16_TRACK is built for.  At 256 / 512 several slots share a wave (the load form's
+# branch may diverge; 512 configuration 1 puts four windows in one wave), 1024 is the smallest size where none does.  The three entries that carry the
+# full chain list came first; the others run the chains that differ in the transform launch: step-major rows straight into d_out (fft, fft_r16),
+# stream-major rows for the scan (chain, gl_chain_r16) and the mono mix
+FULL_SIZES = [(256, 0), (1024, 0), (1024, 1)]
+SIZES = [(256, 0)] + [(n, v) for n in (512, 1024, 2048, 4096, 8192, 16384, 32768) for v in (0, 1)]
+REDUCED_CHAINS = ["fft", "fft_r16", "chain", "gl_chain_r16", "chain_mono"]
+CHAIN_SIZES = [(c, n, v) for c in CHAIN_NAMES for n, v in SIZES if (n, v) in FULL_SIZES or c in REDUCED_CHAINS]
 
 
 def _hops(n):
@@ -136,8 +142,7 @@ def _hops(n):
 # ---- 1. the contract against sequential calls, recording aligned and one frame off ------------------------------------------------------
 @pytest.mark.parametrize("odd", [False, True])
 @pytest.mark.parametrize("log_mode", [0, 1])
-@pytest.mark.parametrize("n,variant", SIZES)
-@pytest.mark.parametrize("chain", CHAIN_NAMES)
+@pytest.mark.parametrize("chain,n,variant", CHAIN_SIZES)
 def test_track_windows_equals_sequential_calls(glvlib, chain, n, variant, log_mode, odd):
     G = glvlib
     kw, mask, ops = _chains(G)[chain]
