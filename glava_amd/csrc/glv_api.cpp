@@ -228,7 +228,7 @@ struct Tables {
         glv::make_window(win.data(), n);
         HIP_TRY(t->d_tw.upload(tw));
         HIP_TRY(t->d_win.upload(win));
-        {   // the split window: searched and proven on the device for every s16 sample value (glv_misc.hip)
+        {   // the split window: searched and proven on the device for every s16 sample value (glv_misc.hip launch_window_split)
             int* d_fs = nullptr;
             HIP_TRY(t->d_win_split.alloc(2 * (size_t) n, false));
             HIP_TRY(hipMalloc(&d_fs, 2 * sizeof(int)));
@@ -657,16 +657,34 @@ int ensure_smooth_tables(glv_batch* b) {
     return GLV_OK;
 }
 
-// the integer tables of a pass over texel rows for the smallest LDS ring that takes them (glv_misc.hip launch_bars_i8: the rings the kernel is
+// the integer tables of a pass over texel rows for the smallest LDS ring that takes them (glv_launch.h kRowsI8Rings: the rings the kernel is
 // built for); returns that ring, 0 (irounds empty) when none does
 uint32_t make_itiles_any_ring(std::vector<glv::BarMTile>& itiles, std::vector<int8_t>& wq, std::vector<glv::BarIFin>& fin, std::vector<glv::BarTile>& irounds,
                               const std::vector<glv::BarDesc>& desc, const std::vector<float>& w, uint32_t n) {
-    for (uint32_t bins : {160u, 288u, 448u, 832u, 1600u}) {
-        if (!glv::make_bar_itiles(itiles, wq, fin, irounds, desc, w, n, bins, 4u)) { irounds.clear(); break; }
+    for (uint32_t bins : glv::kRowsI8Rings) {
+        if (!glv::make_bar_itiles(itiles, wq, fin, irounds, desc, w, n, bins, (uint32_t) glv::kRowsWaves)) { irounds.clear(); break; }
         if (!irounds.empty()) return bins;
     }
     irounds.clear();
     return 0;
+}
+
+// For each kernel configuration of the size: may it compute the results of `desc` inside the frame kernel, behind the finished row in LDS -- whole
+// waves per row, one exchange region, and room(lanes): the results and the dump slot fit the slack behind the row -- and if so its work list (the
+// configurations' lanes per row differ), made and uploaded.  zero_off: the chunk of zero weights the padding items point at.
+template <class Room>
+int upload_fused_items(const glv_batch* b, BarTableSet& s, const std::vector<glv::BarDesc>& desc, uint32_t zero_off, Room room) {
+    const uint32_t chunk = glv::bar_chunk_of(b->p.n), gl = (uint32_t) glv::bar_lanes_of(b->p.n);
+    const int nv = glv::frame_variants(b->log_nn);
+    for (int v = 0; v < nv && v < kMaxVariants; ++v) {
+        const glv::FrameGeometry geo = glv::frame_geometry(b->log_nn, v);
+        s.fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && room((uint32_t) geo.lanes);
+        if (!s.fusable[v]) continue;
+        std::vector<glv::BarItem> fitems;
+        s.fnsteps[v] = glv::make_bar_items(fitems, desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
+        HIP_TRY(s.fitems[v].upload(fitems));
+    }
+    return GLV_OK;
 }
 
 // GLV_OP_BARS tables: taps, weights, the work lists of glv_bars_kernel and one fused work list per kernel configuration of the
@@ -702,17 +720,9 @@ int ensure_bar_tables(glv_batch* b) {
     std::vector<glv::BarItem> items;
     x.nsteps = glv::make_bar_items(items, desc, 256 / gl, zero_off, chunk);
     HIP_TRY(x.items.upload(items));
-    const int nv = glv::frame_variants(b->log_nn);
-    for (int v = 0; v < nv && v < kMaxVariants; ++v) {
-        const glv::FrameGeometry geo = glv::frame_geometry(b->log_nn, v);
-        // bar totals + the dump slot fit the 2 * lanes floats of slack behind the row in LDS
-        // (from 256 bars up a bar is one fma chain, glv_tables.h make_bar_mtiles: the chunked loop of the epilogue does not apply)
-        s.fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && b->p.bars + 1 <= 2 * (uint32_t) geo.lanes && b->p.bars < glv::kBarSeqMin && averaging;
-        if (!s.fusable[v]) continue;
-        std::vector<glv::BarItem> fitems;
-        s.fnsteps[v] = glv::make_bar_items(fitems, desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
-        HIP_TRY(s.fitems[v].upload(fitems));
-    }
+    // bar totals + the dump slot fit the 2 * lanes floats of slack behind the row in LDS
+    // (from 256 bars up a bar is one fma chain, glv_tables.h make_bar_mtiles: the chunked loop of the epilogue does not apply)
+    if (int rc = upload_fused_items(b, s, desc, zero_off, [&](uint32_t lanes) { return b->p.bars + 1 <= 2 * lanes && b->p.bars < glv::kBarSeqMin && averaging; })) return rc;
     HIP_TRY(s.desc.upload(desc));
     HIP_TRY(s.w.upload(w));
     x.count = b->p.bars; x.factor = b->p.smooth_factor; x.phase = b->p.bar_phase; x.shape_of = b->p;
@@ -732,8 +742,8 @@ int ensure_bar_tables(glv_batch* b) {
         std::vector<glv::BarMTile> mtiles;
         std::vector<glv::BarTile> rounds;
         std::vector<float> wt, wsum;
-        for (uint32_t bins : {160u, 288u, 448u, 832u}) {                          // glv_misc.hip launch_bars: the ring sizes the kernel is built for
-            if (!glv::make_bar_mtiles(mtiles, wt, wsum, rounds, desc, w, b->p.n, bins, 4u))       // 4 = glv_misc.hip kRowsWaves
+        for (uint32_t bins : glv::kRowsRings) {
+            if (!glv::make_bar_mtiles(mtiles, wt, wsum, rounds, desc, w, b->p.n, bins, (uint32_t) glv::kRowsWaves))
                 return fail(GLV_ERR_INVALID, "bars: no tile table (bars=%u)", b->p.bars);
             if (!rounds.empty()) { x.ring_bins = bins; break; }
         }
@@ -749,7 +759,7 @@ int ensure_bar_tables(glv_batch* b) {
             const glv::BarRowsTables rt = rows_tables(b->p, x, s);
             HIP_TRY(glv::prepare_bars_rows(b->p.n, &rt));
         }
-        // texel rows: the integer tables, for the smallest ring that takes them (glv_misc.hip launch_bars_i8: the rings the kernel is built for)
+        // texel rows: the integer tables, for the smallest ring that takes them
         if (want_i8) {
             std::vector<glv::BarMTile> itiles;
             std::vector<glv::BarTile> irounds;
@@ -780,6 +790,7 @@ int ensure_scratch(glv_batch* b) {
 }
 
 bool bars_fusable(const glv_batch* b, unsigned ops);
+bool bars_need_rows(const glv_batch* b, const BarTableSet& s);
 // glv_batch_set_column_texels: the most distinct texels the frame kernel's epilogue takes; more go to the second launch (glv_columns_kernel).
 // Measured at N = 4096, 64 K streams (profiles/r08/column_texels.txt): 321 texels fused 1.61 ms, the second launch 2.10 ms, the twin plus a gather 2.09 ms --
 // and the second launch loses to the twin from there up (801 texels 4.08 against 3.23 ms), so whatever fits behind the row is fused: the bound is the room
@@ -815,23 +826,15 @@ int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex, bool colum
     if (!glv::bar_chunks_in_row(desc, n)) return fail(GLV_ERR_INVALID, "bar texels: a tap chunk would leave the row (n=%u smooth_factor=%g)", n, (double) b->p.smooth_factor);
     s.bins = bins_reached(desc);
     if (s.bins == 0) s.bins = 64u;
-    const int nv = glv::frame_variants(b->log_nn);
     if (averaging) {
         std::vector<uint32_t> wi;
         if (!glv::make_bar_snap_weights(wi, desc, w)) return fail(GLV_ERR_INVALID, "bar texels: a bar's integer weights do not exist for these parameters");
         const uint32_t zero_off = (uint32_t) wi.size(), chunk = glv::bar_chunk_of(n), gl = (uint32_t) glv::bar_lanes_of(n);
         wi.resize(wi.size() + chunk, 0u);
         HIP_TRY(s.w.upload(reinterpret_cast<const float*>(wi.data()), wi.size()));      // (the uint32 weights W' travel as the bits of float weights)
-        for (int v = 0; v < nv && v < kMaxVariants; ++v) {
-            const glv::FrameGeometry geo = glv::frame_geometry(b->log_nn, v);
-            // every result is 4 bytes behind the row, as the unsnapped totals: bars + the dump slot in the 2 * lanes floats of slack
-            // (columns keep 16-bit texels there: twice as many.  kColumnsFuseMax: beyond it the second launch is the quicker route)
-            s.fusable[v] = geo.lanes % 64 == 0 && geo.nbuf == 1 && (columns ? bars + 1 <= 4 * (uint32_t) geo.lanes && bars <= kColumnsFuseMax : bars + 1 <= 2 * (uint32_t) geo.lanes);
-            if (!s.fusable[v]) continue;
-            std::vector<glv::BarItem> fitems;
-            s.fnsteps[v] = glv::make_bar_items(fitems, desc, (uint32_t) geo.lanes / gl, zero_off, chunk, (uint32_t) geo.bar_batch);
-            HIP_TRY(s.fitems[v].upload(fitems));
-        }
+        // every result is 4 bytes behind the row, as the unsnapped totals: bars + the dump slot in the 2 * lanes floats of slack
+        // (columns keep 16-bit texels there: twice as many.  kColumnsFuseMax: beyond it the second launch is the quicker route)
+        if (int rc = upload_fused_items(b, s, desc, zero_off, [&](uint32_t lanes) { return columns ? bars + 1 <= 4 * lanes && bars <= kColumnsFuseMax : bars + 1 <= 2 * lanes; })) return rc;
         if (columns) {
             std::vector<glv::BarItem> citems;
             x.col_nsteps = glv::make_bar_items(citems, desc, 256u / gl, zero_off, chunk, (uint32_t) glv::kBarBatch);
@@ -851,10 +854,8 @@ int build_snap_tables(glv_batch* b, const std::vector<uint32_t>& tex, bool colum
     }
     HIP_TRY(s.desc.upload(desc));
     x.tex = tex; x.of = b->p;
-    // a second launch needs the chain's rows: the internal rows, unless every chain the creation mask announces fuses in every configuration
-    bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
-    for (int v = 0; v < nv && v < kMaxVariants; ++v) all_fused = all_fused && s.fusable[v];
-    return all_fused ? GLV_OK : ensure_scratch(b);
+    // a second launch needs the chain's rows
+    return bars_need_rows(b, s) ? ensure_scratch(b) : GLV_OK;
 }
 void commit_snap_tables(glv_batch* b, BarTableSet& s, SnapExtras& x) {
     b->snap = std::move(s); b->snap_x = std::move(x);
@@ -901,6 +902,14 @@ bool bars_fusable(const glv_batch* b, unsigned ops) {
     return (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !(ops & GLV_OP_SMOOTH) && !b->unfused_bars
            && (b->p.gl_storage == 0 ? !(ops & GLV_OP_R16) : b->p.gl_storage == 1 && b->p.log_mode != 2);
 }
+// Do the bars of table set `s` need the internal rows -- true unless every chain the creation mask announces fuses them in every kernel
+// configuration.  One difference from process(): under the audit log (log_mode 2) a float chain fuses its bars and gets the rows all the
+// same -- which batches hold them is kept as it was.
+bool bars_need_rows(const glv_batch* b, const BarTableSet& s) {
+    bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
+    for (int v = 0; v < glv::frame_variants(b->log_nn) && v < kMaxVariants; ++v) all_fused = all_fused && s.fusable[v];
+    return !all_fused;
+}
 
 // Everything the process calls need besides the state arrays, made from b->p: tilt table, the gravity step on texels, and -- as
 // announced by the creation mask -- bar tables, smooth bounds, the internal spectra rows.  Called by creation and by
@@ -928,12 +937,9 @@ int batch_prepare(glv_batch* b) {
         // array holds the spectra -- unless every chain the creation mask announces fuses its bars in every kernel configuration
         // (bars_fusable: 16384 stereo streams of N = 4096 would hold 512 MiB nothing reads).  The mask's R16 bit is the hint that a float
         // chain's bars are wanted as GL_R16 texels (they leave through glv_bars_kernel, from the scratch rows); gravity-only chains read the
-        // state.  One difference from process(): under the audit log (log_mode 2) a float chain fuses its bars and gets the rows all the
-        // same -- which batches hold them is kept as it was.
-        bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
-        for (int v = 0; v < glv::frame_variants(b->log_nn) && v < kMaxVariants; ++v) all_fused = all_fused && b->bar.fusable[v];
+        // state.
         // GLV_OP_WAVE | GLV_OP_BARS in two launches: the waveform kernel's texels (or their floats) wait for the bars kernel in the same rows
-        if (!all_fused || (b->ops_mask & GLV_OP_WAVE)) if (int rc = ensure_scratch(b)) return rc;
+        if (bars_need_rows(b, b->bar) || (b->ops_mask & GLV_OP_WAVE)) if (int rc = ensure_scratch(b)) return rc;
         if (int rc = ensure_snap_tables(b)) return rc;
         b->update_live_bins();
     }

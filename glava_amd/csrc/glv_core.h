@@ -1,7 +1,7 @@
 // glv_core.h -- per-thread arithmetic and index maps of the spectrum kernels.
 //
 // Everything here is `GLV_HD` so the *same* code is compiled (a) by hipcc into the gfx950
-// kernels (glv_kernel_tmpl.h via glv_inst.hip, glv_misc.hip) and (b) by g++ into tests/emu (a host "kernel emulator" that
+// kernels (glv_kernel_tmpl.h via glv_inst.hip, glv_misc.hip, glv_bars.hip) and (b) by g++ into tests/emu (a host "kernel emulator" that
 // walks the phases thread by thread) -- index maps and butterflies get exercised against
 // the oracle on the CPU before a GPU is ever touched.
 //

@@ -1,7 +1,7 @@
 // glv_frame.h -- the phases one FFT "slot" (T = nn/E cooperating lanes, E = 8, 16 or 32 points per lane) runs
 // per channel row, and the arithmetic of the operators that follow the transform.
 //
-// Shared between the gfx950 kernels (glv_kernel_tmpl.h, glv_misc.hip) and the host emulator (tests/emu):
+// Shared between the gfx950 kernels (glv_kernel_tmpl.h, glv_misc.hip, glv_bars.hip) and the host emulator (tests/emu):
 // every function takes the lane id explicitly and touches memory only through the pointers it is given,
 // so the emulator can call the same phase for tid = 0..T-1 in turn where the kernel has T lanes and a
 // slot-scoped synchronisation.
@@ -179,7 +179,7 @@ struct FrameArgs {
 // boundary) is a tap of weight +0.
 // FROM 256 BARS UP (the pre-smoothing pass, bars == n) the contract is simpler: ONE fused-multiply-add chain over the bar's taps in
 // bin order from +0, acc = fma(w, x, acc), then / weight_sum -- what the matrix cores compute for 32 bars x 64 rows at a time
-// (glv_tables.h make_bar_mtiles, glv_misc.hip glv_bars_rows_kernel / glv_bars_seq_kernel; never fused into the frame kernel).
+// (glv_tables.h make_bar_mtiles, glv_bars.hip glv_bars_rows_kernel / glv_bars_seq_kernel; never fused into the frame kernel).
 // Why this shape: the loop is VALU-issue bound (the chip runs at its power limit, time follows the instruction count).
 // Round 2's version (16 lanes x 4 taps, mul + add, flags unpacked from a bit field) spent 41 instructions per 4 taps;
 // this one spends ~32 per 8: per-step bookkeeping is amortised over twice the taps, one DPP level is gone, multiplies
@@ -280,7 +280,7 @@ GLV_HD uint64_t bar_snap_lane_sum(const BarTaps& s) {
     }
     return acc;
 }
-// the results, as the twin's i8 pass gives them (glv_misc.hip glv_bars_rows_i8_kernel, oracle glvo_bars_int_at): floor(T / 2^31 + 1/2), and the float
+// the results, as the twin's i8 pass gives them (glv_bars.hip glv_bars_rows_i8_kernel, oracle glvo_bars_int_at): floor(T / 2^31 + 1/2), and the float
 // form ldexp((double) T, -31) / 65535 (which the caller divides by the bar's weight_sum, 1 -- or NaN for a bar whose weights sum to 0)
 GLV_HD uint32_t bar_snap_texel(uint64_t total) { return (uint32_t) ((total + (1ull << 30)) >> 31); }
 GLV_HD float bar_snap_float(uint64_t total) { return (float) (__builtin_ldexp((double) total, -31) / 65535.0); }

@@ -29,7 +29,7 @@ struct FrameGeometry {
 GLV_DECL_INST(7) GLV_DECL_INST(8) GLV_DECL_INST(9) GLV_DECL_INST(10) GLV_DECL_INST(11) GLV_DECL_INST(12) GLV_DECL_INST(13) GLV_DECL_INST(14)
 #undef GLV_DECL_INST
 
-// glv_misc.hip
+// glv_misc.hip (the bars launchers below: glv_bars.hip)
 hipError_t launch_frame(int log_nn, int in_mode, int log_mode, int variant, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 int frame_variants(int log_nn);                                        // kernel configurations built for this size (>= 1)
 bool frame_variant_ok(int log_nn, int in_mode, int log_mode, int variant);   // is `variant` built for this input / log mode
@@ -61,8 +61,14 @@ hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin,
 // the s16 window table as float pairs (glv_core.h WinSplit): split = float [n/2][4]; d_fail_shifted = int [2], zeroed by the caller
 hipError_t launch_window_split(const double* w_tab, float* split, uint32_t n, int* d_fail_shifted, hipStream_t st);
 hipError_t launch_window_split_check(const double* w_tab, const float* split, uint32_t n, unsigned long long* d_mismatches, hipStream_t st);
+// The matrix-core kernels of the many-bars pass (glv_bars.hip glv_bars_rows_kernel over float rows, glv_bars_rows_i8_kernel over texel rows): kRowsWaves
+// waves per workgroup, one tile of a round each, and the LDS rings (bins) each kernel is built for, smallest first -- the host cuts a table's rounds for the
+// first ring that takes them.  (The rows a workgroup takes with each ring: the kernels' dispatchers, which a static_assert holds to these lists.)
+constexpr int kRowsWaves = 4;
+constexpr uint32_t kRowsRings[] = {160, 288, 448, 832};
+constexpr uint32_t kRowsI8Rings[] = {160, 288, 448, 832, 1600};
 // rt: the tables of the many-bars kernels (>= 256 bars; glv_tables.h make_bar_mtiles): tiles of 32 bars with their weights, the bars'
-// weight sums, and -- when they could be cut -- the rounds of the matrix-core kernel for an LDS ring of ring_bins (160, 288, 448 or 832) bins
+// weight sums, and -- when they could be cut -- the rounds of the matrix-core kernel for an LDS ring of ring_bins bins (one of kRowsRings)
 // mode != 0 (glv_params.sample_mode maximum / hybrid): the block-transposed weights of glv_bars_mode_kernel (glv_tables.h make_bar_mode_blocks) and the
 // bins of a row its bars sample; the other tables are then unused
 struct BarRowsTables {
@@ -74,7 +80,7 @@ hipError_t launch_bars(const float* spec, float* bars_out, size_t nrows, uint32_
                        const BarItem* items, const BarDesc* desc, const float* tap_w, hipStream_t st, bool r16 = false, const BarRowsTables* rt = nullptr);
 hipError_t prepare_bars_rows(uint32_t n, const BarRowsTables* rt);      // function attributes of the kernel launch_bars would pick
 // the tables of the i8 matrix-core kernel for texel rows (glv_tables.h make_bar_itiles): tiles (origin a multiple of 16 bins, steps of 32),
-// the digit planes of the integer weights in operand layout, per bar the rounding constant and shift, the rounds for a ring of ring_bins bins
+// the digit planes of the integer weights in operand layout, per bar the rounding constant and shift, the rounds for a ring of ring_bins bins (one of kRowsI8Rings)
 struct BarIRowsTables {
     const BarMTile* tiles; uint32_t ntiles; const void* wq; const BarIFin* fin;
     const BarTile* rounds; uint32_t nrounds, ring_bins;

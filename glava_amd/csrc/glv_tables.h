@@ -157,7 +157,7 @@ inline void make_bar_taps(std::vector<BarDesc>& desc, std::vector<float>& tap_w,
     }
 }
 
-// SAMPLE_MODE maximum / hybrid (glv_misc.hip glv_bars_mode_kernel): blocks of 64 bars, lane l = bar 64 b + l; the block's weights as [tap j][lane], +0 behind a
+// SAMPLE_MODE maximum / hybrid (glv_bars.hip glv_bars_mode_kernel): blocks of 64 bars, lane l = bar 64 b + l; the block's weights as [tap j][lane], +0 behind a
 // bar's own taps up to the block's longest bar (and for bars past the last one)
 inline void make_bar_mode_blocks(std::vector<BarModeBlock>& blocks, std::vector<float>& mw, const std::vector<BarDesc>& desc, const std::vector<float>& tap_w) {
     blocks.clear(); mw.clear();
@@ -319,7 +319,7 @@ inline bool make_bar_mtiles(std::vector<BarMTile>& mtiles, std::vector<float>& w
 }
 
 // ---- many bars over TEXEL rows (the GL chains, gl_storage != 0: what the reference's pre-smoothing pass samples is a GL_R16 texture,
-// render.c:2277-2303) -- exact integer arithmetic on the i8 matrix cores (glv_misc.hip glv_bars_rows_i8_kernel) ----------------------
+// render.c:2277-2303) -- exact integer arithmetic on the i8 matrix cores (glv_bars.hip glv_bars_rows_i8_kernel) ----------------------
 // The texels c_j are 16-bit integers, so the weighted mean  sum w_j c_j / sum w_j  can be computed EXACTLY once the weights are integers:
 //     ws = sum_j (double) w_j (tap order);   P = max(17, 21 + ceil(log2 ws))   (so that every W_j <= 2^22)
 //     W_j = llrint(ldexp((double) w_j, P) / ws);   the first largest W_j takes the residue 2^P - sum W_j   =>  sum_j W_j == 2^P exactly
@@ -337,7 +337,7 @@ inline bool make_bar_mtiles(std::vector<BarMTile>& mtiles, std::vector<float>& w
 //   fin[k]:    {c, s}: texel = (uint32) (floor(T / 2^16) + c) >> s with s = P - 16 in [1, 15] and c = 32896 * 2^s + 2^(s-1); weights that sum to 0: {0, kBarIFinNone}, every digit 0
 //   rounds:    as make_bar_mtiles (tile ends rounded up to 8 bins: the ring is filled 8 texels = 16 bytes at a time)
 // bins per step; steps of zeros behind the last tile: the kernel requests a wave's weights PF = 3 steps ahead of the step it runs, so the
-// stream that lies last in memory is read up to three steps past its last tile (glv_misc.hip glv_bars_rows_i8_kernel)
+// stream that lies last in memory is read up to three steps past its last tile (glv_bars.hip glv_bars_rows_i8_kernel)
 constexpr uint32_t kBarIStepBins = 32;                    // (kBarILookAhead: glv_frame.h, shared with the kernel)
 // the integer weights of one bar (W: count values); returns P, or -1 when the float weights sum to 0 / NaN, or -2 when P would exceed 31
 inline int bar_int_weights(const float* w, uint32_t count, std::vector<int32_t>& W) {

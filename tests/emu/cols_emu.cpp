@@ -1,7 +1,7 @@
 // cols_emu.cpp -- host walk of the columns of glv_batch_set_column_texels (means of three texels of the pre-smoothing pass), built by
 // tests/test_column_texels_host.py with g++ -ffp-contract=off: the fused epilogue's step (glava_amd/csrc/glv_kernel_tmpl.h, kernel classes
 // FC_GL16_COLS*: the snapped loop over the distinct texels, kept as 16-bit values behind the row, then one column per lane) and the row loop of the
-// second launch (glv_misc.hip glv_columns_kernel, sample_mode average).  The tables are the library's own (glv_tables.h) and the arithmetic is the
+// second launch (glv_bars.hip glv_columns_kernel, sample_mode average).  The tables are the library's own (glv_tables.h) and the arithmetic is the
 // shared GLV_HD code of glv_frame.h (bar_item_load, bar_snap_lane_sum, bar_snap_texel, column_mean); only the lane loops, the order-free integer
 // group reduction and the de-duplication (glv_api.cpp set_snap_texels) are spelled out here.
 #include <stdint.h>

@@ -395,7 +395,7 @@ int glvemu_bars_rows(const float* tex, int n, int bars, float smooth_factor, flo
     return 0;
 }
 
-// The i8 matrix-core form of the many-bars pass over TEXEL rows (glv_tables.h make_bar_itiles, glv_misc.hip glv_bars_rows_i8_kernel) on the
+// The i8 matrix-core form of the many-bars pass over TEXEL rows (glv_tables.h make_bar_itiles, glv_bars.hip glv_bars_rows_i8_kernel) on the
 // host, off the same tables, the way the kernel consumes them: the ring of `bins` bins per row as two planes of signed bytes (c ^ 0x8080),
 // filled round by round (a slot is OVERWRITTEN when the ring wraps, exactly as on the device: a table whose rounds let a wave read a bin
 // that is gone shows up here), per tile / step / digit the 64 x 16 bytes of the b-operand against the 16 bytes per lane of the a-operand,
@@ -459,7 +459,7 @@ int glvemu_bars_int(const uint16_t* tex, int n, int bars, float smooth_factor, f
     return 0;
 }
 
-// The rows kernel's three-instruction division by a bar's weight sum (glv_tables.h bar_rcp_division_ok; glv_misc.hip): for every bar
+// The rows kernel's three-instruction division by a bar's weight sum (glv_tables.h bar_rcp_division_ok; glv_bars.hip): for every bar
 // of the table, q0 = a * r, rem = fma(-q0, b, a), q = fma(rem, r, q0) against a / b for EVERY significand of a in two binades around
 // b -- every b_stride-th distinct weight sum -- (scaling a by a power of two scales everything exactly while nothing leaves the normal range, which the kernel's 2^-90 guard and
 // totals <= 2^8 ensure), and at the guard's edge.  Returns the number of mismatches; *checked = quotients compared.

@@ -9,7 +9,7 @@ FORBIDDEN = ["hipMalloc", "hipFree", "hipMemcpy(", "hipMemset(", "hipMemcpyAsync
              # glv_api.cpp's DeviceArray hides hipMalloc / hipMemcpy / hipMemset / hipFree behind these methods
              "upload(", "alloc(", "renew(", "reset("]
 # the helpers that DO allocate: reachable from creation / set_params only
-ALLOCATING_HELPERS = ["ensure_bar_tables", "ensure_smooth_tables", "batch_prepare", "set_tilt", "batch_alloc", "ensure_scratch", "build_snap_tables"]
+ALLOCATING_HELPERS = ["ensure_bar_tables", "ensure_smooth_tables", "batch_prepare", "set_tilt", "batch_alloc", "ensure_scratch", "build_snap_tables", "upload_fused_items"]
 
 
 def read_csrc(name):

@@ -1,4 +1,4 @@
-"""The integer pre-smoothing pass (glava_amd/csrc/glv_misc.hip glv_bars_rows_i8_kernel) requests its weight fragments with inline-asm loads and
+"""The integer pre-smoothing pass (glava_amd/csrc/glv_bars.hip glv_bars_rows_i8_kernel) requests its weight fragments with inline-asm loads and
 awaits them with hand-placed `s_waitcnt vmcnt(6)` -- the compiler does not know those registers are in flight.  That is only sound if nothing
 but the MFMAs (behind the wait) ever reads them: a copy the register allocator slipped in between request and wait would read stale data, and
 only sometimes.  This test compiles the translation unit to assembly with the product's flags (hipcc cross-compiles, no GPU) and checks
@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_weight_fragments_of_the_integer_pass_are_touched_by_the_matrix_cores_only(tmp_path):
     from glava_amd import build as B
-    src = os.path.join(ROOT, "glava_amd", "csrc", "glv_misc.hip")
-    out = str(tmp_path / "glv_misc.s")
+    src = os.path.join(ROOT, "glava_amd", "csrc", "glv_bars.hip")
+    out = str(tmp_path / "glv_bars.s")
     flags = [f for f in B.HIPFLAGS if f != "-fPIC"]
     subprocess.run([B._hipcc(), *flags, "--cuda-device-only", "-S", src, "-o", out], check=True, capture_output=True)
     text = open(out).read()

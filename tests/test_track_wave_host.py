@@ -58,10 +58,10 @@ def test_track_wave_path_has_no_allocating_or_synchronising_call():
     body = strip_comments(function_body(src, r"\nint track_wave\(glv_batch\* b,"))
     assert "d_scratch" not in body and "d_work" in body
     # the launchers the path calls launch and nothing else
-    misc = read_csrc("glv_misc.hip")
-    for sig, kernels in ((r"\nhipError_t launch_wave_track\(", (r"glv_wave_kernel<3, true>", r"glv_wave_kernel<3, false>")),
-                         (r"\nhipError_t launch_bars_i8_pcm_track\(", (r"launch_bars_i8_in<I8_PCM_TRACK, true>", r"launch_bars_i8_in<I8_PCM_TRACK, false>"))):
-        assert_launch_only(misc, [sig])
-        body = strip_comments(function_body(misc, sig))
+    misc, bars = read_csrc("glv_misc.hip"), read_csrc("glv_bars.hip")
+    for text, sig, kernels in ((misc, r"\nhipError_t launch_wave_track\(", (r"glv_wave_kernel<3, true>", r"glv_wave_kernel<3, false>")),
+                               (bars, r"\nhipError_t launch_bars_i8_pcm_track\(", (r"launch_bars_i8_in<I8_PCM_TRACK, true>", r"launch_bars_i8_in<I8_PCM_TRACK, false>"))):
+        assert_launch_only(text, [sig])
+        body = strip_comments(function_body(text, sig))
         for k in kernels:
             assert re.search(k, body), (sig, k)

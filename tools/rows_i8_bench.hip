@@ -1,7 +1,7 @@
 // tools/rows_i8_bench.hip -- the integer pre-smoothing pass (glv_bars_rows_i8_kernel) alone, as a stand-alone executable: timing of A/B builds
 // (GLV_EXP_I8_* switches) without rebuilding the product library, and a check of the plain build against the integer formula on the host.
 // Not part of the product; built by tools/rows_i8_bench.sh.     rows_i8_bench [n] [rows] [reps]
-#include "../glava_amd/csrc/glv_misc.hip"
+#include "../glava_amd/csrc/glv_bars.hip"
 #include "../glava_amd/csrc/glv_tables.h"
 
 #include <cstdio>

@@ -3,7 +3,7 @@
 // per CU instead of two.  Same ring, rounds, weight stream and epilogue as glv_bars_rows_i8_kernel (the text below is that kernel with the tile
 // geometry changed); own host tables (tiles of 16 bars, weight fragments in the 16x16x64 b-operand layout).  Checked against the integer formula on the
 // host like rows_i8_bench.  Built by tools/rows_i8_bench.sh x16 (same flags).     rows_i8x16_bench [n] [rows] [reps]
-#include "../glava_amd/csrc/glv_misc.hip"
+#include "../glava_amd/csrc/glv_bars.hip"
 #include "../glava_amd/csrc/glv_tables.h"
 
 #include <cstdio>
