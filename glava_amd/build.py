@@ -25,6 +25,7 @@ HIPFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", 
             "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 SIZES = (7, 8, 9, 10, 11, 12, 13, 14)
 SMALL = ("glv_bars", "glv_misc")    # the kernels beside the frame kernel, one object each: the bars passes of a second launch (slow to compile) / the small kernels
+HOST = ("glv_api", "glv_wisdom", "glv_device_state", "glv_bar_tables", "glv_chain", "glv_track", "glv_multi")    # the host units (.cpp, compiled as HIP for the launch syntax of the headers)
 PARTS = (0, 1, 2, 3)     # glv_inst.hip is compiled per (size, part): s16 inputs / f32 inputs / the runner-up configuration / a track call's windows
 
 
@@ -32,7 +33,7 @@ def _inst_jobs(obj_dir: str, sizes, extra: list[str]):
     """largest sizes first: they compile slowest, the pool should not end on them"""
     return [("glv_inst.hip", os.path.join(obj_dir, f"glv_inst_{k}_{p}.o"), [f"-DGLV_LOG_NN={k}", f"-DGLV_INST_PART={p}", *extra])
             for k in sorted(sizes, reverse=True) for p in PARTS]
-HEADERS = ["glv_core.h", "glv_frame.h", "glv_kernel_tmpl.h", "glv_launch.h", "glv_launch_util.h", "glv_tables.h", "glv_winsplit.h",
+HEADERS = ["glv_core.h", "glv_frame.h", "glv_kernel_tmpl.h", "glv_launch.h", "glv_launch_util.h", "glv_tables.h", "glv_winsplit.h", "glv_host.h",
            os.path.join("..", "..", "include", "glv_spectrum.h")]
 
 
@@ -103,15 +104,14 @@ def build_variant(name: str, extra_flags: list[str], sizes=SIZES, kernels_only: 
     reused = []
     if kernels_only:
         reused = [os.path.join(OBJ, f"glv_inst_{k}_{p}.o") for k in SIZES if k not in sizes for p in PARTS]
-        reused += [os.path.join(OBJ, o) for o in ("glv_api.o", "glv_multi.o")]
+        reused += [os.path.join(OBJ, f"{u}.o") for u in HOST]
         if misc:        # the flags (also) touch the kernels of glv_misc.hip / glv_bars.hip: sizes=() compiles nothing else
             jobs += [(f"{m}.hip", os.path.join(obj_dir, f"{m}.o"), list(extra_flags)) for m in SMALL]
         else:
             reused += [os.path.join(OBJ, f"{m}.o") for m in SMALL]
     else:
         jobs += [(f"{m}.hip", os.path.join(obj_dir, f"{m}.o"), list(extra_flags)) for m in SMALL]
-        jobs.append(("glv_api.cpp", os.path.join(obj_dir, "glv_api.o"), ["-x", "hip", *extra_flags]))
-        jobs.append(("glv_multi.cpp", os.path.join(obj_dir, "glv_multi.o"), ["-x", "hip", *extra_flags]))
+        jobs += [(f"{u}.cpp", os.path.join(obj_dir, f"{u}.o"), ["-x", "hip", *extra_flags]) for u in HOST]
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 2)) as ex:
         objs = list(ex.map(lambda j: _compile(*j), jobs))
     lib = os.path.join(CSRC, f"libglvspectrum_{name}.so")
@@ -123,7 +123,7 @@ def build(tune: bool = False, verbose: bool = False) -> str:
     lib = os.path.join(CSRC, "libglvspectrum.so")
     # the built library travels to the GPU box, the objects need not: nothing to do when the library's stamp (newest source
     # mtime, taken when its build STARTED -- an edit during a build must not look built) still matches the sources
-    srcs = [os.path.join(CSRC, f) for f in ("glv_inst.hip", "glv_misc.hip", "glv_bars.hip", "glv_api.cpp", "glv_multi.cpp")] + [os.path.join(CSRC, h) for h in HEADERS]
+    srcs = [os.path.join(CSRC, f) for f in ("glv_inst.hip", *(f"{m}.hip" for m in SMALL), *(f"{u}.cpp" for u in HOST))] + [os.path.join(CSRC, h) for h in HEADERS]
     stamp_path = lib + ".stamp"
     stamp = repr(max(os.path.getmtime(f) for f in srcs))
     if not tune and os.path.exists(lib) and os.path.exists(stamp_path) and open(stamp_path).read() == stamp:
@@ -133,8 +133,7 @@ def build(tune: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     jobs = _inst_jobs(OBJ, SIZES, [])
     jobs += [(f"{m}.hip", os.path.join(OBJ, f"{m}.o"), []) for m in SMALL]
-    jobs.append(("glv_api.cpp", os.path.join(OBJ, "glv_api.o"), ["-x", "hip"]))
-    jobs.append(("glv_multi.cpp", os.path.join(OBJ, "glv_multi.o"), ["-x", "hip"]))
+    jobs += [(f"{u}.cpp", os.path.join(OBJ, f"{u}.o"), ["-x", "hip"]) for u in HOST]
     for _, _, extra in jobs:
         _refuse_experiment_flags(extra)
     if tune:

@@ -1,0 +1,262 @@
+// glv_device_state.cpp -- what a batch keeps in device memory besides the bar tables: the constant tables of its transform size (shared per device
+// and size), the tilt factors, the state arrays (gravity store, history ring) with their allocation policies and their placement tuning, the PCM rings.
+#include <cstdlib>
+#include <mutex>
+#include <new>
+#include <utility>
+
+#include "glv_host.h"
+#include "glv_tables.h"       // make_twiddles / make_window / make_log_table / make_tilt
+
+namespace glvh __attribute__((visibility("hidden"))) {
+// Device-resident constants of one transform size.  The size-only tables -- twiddles, the window in both forms (the float-pair
+// form is SEARCHED on the device: n workgroups trying 65 536 sample values per position), the log table -- are made once per
+// (device, n) and shared by every batch of that size with a reference count (glv_multi shards, the five configs[4]
+// batches and the audio backends used to repeat the search and its synchronisation points); the tilt factors depend on a batch's
+// parameters and stay per batch.
+struct SharedTables {
+    int device = 0; uint32_t n = 0; int refs = 0;
+    DeviceArray<glv::cf> d_tw; DeviceArray<double> d_win; DeviceArray<float> d_win_split; DeviceArray<glv::LogEntry> d_log;
+    int win_shifted = 0;
+};
+std::mutex g_tab_mu;
+std::vector<SharedTables*> g_tabs;
+
+// (re)generate the tilt factors when fft_scale / fft_cutoff / log mode change (render.c:845)
+int Tables::set_tilt(float fft_scale, float fft_cutoff, bool fold) {
+    if (d_tilt && fft_scale == tilt_scale && fft_cutoff == tilt_cutoff && fold == tilt_fold) return GLV_OK;
+    std::vector<float> t(n_);
+    glv::make_tilt(t.data(), n_, fft_scale, fft_cutoff, fold);
+    tilt_fold = fold;
+    // (rewritten where they are once they exist: the array a captured launch points at stays the one the next call reads)
+    if (!d_tilt) HIP_TRY(d_tilt.upload(t));
+    else HIP_TRY(hipMemcpy(d_tilt, t.data(), sizeof(float) * n_, hipMemcpyHostToDevice));
+    tilt_scale = fft_scale; tilt_cutoff = fft_cutoff;
+    return GLV_OK;
+}
+int Tables::make_shared(SharedTables* t) {
+    const uint32_t n = t->n, nn = n / 2;
+    std::vector<glv::cf> tw(nn, glv::cf{0.0f, 0.0f});
+    std::vector<double> win(n);
+    glv::make_twiddles(tw.data(), nn);
+    glv::make_window(win.data(), n);
+    HIP_TRY(t->d_tw.upload(tw));
+    HIP_TRY(t->d_win.upload(win));
+    {   // the split window: searched and proven on the device for every s16 sample value (glv_misc.hip launch_window_split)
+        int* d_fs = nullptr;
+        HIP_TRY(t->d_win_split.alloc(2 * (size_t) n, false));
+        HIP_TRY(hipMalloc(&d_fs, 2 * sizeof(int)));
+        HIP_TRY(hipMemset(d_fs, 0, 2 * sizeof(int)));
+        hipError_t e = glv::launch_window_split(t->d_win, t->d_win_split, n, d_fs, nullptr);
+        int fs[2] = {0, 0};
+        if (e == hipSuccess) e = hipMemcpy(fs, d_fs, sizeof(fs), hipMemcpyDeviceToHost);
+        (void) hipFree(d_fs);
+        HIP_TRY(e);
+        if (fs[0]) return fail(GLV_ERR_HIP, "window table of n=%u has no exact float-pair form on this host's cos()", n);
+        t->win_shifted = fs[1];
+    }
+    glv::LogEntry lt[glv::kLogTabMaxSize];
+    glv::make_log_table(lt);
+    HIP_TRY(t->d_log.upload(lt, glv::kLogTabMaxSize));
+    return GLV_OK;
+}
+int Tables::create(uint32_t n, int device) {
+    n_ = n;
+    std::lock_guard<std::mutex> lock(g_tab_mu);       // held across the creation: a second batch of the size waits instead of searching too
+    for (SharedTables* t : g_tabs) if (t->device == device && t->n == n) { shared = t; break; }
+    if (!shared) {
+        SharedTables* t = new (std::nothrow) SharedTables();
+        if (!t) return fail(GLV_ERR_NOMEM, "out of host memory");
+        t->device = device; t->n = n;
+        if (int rc = make_shared(t)) { delete t; return rc; }
+        g_tabs.push_back(t);
+        shared = t;
+    }
+    ++shared->refs;
+    d_tw = shared->d_tw; d_win = shared->d_win; d_win_split = shared->d_win_split; d_log = shared->d_log; win_shifted = shared->win_shifted;
+    return GLV_OK;
+}
+void Tables::destroy() {
+    d_tilt.reset();
+    if (shared) {
+        std::lock_guard<std::mutex> lock(g_tab_mu);
+        if (--shared->refs == 0) {
+            for (size_t i = 0; i < g_tabs.size(); ++i) if (g_tabs[i] == shared) { g_tabs.erase(g_tabs.begin() + (long) i); break; }
+            delete shared;
+        }
+        shared = nullptr;
+    }
+    d_tw = nullptr; d_win = nullptr; d_win_split = nullptr; d_log = nullptr;
+}
+}  // namespace glvh
+namespace {
+// The large state arrays (gravity store, history ring): hipMalloc -- or, for the placement experiments of profiles/r06/modes.txt (the stateful
+// chains run at one of two or three speeds per PROCESS), what GLV_STATE_ALLOC asks for (read when a batch is created; diagnostics, not API):
+//   vmm:<MiB>   virtual memory management: one address range, physical memory created and mapped in chunks of <MiB> MiB (0: one chunk),
+//               rounded up to the device's recommended granularity
+//   fine        hipExtMallocWithFlags(hipDeviceMallocFinegrained);   uncached   ... (hipDeviceMallocUncached)
+struct StateAlloc {                                                             // one vmm address range and the chunks made for it so far, in address order
+    void* ptr = nullptr; size_t size = 0;
+    struct Chunk { hipMemGenericAllocationHandle_t handle; size_t size; bool mapped; };
+    std::vector<Chunk> chunks;
+};
+static std::mutex g_state_mu;
+static std::vector<StateAlloc> g_state_allocs;                                  // (vmm allocations only: what state_free must unmap)
+// gives back whatever of `a` exists, chunk by chunk as it was mapped: state_free, and every error return of state_malloc after the reservation
+void vmm_release(const StateAlloc& a) {
+    char* at = static_cast<char*>(a.ptr);
+    for (const StateAlloc::Chunk& c : a.chunks) {
+        if (c.mapped) (void) hipMemUnmap(at, c.size);
+        (void) hipMemRelease(c.handle);
+        at += c.size;
+    }
+    (void) hipMemAddressFree(a.ptr, a.size);
+}
+
+hipError_t state_malloc(void** out, size_t bytes, int device) {
+    const char* pol = std::getenv("GLV_STATE_ALLOC");
+    if (!pol || !*pol || !std::strcmp(pol, "malloc")) return hipMalloc(out, bytes);
+    if (!std::strcmp(pol, "fine")) return hipExtMallocWithFlags(out, bytes, hipDeviceMallocFinegrained);
+    if (!std::strcmp(pol, "uncached")) return hipExtMallocWithFlags(out, bytes, hipDeviceMallocUncached);
+    if (!std::strncmp(pol, "vmm:", 4)) {
+        hipMemAllocationProp prop = {};
+        prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = device;
+        size_t gran = 0;
+        hipError_t e = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended);
+        if (e != hipSuccess) return e;
+        size_t chunk = (size_t) std::atol(pol + 4) << 20;
+        const size_t total = (bytes + gran - 1) / gran * gran;
+        if (chunk == 0 || chunk > total) chunk = total;
+        chunk = (chunk + gran - 1) / gran * gran;
+        StateAlloc a; a.size = total;
+        if ((e = hipMemAddressReserve(&a.ptr, total, gran, nullptr, 0)) != hipSuccess) return e;
+        for (size_t off = 0; off < total; off += chunk) {
+            const size_t sz = off + chunk <= total ? chunk : total - off;
+            hipMemGenericAllocationHandle_t h;
+            if ((e = hipMemCreate(&h, sz, &prop, 0)) != hipSuccess) { vmm_release(a); return e; }
+            a.chunks.push_back(StateAlloc::Chunk{h, sz, false});
+            if ((e = hipMemMap(static_cast<char*>(a.ptr) + off, sz, 0, h, 0)) != hipSuccess) { vmm_release(a); return e; }
+            a.chunks.back().mapped = true;
+        }
+        hipMemAccessDesc acc = {}; acc.location = prop.location; acc.flags = hipMemAccessFlagsProtReadWrite;
+        if ((e = hipMemSetAccess(a.ptr, total, &acc, 1)) != hipSuccess) { vmm_release(a); return e; }
+        *out = a.ptr;
+        std::lock_guard<std::mutex> lk(g_state_mu);
+        g_state_allocs.push_back(std::move(a));
+        return hipSuccess;
+    }
+    return hipErrorInvalidValue;
+}
+}  // namespace
+namespace glvh __attribute__((visibility("hidden"))) {
+void state_free(void* p) {
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> lk(g_state_mu);
+        for (size_t i = 0; i < g_state_allocs.size(); ++i)
+            if (g_state_allocs[i].ptr == p) {
+                StateAlloc a = std::move(g_state_allocs[i]);
+                g_state_allocs.erase(g_state_allocs.begin() + (long) i);
+                vmm_release(a);
+                return;
+            }
+    }
+    (void) hipFree(p);
+}
+
+int batch_alloc(glv_batch* b) {
+    const size_t n = b->p.n;
+    b->state16 = b->p.gl_storage == 1;
+    if ((b->ops_mask & GLV_OP_AVERAGE)) {
+        HIP_TRY(state_malloc(reinterpret_cast<void**>(&b->d_hist), b->hist_bytes(), b->device));
+        HIP_TRY(hipMemset(b->d_hist, 0, b->hist_bytes()));
+    }
+    if ((b->ops_mask & GLV_OP_GRAVITY)) {
+        // kept even when the ring also exists: the single-op glv_gravity() drop-in owns its own
+        // `applied` buffer exactly like the reference's separate udata slot (render.c:724)
+        HIP_TRY(state_malloc(reinterpret_cast<void**>(&b->d_grav), b->grav_bytes(), b->device));
+        HIP_TRY(hipMemset(b->d_grav, 0, b->grav_bytes()));
+        b->grav_cur = b->d_grav;
+    }
+    // the device rings of the FIFO / PulseAudio modes, when the creation mask announces them
+    if (b->ops_mask & GLV_OP_RING_S16) HIP_TRY(b->d_ring.alloc(2 * n * b->streams, true));          // == the calloc'd rings of glava.c:487-494
+    if (b->ops_mask & GLV_OP_RING_F32) HIP_TRY(b->d_ring_f32.alloc(2 * n * b->streams, true));
+    return GLV_OK;
+}
+}  // namespace glvh
+
+extern "C" {
+// Placement wisdom (round 6; profiles/r06/modes.txt).  A stateful chain runs at one of two or three speeds, 7 - 14 % apart, and which one is a property of
+// WHERE ITS STATE ARRAYS LIE in physical memory relative to the caller's output buffer: K batches of one process, created one after the other, each keep
+// their own speed against the same buffers, and one batch changes speed with the output buffer it is given -- not with the allocator (hipMalloc, virtual
+// memory management in one or many chunks, fine-grained: the same mix), not with the TLB (UTCL1 misses 3e4 of 2.8e8 requests in every mode), not with
+// clocks, power or temperature.  So the library does what it does for the launch geometry: it measures.  The current placement is timed with the caller's
+// real buffers, then up to `candidates` - 1 fresh allocations of the state arrays (the earlier ones stay allocated meanwhile, so every candidate lies on
+// other frames); the fastest is kept, the others are freed, the state is reset.
+int glv_batch_tune_placement(glv_batch* b, const int16_t* d_pcm, void* d_out, unsigned ops, int candidates, void* hip_stream, float* first_ms, float* best_ms) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!(ops & GLV_OP_FFT) || !(ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) return fail(GLV_ERR_INVALID, "glv_batch_tune_placement tunes a stateful chain: ops needs GLV_OP_FFT and GLV_OP_GRAVITY / GLV_OP_AVERAGE");
+    if (int rc = check_ops(b, ops, static_cast<float*>(d_out))) return rc;
+    if (!d_pcm || !d_out) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (candidates < 1) candidates = 1;
+    if (candidates > 16) candidates = 16;
+    hipStream_t st = (hipStream_t) hip_stream;
+    HIP_TRY(hipSetDevice(b->device));
+    const uint32_t units = b->streams * 2;
+    const size_t hist_bytes = b->d_hist ? b->hist_bytes() : 0, grav_bytes = b->d_grav ? b->grav_bytes() : 0;
+    EventPair ev; HIP_TRY(ev.create());
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    int rc = GLV_OK;
+    auto measure = [&](float* ms) -> int {
+        if (int r = glv_batch_reset(b)) return r;
+        for (int i = 0; i < 4; ++i) if (int r = process(b, d_pcm, glv::IN_S16_STEREO, static_cast<float*>(d_out), ops, units, 0, st)) return r;
+        if (hipEventRecord(e0, st) != hipSuccess) return fail(GLV_ERR_HIP, "hipEventRecord failed");
+        const int iters = 10;
+        for (int i = 0; i < iters; ++i) if (int r = process(b, d_pcm, glv::IN_S16_STEREO, static_cast<float*>(d_out), ops, units, 0, st)) return r;
+        if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(ms, e0, e1) != hipSuccess) return fail(GLV_ERR_HIP, "event timing failed");
+        *ms /= (float) iters;
+        return GLV_OK;
+    };
+    float cur = 0.f;
+    for (int i = 0; i < 24 && rc == GLV_OK; ++i) rc = process(b, d_pcm, glv::IN_S16_STEREO, static_cast<float*>(d_out), ops, units, 0, st);      // clocks up
+    if (rc == GLV_OK) rc = measure(&cur);
+    const float first = cur;
+    std::vector<std::pair<void*, void*>> losers;                                 // (hist, grav) of the placements that lost: freed at the end
+    for (int c = 1; c < candidates && rc == GLV_OK; ++c) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * (hist_bytes + grav_bytes) + ((size_t) 1 << 30)) break;      // room for this candidate and slack
+        void *nh = nullptr, *ng = nullptr;
+        if (hist_bytes && state_malloc(&nh, hist_bytes, b->device) != hipSuccess) { (void) hipGetLastError(); break; }
+        if (grav_bytes && state_malloc(&ng, grav_bytes, b->device) != hipSuccess) { (void) hipGetLastError(); state_free(nh); break; }
+        void *oh = b->d_hist, *og = b->d_grav;
+        if (nh) b->d_hist = static_cast<float*>(nh);
+        if (ng) b->d_grav = static_cast<float*>(ng);
+        float ms = 0.f;
+        rc = measure(&ms);
+        // (a candidate that lost gives its arrays back: grav_cur must not keep pointing into them -- also where measure() failed and no reset follows)
+        if (rc == GLV_OK && ms < cur * 0.985f) { cur = ms; losers.emplace_back(oh, og); }
+        else { b->d_hist = static_cast<float*>(oh); b->d_grav = static_cast<float*>(og); losers.emplace_back(nh, ng); b->rewind_state(); }
+    }
+    (void) hipStreamSynchronize(st);
+    for (auto& l : losers) { state_free(l.first); state_free(l.second); }
+    if (rc != GLV_OK) return rc;
+    if (int r = glv_batch_reset(b)) return r;
+    if (first_ms) *first_ms = first;
+    if (best_ms) *best_ms = cur;
+    return GLV_OK;
+}
+
+int glv_batch_window_selftest(glv_batch* b, unsigned long long* mismatches, int* shifted) {
+    if (!b || !mismatches) return fail(GLV_ERR_INVALID, "glv_batch_window_selftest: NULL argument");
+    HIP_TRY(hipSetDevice(b->device));
+    unsigned long long* d_m = nullptr;
+    HIP_TRY(hipMalloc(&d_m, sizeof(*d_m)));
+    hipError_t e = hipMemset(d_m, 0, sizeof(*d_m));
+    if (e == hipSuccess) e = glv::launch_window_split_check(b->tab.d_win, b->tab.d_win_split, b->p.n, d_m, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(mismatches, d_m, sizeof(*d_m), hipMemcpyDeviceToHost);
+    (void) hipFree(d_m);
+    HIP_TRY(e);
+    if (shifted) *shifted = b->tab.win_shifted;
+    return GLV_OK;
+}
+}  // extern "C"

@@ -1,0 +1,305 @@
+// glv_track.cpp -- track mode: every update of a recording in one call.  The plans of the three entries, the executor of the two FFT forms with its
+// stages, the wave module's form, and the C entries with their sizing queries.
+#include "glv_host.h"
+#include "glv_tables.h"       // kBarSeqMin
+
+namespace {
+// ---- track mode: `steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16, glv_batch_track_windows_s16) ------------
+// One executor (`track`) carries out a TrackPlan in three stages, kernels only.  (1) The transform, with the stateless frame kernels as they are, in
+// one of two forms.  Residues (plan_track: hop a power of two, track_residues): the whole [streams * pitch] frame sequence is cut into
+// back-to-back windows of n frames q = n / hop times, launch r starting r * hop frames in -- window t of stream s, which starts at a multiple h of
+// hop, is row h / q of launch h % q.  Windows (plan_track_windows: any hop, track_windows): ONE launch in the kernel's IN_S16_TRACK mode over
+// the steps * streams windows the call names, each read where it lies (glv_frame.h TrackWindows) -- rows step-major straight into d_out (a stateless
+// chain without bars: nothing else runs), step-major into the workspace (stateless with bars), or stream-major into the workspace for the scan, whose
+// geometry with one residue (log_q = 0) and hops_per_pitch = steps IS [stream][step][channel].  Either way the rows are texels where the chain's
+// first act is the GL_R16 upload.  (2) glv_track_scan_kernel (track_scan) walks the steps per bin with the state on chip and writes every
+// step's result -- into d_out, or with GLV_OP_BARS into the workspace's second region in the row format the bars kernel takes.  (3) The bars of a
+// second launch over steps * streams * 2 finished rows.
+struct TrackPlan {
+    uint32_t q = 0, log_q = 0;          // residue launches
+    uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
+    uint64_t k0 = 0;                    // windows of launch 0 (launch r: (frames - r * hop) / n, k0 or k0 - 1)
+    bool windows = false;               // stage (1) is the one launch over the windows where they lie, else the q residue launches
+    bool to_out = false;                // stage (1) writes d_out and nothing else runs, else it writes the start of the workspace
+    bool scan = false;                  // stage (2) runs: the chain keeps state, or stage (1) left residues (which only the scan puts in step order)
+    uint32_t hops_per_pitch = 0, residue_rows = 0;   // TrackGeometry, with log_q: where the scan finds window t of stream s among stage (1)'s rows
+    bool state = false;                 // the chain keeps gravity / average state
+    bool in16 = false;                  // the transform's rows are GL_R16 texels (kernel class FC_R16), else floats (FC_PLAIN)
+    bool out16 = false;                 // the scan's results are texels
+    ChainPlan::Bars bars = ChainPlan::NO_BARS;
+    uint64_t rows_bytes = 0, work_bytes = 0;   // the transform's region of the workspace (a multiple of 256 bytes), and all of it
+    uint64_t out_rows = 0;              // steps * streams * 2
+};
+// What the two track entries (glv_batch_track_s16, glv_batch_track_windows_s16) share, written once so that they cannot disagree: the refusals that are
+// not about hop or pitch, and what the chain's stages carry.  In the order the checks have always run: (1) the arguments ...
+int track_args(unsigned ops, uint32_t steps) {
+    if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "a track call transforms: GLV_OP_FFT is required (ops 0x%x)", ops);
+    const unsigned allowed = GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_BARS | GLV_OP_R16 | GLV_OP_PRIVATE_STATE;
+    if (ops & ~allowed)
+        return fail(GLV_ERR_INVALID, "a track call takes GLV_OP_FFT with GLV_OP_GRAVITY / AVERAGE / BARS / R16 only (no RAW, SMOOTH, WAVE, WRANGE, MAGNITUDE, OUTPUT_IS_STATE; ops 0x%x)", ops);
+    if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
+    return GLV_OK;
+}
+// ... (2) each entry's own hop and pitch rules, then (3) the batch, the rows of the output, and the decisions
+int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by the entry)
+    if (b->p.gl_storage == 2) return fail(GLV_ERR_STATE, "gl_storage 2 is the pass-by-pass checker form: a track call runs on gl_storage 0 and 1");
+    if (b->ops_mask & GLV_OP_BARS_ONLY)
+        return fail(GLV_ERR_STATE, "the batch was created with GLV_OP_BARS_ONLY: its state beyond the live bins does not exist, which the scan over time would read");
+    if (b->columns()) return fail(GLV_ERR_STATE, "column texels are set (glv_batch_set_column_texels): a track call has no columns form");
+    if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
+    if (int rc = check_ops(b, ops, &some_output)) return rc;
+    tp.out_rows = (uint64_t) steps * b->streams * 2u;
+    if (tp.out_rows > 0xffffffffull)                              // (the transform and the scan count their rows in FrameArgs::units, a uint32_t)
+        return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
+    tp.state = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
+    const bool gl = tp.state && b->state16;                       // the GL_R16 chain, texel state (log_mode 2: its passes one by one -- the same texels)
+    const bool snap = (ops & GLV_OP_BARS) && b->snapped();        // (check_ops: a GL chain's texel rows)
+    // the bars of a second launch, as plan_chain picks them for a chain whose transform kernel does not take them
+    if (!(ops & GLV_OP_BARS)) tp.bars = ChainPlan::NO_BARS;
+    else if (snap) tp.bars = b->p.sample_mode != GLV_SAMPLE_AVERAGE ? ChainPlan::BARS_SNAP_MODE : b->p.log_mode != 2 ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_FLOATS;
+    else if (gl && b->p.bars >= glv::kBarSeqMin && b->bar_x.i8()) tp.bars = b->p.log_mode != 2 ? ChainPlan::BARS_I8 : ChainPlan::BARS_I8_FLOATS;
+    else tp.bars = ChainPlan::BARS_F32;
+    tp.in16 = tp.state ? gl : ((ops & GLV_OP_R16) && !(ops & GLV_OP_BARS));
+    // with bars the texel conversion applies to the bars: the rows stay floats, unless the bars kernel takes texel rows
+    tp.out16 = (ops & GLV_OP_BARS) ? (tp.bars == ChainPlan::BARS_I8 || tp.bars == ChainPlan::BARS_SNAP) : (ops & GLV_OP_R16) != 0;
+    return GLV_OK;
+}
+uint64_t up256(uint64_t v) { return (v + 255u) & ~(uint64_t) 255u; }
+bool pitch_too_short(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps) {
+    if ((uint64_t) pitch_frames >= (uint64_t) n + (uint64_t) (steps - 1) * hop) return false;
+    (void) fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%u frames every hop=%u", pitch_frames, steps, n, hop);
+    return true;
+}
+// Everything about a track call that does not depend on its pointers or on what the batch did before: refusals, geometry, workspace.
+int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    const uint32_t n = b->p.n;
+    if (int rc = track_args(ops, steps)) return rc;
+    const int lh = log2_exact(hop);
+    if (lh < 2 || hop > n) return fail(GLV_ERR_INVALID, "hop=%u: must be a power of two in [4, n=%u]", hop, n);
+    if (pitch_frames % hop != 0) return fail(GLV_ERR_INVALID, "pitch_frames=%u is not a multiple of hop=%u", pitch_frames, hop);
+    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
+    if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
+    tp.q = n / hop; tp.log_q = (uint32_t) log2_exact(tp.q);
+    tp.frames = (uint64_t) (b->streams - 1) * pitch_frames + (uint64_t) (steps - 1) * hop + n;
+    tp.k0 = tp.frames / n;
+    if (2u * tp.k0 > 0xffffffffull || (uint64_t) b->streams * (pitch_frames / hop) + steps > 0xffffffffull)
+        return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
+    tp.scan = true; tp.hops_per_pitch = pitch_frames / hop; tp.residue_rows = (uint32_t) (2u * tp.k0);
+    tp.rows_bytes = up256((uint64_t) tp.q * 2u * tp.k0 * n * (tp.in16 ? 2u : 4u));
+    tp.work_bytes = tp.rows_bytes + ((ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+    return GLV_OK;
+}
+// glv_batch_track_windows_s16: any hop >= 1, any pitch that holds the windows.  One transform launch over exactly the windows asked for, so its region of the
+// workspace is steps * streams * 2 rows; a stateless chain without bars writes d_out directly and needs none (256: 0 stays "refused").  The scan's region
+// exists where a scan runs AND bars follow it.
+int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    const uint32_t n = b->p.n;
+    if (int rc = track_args(ops, steps)) return rc;
+    if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
+    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
+    if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
+    tp.windows = true; tp.scan = tp.state; tp.hops_per_pitch = steps;      // (one residue: log_q and residue_rows stay 0)
+    tp.to_out = !tp.state && !(ops & GLV_OP_BARS);
+    if (tp.to_out) { tp.rows_bytes = 0; tp.work_bytes = 256; return GLV_OK; }
+    tp.rows_bytes = up256(tp.out_rows * n * (tp.in16 ? 2u : 4u));
+    tp.work_bytes = tp.rows_bytes + (tp.state && (ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+    return GLV_OK;
+}
+
+int refuse_track_pointers(const void* d_pcm, const void* d_out, const void* d_work) {
+    if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
+    return GLV_OK;
+}
+// (1) as residues: q launches of the stateless kernel class, each over back-to-back windows -- the only loop of launches on the track path
+int track_residues(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::FrameClass cls, const int16_t* d_pcm, uint32_t hop, char* work, hipStream_t st) {
+    const uint32_t n = b->p.n;
+    for (uint32_t r = 0; r < tp.q; ++r) {
+        const uint64_t k_r = (tp.frames - (uint64_t) r * hop) / n;            // k0 or k0 - 1; never past the last window any step reads
+        if (k_r == 0) continue;                                                // (counted all the same: the launch count is n / hop)
+        a.in = d_pcm + (size_t) r * hop * 2u;
+        a.out = reinterpret_cast<float*>(work + (size_t) r * 2u * tp.k0 * n * (tp.in16 ? 2u : 4u));
+        a.units = (uint32_t) (2u * k_r);
+        int variant = 0, grid = 0;
+        launch_plan(b, a.units, glv::IN_S16_STEREO, a.ops, &variant, &grid);
+        b->last_grid = grid; b->last_variant = variant;
+        const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_STEREO, (int) b->p.log_mode, variant, cls, a, grid, st);
+        if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    }
+    b->last_launches += (int) tp.q;
+    return GLV_OK;
+}
+// (1) as windows: every window of the call where it lies, one launch, into `rows`
+int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::FrameClass cls, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps,
+                        float* rows, hipStream_t st) {
+    a.in = d_pcm; a.out = rows; a.units = (uint32_t) tp.out_rows;
+    a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
+    int variant = 0, grid = 0;
+    launch_plan(b, a.units, glv::IN_S16_TRACK, a.ops, &variant, &grid);
+    b->last_grid = grid; b->last_variant = variant;
+    const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_TRACK, (int) b->p.log_mode, variant, cls, a, grid, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    b->kernel_name = "glv_frame_kernel";
+    return GLV_OK;
+}
+// (2) the scan over time, from stage (1)'s rows at the start of the workspace into `out`
+int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t steps, const char* work, float* out, unsigned ops, hipStream_t st) {
+    a.in = work; a.out = out;
+    a.units = b->streams * 2u; a.ops = ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE);
+    a.grav = b->grav_cur; a.grav_w = b->d_grav; a.hist = b->d_hist; a.head = b->head;
+    a.grav_sub = b->grav_sub; a.grav_int = b->grav_int ? 1u : 0u; a.gl_storage = tp.in16 && tp.state ? 1u : 0u;
+    glv::TrackGeometry g;
+    g.n = b->p.n; g.steps = steps; g.hops_per_pitch = tp.hops_per_pitch; g.log_q = tp.log_q; g.residue_rows = tp.residue_rows; g.out_texels = tp.out16 ? 1u : 0u;
+    const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
+    b->kernel_name = "glv_track_scan_kernel";
+    // the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
+    if (ops & GLV_OP_AVERAGE) b->head = (uint32_t) (((uint64_t) b->head + steps) % b->p.avg_frames);
+    if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
+    return GLV_OK;
+}
+// Carries a plan out: what the plan could not know (the pointers, what the batch did before), then the stages.  A refused call leaves the batch untouched.
+int track(glv_batch* b, const TrackPlan& tp, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (int rc = refuse_track_pointers(d_pcm, d_out, d_work)) return rc;
+    if (int rc = refuse_gravity_mix(b, ops)) return rc;
+    if (int rc = refuse_stale_tilt(b)) return rc;
+    b->last_launches = 0;
+    HIP_TRY(hipSetDevice(b->device));
+    commit_gravity_form(b, ops);
+    char* const work = static_cast<char*>(d_work);
+    float* const out = static_cast<float*>(d_out);
+    if (int rc = timed_launch_begin(b, st)) return rc;
+    glv::FrameArgs a;
+    fill_common(a, b->p, b->tab);
+    a.ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u); a.log_mode = b->p.log_mode;
+    const glv::FrameClass cls = glv::frame_class(false, false, false, a.ops);
+    if (int rc = tp.windows ? track_windows(b, tp, a, cls, d_pcm, pitch_frames, hop, steps, tp.to_out ? out : reinterpret_cast<float*>(work), st)
+                            : track_residues(b, tp, a, cls, d_pcm, hop, work, st)) return rc;
+    ChainPlan pl;
+    pl.bars = tp.bars;
+    pl.rows = reinterpret_cast<float*>(work + (tp.scan ? tp.rows_bytes : 0u));       // what the bars read: the scan's results, or a stateless transform's rows
+    if (tp.scan) if (int rc = track_scan(b, tp, a, steps, work, (ops & GLV_OP_BARS) ? pl.rows : out, ops, st)) return rc;
+    // (3) the bars of every step's rows
+    if (int rc = launch_bars_pass(b, pl, out, (size_t) steps * b->streams * 2u, (ops & GLV_OP_R16) != 0, st)) return rc;
+    return timed_launch_end(b, st);
+}
+
+// ---- track mode for the wave module: the texture of every update of a recording in one call (glv_batch_track_wave_s16) -------------
+// GLV_OP_WAVE is stateless and transforms nothing: a call is plan_wave's one or two launches over steps * streams * 2 rows instead of streams * 2,
+// the kernels' windows cut out of the recordings by glv::WaveWindows.  The bars arithmetic, what the waveform kernel writes and how much of a row are
+// plan_wave's own choices (track and process cannot disagree); the rows between two launches live in the caller's workspace, not in the scratch rows
+// (sized for one update).
+struct TrackWavePlan {
+    ChainPlan pl;                   // the one or two launches of windows that start at any frame
+    bool one_launch = false;        // with bars: plan_wave fuses where hop and pitch keep every window on a group of 8 frames -- of a 32-byte aligned d_pcm, which
+                                    // only the call sees: on any other it runs `pl`
+    uint64_t rows = 0;              // steps * streams * 2
+    uint64_t work_bytes = 256;      // (without bars there is no second launch and nothing to park: the convention keeps 0 for "refused")
+};
+int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackWavePlan& tp) {
+    static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by track_wave)
+    const uint32_t n = b->p.n;
+    if (!(ops & GLV_OP_WAVE)) return fail(GLV_ERR_INVALID, "a wave track call needs GLV_OP_WAVE (ops 0x%x; GLV_OP_FFT chains: glv_batch_track_s16)", ops);
+    if (ops & ~(unsigned) (GLV_OP_WAVE | GLV_OP_BARS | GLV_OP_R16))
+        return fail(GLV_ERR_INVALID, "a wave track call takes GLV_OP_WAVE with GLV_OP_BARS / GLV_OP_R16 only (ops 0x%x)", ops);
+    if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
+    if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
+    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
+    if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
+    tp.rows = (uint64_t) steps * b->streams * 2u;
+    if (tp.rows > 0x100000000ull)                 // (a COUNT of rows, steps * units, which the launchers take as a size_t: exactly 2^32 rows pass)
+        return fail(GLV_ERR_INVALID, "steps=%u of %u streams: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams);
+    if (int rc = check_ops(b, ops, &some_output)) return rc;
+    // The sizing query does not see d_pcm, so with bars the workspace is always what the two launches need: plan_wave is asked twice, for windows that
+    // start anywhere (the plan every call can fall back on) and for this call's hop and pitch.
+    if (int rc = plan_wave(b, glv::IN_S16_STEREO, ops, 0, nullptr, tp.pl, false)) return rc;
+    if (ops & GLV_OP_BARS) {
+        ChainPlan grouped;
+        if (int rc = plan_wave(b, glv::IN_S16_STEREO, ops, 0, nullptr, grouped, hop % 8u == 0u && pitch_frames % 8u == 0u)) return rc;
+        tp.one_launch = grouped.wave_fused;
+        tp.work_bytes = up256(tp.rows * n * (tp.pl.wave_r16 ? 2u : 4u));
+    }
+    return GLV_OK;
+}
+
+int track_wave(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (int rc = refuse_track_pointers(d_pcm, d_out, d_work)) return rc;
+    TrackWavePlan tp;
+    if (int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    ChainPlan& pl = tp.pl;
+    const bool fused = tp.one_launch && (reinterpret_cast<uintptr_t>(d_pcm) & 31u) == 0u;
+    b->last_launches = 0;
+    HIP_TRY(hipSetDevice(b->device));
+    const bool mono = b->p.channels == 1, r16 = (ops & GLV_OP_R16) != 0;
+    glv::WaveWindows w;
+    w.units = b->streams * 2u; w.steps = steps; w.hop = hop; w.pitch_frames = pitch_frames;
+    // (a store's 32-bit lane offset spans 4 rows of the workgroup: `units` rows apart by steps)
+    w.by_steps = b->track_wave_by_steps && (4ull * w.units + 2u) * b->p.bars * 4u <= 0xffffffffull ? 1u : 0u;
+    if (int rc = timed_launch_begin(b, st)) return rc;
+    hipError_t e;
+    if (fused) {
+        const glv::BarIRowsTables irt = b->bar_x.irows_tables();
+        e = glv::launch_bars_i8_pcm_track(d_pcm, w, mono, d_out, b->p.n, b->p.bars, &irt, st, r16);
+        b->kernel_name = "glv_bars_rows_i8_kernel";
+    } else {
+        if (ops & GLV_OP_BARS) pl.out = pl.rows = static_cast<float*>(d_work);
+        else pl.out = static_cast<float*>(d_out);
+        e = glv::launch_wave_track(d_pcm, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
+        b->kernel_name = "glv_wave_kernel";
+    }
+    ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    if (!fused) if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) tp.rows, r16, st)) return rc;
+    return timed_launch_end(b, st);
+}
+
+// The sizing query of a track entry: its plan's workspace, or 0 where the plan refuses (no return code to carry it: the message names the code).
+template <class Plan>
+uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, uint32_t, uint32_t, uint32_t, unsigned, Plan&), uint32_t pitch_frames, uint32_t hop, uint32_t steps,
+                            unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    Plan tp;
+    if (const int rc = plan(b, pitch_frames, hop, steps, ops, tp)) {
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return tp.work_bytes;
+}
+}  // namespace
+
+extern "C" {
+uint64_t glv_batch_track_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    return planned_work_bytes(b, plan_track, pitch_frames, hop, steps, ops);
+}
+
+int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                        unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    TrackPlan tp;
+    if (int rc = plan_track(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+uint64_t glv_batch_track_windows_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    return planned_work_bytes(b, plan_track_windows, pitch_frames, hop, steps, ops);
+}
+
+int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    TrackPlan tp;
+    if (int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    return planned_work_bytes(b, plan_track_wave, pitch_frames, hop, steps, ops);
+}
+
+int glv_batch_track_wave_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    return track_wave(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+}  // extern "C"

@@ -121,7 +121,7 @@ void glv_hip_scan_shape(const char* rpath, const char* text, size_t len) {
     if ((v = glv_hip_last_define(text, len, "SAMPLE_HYBRID_WEIGHT", &vl)) && !glv_hip_literal(v, vl, &glv_hip_shape.hybrid)) glv_hip_shape.readable = false;
     if ((v = glv_hip_last_define(text, len, "SAMPLE_SCALE", &vl)) && !glv_hip_literal(v, vl, &glv_hip_shape.scale)) glv_hip_shape.readable = false;
     if ((v = glv_hip_last_define(text, len, "SAMPLE_RANGE", &vl)) && !glv_hip_literal(v, vl, &glv_hip_shape.range)) glv_hip_shape.readable = false;
-    /* what the library refuses (glv_api.cpp ensure_bar_tables: positions past the end of the texture) stays on the GL as well */
+    /* what the library refuses (glv_bar_tables.cpp ensure_bar_tables: positions past the end of the texture) stays on the GL as well */
     const float sc = glv_hip_shape.scale != 0.0f ? glv_hip_shape.scale : 8.0f, rg = glv_hip_shape.range != 0.0f ? glv_hip_shape.range : 0.9f;
     const float hw = glv_hip_shape.hybrid != 0.0f ? glv_hip_shape.hybrid : 0.65f;
     if (!(sc > 0.0f && sc <= 1e6f) || !(rg > 0.0f && rg < 1.0f) || !(-logf(1.0f - rg) / sc <= 1.0f) || !(hw > 0.0f && hw <= 1.0f)) glv_hip_shape.readable = false;

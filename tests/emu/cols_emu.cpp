@@ -3,7 +3,7 @@
 // FC_GL16_COLS*: the snapped loop over the distinct texels, kept as 16-bit values behind the row, then one column per lane) and the row loop of the
 // second launch (glv_bars.hip glv_columns_kernel, sample_mode average).  The tables are the library's own (glv_tables.h) and the arithmetic is the
 // shared GLV_HD code of glv_frame.h (bar_item_load, bar_snap_lane_sum, bar_snap_texel, column_mean); only the lane loops, the order-free integer
-// group reduction and the de-duplication (glv_api.cpp set_snap_texels) are spelled out here.
+// group reduction and the de-duplication (glv_bar_tables.cpp set_snap_texels) are spelled out here.
 #include <stdint.h>
 #include <string.h>
 

@@ -1,4 +1,5 @@
-"""Source scanners shared by the host tests that pin a call path of glava_amd/csrc/glv_api.cpp to launches and asynchronous device-to-device copies
+"""Source scanners shared by the host tests that pin a call path of the host units (glava_amd/csrc: glv_host.h and the .cpp files of HOST_UNITS, read as
+one text by read_host_src) to launches and asynchronous device-to-device copies
 (tests/test_stream_order.py and the test_track*_host.py files): a plain module, like oracle_lib.py."""
 import os
 import re
@@ -6,14 +7,22 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FORBIDDEN = ["hipMalloc", "hipFree", "hipMemcpy(", "hipMemset(", "hipMemcpyAsync(", "hipStreamSynchronize", "hipDeviceSynchronize",
              "hipHostMalloc", "hipEventSynchronize", "hipMemcpyToSymbol", "hipMemcpyFromSymbol",
-             # glv_api.cpp's DeviceArray hides hipMalloc / hipMemcpy / hipMemset / hipFree behind these methods
+             # glv_host.h's DeviceArray hides hipMalloc / hipMemcpy / hipMemset / hipFree behind these methods
              "upload(", "alloc(", "renew(", "reset("]
 # the helpers that DO allocate: reachable from creation / set_params only
 ALLOCATING_HELPERS = ["ensure_bar_tables", "ensure_smooth_tables", "batch_prepare", "set_tilt", "batch_alloc", "ensure_scratch", "build_snap_tables", "upload_fused_items"]
 
 
+HOST_UNITS = ["glv_host.h", "glv_api.cpp", "glv_wisdom.cpp", "glv_device_state.cpp", "glv_bar_tables.cpp", "glv_chain.cpp", "glv_track.cpp"]
+
+
 def read_csrc(name):
     return open(os.path.join(ROOT, "glava_amd", "csrc", name)).read()
+
+
+def read_host_src():
+    """the host layer behind the C ABI as one text, in a fixed order (a function's definition is found by its signature wherever it lives)"""
+    return "\n".join(read_csrc(name) for name in HOST_UNITS)
 
 
 def function_body(src, signature_re):

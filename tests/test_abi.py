@@ -174,7 +174,8 @@ def test_experiment_macro_without_the_tune_switch_does_not_compile(tmp_path):
 
 def test_no_experiment_switch_is_left_in_the_kernel_sources():
     """the GLV_EXP_* family (loads / stores / barriers removed for timing, store waves, shuffles, ...) does not come back unnoticed"""
-    for f in ("glv_core.h", "glv_frame.h", "glv_kernel_tmpl.h", "glv_misc.hip", "glv_bars.hip", "glv_launch_util.h", "glv_inst.hip", "glv_api.cpp", "glv_tables.h"):
+    for f in ("glv_core.h", "glv_frame.h", "glv_kernel_tmpl.h", "glv_misc.hip", "glv_bars.hip", "glv_launch_util.h", "glv_inst.hip", "glv_api.cpp", "glv_host.h", "glv_wisdom.cpp",
+              "glv_device_state.cpp", "glv_bar_tables.cpp", "glv_chain.cpp", "glv_track.cpp", "glv_tables.h"):
         txt = open(os.path.join(ROOT, "glava_amd", "csrc", f)).read()
         assert "GLV_EXP_" not in txt, f
 

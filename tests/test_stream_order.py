@@ -4,7 +4,7 @@ Everything a process call needs -- tilt table, bar tables and work lists, smooth
 rings, the state arrays -- is made by glv_batch_create (or glv_batch_set_params).  The process calls and ring updates launch
 kernels and asynchronous device-to-device copies, nothing else:
 
-  CPU   the bodies of the functions on that path in glava_amd/csrc/glv_api.cpp contain no allocating / synchronising HIP call;
+  CPU   the bodies of the functions on that path in the host units of glava_amd/csrc contain no allocating / synchronising HIP call;
   GPU   the FIRST glv_batch_process_s16 after creation is captured into a hipGraph (hipStreamBeginCapture, global mode: any
         allocation or synchronous copy would invalidate the capture) and replayed; results equal eager execution bit for bit,
         for BASELINE configs[1] (stateless pass), the F = 5 chain, fused bars, the GL_R16 chain and a ring update.
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from oracle_lib import lcg_pcm_fast
-from src_scan import STATE_CHECKS, assert_launch_only, read_csrc
+from src_scan import STATE_CHECKS, assert_launch_only, read_host_src
 
 
 def test_process_path_has_no_allocating_or_synchronising_call():
@@ -24,7 +24,7 @@ def test_process_path_has_no_allocating_or_synchronising_call():
             r"\nint glv_batch_ring_append_f32\(", r"\nint glv_batch_ring_planar\(", r"\nint glv_batch_bars\(", r"\nint timed_launch_end\("] + STATE_CHECKS
     # the one copy the path may issue: the asynchronous device-to-device row copy of operator-only chains; and the helpers that DO allocate are
     # reachable from creation / set_params only
-    assert_launch_only(read_csrc("glv_api.cpp"), path,
+    assert_launch_only(read_host_src(), path,
                        allowed=["hipMemcpyAsync(d_out, d_in, sizeof(float) * (size_t) units * b->p.n, hipMemcpyDeviceToDevice, st)"])
 
 

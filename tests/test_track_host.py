@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from src_scan import ROOT, TRACK_EXECUTOR, assert_launch_only, function_body, read_csrc, strip_comments
+from src_scan import ROOT, TRACK_EXECUTOR, assert_launch_only, function_body, read_csrc, read_host_src, strip_comments
 
 
 def test_track_symbols_are_exported_and_bound(glvlib):
@@ -49,7 +49,7 @@ def test_every_window_is_one_row_of_one_launch(glvlib, n):
 
 
 def test_track_path_has_no_allocating_or_synchronising_call():
-    src = read_csrc("glv_api.cpp")
+    src = read_host_src()
     assert_launch_only(src, [r"\nint plan_track\(", r"\nint glv_batch_track_s16\(", r"\nuint64_t glv_batch_track_work_bytes\("] + TRACK_EXECUTOR)
     # the residue stage holds the only loop of launches on the path: the executor and the other stages have none
     assert "for (" in strip_comments(function_body(src, r"\nint track_residues\("))

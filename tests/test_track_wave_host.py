@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from src_scan import ROOT, TRACK_COMMON, assert_launch_only, function_body, read_csrc, strip_comments
+from src_scan import ROOT, TRACK_COMMON, assert_launch_only, function_body, read_csrc, read_host_src, strip_comments
 
 
 def test_track_wave_symbols_are_exported_and_bound(glvlib):
@@ -51,7 +51,7 @@ def test_every_output_row_starts_where_its_window_does(glvlib, n):
 
 
 def test_track_wave_path_has_no_allocating_or_synchronising_call():
-    src = read_csrc("glv_api.cpp")
+    src = read_host_src()
     assert_launch_only(src, [r"\nint plan_track_wave\(", r"\nbool pitch_too_short\(", r"\nint track_wave\(glv_batch\* b,", r"\nint plan_wave\(", r"\nint glv_batch_track_wave_s16\(",
                              r"\nuint64_t glv_batch_track_wave_work_bytes\("] + TRACK_COMMON)
     # the rows between the two launches live in the caller's workspace, not in the scratch rows of one update

@@ -4,7 +4,7 @@ HIP calls (the method of tests/test_track_host.py)."""
 import ctypes as C
 import os
 
-from src_scan import ROOT, TRACK_EXECUTOR, assert_launch_only, function_body, read_csrc, strip_comments
+from src_scan import ROOT, TRACK_EXECUTOR, assert_launch_only, function_body, read_csrc, read_host_src, strip_comments
 
 
 def test_track_windows_symbols_are_exported_and_bound(glvlib):
@@ -49,7 +49,7 @@ def test_every_window_is_one_row_in_both_orders(glvlib):
 
 
 def test_track_windows_path_has_no_allocating_or_synchronising_call():
-    src = read_csrc("glv_api.cpp")
+    src = read_host_src()
     assert_launch_only(src, [r"\nint plan_track_windows\(", r"\nint glv_batch_track_windows_s16\(", r"\nuint64_t glv_batch_track_windows_work_bytes\("] + TRACK_EXECUTOR)
     body = strip_comments(function_body(src, r"\nint track_windows\("))
     assert body.count("glv::launch_frame(") == 1 and "IN_S16_TRACK" in body                       # ONE transform launch, in the track input mode
@@ -64,7 +64,7 @@ def test_track_windows_path_has_no_allocating_or_synchronising_call():
 def test_the_two_track_entries_share_their_decisions():
     """state / in16 / out16 / bars and every refusal that is not about hop or pitch are written once (track_chain, track_args) and both plans call them;
     what a call asks of the batch's earlier calls, and the scan, are written once for every entry"""
-    src = strip_comments(read_csrc("glv_api.cpp"))
+    src = strip_comments(read_host_src())
     for sig in (r"\nint plan_track\(", r"\nint plan_track_windows\("):
         body = function_body(src, sig)
         assert "track_args(" in body and "track_chain(" in body, sig
