@@ -176,17 +176,36 @@ double glvo_frame_weight(size_t f, size_t F, int use_window) {
     if (!use_window) return 1.0;
     return 0.6 - (0.4 * cos(GLVO_TWOPI * (double) f / (double) F - 1));
 }
+double glvo_gl_frame_weight(size_t f, size_t F, int use_window);
+/* The weight and the ring slot of frame f do not depend on the bin: both are evaluated once per call (F cosines, not F * sz -- the same
+ * function of the same arguments, so the same doubles), which is what makes F = 64 at sz = 16384 affordable in the tests. */
+#define GLVO_RING_BLOCK 512
+typedef struct { double w; float wf; const float* row; } glvo_ring_frame;
+static glvo_ring_frame* glvo_ring_frames(const float* hist, size_t head, size_t sz, size_t F, int use_window, int gl) {
+    glvo_ring_frame* fr = malloc(sizeof(glvo_ring_frame) * F);
+    for (size_t f = 0; f < F; ++f) {
+        fr[f].w = gl ? glvo_gl_frame_weight(f, F, use_window) : glvo_frame_weight(f, F, use_window);
+        fr[f].wf = (float) fr[f].w;
+        fr[f].row = hist + ((head + 1 + f) % F) * sz;
+    }
+    return fr;
+}
 void glvo_average(float* b, float* hist, size_t* head, size_t sz, size_t F, int use_window) {
     memcpy(hist + (*head) * sz, b, sz * sizeof(float));
-    for (size_t t = 0; t < sz; ++t) {
-        float v = 0.0F;
+    glvo_ring_frame* fr = glvo_ring_frames(hist, *head, sz, F, use_window, 0);
+    /* (bins in blocks, frames outermost inside a block: every bin still adds its frames oldest first, and a frame's row is read in a run) */
+    for (size_t t0 = 0; t0 < sz; t0 += GLVO_RING_BLOCK) {
+        const size_t m = sz - t0 < GLVO_RING_BLOCK ? sz - t0 : GLVO_RING_BLOCK;
+        float v[GLVO_RING_BLOCK];
+        for (size_t i = 0; i < m; ++i) v[i] = 0.0F;
         for (size_t f = 0; f < F; ++f) {
-            size_t slot = (*head + 1 + f) % F;
-            if (use_window) v = (float) ((double) v + glvo_frame_weight(f, F, 1) * (double) hist[slot * sz + t]);
-            else            v = v + (float) 1 * hist[slot * sz + t];
+            const float* row = fr[f].row + t0;
+            if (use_window) for (size_t i = 0; i < m; ++i) v[i] = (float) ((double) v[i] + fr[f].w * (double) row[i]);
+            else            for (size_t i = 0; i < m; ++i) v[i] = v[i] + (float) 1 * row[i];
         }
-        b[t] = v / (float) F;
+        for (size_t i = 0; i < m; ++i) b[t0 + i] = v[i] / (float) F;
     }
+    free(fr);
     *head = (*head + 1) % F;
 }
 
@@ -382,17 +401,21 @@ void glvo_gl_chain_r16(float* row, float* store, float* hist, size_t* head, size
     }
     if (!do_average) return;
     memcpy(hist + (*head) * sz, row, sz * sizeof(float));
-    if (F > 1)
-        for (size_t t = 0; t < sz; ++t) {
-            float v = 0.0F;
+    if (F > 1) {
+        glvo_ring_frame* fr = glvo_ring_frames(hist, *head, sz, F, use_window, 1);
+        for (size_t t0 = 0; t0 < sz; t0 += GLVO_RING_BLOCK) {
+            const size_t m = sz - t0 < GLVO_RING_BLOCK ? sz - t0 : GLVO_RING_BLOCK;
+            float v[GLVO_RING_BLOCK];
+            for (size_t i = 0; i < m; ++i) v[i] = 0.0F;
             for (size_t f = 0; f < F; ++f) {
-                size_t slot = (*head + 1 + f) % F;
-                float w = (float) glvo_gl_frame_weight(f, F, use_window);
-                float p = (use_window && F != 2) ? w * hist[slot * sz + t] : hist[slot * sz + t];
-                v = v + p;
+                const float* slot = fr[f].row + t0;
+                if (use_window && F != 2) for (size_t i = 0; i < m; ++i) { float p = fr[f].wf * slot[i]; v[i] = v[i] + p; }
+                else                      for (size_t i = 0; i < m; ++i) v[i] = v[i] + slot[i];
             }
-            row[t] = glvo_q16(v / (float) F);
+            for (size_t i = 0; i < m; ++i) row[t0 + i] = glvo_q16(v[i] / (float) F);
         }
+        free(fr);
+    }
     *head = (*head + 1) % F;
 }
 

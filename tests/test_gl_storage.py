@@ -72,7 +72,8 @@ def test_gravity_step_on_texels_is_an_integer_subtraction(emu):
 
 
 @pytest.mark.parametrize("log_e", [4, 3, 5])
-@pytest.mark.parametrize("n,F,win", [(512, 5, True), (1024, 6, False), (2048, 2, True), (4096, 5, True), (1024, 1, True), (16384, 3, True)])
+@pytest.mark.parametrize("n,F,win", [(512, 5, True), (1024, 6, False), (2048, 2, True), (4096, 5, True), (1024, 1, True), (16384, 3, True),
+                                     (512, 7, True), (512, 64, True), (1024, 63, False)])       # the last entries of the 64 weights; an odd count (tests/test_frame_count.py)
 def test_emulated_fused_gl_chain_equals_the_oracle_model(emu, n, F, win, log_e):
     """The fused GL_R16 epilogue (glv_frame.h epilogue_gl16 / gl16_state_block: upload quantisation, GL_MAX + gravity, ring,
     average on uint16 state inside the transform's kernel) walked lane by lane on the host, from s16 PCM, against the oracle's
@@ -140,7 +141,7 @@ def test_texel_readback_division_every_texel(emu):
 
 
 @pytest.mark.parametrize("gl", [1, 2])
-@pytest.mark.parametrize("F,win", [(5, True), (6, False), (2, True), (1, True)])
+@pytest.mark.parametrize("F,win", [(5, True), (6, False), (2, True), (1, True), (7, True), (64, True), (63, False)])
 def test_host_twin_equals_the_oracle_model(emu, F, win, gl):
     """gl 2: the state as floats c / 65535 (the pass-by-pass form); gl 1: the same state as uint16 texels (what the fused
     kernel keeps) -- identical outputs, and the texel arrays ARE the float arrays' texels"""
