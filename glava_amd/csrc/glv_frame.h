@@ -22,7 +22,8 @@
 namespace glv {
 
 enum InMode { IN_S16_STEREO = 0, IN_F32_PLANAR = 1, IN_S16_RING = 2, IN_F32_STEREO = 3, IN_F32_RING = 4,
-              IN_S16_TRACK = 5 };    // s16 windows cut out of [streams][pitch_frames][2] recordings where they lie (TrackWindows; never a ring)
+              IN_S16_TRACK = 5,      // s16 windows cut out of [streams][pitch_frames][2] recordings where they lie (TrackWindows; never a ring)
+              IN_F32_TRACK = 6 };    // the same for interleaved stereo f32 recordings, 8 bytes per frame (glv_batch_track_windows_f32)
 enum Epi { EPI_RAW = 0, EPI_MAG = 1, EPI_MAG_STATE = 2, EPI_RAW_STATE = 3 };
 
 // ops bits as in include/glv_spectrum.h
@@ -96,9 +97,9 @@ GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, u
     return (ops & OP_R16) ? FC_R16 : FC_PLAIN;
 }
 
-// IN_S16_TRACK (glv_batch_track_windows_s16): where the windows of a launch lie and where their rows go.  The kernel enumerates frames stream-major,
+// IN_S16_TRACK / IN_F32_TRACK (glv_batch_track_windows_s16 / _f32): where the windows of a launch lie and where their rows go.  The kernel enumerates frames stream-major,
 // f = s * steps + t -- neighbouring slots and workgroups then hold overlapping windows of ONE stream at the same moment and the overlap meets in L1 / L2 --
-// and frame f reads the n stereo frames from s * pitch_frames + t * hop on (64-bit arithmetic).  Its two channel rows go to row 2 f + ch (stream-major:
+// and frame f reads the n stereo frames (4 bytes each as s16, 8 as f32) from s * pitch_frames + t * hop on (64-bit arithmetic).  Its two channel rows go to row 2 f + ch (stream-major:
 // what glv_track_scan_kernel reads with log_q = 0, hops_per_pitch = steps) or to row (t * streams + s) * 2 + ch (step_major: what d_out and the bars pass take).
 struct TrackWindows {
     uint64_t pitch_frames, hop;
@@ -160,7 +161,7 @@ struct FrameArgs {
                                 // (kernel classes FC_GL16_SNAP*: bar_w holds the uint32 weights W' of bar_snap_lane_sum as float bits)
     const ColumnMap* col_map;   // kernel classes FC_GL16_COLS* (glv_batch_set_column_texels): [bars] columns, bars_out float [units][bars]; the work
                                 // lists cover the DISTINCT texels the columns read and BarItem::res indexes those
-    TrackWindows trk;           // IN_S16_TRACK kernels only (units = 2 * streams * steps), as `rot` serves the ring kinds; appended: every field above keeps its offset
+    TrackWindows trk;           // IN_S16_TRACK / IN_F32_TRACK kernels only (units = 2 * streams * steps), as `rot` serves the ring kinds; appended: every field above keeps its offset
 };
 
 // ---- GLV_OP_BARS arithmetic (smooth.glsl:25-40; tex clamped to [0,1] like the GL_R16 texture the
@@ -891,7 +892,8 @@ struct Frame {
     // channels (L[2c], R[2c], L[2c+1], R[2c+1]); mono = (L + R) / 2 in float (pulse_input.c:167)
     struct alignas(16) f4 { float a, b, c, d; };
     // RING: the frame is a circular buffer whose oldest complex point sits at `rot` (glv_batch_ring_update_f32)
-    template <bool RING = false>
+    // HALVES: complex point c as its two frames (2c, 2c + 1), 8 bytes each and naturally aligned, of a frame that starts 8-byte aligned and no more
+    template <bool RING = false, bool HALVES = false>
     GLV_HD static void load_f32_stereo_window(cf (&v)[E], const void* frame, const void* win, int tid, uint32_t ch, bool mono,
                                               uint32_t rot = 0) {
 #pragma unroll
@@ -901,6 +903,10 @@ struct Frame {
                 const uint32_t f0 = (uint32_t) (2 * (i * T + tid)) + rot;
                 const cf lo = ld<cf>(frame, (f0 & (uint32_t) (N - 1)) * 8u), hi = ld<cf>(frame, ((f0 + 1u) & (uint32_t) (N - 1)) * 8u);
                 u.a = lo.x; u.b = lo.y; u.c = hi.x; u.d = hi.y;
+            } else if constexpr (HALVES) {
+                const uint32_t poff = (uint32_t) tid * 16u + (uint32_t) (i * T) * 16u;
+                const cf lo = ld<cf>(frame, poff), hi = ld<cf>(frame, poff + 8u);
+                u.a = lo.x; u.b = lo.y; u.c = hi.x; u.d = hi.y;
             } else u = ld<f4>(frame, (uint32_t) tid * 16u + (uint32_t) (i * T) * 16u);
             const d2 w = ld<d2>(win, (uint32_t) tid * 16u + (uint32_t) (i * T) * 16u);
             float s0, s1;
@@ -909,6 +915,15 @@ struct Frame {
             v[i].x = apply_window(s0, w.x);
             v[i].y = apply_window(s1, w.y);
         }
+    }
+
+    // IN_F32_TRACK: a window starts at ANY frame of a recording, so its first byte is 8-byte aligned and no more.  One whose first byte is 16-byte aligned
+    // takes the 16-byte loads of a back-to-back frame; any other takes complex point c as its two naturally aligned 8-byte frames (HALVES), as load_pcm_at
+    // chooses for s16.  The choice is per window: uniform where a wave never straddles two slots (T % 64 == 0), a divergent branch at N = 256 / 512.
+    // Either way the lane reads bytes [16 c, 16 c + 16) of the window, c < NN: exactly the window's n frames.
+    GLV_HD static void load_f32_stereo_window_at(cf (&v)[E], const void* window, const void* win, int tid, uint32_t ch, bool mono) {
+        if ((reinterpret_cast<uintptr_t>(window) & 15u) == 0u) load_f32_stereo_window<false, false>(v, window, win, tid, ch, mono);
+        else load_f32_stereo_window<false, true>(v, window, win, tid, ch, mono);
     }
 
     // interleaved stereo f32, one channel of complex point i*T + tid: floats 4c + ch and 4c + 2 + ch of the

@@ -38,7 +38,7 @@ inline bool same_shape(const glv_params& a, const glv_params& b) {
            && same_bits(a.sample_scale, b.sample_scale) && same_bits(a.sample_range, b.sample_range);
 }
 
-constexpr int kOpsClasses = 7, kInKinds = 6;     // wisdom classes (wisdom_class): glv::FrameClass 0..6
+constexpr int kOpsClasses = 7, kInKinds = 7;     // wisdom classes (wisdom_class): glv::FrameClass 0..6
 constexpr int kMaxVariants = 4;
 // glv_batch_track_wave_s16, bars in one launch: a workgroup's rows are consecutive output rows (false) or consecutive steps of one channel row (true).
 // profiles/r11/track_wave.txt (N = 4096, hop 256, ms by rows / by steps): 1 stream x 2048 steps 0.066 / 0.048, 8 streams 0.207 / 0.178, 64 streams 1.38 / 1.43,

@@ -205,6 +205,7 @@ glv_frame_kernel(const FrameArgs a) {
     constexpr int T = FR::T, N = FR::N;
     constexpr bool RING = IN_MODE == IN_S16_RING;
     constexpr bool TRACK = IN_MODE == IN_S16_TRACK;    // windows where they lie in a recording (a.trk): never a ring, stateless classes only (launch_variant)
+    constexpr bool TRACKF = IN_MODE == IN_F32_TRACK;   // the same over interleaved stereo f32 recordings: the f32 stereo pipeline and generic loop, another address per frame
     constexpr bool S16 = IN_MODE == IN_S16_STEREO || RING || TRACK;
     constexpr bool WSPLIT = S16 && win_split_of(LOG_NN, STATEFUL);     // s16 samples: the window product without fp64 (glv_core.h apply_window_split)
     // f32 rows may hold -0.0, Inf and NaN: no unit-twiddle shortcut, non-finite values through the bit-faithful log
@@ -439,16 +440,18 @@ glv_frame_kernel(const FrameArgs a) {
         return r < a.units ? r : a.units - 1;
     };
 
-    // IN_S16_TRACK: where frame f = s * steps + t of the launch begins and where its channel-0 row goes (glv_frame.h TrackWindows).  One 32-bit division per
-    // call, on a value that is wave-uniform wherever `slot` is (WAVE_SLOT); the window's start in 64-bit arithmetic.
+    // IN_S16_TRACK / IN_F32_TRACK: where frame f = s * steps + t of the launch begins and where its channel-0 row goes (glv_frame.h TrackWindows).  One 32-bit
+    // division per call, on a value that is wave-uniform wherever `slot` is (WAVE_SLOT); the window's start in 64-bit arithmetic, 4 or 8 bytes per frame.
     // Bounded reads: every caller passes f < units / 2 = streams * steps (frame_of / row_of clamp an idle slot and the look-ahead of a slot's last frame to
     // the LAST frame, as they do for back-to-back frames), so s < streams and t < steps: the address is the start of a window the call names, and
     // load_pcm_at reads that window's n frames and not a byte more.  No launch reads outside the windows [s * pitch + t * hop, + n) of the call.
+    // IN_F32_TRACK: the same f, so the same windows; load_f32s_raw (pipelined: dwords at 16 c + 4 ch and 16 c + 8 + 4 ch, c < NN, ch < 2) and
+    // load_f32_stereo_window_at (generic loop: bytes [16 c, 16 c + 16), c < NN) both stay inside the window's 8 n bytes.
     struct TrackAt { const void* win; size_t row0; };
     auto track_at = [&](uint32_t f) -> TrackAt {
         const uint32_t s = f / a.trk.steps, t = f - s * a.trk.steps;
         const uint64_t start = (uint64_t) s * a.trk.pitch_frames + (uint64_t) t * a.trk.hop;
-        return { static_cast<const char*>(a.in) + start * 4u, a.trk.step_major ? ((size_t) t * a.trk.streams + s) * 2u : (size_t) f * 2u };
+        return { static_cast<const char*>(a.in) + start * (TRACKF ? 8u : 4u), a.trk.step_major ? ((size_t) t * a.trk.streams + s) * 2u : (size_t) f * 2u };
     };
     (void) track_at;
 
@@ -556,7 +559,7 @@ glv_frame_kernel(const FrameArgs a) {
         }
         return;
     }
-    constexpr bool F32S = IN_MODE == IN_F32_STEREO || IN_MODE == IN_F32_RING;
+    constexpr bool F32S = IN_MODE == IN_F32_STEREO || IN_MODE == IN_F32_RING || TRACKF;
     constexpr bool RINGF = IN_MODE == IN_F32_RING;
     if constexpr (F32S && PREFETCH == 1 && LOG_E <= 4) {
         // interleaved stereo f32 (PulseAudio), stereo only (the rare mono mix takes the generic loop below): one
@@ -573,9 +576,13 @@ glv_frame_kernel(const FrameArgs a) {
             auto frame_ptr = [&](uint32_t f) -> const void* { return static_cast<const char*>(a.in) + (size_t) f * ((size_t) N * 8); };
             cf v[E];
             typename FR::RawF raw;
+            size_t trow = 0, trow_next = 0;      // TRACKF: channel-0 row of the slot's current frame / of the frame whose channel-0 samples `raw` holds or held last
+            (void) trow; (void) trow_next; (void) frame_ptr;
             if (blockIdx.x * SLOTS < nframes) {
                 int tid = tid_outer;
                 asm volatile("" : "+v"(tid));
+                if constexpr (TRACKF) { const TrackAt w = track_at(frame_of(0)); FR::template load_f32s_raw<false>(raw, w.win, tid, 0u); trow = w.row0; }
+                else
                 FR::template load_f32s_raw<RINGF>(raw, frame_ptr(frame_of(0)), tid, 0u, a.rot);
                 FR::window_f32_raw(v, raw, win, tid);
             }
@@ -587,11 +594,18 @@ glv_frame_kernel(const FrameArgs a) {
                 asm volatile("" : "+v"(tid));
                 const bool active = blockIdx.x * SLOTS + m * fstride + slot < nframes;
                 const uint32_t f = frame_of(m);
+                if constexpr (TRACKF) {                                                              // A (unconditional): ch 0 fetches its own window's other channel
+                    const TrackAt w = track_at(frame_of(m + ch));
+                    FR::template load_f32s_raw<false>(raw, w.win, tid, ch ^ 1u);
+                    if (ch) trow_next = w.row0;
+                } else
                 FR::template load_f32s_raw<RINGF>(raw, frame_ptr(frame_of(m + ch)), tid, ch ^ 1u, a.rot);   // A (unconditional)
                 GLV_SCHED_FENCE();
                 BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);                // B
                 GLV_SCHED_FENCE();
                 __builtin_amdgcn_s_waitcnt(0x0F70);                                              // W
+                if constexpr (TRACKF) { finish_row(v, trow + ch, tid, active); if (ch) trow = trow_next; }   // D
+                else
                 finish_row(v, (size_t) f * 2 + ch, tid, active);                                 // D
                 GLV_SCHED_FENCE();
                 FR::window_f32_raw(v, raw, win, tid);                                            // C
@@ -617,6 +631,14 @@ glv_frame_kernel(const FrameArgs a) {
             FR::load_pcm_at(raw, w.win, tid);
             GLV_SCHED_FENCE();
             FR::template unpack_window<0, WSPLIT>(v, raw, win, tid, row & 1u, a.mono != 0);
+            BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
+            finish_row(v, w.row0 + (row & 1u), tid, active);
+            continue;
+        } else
+        if constexpr (TRACKF) {
+            // mono at every size, every chain where the configuration is not pipelined for f32 (LOG_E 5): one slot = one channel row of the window its frame names
+            const TrackAt w = track_at(row >> 1);
+            FR::load_f32_stereo_window_at(v, w.win, win, tid, row & 1u, a.mono != 0);
             BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
             finish_row(v, w.row0 + (row & 1u), tid, active);
             continue;
@@ -676,8 +698,8 @@ hipError_t launch_variant(FrameClass cls, const FrameArgs& a, int grid, hipStrea
     // region (NBUF 1); the GL_R16 chain is built for log modes 0 and 1
     auto launch_class = [&](auto c) -> hipError_t {
         constexpr int C = decltype(c)::value;
-        // (IN_S16_TRACK: a track call's transform is always stateless -- the other twelve classes are not instantiated for it)
-        if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2) || (IN_MODE == IN_S16_TRACK && fc_has_state(C))) return hipErrorInvalidValue;
+        // (IN_S16_TRACK / IN_F32_TRACK: a track call's transform is always stateless -- the other twelve classes are not instantiated for them)
+        if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2) || ((IN_MODE == IN_S16_TRACK || IN_MODE == IN_F32_TRACK) && fc_has_state(C))) return hipErrorInvalidValue;
         else if constexpr (fc_has_state(C))
             return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE_S>, done[C]);
         else return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TWREG, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE>, done[C]);

@@ -45,7 +45,7 @@ struct TrackGeometry {
     uint32_t out_texels;       // results as GL_R16 texels (uint16 rows) instead of floats
 };
 hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool rows_texels, hipStream_t st);
-// Where the windows of the s16 sources of GLV_OP_WAVE lie (glv_wave_kernel, glv_bars_rows_i8_kernel).  A process call's windows lie back to back -- the
+// Where the windows of the track sources of GLV_OP_WAVE lie (glv_wave_kernel, glv_bars_rows_i8_kernel).  A process call's windows lie back to back -- the
 // identity geometry, which those kernels' existing kinds have built in and never read from here.  A track call (glv_batch_track_wave_s16) cuts them
 // out of [streams][pitch_frames][2] recordings: output row r = t * units + 2 s + c is channel c of the n frames from s * pitch_frames + t * hop on,
 // in 64-bit arithmetic.  by_steps (the one-launch form): a workgroup of the bars kernel takes RB consecutive steps of ONE channel row, whose windows
@@ -94,8 +94,9 @@ hipError_t launch_bars_i8_pcm(const void* pcm, uint32_t rot, bool mono, void* ba
 // first `limit` samples (a multiple of 8) of every row; out rows keep a pitch of n.  in_mode: glv_frame.h InMode; units: channel rows
 hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint32_t rot, size_t units, void* out, bool r16, uint32_t limit, hipStream_t st);
 // ... and both over every window of a track call (interleaved s16 recordings, any window start): out / bars_out hold w.steps * w.units rows, step-major.
+// launch_wave_track with f32: the recordings are interleaved stereo floats, 8 bytes per frame (pcm 8-byte aligned).
 // launch_bars_i8_pcm_track needs window starts on groups of 8 frames (pcm 32-byte aligned, hop and pitch multiples of 8) and refuses others
-hipError_t launch_wave_track(const void* pcm, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st);
+hipError_t launch_wave_track(const void* pcm, bool f32, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st);
 hipError_t launch_bars_i8_pcm_track(const void* pcm, const WaveWindows& w, bool mono, void* bars_out, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st,
                                     bool r16);
 // bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels) over texel rows: uint16, or floats c / 65535 (rows_f32); one lane per bar and row

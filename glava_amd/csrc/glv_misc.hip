@@ -206,6 +206,9 @@ typedef unsigned int glv_wave_u4 __attribute__((ext_vector_type(4)));
 // KIND 3 (glv_batch_track_wave_s16): KIND 0's arithmetic over every window of a track call -- `s` counts windows, step-major (window t * streams + stream),
 // whose frames start at stream * pitch_frames + t * hop of the recordings (WaveWindows; the other kinds never read it).  A window starts at any frame:
 // frames are dwords, so a group whose first frame is not 16-byte aligned takes its 8 frames one naturally aligned dword at a time.
+// KIND 4 (glv_batch_track_wave_f32): KIND 1's unpack over the same windows of float recordings, 8 bytes per frame.  A group's first frame is 8-byte
+// aligned and no more: 16-byte aligned it takes KIND 1's four 16-byte loads, otherwise its 8 frames one naturally aligned 8-byte load at a time.
+// Bounded reads (KIND 3 and 4): s < steps * streams and t + 8 <= limit <= n, so a lane reads frames [t, t + 8) of a window the call names and no others.
 template <int KIND, bool R16>
 __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ in, void* __restrict__ out, size_t groups_total, uint32_t n, uint32_t limit,
                                                        uint32_t rot, int mono, const WaveWindows w) {
@@ -257,6 +260,28 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
                 if (mono) { l[q] = unpack_s16_mono(a, b); r[q] = l[q]; } else { l[q] = unpack_s16(a); r[q] = unpack_s16(b); }
             }
             emit(2 * s, t, l);                                           // (row t' * units + 2 stream + c = 2 s + c)
+            emit(2 * s + 1, t, r);
+        } else if constexpr (KIND == 4) {
+            const uint32_t streams = w.units / 2u;
+            const uint64_t first = (uint64_t) (s % streams) * w.pitch_frames + (uint64_t) (s / streams) * w.hop + t;      // the group's first frame
+            const cf* src = static_cast<const cf*>(in) + first;
+            cf f[8];
+            if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q) {
+                    const BarW4 a = ld<BarW4>(src, q * 16u);
+                    f[2 * q] = cf{a.w[0], a.w[1]}; f[2 * q + 1] = cf{a.w[2], a.w[3]};
+                }
+            } else {
+#pragma unroll
+                for (uint32_t q = 0; q < 8; ++q) f[q] = src[q];
+            }
+            float l[8], r[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                if (mono) { l[q] = (f[q].x + f[q].y) / 2; r[q] = l[q]; } else { l[q] = f[q].x; r[q] = f[q].y; }     // pulse_input.c:167
+            }
+            emit(2 * s, t, l);
             emit(2 * s + 1, t, r);
         } else {
             float l[8], r[8];
@@ -545,10 +570,15 @@ hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint3
 #undef GLV_WAVE_LAUNCH
     return hipGetLastError();
 }
-hipError_t launch_wave_track(const void* pcm, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st) {
+hipError_t launch_wave_track(const void* pcm, bool f32, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st) {
     if (limit == 0 || limit > n || (limit & 7u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || w.hop == 0) return hipErrorInvalidValue;
     const size_t total = (size_t) w.steps * (w.units / 2u) * (limit / 8u);
     const unsigned grid = grid_256(total);
+    if (f32) {
+        if (r16) hipLaunchKernelGGL((glv_wave_kernel<4, true>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);
+        else hipLaunchKernelGGL((glv_wave_kernel<4, false>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);
+        return hipGetLastError();
+    }
     if (r16) hipLaunchKernelGGL((glv_wave_kernel<3, true>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);
     else hipLaunchKernelGGL((glv_wave_kernel<3, false>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);
     return hipGetLastError();

@@ -4,11 +4,12 @@
 #include "glv_tables.h"       // kBarSeqMin
 
 namespace {
-// ---- track mode: `steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16, glv_batch_track_windows_s16) ------------
+// ---- track mode: `steps` consecutive updates of every stream from one long buffer (glv_batch_track_s16, glv_batch_track_windows_s16 / _f32) -----
 // One executor (`track`) carries out a TrackPlan in three stages, kernels only.  (1) The transform, with the stateless frame kernels as they are, in
 // one of two forms.  Residues (plan_track: hop a power of two, track_residues): the whole [streams * pitch] frame sequence is cut into
 // back-to-back windows of n frames q = n / hop times, launch r starting r * hop frames in -- window t of stream s, which starts at a multiple h of
-// hop, is row h / q of launch h % q.  Windows (plan_track_windows: any hop, track_windows): ONE launch in the kernel's IN_S16_TRACK mode over
+// hop, is row h / q of launch h % q.  Windows (plan_track_windows: any hop, track_windows): ONE launch in the kernel's IN_S16_TRACK mode -- IN_F32_TRACK
+// for a float recording (TrackPlan::f32, the one thing the float entry adds: every stage after the transform sees rows, not samples) -- over
 // the steps * streams windows the call names, each read where it lies (glv_frame.h TrackWindows) -- rows step-major straight into d_out (a stateless
 // chain without bars: nothing else runs), step-major into the workspace (stateless with bars), or stream-major into the workspace for the scan, whose
 // geometry with one residue (log_q = 0) and hops_per_pitch = steps IS [stream][step][channel].  Either way the rows are texels where the chain's
@@ -20,6 +21,7 @@ struct TrackPlan {
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
     uint64_t k0 = 0;                    // windows of launch 0 (launch r: (frames - r * hop) / n, k0 or k0 - 1)
     bool windows = false;               // stage (1) is the one launch over the windows where they lie, else the q residue launches
+    bool f32 = false;                   // the recording is interleaved stereo f32 (8 bytes per frame), else s16; set by the entry, windows form only
     bool to_out = false;                // stage (1) writes d_out and nothing else runs, else it writes the start of the workspace
     bool scan = false;                  // stage (2) runs: the chain keeps state, or stage (1) left residues (which only the scan puts in step order)
     uint32_t hops_per_pitch = 0, residue_rows = 0;   // TrackGeometry, with log_q: where the scan finds window t of stream s among stage (1)'s rows
@@ -90,7 +92,7 @@ int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t
     tp.work_bytes = tp.rows_bytes + ((ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
     return GLV_OK;
 }
-// glv_batch_track_windows_s16: any hop >= 1, any pitch that holds the windows.  One transform launch over exactly the windows asked for, so its region of the
+// glv_batch_track_windows_s16 / _f32: any hop >= 1, any pitch that holds the windows.  One transform launch over exactly the windows asked for, so its region of the
 // workspace is steps * streams * 2 rows; a stateless chain without bars writes d_out directly and needs none (256: 0 stays "refused").  The scan's region
 // exists where a scan runs AND bars follow it.
 int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
@@ -107,8 +109,9 @@ int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, 
     return GLV_OK;
 }
 
-int refuse_track_pointers(const void* d_pcm, const void* d_out, const void* d_work) {
+int refuse_track_pointers(const void* d_pcm, bool f32, const void* d_out, const void* d_work) {
     if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (f32 && (reinterpret_cast<uintptr_t>(d_pcm) & 7u)) return fail(GLV_ERR_INVALID, "d_pcm must be aligned like a float frame: 8 bytes");
     if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
     return GLV_OK;
 }
@@ -131,14 +134,15 @@ int track_residues(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::Fr
     return GLV_OK;
 }
 // (1) as windows: every window of the call where it lies, one launch, into `rows`
-int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::FrameClass cls, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps,
+int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::FrameClass cls, const void* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps,
                         float* rows, hipStream_t st) {
     a.in = d_pcm; a.out = rows; a.units = (uint32_t) tp.out_rows;
     a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
+    const int mode = tp.f32 ? glv::IN_F32_TRACK : glv::IN_S16_TRACK;
     int variant = 0, grid = 0;
-    launch_plan(b, a.units, glv::IN_S16_TRACK, a.ops, &variant, &grid);
+    launch_plan(b, a.units, mode, a.ops, &variant, &grid);
     b->last_grid = grid; b->last_variant = variant;
-    const hipError_t e = glv::launch_frame(b->log_nn, glv::IN_S16_TRACK, (int) b->p.log_mode, variant, cls, a, grid, st); ++b->last_launches;
+    const hipError_t e = glv::launch_frame(b->log_nn, mode, (int) b->p.log_mode, variant, cls, a, grid, st); ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     b->kernel_name = "glv_frame_kernel";
     return GLV_OK;
@@ -160,8 +164,8 @@ int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t st
     return GLV_OK;
 }
 // Carries a plan out: what the plan could not know (the pointers, what the batch did before), then the stages.  A refused call leaves the batch untouched.
-int track(glv_batch* b, const TrackPlan& tp, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
-    if (int rc = refuse_track_pointers(d_pcm, d_out, d_work)) return rc;
+int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (int rc = refuse_track_pointers(d_pcm, tp.f32, d_out, d_work)) return rc;
     if (int rc = refuse_gravity_mix(b, ops)) return rc;
     if (int rc = refuse_stale_tilt(b)) return rc;
     b->last_launches = 0;
@@ -175,7 +179,7 @@ int track(glv_batch* b, const TrackPlan& tp, const int16_t* d_pcm, uint32_t pitc
     a.ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u); a.log_mode = b->p.log_mode;
     const glv::FrameClass cls = glv::frame_class(false, false, false, a.ops);
     if (int rc = tp.windows ? track_windows(b, tp, a, cls, d_pcm, pitch_frames, hop, steps, tp.to_out ? out : reinterpret_cast<float*>(work), st)
-                            : track_residues(b, tp, a, cls, d_pcm, hop, work, st)) return rc;
+                            : track_residues(b, tp, a, cls, static_cast<const int16_t*>(d_pcm), hop, work, st)) return rc;
     ChainPlan pl;
     pl.bars = tp.bars;
     pl.rows = reinterpret_cast<float*>(work + (tp.scan ? tp.rows_bytes : 0u));       // what the bars read: the scan's results, or a stateless transform's rows
@@ -185,15 +189,16 @@ int track(glv_batch* b, const TrackPlan& tp, const int16_t* d_pcm, uint32_t pitc
     return timed_launch_end(b, st);
 }
 
-// ---- track mode for the wave module: the texture of every update of a recording in one call (glv_batch_track_wave_s16) -------------
+// ---- track mode for the wave module: the texture of every update of a recording in one call (glv_batch_track_wave_s16 / _f32) ------
 // GLV_OP_WAVE is stateless and transforms nothing: a call is plan_wave's one or two launches over steps * streams * 2 rows instead of streams * 2,
 // the kernels' windows cut out of the recordings by glv::WaveWindows.  The bars arithmetic, what the waveform kernel writes and how much of a row are
 // plan_wave's own choices (track and process cannot disagree); the rows between two launches live in the caller's workspace, not in the scratch rows
 // (sized for one update).
 struct TrackWavePlan {
+    bool f32 = false;               // the recording is interleaved stereo f32, else s16; set before the plan is made (the sizing query's is s16: the same bytes)
     ChainPlan pl;                   // the one or two launches of windows that start at any frame
     bool one_launch = false;        // with bars: plan_wave fuses where hop and pitch keep every window on a group of 8 frames -- of a 32-byte aligned d_pcm, which
-                                    // only the call sees: on any other it runs `pl`
+                                    // only the call sees: on any other it runs `pl`.  Never from floats: the integer pass reads s16 frames, as in a process call
     uint64_t rows = 0;              // steps * streams * 2
     uint64_t work_bytes = 256;      // (without bars there is no second launch and nothing to park: the convention keeps 0 for "refused")
 };
@@ -213,19 +218,21 @@ int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uin
     if (int rc = check_ops(b, ops, &some_output)) return rc;
     // The sizing query does not see d_pcm, so with bars the workspace is always what the two launches need: plan_wave is asked twice, for windows that
     // start anywhere (the plan every call can fall back on) and for this call's hop and pitch.
-    if (int rc = plan_wave(b, glv::IN_S16_STEREO, ops, 0, nullptr, tp.pl, false)) return rc;
+    const int in_mode = tp.f32 ? glv::IN_F32_STEREO : glv::IN_S16_STEREO;
+    if (int rc = plan_wave(b, in_mode, ops, 0, nullptr, tp.pl, false)) return rc;
     if (ops & GLV_OP_BARS) {
         ChainPlan grouped;
-        if (int rc = plan_wave(b, glv::IN_S16_STEREO, ops, 0, nullptr, grouped, hop % 8u == 0u && pitch_frames % 8u == 0u)) return rc;
+        if (int rc = plan_wave(b, in_mode, ops, 0, nullptr, grouped, hop % 8u == 0u && pitch_frames % 8u == 0u)) return rc;
         tp.one_launch = grouped.wave_fused;
         tp.work_bytes = up256(tp.rows * n * (tp.pl.wave_r16 ? 2u : 4u));
     }
     return GLV_OK;
 }
 
-int track_wave(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
-    if (int rc = refuse_track_pointers(d_pcm, d_out, d_work)) return rc;
+int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (int rc = refuse_track_pointers(d_pcm, f32, d_out, d_work)) return rc;
     TrackWavePlan tp;
+    tp.f32 = f32;
     if (int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) return rc;
     ChainPlan& pl = tp.pl;
     const bool fused = tp.one_launch && (reinterpret_cast<uintptr_t>(d_pcm) & 31u) == 0u;
@@ -245,7 +252,7 @@ int track_wave(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32
     } else {
         if (ops & GLV_OP_BARS) pl.out = pl.rows = static_cast<float*>(d_work);
         else pl.out = static_cast<float*>(d_out);
-        e = glv::launch_wave_track(d_pcm, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
+        e = glv::launch_wave_track(d_pcm, f32, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
         b->kernel_name = "glv_wave_kernel";
     }
     ++b->last_launches;
@@ -281,6 +288,7 @@ int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frame
     return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
+// (the workspace holds the transform's rows and the scan's: neither depends on the recording's type, one query for glv_batch_track_windows_s16 and _f32)
 uint64_t glv_batch_track_windows_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
     return planned_work_bytes(b, plan_track_windows, pitch_frames, hop, steps, ops);
 }
@@ -293,6 +301,7 @@ int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pit
     return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
+// (the rows between the two launches are texels or floats of the waveform, whatever the recording's type: one query for glv_batch_track_wave_s16 and _f32)
 uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
     return planned_work_bytes(b, plan_track_wave, pitch_frames, hop, steps, ops);
 }
@@ -300,6 +309,21 @@ uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_fram
 int glv_batch_track_wave_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                              unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    return track_wave(b, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+    return track_wave(b, d_pcm, false, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_windows_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    TrackPlan tp;
+    if (int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    tp.f32 = true;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_wave_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    return track_wave(b, d_pcm, true, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 }  // extern "C"

@@ -11,7 +11,7 @@
 #ifndef GLV_TUNE_LOG_NN
 #define GLV_TUNE_LOG_NN 11
 #endif
-#ifndef GLV_TUNE_IN_MODE          // -DGLV_TUNE_IN_MODE=IN_S16_TRACK: the variants' kernels for a track call's windows (tools/isa_compile.sh: registers, scratch)
+#ifndef GLV_TUNE_IN_MODE          // -DGLV_TUNE_IN_MODE=IN_S16_TRACK / IN_F32_TRACK: the variants' kernels for a track call's windows (tools/isa_compile.sh: registers, scratch)
 #define GLV_TUNE_IN_MODE IN_S16_STEREO
 #endif
 

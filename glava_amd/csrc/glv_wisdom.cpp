@@ -124,6 +124,8 @@ void launch_plan(glv_batch* b, uint32_t units, int in_mode, unsigned ops, int* v
             // glv_batch_autotune measures) serves it until an entry of its own exists
             // (... and a track call's windows run it with another address per frame: glv::IN_S16_TRACK)
             if (!pc.hit && (in_mode == glv::IN_S16_RING || in_mode == glv::IN_S16_TRACK)) pc.hit = wisdom_lookup(wisdom_key(b, glv::IN_S16_STEREO, ops), &pc.variant, &pc.grid);
+            // (... and those of a float recording, glv::IN_F32_TRACK, the interleaved f32 frames' kernel)
+            if (!pc.hit && in_mode == glv::IN_F32_TRACK) pc.hit = wisdom_lookup(wisdom_key(b, glv::IN_F32_STEREO, ops), &pc.variant, &pc.grid);
             pc.gen = gen;
         }
         if (pc.hit) { v = pc.variant; g = pc.grid; }

@@ -148,6 +148,8 @@ def _bind_track_pair(L, form: str) -> None:
     query.argtypes = [vp, u32, u32, u32, C.c_uint]
     query.restype = C.c_uint64
     getattr(L, f"glv_batch_{form}_s16").argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint, vp]
+    if hasattr(L, f"glv_batch_{form}_f32"):         # the float twin (track_windows, track_wave), sized by the same query
+        getattr(L, f"glv_batch_{form}_f32").argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint, vp]
 
 
 def _check(rc: int) -> None:
@@ -236,9 +238,9 @@ class Batch:
             raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)
         return nbytes
 
-    def _track_call(self, form: str, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None) -> None:
-        """glv_batch_<form>_s16"""
-        _check(getattr(lib(), f"glv_batch_{form}_s16")(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+    def _track_call(self, form: str, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None, kind: str = "s16") -> None:
+        """glv_batch_<form>_<kind>"""
+        _check(getattr(lib(), f"glv_batch_{form}_{kind}")(self._h, _ptr(d_pcm), pitch_frames, hop, steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
 
     def track_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_s16 needs for these arguments (glv_batch_track_work_bytes); raises on arguments the call refuses"""
@@ -261,6 +263,12 @@ class Batch:
         the sequential calls; stream-ordered, kernels only."""
         self._track_call("track_windows", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream)
 
+    def track_windows_f32(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_windows_s16 from a float recording (glv_batch_track_windows_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte
+        aligned; any hop >= 1; d_work at least track_windows_work_bytes(...) bytes (the same query), 256-byte aligned.  Output and state bit for bit
+        those of `steps` process_f32_stereo calls on the windows; stream-ordered, kernels only."""
+        self._track_call("track_windows", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream, "f32")
+
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on
         arguments the call refuses"""
@@ -272,6 +280,12 @@ class Batch:
         step-major, step t bit for bit what process_s16 on window t would have written; d_work at least track_wave_work_bytes(...) bytes, 256-byte
         aligned.  Stateless; stream-ordered, kernels only."""
         self._track_call("track_wave", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream)
+
+    def track_wave_f32(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_wave_s16 from a float recording (glv_batch_track_wave_f32): d_pcm float32 [streams][pitch_frames][2], 8-byte aligned; step t bit for
+        bit what process_f32_stereo on window t would have written; d_work at least track_wave_work_bytes(...) bytes (the same query).  With OP_BARS
+        always two launches."""
+        self._track_call("track_wave", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream, "f32")
 
     def ring_update_s16(self, d_new, new_frames: int, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         _check(lib().glv_batch_ring_update_s16(self._h, _ptr(d_new), new_frames, _ptr(d_out), ops, _ptr(stream)))

@@ -424,7 +424,7 @@ int glv_batch_track_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frame
  *   2.54 against 2.75, 5.19 against 6.65 (1.28 x), 7.65 against 10.6 (1.39 x), with 8 against 12.5 GiB of workspace at 1024 streams.
  * Which entry for a power-of-two hop: this one, at every stream count measured (1 to 1024) -- it was behind at none, its time and workspace do not grow with
  * the pitch, and from 64 streams on a recording with slack behind its windows runs 1.3-1.4 x faster.  Neither entry delegates to the other. */
-uint64_t glv_batch_track_windows_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0: refused */
+uint64_t glv_batch_track_windows_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0: refused; also sizes glv_batch_track_windows_f32 */
 int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                                 unsigned ops, void* hip_stream);
 /* Track mode for the wave module: the texture of every update of a recording in ONE call (glv_batch_track_s16 refuses GLV_OP_WAVE; these are the entry
@@ -460,8 +460,42 @@ int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pit
  * 22.4 ms (349 x).  The one-by-one form costs ~11 us per update until the chip fills; the track call was the faster at every point measured.  By steps
  * instead of by rows: 0.048 / 0.178 / 1.43 / 2.65 ms at 1 / 8 / 64 / 1024 streams -- ahead at few streams, behind at many, by about the round-to-round
  * spread either way (the hop-735 point, where the order plays no part, shows the same 0.064 / 0.044 between the two batches). */
-uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);
+uint64_t glv_batch_track_wave_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* also sizes glv_batch_track_wave_f32 */
 int glv_batch_track_wave_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream);
+/* Track mode from float recordings: glv_batch_track_windows_s16 and glv_batch_track_wave_s16 for the layout a PulseAudio source or an audio decoder
+ * delivers.  Added within ABI 7 without a version change: detect them by the symbol.
+ *   d_pcm   float [streams][pitch_frames][2], interleaved L R (glv_batch_process_f32_stereo's frames), aligned like a float frame: 8 bytes, anything
+ *           less is GLV_ERR_INVALID.  Window t of stream s = its frames [t * hop, t * hop + n); any hop >= 1, hop > n included; any
+ *           pitch_frames >= n + (steps - 1) * hop.  A seek to any frame of a 16-byte aligned recording is a valid d_pcm: windows start 8-byte aligned
+ *           and no more.
+ * Contract: that of the s16 entry of the same name with glv_batch_process_f32_stereo as the sequential side.  The output of step t -- and for
+ * glv_batch_track_windows_f32 the batch's state afterwards: gravity store, history ring, ring head, gravity form -- is bit for bit what `steps` consecutive
+ * glv_batch_process_f32_stereo(b, window_t, out_t, ops, stream) calls produce and leave, -0 / Inf / NaN / denormal samples included; channels == 1 mixes
+ * (L + R) / 2 in float as that call does.  Chunks compose; calls mix with process, ring and s16 track calls on the same batch.  Accepted and refused ops,
+ * the GLV_ERR_STATE cases and "a refused call launches nothing" are those of glv_batch_track_windows_s16 / glv_batch_track_wave_s16.  Stream-ordered:
+ * kernels and nothing else -- nothing is allocated or synchronised, the first call can be captured, glv_batch_timing_* covers it.
+ * Workspace: glv_batch_track_windows_work_bytes / glv_batch_track_wave_work_bytes, the queries of the s16 entries -- the rows between launches do not
+ * depend on the input's type.
+ * Launches (glv_batch_last_launches, glv_batch_kernel_name as for the s16 entries): glv_batch_track_windows_f32 1 for a stateless chain without bars, 2
+ * with bars or with state, 3 with both.  glv_batch_track_wave_f32 1 without bars; with bars ALWAYS 2 (glv_wave_kernel, then the bars kernel): the integer
+ * pass reads s16 frames only, as in the float process call -- the query already reports the two-launch size.
+ * The transform reads a window whose first byte is 16-byte aligned with the loads of a back-to-back frame, any other in naturally aligned 8-byte (mono and
+ * N >= 16384) or 4-byte pieces; no launch reads a byte outside the windows the call names.  There is no float twin of glv_batch_track_s16 (the residue
+ * form): the windows entry is the recommended one at every hop.
+ * Measured (tools/track_f32_bench.py; profiles/r13/track_f32.txt: one MI355X, N = 4096, hop 735, an odd pitch; a host clock around the calls and the synchronise
+ * that ends them, medians of 7 alternating rounds; 1 / 8 / 64 streams x 2048 steps, 1024 x 256), each float track call against the same windows through
+ * glv_batch_process_f32_stereo one by one (window cutting not counted) and against the s16 entry on an s16 recording of the same shape:
+ *   glv_batch_track_windows_f32, the GL chain with F = 5 and the pre-smoothing pass, texels out: 1.99 against 44.9 ms one by one (22.6 x) and 1.99 ms from
+ *   s16; 2.58 against 47.1 (18.3 x) and 2.56; 5.83 against 48.3 (8.3 x) and 5.52; 8.46 against 12.7 (1.50 x) and 7.79.
+ *   glv_batch_track_wave_f32, GLV_OP_WAVE | GLV_OP_BARS | GLV_OP_R16 (two launches in both forms at this hop): 0.045 against 18.3 ms one by one (409 x) and 0.054 ms
+ *   from s16; 0.213 against 20.5 (96 x) and 0.212; 1.57 against 22.0 (14.1 x) and 1.38; 3.01 against 6.36 (2.1 x) and 2.81.
+ * Ahead of the one-by-one form at every point.  Against the s16 form: inside the round-to-round spread at 1 and 8 streams, where the scan and the launches
+ * dominate; BEHIND it at 64 and 1024 streams, by 6 % and 9 % (FFT chains) and 13 % and 7 % (wave), more than the spread: there the first launch is bound by
+ * the input it reads, and a float recording is twice the bytes. */
+int glv_batch_track_windows_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream);
+int glv_batch_track_wave_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                              unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
