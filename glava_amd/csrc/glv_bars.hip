@@ -933,8 +933,11 @@ hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, siz
 // tap_w holds W' as float bits).  MODE 1 / 2 (maximum / hybrid): one lane per texel walks its taps in bin order as glv_bars_mode_kernel does --
 // v = x * w, vmax, avg += v, each rounded on its own -- and converts the result to its texel as that kernel's r16 output does; tap_w holds the
 // float weights in tap order (desc[t].tap_offset).  The texels never reach HBM.
-template <int GL, int MODE>
-__global__ void __launch_bounds__(256) glv_columns_kernel(const float* __restrict__ rows, float* __restrict__ cols_out, size_t nrows, uint32_t n, uint32_t ntex,
+// TEXROWS (a columns track call, whose scan writes texels): the rows are uint16 [nrows][n].  MODE 0 reads them as glv_bars_snap_kernel's texel form
+// does and sums as above (bar_item_texel_sum: no conversion either way); MODE 1 / 2 take x = c / 65535 correctly rounded, what texelFetch returns and
+// what the float rows hold.
+template <int GL, int MODE, bool TEXROWS = false>
+__global__ void __launch_bounds__(256) glv_columns_kernel(const void* __restrict__ rows, float* __restrict__ cols_out, size_t nrows, uint32_t n, uint32_t ntex,
                                                           uint32_t cols, uint32_t nsteps, const BarItem* __restrict__ items, const BarDesc* __restrict__ desc,
                                                           const float* __restrict__ tap_w, const ColumnMap* __restrict__ map, float hyb, float one_minus_hyb) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -942,20 +945,29 @@ __global__ void __launch_bounds__(256) glv_columns_kernel(const float* __restric
     constexpr uint32_t G = 256 / GL;
     const int sub = threadIdx.x & (GL - 1);
     const uint32_t g = threadIdx.x / GL;
+    using Row = typename std::conditional<TEXROWS, uint16_t, float>::type;
     for (size_t row = blockIdx.x; row < nrows; row += gridDim.x) {
-        const float* tex = rows + row * n;
+        const Row* tex = static_cast<const Row*>(rows) + row * n;
         if constexpr (MODE == 0) {
             uint64_t total = 0;
             for (uint32_t s0 = 0; s0 < nsteps; s0 += kBarBatch) {
                 BarItem it[kBarBatch];
-                BarTaps tp[kBarBatch];
+                uint64_t lane[kBarBatch];
 #pragma unroll
                 for (int b = 0; b < kBarBatch; ++b) it[b] = items[(size_t) (s0 + b) * G + g];
+                if constexpr (TEXROWS) {
 #pragma unroll
-                for (int b = 0; b < kBarBatch; ++b) tp[b] = bar_item_load(tex, tap_w, it[b], sub);     // whole chunks lie inside the row (bar_chunks_in_row)
+                    for (int b = 0; b < kBarBatch; ++b) lane[b] = bar_item_texel_sum(tex, tap_w, it[b], sub);
+                } else {
+                    BarTaps tp[kBarBatch];
+#pragma unroll
+                    for (int b = 0; b < kBarBatch; ++b) tp[b] = bar_item_load(tex, tap_w, it[b], sub);     // whole chunks lie inside the row (bar_chunks_in_row)
+#pragma unroll
+                    for (int b = 0; b < kBarBatch; ++b) lane[b] = bar_snap_lane_sum(tp[b]);
+                }
 #pragma unroll
                 for (int b = 0; b < kBarBatch; ++b) {
-                    const uint64_t chunk_sum = group_sum64<GL>(bar_snap_lane_sum(tp[b]));
+                    const uint64_t chunk_sum = group_sum64<GL>(lane[b]);
                     total = it[b].keep != 0.0f ? total + chunk_sum : chunk_sum;
                     if (sub == 0) glv_col_tex[it[b].res] = (uint16_t) bar_snap_texel(total);             // res <= ntex
                 }
@@ -965,7 +977,9 @@ __global__ void __launch_bounds__(256) glv_columns_kernel(const float* __restric
                 const BarDesc d = desc[t];
                 float vmax = 0.0f, avg = 0.0f;
                 for (uint32_t j = 0; j < d.count; ++j) {                                              // first_bin + count <= n
-                    float x = tex[d.first_bin + j];
+                    float x;
+                    if constexpr (TEXROWS) x = unorm16_to_float(tex[d.first_bin + j]);
+                    else x = tex[d.first_bin + j];
                     x = x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f;                                         // NaN -> 0
                     const float v = __fmul_rn(x, tap_w[d.tap_offset + j]);
                     vmax = vmax < v ? v : vmax;
@@ -992,10 +1006,28 @@ hipError_t launch_columns(const float* rows, float* cols_out, size_t nrows, uint
     if (lds > 64u * 1024u || ntex == 0 || !desc || !tap_w || !map || (mode == 0u && !items)) return hipErrorInvalidValue;   // (glv_api.cpp refuses such tables)
     const dim3 grid(capped_grid(nrows, 1, kGridCap));
     const float h = hybrid_weight, omh = 1.0f - hybrid_weight;
-#define GLV_COLS_LAUNCH(GLN, MODE) hipLaunchKernelGGL((glv_columns_kernel<GLN, MODE>), grid, dim3(256), lds, st, rows, cols_out, nrows, n, ntex, cols, nsteps, items, desc, tap_w, map, h, omh)
+#define GLV_COLS_LAUNCH(GLN, MODE) hipLaunchKernelGGL((glv_columns_kernel<GLN, MODE>), grid, dim3(256), lds, st, static_cast<const void*>(rows), cols_out, nrows, n, ntex, cols, nsteps, items, desc, tap_w, map, h, omh)
     if (mode == 1u) GLV_COLS_LAUNCH(8, 1);
     else if (mode == 2u) GLV_COLS_LAUNCH(8, 2);
     else switch (bar_lanes_of(n)) {                                  // the work lists were made for 256 / bar_lanes_of(n) groups
+        case 2: GLV_COLS_LAUNCH(2, 0); break;
+        case 4: GLV_COLS_LAUNCH(4, 0); break;
+        default: GLV_COLS_LAUNCH(8, 0); break;
+    }
+#undef GLV_COLS_LAUNCH
+    return hipGetLastError();
+}
+hipError_t launch_columns_texels(const uint16_t* rows, float* cols_out, size_t nrows, uint32_t n, uint32_t ntex, uint32_t cols, uint32_t nsteps,
+                                 const BarItem* items, const BarDesc* desc, const float* tap_w, const ColumnMap* map, uint32_t mode, float hybrid_weight, hipStream_t st) {
+    if (nrows == 0 || cols == 0) return hipSuccess;
+    const size_t lds = sizeof(uint16_t) * ((size_t) ntex + 2u);
+    if (lds > 64u * 1024u || ntex == 0 || !desc || !tap_w || !map || (mode == 0u && !items)) return hipErrorInvalidValue;
+    const dim3 grid(capped_grid(nrows, 1, kGridCap));
+    const float h = hybrid_weight, omh = 1.0f - hybrid_weight;
+#define GLV_COLS_LAUNCH(GLN, MODE) hipLaunchKernelGGL((glv_columns_kernel<GLN, MODE, true>), grid, dim3(256), lds, st, static_cast<const void*>(rows), cols_out, nrows, n, ntex, cols, nsteps, items, desc, tap_w, map, h, omh)
+    if (mode == 1u) GLV_COLS_LAUNCH(8, 1);
+    else if (mode == 2u) GLV_COLS_LAUNCH(8, 2);
+    else switch (bar_lanes_of(n)) {
         case 2: GLV_COLS_LAUNCH(2, 0); break;
         case 4: GLV_COLS_LAUNCH(4, 0); break;
         default: GLV_COLS_LAUNCH(8, 0); break;

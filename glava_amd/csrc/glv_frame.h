@@ -281,6 +281,24 @@ GLV_HD uint64_t bar_snap_lane_sum(const BarTaps& s) {
     }
     return acc;
 }
+// The same lane sum over a row of the texels themselves (uint16: glv_columns_kernel's texel-row kind, the scan results of a columns track call): the
+// lane's eight taps are eight 2-byte loads, as glv_bars_snap_kernel's texel form reads them (a chunk starts at any bin: a 2-byte aligned address; whole
+// chunks lie inside the row, glv_tables.h bar_chunks_in_row).
+GLV_HD uint64_t bar_item_texel_sum(const uint16_t* tex_row, const float* tap_w, const BarItem& it, int sub) {
+    const uint32_t lane_byte = 4u * (uint32_t) kBarTaps * (uint32_t) sub;
+    const uint32_t first = it.tex_byte / 4u + (uint32_t) kBarTaps * (uint32_t) sub;
+    uint32_t c[kBarTaps];
+#pragma unroll
+    for (int i = 0; i < kBarTaps; ++i) c[i] = (uint32_t) tex_row[first + (uint32_t) i];
+    uint64_t acc = 0;
+#pragma unroll
+    for (int h = 0; h < kBarTaps / 4; ++h) {
+        const BarW4 w4 = ld<BarW4>(tap_w, it.w_byte + lane_byte + 16u * (uint32_t) h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc += (uint64_t) __builtin_bit_cast(uint32_t, w4.w[i]) * c[4 * h + i];
+    }
+    return acc;
+}
 // the results, as the twin's i8 pass gives them (glv_bars.hip glv_bars_rows_i8_kernel, oracle glvo_bars_int_at): floor(T / 2^31 + 1/2), and the float
 // form ldexp((double) T, -31) / 65535 (which the caller divides by the bar's weight_sum, 1 -- or NaN for a bar whose weights sum to 0)
 GLV_HD uint32_t bar_snap_texel(uint64_t total) { return (uint32_t) ((total + (1ull << 30)) >> 31); }

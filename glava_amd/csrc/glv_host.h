@@ -260,7 +260,8 @@ struct ChainPlan {
                                                                                // integer matrix-core pass), over texel values as floats c / 65535;
                 BARS_SNAP, BARS_SNAP_FLOATS, BARS_SNAP_MODE,                    // bars at texels of the pre-smoothing pass: over texel rows, over
                                                                                // c / 65535, and sample_mode maximum / hybrid (glv_bars_mode_kernel)
-                BARS_COLUMNS } bars = NO_BARS;                                  // means of three such texels (glv_columns_kernel; rows c / 65535)
+                BARS_COLUMNS,                                                   // means of three such texels (glv_columns_kernel; rows c / 65535)
+                BARS_COLUMNS_TEXELS } bars = NO_BARS;                           // ... over texel rows (a columns track call's scan results)
     int variant = 0, grid = 0;                  // the frame kernel's configuration and workgroups (FFT chains)
     glv::FrameClass cls = glv::FC_PLAIN;        // ... and its class
     unsigned ops = 0;                           // what the first kernel runs (FrameArgs::ops)

@@ -106,6 +106,9 @@ hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, siz
 // (desc, tap_w: W' as float bits for mode 0 with work lists `items` for 256 / bar_lanes_of(n) groups; float weights in tap order for modes 1 / 2), cols columns
 hipError_t launch_columns(const float* rows, float* cols_out, size_t nrows, uint32_t n, uint32_t ntex, uint32_t cols, uint32_t nsteps, const BarItem* items,
                           const BarDesc* desc, const float* tap_w, const ColumnMap* map, uint32_t mode, float hybrid_weight, hipStream_t st);
+// ... and over a GL chain's rows as the texels themselves (uint16 [nrows][n]: the scan results of glv_batch_track_columns_s16 / _f32)
+hipError_t launch_columns_texels(const uint16_t* rows, float* cols_out, size_t nrows, uint32_t n, uint32_t ntex, uint32_t cols, uint32_t nsteps,
+                                 const BarItem* items, const BarDesc* desc, const float* tap_w, const ColumnMap* map, uint32_t mode, float hybrid_weight, hipStream_t st);
 hipError_t launch_ring_planar(const void* ring, int is_f32, uint32_t n, uint32_t rot, int mono, size_t streams, float* out, hipStream_t st);
 hipError_t launch_unpack(const int16_t* pcm, size_t frames, int mono, float* l, float* r, hipStream_t st);
 

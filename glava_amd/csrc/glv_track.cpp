@@ -1,4 +1,4 @@
-// glv_track.cpp -- track mode: every update of a recording in one call.  The plans of the three entries, the executor of the two FFT forms with its
+// glv_track.cpp -- track mode: every update of a recording in one call.  The plans of the four entries, the executor of the FFT forms with its
 // stages, the wave module's form, and the C entries with their sizing queries.
 #include "glv_host.h"
 #include "glv_tables.h"       // kBarSeqMin
@@ -15,7 +15,8 @@ namespace {
 // geometry with one residue (log_q = 0) and hops_per_pitch = steps IS [stream][step][channel].  Either way the rows are texels where the chain's
 // first act is the GL_R16 upload.  (2) glv_track_scan_kernel (track_scan) walks the steps per bin with the state on chip and writes every
 // step's result -- into d_out, or with GLV_OP_BARS into the workspace's second region in the row format the bars kernel takes.  (3) The bars of a
-// second launch over steps * streams * 2 finished rows.
+// second launch over steps * streams * 2 finished rows -- or, for a batch with column texels set (plan_track_columns: the windows form, a GL chain), the
+// graph module's columns: glv_columns_kernel's texel-row kind over the scan's texels.
 struct TrackPlan {
     uint32_t q = 0, log_q = 0;          // residue launches
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
@@ -43,18 +44,25 @@ int track_args(unsigned ops, uint32_t steps) {
     return GLV_OK;
 }
 // ... (2) each entry's own hop and pitch rules, then (3) the batch, the rows of the output, and the decisions
-int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsigned ops, TrackPlan& tp) {
+// columns: the entry is the columns form (glv_batch_track_columns_*), which takes exactly the batches the other entries refuse for their column texels
+int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsigned ops, TrackPlan& tp, bool columns = false) {
     static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by the entry)
     if (b->p.gl_storage == 2) return fail(GLV_ERR_STATE, "gl_storage 2 is the pass-by-pass checker form: a track call runs on gl_storage 0 and 1");
     if (b->ops_mask & GLV_OP_BARS_ONLY)
         return fail(GLV_ERR_STATE, "the batch was created with GLV_OP_BARS_ONLY: its state beyond the live bins does not exist, which the scan over time would read");
-    if (b->columns()) return fail(GLV_ERR_STATE, "column texels are set (glv_batch_set_column_texels): a track call has no columns form");
+    if (b->columns() && !columns) return fail(GLV_ERR_STATE, "column texels are set (glv_batch_set_column_texels): a track call has no columns form");
+    if (columns && !b->columns())
+        return fail(GLV_ERR_STATE, "no column texels are set (glv_batch_set_column_texels): bars and bar texels are tracked by glv_batch_track_windows_s16 / _f32");
     if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
     if (int rc = check_ops(b, ops, &some_output)) return rc;
     tp.out_rows = (uint64_t) steps * b->streams * 2u;
     if (tp.out_rows > 0xffffffffull)                              // (the transform and the scan count their rows in FrameArgs::units, a uint32_t)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
     tp.state = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
+    if (columns) {      // (check_ops: GLV_OP_BARS on a GL chain with state, no GLV_OP_R16; gl_storage 2 went above -- texel state, texel rows all the way)
+        tp.bars = ChainPlan::BARS_COLUMNS_TEXELS; tp.in16 = tp.out16 = true;
+        return GLV_OK;
+    }
     const bool gl = tp.state && b->state16;                       // the GL_R16 chain, texel state (log_mode 2: its passes one by one -- the same texels)
     const bool snap = (ops & GLV_OP_BARS) && b->snapped();        // (check_ops: a GL chain's texel rows)
     // the bars of a second launch, as plan_chain picks them for a chain whose transform kernel does not take them
@@ -95,17 +103,34 @@ int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t
 // glv_batch_track_windows_s16 / _f32: any hop >= 1, any pitch that holds the windows.  One transform launch over exactly the windows asked for, so its region of the
 // workspace is steps * streams * 2 rows; a stateless chain without bars writes d_out directly and needs none (256: 0 stays "refused").  The scan's region
 // exists where a scan runs AND bars follow it.
-int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
-    const uint32_t n = b->p.n;
-    if (int rc = track_args(ops, steps)) return rc;
+int windows_args(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps) {
     if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
-    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
-    if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
+    return pitch_too_short(n, pitch_frames, hop, steps) ? GLV_ERR_INVALID : GLV_OK;
+}
+void windows_geometry(const glv_batch* b, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    const uint32_t n = b->p.n;
     tp.windows = true; tp.scan = tp.state; tp.hops_per_pitch = steps;      // (one residue: log_q and residue_rows stay 0)
     tp.to_out = !tp.state && !(ops & GLV_OP_BARS);
-    if (tp.to_out) { tp.rows_bytes = 0; tp.work_bytes = 256; return GLV_OK; }
+    if (tp.to_out) { tp.rows_bytes = 0; tp.work_bytes = 256; return; }
     tp.rows_bytes = up256(tp.out_rows * n * (tp.in16 ? 2u : 4u));
     tp.work_bytes = tp.rows_bytes + (tp.state && (ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+}
+int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    if (int rc = track_args(ops, steps)) return rc;
+    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps)) return rc;
+    if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
+    windows_geometry(b, steps, ops, tp);
+    return GLV_OK;
+}
+// glv_batch_track_columns_s16 / _f32: the windows form of a GL chain with state (track_chain sees to that), texel rows in both regions of the workspace, and
+// the columns as the third stage.  (The scan stores every bin of a step, though the columns read only those below the last tap of any distinct texel: a
+// store limit was built and measured level with full stores at 64 streams, profiles/r14/track_columns.txt, and taken out again.)
+int plan_track_columns(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    if (int rc = track_args(ops, steps)) return rc;
+    if (!(ops & GLV_OP_BARS)) return fail(GLV_ERR_INVALID, "a columns track call samples: GLV_OP_BARS is required (ops 0x%x)", ops);
+    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps)) return rc;
+    if (int rc = track_chain(b, pitch_frames, steps, ops, tp, true)) return rc;
+    windows_geometry(b, steps, ops, tp);
     return GLV_OK;
 }
 
@@ -163,6 +188,16 @@ int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t st
     if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
     return GLV_OK;
 }
+// (3) for a batch with column texels: the columns of every step's row, from the scan's texels
+int track_columns(glv_batch* b, const TrackPlan& tp, const float* rows, float* out, hipStream_t st) {
+    const hipError_t e = glv::launch_columns_texels(reinterpret_cast<const uint16_t*>(rows), out, (size_t) tp.out_rows, b->p.n,
+                                                    (uint32_t) b->snap_x.tex.size(), b->p.bars, b->snap_x.col_nsteps, b->snap_x.col_items, b->snap.desc, b->snap.w,
+                                                    b->snap_x.col_map, b->p.sample_mode, shape_hybrid(b->p), st);
+    ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "columns launch failed: %s", hipGetErrorString(e));
+    b->kernel_name = "glv_columns_kernel";
+    return GLV_OK;
+}
 // Carries a plan out: what the plan could not know (the pointers, what the batch did before), then the stages.  A refused call leaves the batch untouched.
 int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
     if (int rc = refuse_track_pointers(d_pcm, tp.f32, d_out, d_work)) return rc;
@@ -184,8 +219,9 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     pl.bars = tp.bars;
     pl.rows = reinterpret_cast<float*>(work + (tp.scan ? tp.rows_bytes : 0u));       // what the bars read: the scan's results, or a stateless transform's rows
     if (tp.scan) if (int rc = track_scan(b, tp, a, steps, work, (ops & GLV_OP_BARS) ? pl.rows : out, ops, st)) return rc;
-    // (3) the bars of every step's rows
-    if (int rc = launch_bars_pass(b, pl, out, (size_t) steps * b->streams * 2u, (ops & GLV_OP_R16) != 0, st)) return rc;
+    // (3) the bars of every step's rows, or the columns
+    if (tp.bars == ChainPlan::BARS_COLUMNS_TEXELS) { if (int rc = track_columns(b, tp, pl.rows, out, st)) return rc; }
+    else if (int rc = launch_bars_pass(b, pl, out, (size_t) steps * b->streams * 2u, (ops & GLV_OP_R16) != 0, st)) return rc;
     return timed_launch_end(b, st);
 }
 
@@ -298,6 +334,28 @@ int glv_batch_track_windows_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pit
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     TrackPlan tp;
     if (int rc = plan_track_windows(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (texel rows in both regions of the workspace, whatever the recording's type: one query for glv_batch_track_columns_s16 and _f32)
+uint64_t glv_batch_track_columns_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    return planned_work_bytes(b, plan_track_columns, pitch_frames, hop, steps, ops);
+}
+
+int glv_batch_track_columns_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    TrackPlan tp;
+    if (int rc = plan_track_columns(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_columns_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    TrackPlan tp;
+    if (int rc = plan_track_columns(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    tp.f32 = true;
     return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 

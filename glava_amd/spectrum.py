@@ -101,7 +101,7 @@ def lib() -> C.CDLL:
             L.glv_batch_set_bar_texels.argtypes = [vp, vp, C.c_uint32]
         if hasattr(L, "glv_batch_set_column_texels"):   # (likewise)
             L.glv_batch_set_column_texels.argtypes = [vp, vp, C.c_uint32]
-        for form in ("track", "track_windows", "track_wave"):   # (likewise, each pair by its call's symbol)
+        for form in ("track", "track_windows", "track_wave", "track_columns"):   # (likewise, each pair by its call's symbol)
             _bind_track_pair(L, form)
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
@@ -148,7 +148,7 @@ def _bind_track_pair(L, form: str) -> None:
     query.argtypes = [vp, u32, u32, u32, C.c_uint]
     query.restype = C.c_uint64
     getattr(L, f"glv_batch_{form}_s16").argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint, vp]
-    if hasattr(L, f"glv_batch_{form}_f32"):         # the float twin (track_windows, track_wave), sized by the same query
+    if hasattr(L, f"glv_batch_{form}_f32"):         # the float twin (track_windows, track_wave, track_columns), sized by the same query
         getattr(L, f"glv_batch_{form}_f32").argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint, vp]
 
 
@@ -268,6 +268,23 @@ class Batch:
         aligned; any hop >= 1; d_work at least track_windows_work_bytes(...) bytes (the same query), 256-byte aligned.  Output and state bit for bit
         those of `steps` process_f32_stereo calls on the windows; stream-ordered, kernels only."""
         self._track_call("track_windows", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream, "f32")
+
+    def track_columns_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
+        """bytes of device workspace track_columns_s16 / _f32 need for these arguments (glv_batch_track_columns_work_bytes: two regions of
+        steps * streams * 2 texel rows, each rounded up to 256 bytes); raises on arguments the call refuses"""
+        return self._track_work_bytes("track_columns", pitch_frames, hop, steps, ops)
+
+    def track_columns_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """the graph module's columns of `steps` consecutive updates of every stream from one long buffer (glv_batch_track_columns_s16), on a gl_storage 1
+        batch with set_column_texels: d_pcm int16 [streams][pitch_frames][2], any hop >= 1; d_out float32 [steps][streams * 2][cols], step t bit for bit
+        what process_s16 on window t would have written, the state afterwards what those calls leave; ops OP_FFT | OP_BARS with OP_GRAVITY / OP_AVERAGE;
+        d_work at least track_columns_work_bytes(...) bytes, 256-byte aligned.  Stream-ordered, three kernels."""
+        self._track_call("track_columns", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream)
+
+    def track_columns_f32(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_columns_s16 from a float recording (glv_batch_track_columns_f32): d_pcm float32 [streams][pitch_frames][2], 8-byte aligned; step t bit for
+        bit what process_f32_stereo on window t would have written; the same workspace query."""
+        self._track_call("track_columns", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream, "f32")
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

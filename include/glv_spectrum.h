@@ -497,6 +497,48 @@ int glv_batch_track_windows_f32(glv_batch* b, const float* d_pcm, uint32_t pitch
                                 unsigned ops, void* hip_stream);
 int glv_batch_track_wave_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                              unsigned ops, void* hip_stream);
+/* Track mode for the graph module: the columns of every update of a recording in ONE call (the other track entries refuse a batch with column texels
+ * set; these are the entry points that take it).  Added within ABI 7; detect by the symbol.
+ *   d_pcm, pitch_frames, hop, steps: as for glv_batch_track_windows_s16 / _f32 -- any hop >= 1 (hop > n too), any pitch_frames >= n + (steps - 1) * hop; the
+ *           s16 recording 4-byte aligned, the f32 one 8-byte aligned.  There is no residue-form twin.
+ *   batch   gl_storage 1, created with GLV_OP_BARS and the chain's state bits, a column table set (glv_batch_set_column_texels).
+ *   ops     GLV_OP_FFT | GLV_OP_BARS with GLV_OP_GRAVITY and / or GLV_OP_AVERAGE (GLV_OP_PRIVATE_STATE is ignored): the GL chains for which a process call takes
+ *           columns.  Every log_mode, channels 1 and 2, every sample_mode.
+ *   d_out   float [steps][streams][2][cols]: the block at d_out + t * streams * 2 * cols * 4 is what process call t writes.
+ *   d_work  caller-owned, 256-byte aligned, at least glv_batch_track_columns_work_bytes(...) bytes (0: refused, glv_last_error starts with the code's name).
+ * Contract: glv_batch_track_windows_s16's with columns as the output -- step t's columns and the batch's state afterwards (gravity store, history ring, ring
+ * head, gravity form, over ALL n bins) are bit for bit what `steps` consecutive glv_batch_process_s16 (_f32: glv_batch_process_f32_stereo) calls with the same
+ * table produce and leave behind.  Chunks compose; calls mix with process and ring calls on the same batch, and with the other track calls once the table
+ * is cleared.  Stream-ordered: kernels only, nothing allocated or synchronised; the first call can be captured into a hipGraph; glv_batch_timing_* covers it.
+ * Refused, launching nothing and leaving the batch untouched -- GLV_ERR_INVALID: any other ops bit, no GLV_OP_FFT or no GLV_OP_BARS, steps or hop 0, a pitch
+ * too short, a NULL pointer, a workspace not 256-byte aligned, an f32 d_pcm not 8-byte aligned, more than 2^32 - 1 rows.  GLV_ERR_STATE: no column table set
+ * (glv_batch_track_windows_* takes bars), GLV_OP_R16 (the columns are floats, as in a process call), gl_storage 0 or 2, a GLV_OP_BARS_ONLY batch, a
+ * single-row batch, a chain without state, and whatever the process call refuses (the gravity form mix, unannounced state, stale parameters).
+ * Launches (glv_batch_last_launches 3, glv_batch_kernel_name "glv_columns_kernel"): the transform over the windows where they lie, texel rows
+ * [stream][step][channel] into the workspace; glv_track_scan_kernel, every step's texels into the workspace's second region; glv_columns_kernel in its
+ * texel-row kind over steps * streams * 2 rows -- sample_mode average: the exact integer sums over the table's work lists; maximum / hybrid: x = c / 65535
+ * correctly rounded, then the float walk of the process call.  The texels between launches are half the bytes of the floats c / 65535 the process call's
+ * second launch reads.
+ * Workspace: R = steps * streams * 2 rows; R * n * 2 bytes for the transform's texels and R * n * 2 for the scan's, each rounded up to 256.
+ * Measured (tools/track_columns_bench.py; profiles/r14/track_columns.txt: one MI355X, N = 4096, hop 735, an odd pitch, the GL chain with F = 5; a host clock
+ * around the calls and the synchronise that ends them, medians of 7 alternating rounds; 1 / 8 / 64 streams x 2048 steps, 1024 x 256) against the same windows
+ * through glv_batch_process_s16 one by one with the same table (window cutting not counted):
+ *   an 800-pixel window (401 columns over 801 texels; one by one two launches): 2.23 against 54.4 ms (24.4 x), 4.71 against 61.1 (13.0 x), 22.6 against 63.3
+ *   (2.8 x); at 1024 streams BEHIND, 41.8 against 19.8 ms (0.47 x).
+ *   a 320-pixel window (161 columns over 321 texels; one by one one launch): 2.09 against 51.7 ms (24.8 x), 3.45 against 54.6 (15.8 x), 12.9 against 56.1
+ *   (4.3 x); at 1024 streams BEHIND, 22.5 against 10.9 ms (0.48 x).
+ * From 64 streams on the call's time is the columns kernel's, whose texel-row kind reads a lane's eight taps with eight 2-byte loads: once the chip is full
+ * the one-by-one form, which never takes its rows through HBM where it fuses, is the faster -- cut such a track into fewer streams per call, or use
+ * process calls there.
+ * A store limit for the scan (only the bins the columns read, about 0.29 n, in whole 128-bin workgroups) was built with a creation-time switch and measured
+ * in the same file (`full` = every bin stored): full / limit 0.99 and 0.99 at 1 stream, 0.98 and 1.01 at 8, 1.006 and 1.000 at 64 (spread 0.3 and 0.7 ms of
+ * 22.6 and 12.9), 1.03 and 1.05 at 1024 (spread 2.4 and 0.4 ms of 41.8 and 22.5).  Not faster by more than the spread at 64 streams: the limit and its
+ * switch were deleted, the scan stores every bin. */
+uint64_t glv_batch_track_columns_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0: refused; sizes both entries */
+int glv_batch_track_columns_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream);
+int glv_batch_track_columns_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                                unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
