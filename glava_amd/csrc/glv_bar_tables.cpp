@@ -188,6 +188,7 @@ int ensure_bar_tables(glv_batch* b) {
     w.resize(w.size() + chunk, 0.0f);
     std::vector<glv::BarItem> items;
     x.nsteps = glv::make_bar_items(items, desc, 256 / gl, zero_off, chunk);
+    x.chunk_reach = glv::bar_chunk_reach(desc, chunk);
     HIP_TRY(x.items.upload(items));
     // bar totals + the dump slot fit the 2 * lanes floats of slack behind the row in LDS
     // (from 256 bars up a bar is one fma chain, glv_tables.h make_bar_mtiles: the chunked loop of the epilogue does not apply)

@@ -113,6 +113,7 @@ struct BarExtras {
     // they could be cut -- the rounds of glv_bars_rows_kernel for its LDS ring
     DeviceArray<glv::BarMTile> mtiles; DeviceArray<float> wt, wsum; DeviceArray<glv::BarTile> rounds;
     uint32_t ntiles = 0, nrounds = 0, ring_bins = 0, bins_needed = 0;      // bins_needed: bins of a row the many-bars kernels sample (0: all)
+    uint32_t chunk_reach = 0;    // bins of a row the chunked work lists READ: whole chunks, past a bar's last tap with weights of +0 (glv_tables.h bar_chunk_reach)
     // the same pass over TEXEL rows (the GL chains, gl_storage != 0): exact integer arithmetic on the i8 matrix cores (glv_tables.h make_bar_itiles)
     DeviceArray<glv::BarMTile> itiles; DeviceArray<int8_t> wq; DeviceArray<glv::BarIFin> fin; DeviceArray<glv::BarTile> irounds;
     uint32_t intiles = 0, inrounds = 0, iring_bins = 0;

@@ -59,6 +59,8 @@ __global__ void __launch_bounds__(256) glv_post_kernel(const FrameArgs a, const 
 // A lane touches its own column of the ring only: no barrier anywhere.  The step is apply_state's / apply_state_r16's, helper by helper.
 // The row of a step does not depend on the state: kTrackDepth steps' loads are in flight ahead of the one being computed (a register ring,
 // indices compile-time) -- at few streams the loop is a chain of HBM round trips otherwise.
+// A live track call (glv_batch_track_live_s16 / _f32) walks the kept bins only, TrackGeometry::kept of every row's n: units * ceil(kept / 128) workgroups, and
+// a lane whose pair lies at or beyond kept / 2 leaves before it touches state, rows or LDS.
 // Window t of stream s starts at frame s * pitch + t * hop = (s * hops_per_pitch + t) * hop of the whole sequence: with q = n / hop it is row
 // k = h >> log_q of the residue launch r = h & (q - 1), whose rows start at r * residue_rows.
 constexpr int kTrackLanes = 64;          // one wave per workgroup: with few streams the lanes of a row spread over n / 128 CUs
@@ -68,9 +70,10 @@ __global__ void __launch_bounds__(kTrackLanes) glv_track_scan_kernel(const Frame
     using V = typename std::conditional<IN16, uint32_t, cf>::type;         // one lane's element of a row: a texel pair / a float pair
     extern __shared__ __attribute__((aligned(8))) unsigned char track_lds[];
     V* const ring = reinterpret_cast<V*>(track_lds) + threadIdx.x;          // slot f of this lane: ring[f * kTrackLanes]
-    const uint32_t blocks_per_row = t.n / (2u * (uint32_t) kTrackLanes);
+    const uint32_t blocks_per_row = (t.kept + 2u * (uint32_t) kTrackLanes - 1u) / (2u * (uint32_t) kTrackLanes);   // (kept: a multiple of 64 bins; n for every call but a live track call's)
     const uint32_t row = blockIdx.x / blocks_per_row;                       // uniform: a workgroup lies inside one channel row
     const uint32_t pair = (blockIdx.x % blocks_per_row) * (uint32_t) kTrackLanes + threadIdx.x;
+    if (pair >= t.kept / 2u) return;                                        // the last workgroup's upper half-wave where kept is an odd multiple of 64: nothing of it is read or written
     const uint32_t off = pair * (uint32_t) sizeof(V);                       // byte offset in an input / state row
     const size_t row_bytes = (size_t) t.n * (sizeof(V) / 2u);
     const uint32_t F = a.F;
@@ -535,8 +538,8 @@ hipError_t launch_post(const FrameArgs& a, uint32_t n, hipStream_t st) {
 }
 
 hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool rows_texels, hipStream_t st) {
-    const uint64_t blocks = (uint64_t) a.units * (t.n / (2u * (uint32_t) kTrackLanes));
-    if (t.n < 2u * (uint32_t) kTrackLanes || t.steps == 0 || blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint64_t blocks = (uint64_t) a.units * ((t.kept + 2u * (uint32_t) kTrackLanes - 1u) / (2u * (uint32_t) kTrackLanes));
+    if (t.n < 2u * (uint32_t) kTrackLanes || t.kept == 0 || t.kept > t.n || t.kept % 64u != 0 || t.steps == 0 || blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const size_t lds = (a.ops & OP_AVERAGE) ? (size_t) a.F * kTrackLanes * (rows_texels ? sizeof(uint32_t) : sizeof(cf)) : 0;   // <= 32 KiB (F <= 64)
     if (rows_texels) hipLaunchKernelGGL((glv_track_scan_kernel<true>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);
     else hipLaunchKernelGGL((glv_track_scan_kernel<false>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);

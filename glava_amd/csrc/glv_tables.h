@@ -181,6 +181,22 @@ inline bool bar_chunks_in_row(const std::vector<BarDesc>& desc, uint32_t n) {
     return true;
 }
 
+// Bins of a row the chunked work lists read (glv_frame.h bar_item_load takes whole chunks: past a bar's last tap the weights are +0, the bins are read all
+// the same), and from it the kept bins of a live track call (glv_batch_track_live_s16): the smallest multiple of 64 that covers the live bins and everything
+// the call's last kernel can read.  On float rows a bin nobody wrote could be a NaN, and NaN * 0 is not 0.
+inline uint32_t bar_chunk_reach(const std::vector<BarDesc>& desc, uint32_t chunk) {
+    uint32_t reach = 0;
+    for (const BarDesc& d : desc) {
+        const uint32_t end = d.first_bin + (d.count + chunk - 1) / chunk * chunk;
+        reach = d.count != 0 && end > reach ? end : reach;
+    }
+    return reach;
+}
+inline uint32_t track_kept_bins(uint32_t live_bins, uint32_t read_reach) {
+    const uint32_t most = live_bins > read_reach ? live_bins : read_reach;
+    return (most + 63u) & ~63u;
+}
+
 // GLV_OP_BARS work lists for `groups` groups (of chunk / 8 lanes) per row: every bar's chunks go, in order, to one
 // group (longest bars first, each to the least loaded group); step s of group g is items[s * groups + g].
 // Lists are padded with all-zero-weight items (`zero_off`: `chunk` zeros in tap_w; they restart the running

@@ -1,4 +1,4 @@
-// glv_track.cpp -- track mode: every update of a recording in one call.  The plans of the four entries, the executor of the FFT forms with its
+// glv_track.cpp -- track mode: every update of a recording in one call.  The plans of the five entries, the executor of the FFT forms with its
 // stages, the wave module's form, and the C entries with their sizing queries.
 #include "glv_host.h"
 #include "glv_tables.h"       // kBarSeqMin
@@ -17,6 +17,10 @@ namespace {
 // step's result -- into d_out, or with GLV_OP_BARS into the workspace's second region in the row format the bars kernel takes.  (3) The bars of a
 // second launch over steps * streams * 2 finished rows -- or, for a batch with column texels set (plan_track_columns: the windows form, a GL chain), the
 // graph module's columns: glv_columns_kernel's texel-row kind over the scan's texels.
+// A GLV_OP_BARS_ONLY batch (plan_track_live: the windows form, bars or columns as the batch has them) keeps TrackPlan::kept bins of every row from the
+// scan on: the transform finishes whole rows (live classes for it were built and measured level with the full-row ones at 64 streams,
+// profiles/r15/track_live_rule.txt, and taken out again), the scan walks the kept bins (TrackGeometry::kept), the bars and columns kernels never read
+// beyond them -- the rest of every row of the workspace's second region is not written.
 struct TrackPlan {
     uint32_t q = 0, log_q = 0;          // residue launches
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
@@ -32,11 +36,16 @@ struct TrackPlan {
     ChainPlan::Bars bars = ChainPlan::NO_BARS;
     uint64_t rows_bytes = 0, work_bytes = 0;   // the transform's region of the workspace (a multiple of 256 bytes), and all of it
     uint64_t out_rows = 0;              // steps * streams * 2
+    bool live = false;                  // the entry is the live form (glv_batch_track_live_s16 / _f32)
+    uint32_t kept = 0;                  // the live form's kept bins K, a multiple of 64 below n (kept_bins); 0: every bin -- the other entries, and the live form's full-row form
 };
 // What the two track entries (glv_batch_track_s16, glv_batch_track_windows_s16) share, written once so that they cannot disagree: the refusals that are
 // not about hop or pitch, and what the chain's stages carry.  In the order the checks have always run: (1) the arguments ...
-int track_args(unsigned ops, uint32_t steps) {
+// live: the entry is the live form, whose batches keep state only where bars sample -- bars and a state operator are part of the call
+int track_args(unsigned ops, uint32_t steps, bool live = false) {
     if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "a track call transforms: GLV_OP_FFT is required (ops 0x%x)", ops);
+    if (live && (!(ops & GLV_OP_BARS) || !(ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))))
+        return fail(GLV_ERR_INVALID, "a live track call takes GLV_OP_FFT | GLV_OP_BARS with GLV_OP_GRAVITY and / or GLV_OP_AVERAGE (ops 0x%x)", ops);
     const unsigned allowed = GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_BARS | GLV_OP_R16 | GLV_OP_PRIVATE_STATE;
     if (ops & ~allowed)
         return fail(GLV_ERR_INVALID, "a track call takes GLV_OP_FFT with GLV_OP_GRAVITY / AVERAGE / BARS / R16 only (no RAW, SMOOTH, WAVE, WRANGE, MAGNITUDE, OUTPUT_IS_STATE; ops 0x%x)", ops);
@@ -44,11 +53,36 @@ int track_args(unsigned ops, uint32_t steps) {
     return GLV_OK;
 }
 // ... (2) each entry's own hop and pitch rules, then (3) the batch, the rows of the output, and the decisions
+// The kept bins of a live track call: the smallest multiple of 64 that covers the live bins and every bin the call's last kernel can READ, multiplied by a
+// zero weight or not -- where that is less than a row and no more than the live share of every kernel configuration; else 0, the full-row form (the
+// bars sample too far or the chain has no live class: live_bins() is 0; float rows in front of a kernel whose reads are not bounded here).  Texel rows: the
+// integer pass, the snapped bars and the columns never touch what lies beyond their taps, and a texel nobody wrote is a number.  Float rows: the chunked
+// work lists read whole chunks past a bar's last tap and multiply them by +0 (plan_wave draws the same line) -- an unwritten float could be a NaN.
+uint32_t kept_bins(const glv_batch* b, const TrackPlan& tp) {
+    const uint32_t L = b->live_bins();
+    if (L == 0) return 0;
+    uint32_t reach = L;
+    if (!tp.out16) {
+        if (tp.bars != ChainPlan::BARS_F32 || b->p.sample_mode != GLV_SAMPLE_AVERAGE || b->p.bars >= glv::kBarSeqMin) return 0;
+        reach = b->bar_x.chunk_reach;
+    }
+    const uint32_t K = glv::track_kept_bins(L, reach);
+    if (K >= b->p.n) return 0;
+    for (int v = 0; v < glv::frame_variants(b->log_nn); ++v)
+        if (K > 2u * (uint32_t) glv::frame_geometry(b->log_nn, v).live_points) return 0;
+    return K;
+}
 // columns: the entry is the columns form (glv_batch_track_columns_*), which takes exactly the batches the other entries refuse for their column texels
-int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsigned ops, TrackPlan& tp, bool columns = false) {
+// live: the entry is the live form (glv_batch_track_live_*), which takes exactly the batches the other entries refuse for their GLV_OP_BARS_ONLY -- bars, bar
+// texels or columns, whichever the batch has set
+int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsigned ops, TrackPlan& tp, bool columns = false, bool live = false) {
     static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by the entry)
     if (b->p.gl_storage == 2) return fail(GLV_ERR_STATE, "gl_storage 2 is the pass-by-pass checker form: a track call runs on gl_storage 0 and 1");
-    if (b->ops_mask & GLV_OP_BARS_ONLY)
+    if (live) {
+        if (!(b->ops_mask & GLV_OP_BARS_ONLY))
+            return fail(GLV_ERR_STATE, "the batch was not created with GLV_OP_BARS_ONLY: its track entries are glv_batch_track_windows_* / glv_batch_track_columns_*");
+        columns = b->columns();
+    } else if (b->ops_mask & GLV_OP_BARS_ONLY)
         return fail(GLV_ERR_STATE, "the batch was created with GLV_OP_BARS_ONLY: its state beyond the live bins does not exist, which the scan over time would read");
     if (b->columns() && !columns) return fail(GLV_ERR_STATE, "column texels are set (glv_batch_set_column_texels): a track call has no columns form");
     if (columns && !b->columns())
@@ -59,8 +93,10 @@ int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsig
     if (tp.out_rows > 0xffffffffull)                              // (the transform and the scan count their rows in FrameArgs::units, a uint32_t)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
     tp.state = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
+    tp.live = live;
     if (columns) {      // (check_ops: GLV_OP_BARS on a GL chain with state, no GLV_OP_R16; gl_storage 2 went above -- texel state, texel rows all the way)
         tp.bars = ChainPlan::BARS_COLUMNS_TEXELS; tp.in16 = tp.out16 = true;
+        if (live) tp.kept = kept_bins(b, tp);
         return GLV_OK;
     }
     const bool gl = tp.state && b->state16;                       // the GL_R16 chain, texel state (log_mode 2: its passes one by one -- the same texels)
@@ -73,6 +109,7 @@ int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsig
     tp.in16 = tp.state ? gl : ((ops & GLV_OP_R16) && !(ops & GLV_OP_BARS));
     // with bars the texel conversion applies to the bars: the rows stay floats, unless the bars kernel takes texel rows
     tp.out16 = (ops & GLV_OP_BARS) ? (tp.bars == ChainPlan::BARS_I8 || tp.bars == ChainPlan::BARS_SNAP) : (ops & GLV_OP_R16) != 0;
+    if (live) tp.kept = kept_bins(b, tp);
     return GLV_OK;
 }
 uint64_t up256(uint64_t v) { return (v + 255u) & ~(uint64_t) 255u; }
@@ -133,6 +170,15 @@ int plan_track_columns(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, 
     windows_geometry(b, steps, ops, tp);
     return GLV_OK;
 }
+// glv_batch_track_live_s16 / _f32: the windows form on a GLV_OP_BARS_ONLY batch, bars or columns as the batch has them (track_chain), over the kept bins
+// (TrackPlan::kept).  The workspace keeps the windows and columns queries' layout and size: rows at pitch n, of which the kept bins are written.
+int plan_track_live(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    if (int rc = track_args(ops, steps, true)) return rc;
+    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps)) return rc;
+    if (int rc = track_chain(b, pitch_frames, steps, ops, tp, false, true)) return rc;
+    windows_geometry(b, steps, ops, tp);
+    return GLV_OK;
+}
 
 int refuse_track_pointers(const void* d_pcm, bool f32, const void* d_out, const void* d_work) {
     if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
@@ -180,6 +226,7 @@ int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t st
     a.grav_sub = b->grav_sub; a.grav_int = b->grav_int ? 1u : 0u; a.gl_storage = tp.in16 && tp.state ? 1u : 0u;
     glv::TrackGeometry g;
     g.n = b->p.n; g.steps = steps; g.hops_per_pitch = tp.hops_per_pitch; g.log_q = tp.log_q; g.residue_rows = tp.residue_rows; g.out_texels = tp.out16 ? 1u : 0u;
+    g.kept = tp.kept != 0 ? tp.kept : b->p.n;
     const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
     b->kernel_name = "glv_track_scan_kernel";
@@ -198,6 +245,15 @@ int track_columns(glv_batch* b, const TrackPlan& tp, const float* rows, float* o
     b->kernel_name = "glv_columns_kernel";
     return GLV_OK;
 }
+// the kernel (family) of stage (3), which a live track call names (the other entries have always named the scan)
+const char* bars_kernel_name(const glv_batch* b, ChainPlan::Bars bars) {
+    switch (bars) {
+        case ChainPlan::BARS_I8: case ChainPlan::BARS_I8_FLOATS: return "glv_bars_rows_i8_kernel";
+        case ChainPlan::BARS_SNAP: case ChainPlan::BARS_SNAP_FLOATS: return "glv_bars_snap_kernel";
+        case ChainPlan::BARS_SNAP_MODE: return "glv_bars_mode_kernel";
+        default: return b->p.sample_mode != GLV_SAMPLE_AVERAGE ? "glv_bars_mode_kernel" : b->p.bars >= glv::kBarSeqMin ? "glv_bars_rows_kernel" : "glv_bars_kernel";
+    }
+}
 // Carries a plan out: what the plan could not know (the pointers, what the batch did before), then the stages.  A refused call leaves the batch untouched.
 int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
     if (int rc = refuse_track_pointers(d_pcm, tp.f32, d_out, d_work)) return rc;
@@ -213,6 +269,7 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     fill_common(a, b->p, b->tab);
     a.ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u); a.log_mode = b->p.log_mode;
     const glv::FrameClass cls = glv::frame_class(false, false, false, a.ops);
+    if (tp.kept != 0) b->ran_live = true;      // the live form over the kept bins: the scan leaves the state at and beyond bin `kept` as it finds it
     if (int rc = tp.windows ? track_windows(b, tp, a, cls, d_pcm, pitch_frames, hop, steps, tp.to_out ? out : reinterpret_cast<float*>(work), st)
                             : track_residues(b, tp, a, cls, static_cast<const int16_t*>(d_pcm), hop, work, st)) return rc;
     ChainPlan pl;
@@ -222,6 +279,7 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     // (3) the bars of every step's rows, or the columns
     if (tp.bars == ChainPlan::BARS_COLUMNS_TEXELS) { if (int rc = track_columns(b, tp, pl.rows, out, st)) return rc; }
     else if (int rc = launch_bars_pass(b, pl, out, (size_t) steps * b->streams * 2u, (ops & GLV_OP_R16) != 0, st)) return rc;
+    else if (tp.live) b->kernel_name = bars_kernel_name(b, tp.bars);
     return timed_launch_end(b, st);
 }
 
@@ -355,6 +413,28 @@ int glv_batch_track_columns_f32(glv_batch* b, const float* d_pcm, uint32_t pitch
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     TrackPlan tp;
     if (int rc = plan_track_columns(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    tp.f32 = true;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (the workspace of the windows or the columns query, whichever form the batch takes: one query for glv_batch_track_live_s16 and _f32)
+uint64_t glv_batch_track_live_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops) {
+    return planned_work_bytes(b, plan_track_live, pitch_frames, hop, steps, ops);
+}
+
+int glv_batch_track_live_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    TrackPlan tp;
+    if (int rc = plan_track_live(b, pitch_frames, hop, steps, ops, tp)) return rc;
+    return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_live_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    TrackPlan tp;
+    if (int rc = plan_track_live(b, pitch_frames, hop, steps, ops, tp)) return rc;
     tp.f32 = true;
     return track(b, tp, d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }

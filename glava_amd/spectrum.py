@@ -101,7 +101,7 @@ def lib() -> C.CDLL:
             L.glv_batch_set_bar_texels.argtypes = [vp, vp, C.c_uint32]
         if hasattr(L, "glv_batch_set_column_texels"):   # (likewise)
             L.glv_batch_set_column_texels.argtypes = [vp, vp, C.c_uint32]
-        for form in ("track", "track_windows", "track_wave", "track_columns"):   # (likewise, each pair by its call's symbol)
+        for form in ("track", "track_windows", "track_wave", "track_columns", "track_live"):   # (likewise, each pair by its call's symbol)
             _bind_track_pair(L, form)
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
@@ -285,6 +285,23 @@ class Batch:
         """track_columns_s16 from a float recording (glv_batch_track_columns_f32): d_pcm float32 [streams][pitch_frames][2], 8-byte aligned; step t bit for
         bit what process_f32_stereo on window t would have written; the same workspace query."""
         self._track_call("track_columns", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream, "f32")
+
+    def track_live_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
+        """bytes of device workspace track_live_s16 / _f32 need for these arguments (glv_batch_track_live_work_bytes: what the windows or the columns query
+        gives for the same batch without OP_BARS_ONLY); raises on arguments the call refuses"""
+        return self._track_work_bytes("track_live", pitch_frames, hop, steps, ops)
+
+    def track_live_s16(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track mode for a batch created with OP_BARS_ONLY (glv_batch_track_live_s16): the bars, bar texels or columns -- whichever the batch has set -- of
+        `steps` consecutive updates of every stream from one long buffer, d_pcm int16 [streams][pitch_frames][2], any hop >= 1; ops OP_FFT | OP_BARS with
+        OP_GRAVITY / OP_AVERAGE.  Step t bit for bit what process_s16 on window t would have written on this batch, head, gravity form and the state below
+        live_bins() as those calls leave them; d_work at least track_live_work_bytes(...) bytes, 256-byte aligned.  Stream-ordered, three kernels."""
+        self._track_call("track_live", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream)
+
+    def track_live_f32(self, d_pcm, pitch_frames: int, hop: int, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_live_s16 from a float recording (glv_batch_track_live_f32): d_pcm float32 [streams][pitch_frames][2], 8-byte aligned; step t bit for bit
+        what process_f32_stereo on window t would have written; the same workspace query."""
+        self._track_call("track_live", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream, "f32")
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

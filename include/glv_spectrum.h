@@ -539,6 +539,45 @@ int glv_batch_track_columns_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pit
                                 unsigned ops, void* hip_stream);
 int glv_batch_track_columns_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                                 unsigned ops, void* hip_stream);
+/* Track mode for GLV_OP_BARS_ONLY batches: every update of a recording in ONE call, over the live bins only (the other track entries refuse such a
+ * batch -- its state beyond the live bins is not kept; these are the entry points that take it).  Added within ABI 7; detect by the symbol.
+ *   d_pcm, pitch_frames, hop, steps: as for glv_batch_track_windows_s16 / _f32 -- any hop >= 1, any pitch_frames >= n + (steps - 1) * hop; the s16
+ *           recording 4-byte aligned, the f32 one 8-byte aligned.
+ *   batch   created with GLV_OP_BARS_ONLY, gl_storage 0 or 1, channels 1 or 2; bars, bar texels (glv_batch_set_bar_texels) or columns
+ *           (glv_batch_set_column_texels), whichever is set.
+ *   ops     GLV_OP_FFT | GLV_OP_BARS with GLV_OP_GRAVITY and / or GLV_OP_AVERAGE; GLV_OP_R16 and GLV_OP_PRIVATE_STATE wherever the process call takes them.
+ *   d_out   step-major, what the process call writes: bars, bar texels or columns of [steps][streams][2].
+ *   d_work  caller-owned, 256-byte aligned, at least glv_batch_track_live_work_bytes(...) bytes (0: refused, glv_last_error starts with the code's name):
+ *           the value, and the layout, of the windows (columns) query of the same batch without the flag -- two regions of steps * streams * 2 rows at pitch n.
+ * Contract: step t of d_out is bit for bit what the t-th of `steps` consecutive glv_batch_process_s16 (_f32: glv_batch_process_f32_stereo) calls on window t
+ * writes on this batch; afterwards the ring head, the gravity form and the state of every bin below glv_batch_live_bins(b) are those the sequential calls
+ * leave.  The state at and beyond the live bins is unspecified, as after a live process call (and the batch counts as having run live: glv_batch_set_params
+ * and glv_batch_set_bar_texels guard it the same way).  Chunks compose; calls mix with process and ring calls on the same batch.  Stream-ordered: kernels
+ * only, nothing allocated or synchronised; the first call can be captured into a hipGraph; glv_batch_timing_* covers it.
+ * Refused, launching nothing and leaving the batch untouched -- GLV_ERR_INVALID: no GLV_OP_FFT, no GLV_OP_BARS, no state operator, any other ops bit, steps
+ * or hop 0, a pitch too short, a NULL pointer, a workspace not 256-byte aligned, an f32 d_pcm not 8-byte aligned, more than 2^32 - 1 rows.  GLV_ERR_STATE: a
+ * batch without GLV_OP_BARS_ONLY (glv_batch_track_windows_* / glv_batch_track_columns_* take it), gl_storage 2, a single-row batch, and whatever the
+ * process call refuses.
+ * Launches (glv_batch_last_launches 3; glv_batch_kernel_name names the third): the transform over the windows where they lie, whole rows into the
+ * workspace; glv_track_scan_kernel over the kept bins K of every row; the bars or columns kernel.  K is the smallest multiple of 64 that covers the live bins
+ * and every bin the third kernel can read (the chunked float bars read whole chunks past a bar's last tap, with weights of +0).  Nothing at or beyond bin K
+ * of any row of the workspace's second region is written, and the state there is left as the call finds it.  Where the batch has no live bins (the bars
+ * sample too far, log_mode 2) or K exceeds a kernel configuration's live share, the scan walks full rows: the same results, every bin's state kept.
+ * Measured (tools/track_live_bench.py; profiles/r15/track_live_rule.txt, column (d) -- the form that ships -- and profiles/r15/track_live.txt: one MI355X, N = 4096, hop 735, an odd pitch, the shipped pipeline with texels out, F = 5;
+ * a host clock around the call and the synchronise that ends it, medians of 7 alternating rounds; 1 / 8 / 64 streams x 2048 steps, 1024 x 256):
+ *   2.02 / 2.46 / 4.76 / 5.58 ms, against glv_batch_track_windows_s16 on an unflagged batch (the library before this entry) 1.99 / 2.56 / 5.46 / 7.90 ms and
+ *   against the same windows through glv_batch_process_s16 one by one on the flagged batch 35.2 / 37.0 / 38.7 / 9.10 ms.
+ * Level with the unflagged track call at one stream (the difference is inside the spread of 0.08 ms), ahead of it by 4 % at 8 streams, 13 % at 64 and 29 % at
+ * 1024; ahead of the one-by-one live calls at every point, 17 x, 15 x, 8.1 x and 1.63 x.  A caller with a flagged batch takes this entry at every stream count.
+ * Live classes for the transform (magnitude, log, tilt and quantisation for the live register slots only, stores below K) were built behind a creation-time
+ * switch and measured in profiles/r15/track_live_rule.txt: ahead of the full-row classes by 0.115 ms of 4.65 at 64 streams, inside the spread of 0.200 ms, and
+ * by 0.492 ms of 5.09 at 1024 streams (spread 0.400 ms).  Not ahead by more than the spread at both, so by the rule set beforehand the classes, the switch and
+ * their tests were taken out; the transform is the one of glv_batch_track_windows_*. */
+uint64_t glv_batch_track_live_work_bytes(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops);   /* 0: refused; sizes both entries */
+int glv_batch_track_live_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream);
+int glv_batch_track_live_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
+                             unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
