@@ -17,10 +17,15 @@ smooth_factor 0.025, 4 at 0.12 and 6 at 0.5: glv_bars_short_kernel<2>, <4> and t
 What the test cannot see: glv_batch_bars reports no kernel name and no launch count, and glv_batch_bars_arithmetic names the arithmetic,
 not the kernel -- the three chunked-list cases all answer BARS_F32_CHAIN, the matrix-core kernel and the one-lane-per-bar kernel
 (GLV_NO_BARS_ROWS at creation) both BARS_F32_MATRIX.  Which kernel a case runs rests on the step counts above and on that switch; only the
-wave cases tell their two forms apart, by glv_batch_last_launches."""
+wave cases tell their two forms apart, by glv_batch_last_launches.
+
+The last section takes the same sizes through glv_batch_process_s16, two updates each (state rows are read as well as written), for the kernels of a
+process call's last launch that glv_batch_bars over float spectra never reaches: glv_bars_mode_kernel over a GL chain's texel rows, glv_bars_snap_kernel
+and the I8_FLOATS kind of the integer pass over the float rows of the pass-by-pass chain (gl_storage 2), glv_columns_kernel over float rows."""
 import numpy as np
 import pytest
 
+from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
 from oracle_lib import lcg_pcm_fast
 
 gpu = pytest.mark.gpu
@@ -124,3 +129,71 @@ def test_wave_texture_of_a_stream_does_not_depend_on_the_streams_around_it(glvli
     for name, s0 in (("first", 0), ("last", LARGE_STREAMS - SMALL_STREAMS)):
         small = wave_texture(G, SMALL_STREAMS, pcm[s0 * per_stream:(s0 + SMALL_STREAMS) * per_stream].contiguous(), monkeypatch, unfused)
         assert_same_bits(small, large[2 * s0:2 * (s0 + SMALL_STREAMS)], (unfused, name))
+
+
+# ---- the last launch of a process call: the kernels glv_batch_bars never reaches ------------------------------------------------------------------------
+LANES_PER_ROW = 16                      # glv_inst.hip: lanes per row of the one kernel configuration of n = 256 -- no process call fuses bars or columns behind it
+
+
+@pytest.fixture(scope="module")
+def pcm_updates(pcm_frames):
+    """the frames of two updates of LARGE_STREAMS streams: pcm_frames, and the same frames in reverse stream order at a third of the level"""
+    import torch
+    second = torch.div(pcm_frames.view(LARGE_STREAMS, 2 * N).flip(0), 3, rounding_mode="floor").reshape(-1).contiguous()
+    return pcm_frames, second
+
+
+def _second_launch_families(G):
+    """family -> (parameters, table, GLV_OP_R16, launches, bars arithmetic).  launches: the transform and the kernel named -- and between them, for
+    gl_storage 2, the pass-by-pass chain's own pass (glv_post_kernel), which makes the kernel under test the third launch, not the second"""
+    bar = ("bar", radial_bar_texels(N, 160)[0])
+    wide, narrow = ("col", graph_column_texels(N, 200)[0]), ("col", graph_column_texels(N, 40)[0])
+    assert len(np.unique(wide[1])) + 1 > 4 * LANES_PER_ROW                       # more distinct texels than fit behind a row as 16-bit values
+    nb, nw, nn = len(bar[1]), len(wide[1]), len(narrow[1])
+    return {
+        "mode kernel on texel rows": (dict(gl_storage=1, bars=nb, sample_mode=1), bar, True, 2, G.BARS_F32_SEQ),
+        "snap kernel on float rows, texels out": (dict(gl_storage=2, bars=nb), bar, True, 3, G.BARS_I8_EXACT),
+        "snap kernel on float rows, floats out": (dict(gl_storage=2, bars=nb), bar, False, 3, G.BARS_I8_EXACT),
+        "columns kernel on float rows, over the fuse limit": (dict(gl_storage=1, bars=nw), wide, False, 2, G.BARS_I8_EXACT),
+        "columns kernel pass by pass, average": (dict(gl_storage=2, bars=nn, sample_mode=0), narrow, False, 3, G.BARS_I8_EXACT),
+        "columns kernel pass by pass, maximum": (dict(gl_storage=2, bars=nn, sample_mode=1), narrow, False, 3, G.BARS_F32_SEQ),
+        "columns kernel pass by pass, hybrid": (dict(gl_storage=2, bars=nn, sample_mode=2, sample_hybrid_weight=0.25), narrow, False, 3, G.BARS_F32_SEQ),
+        "i8 pass over float rows": (dict(gl_storage=2, bars=N, bar_phase=0.5), None, True, 3, G.BARS_I8_EXACT),
+    }
+
+
+def two_updates(G, kw, table, r16, streams, updates, launches, arithmetic):
+    """the outputs of two glv_batch_process_s16 calls of the GL chain with bars on a batch of `streams` streams"""
+    import torch
+    GA = G.OP_GRAVITY | G.OP_AVERAGE
+    b = G.Batch(G.Params(n=N, avg_window_kind=1, **kw), streams, GA | G.OP_BARS)
+    if table: (b.set_bar_texels if table[0] == "bar" else b.set_column_texels)(table[1])
+    assert b.bars_arithmetic() == arithmetic, b.bars_arithmetic()
+    outs = []
+    for pcm in updates:
+        out = torch.zeros((2 * streams, kw["bars"]), dtype=torch.int16 if r16 else torch.float32, device="cuda")
+        b.process_s16(pcm, out, G.OP_FFT | GA | G.OP_BARS | (G.OP_R16 if r16 else 0))
+        assert b.last_launches() == launches and b.kernel_name() == "glv_frame_kernel", (b.last_launches(), b.kernel_name())    # (a GL chain names its transform)
+        outs.append(out)
+    torch.cuda.synchronize()
+    b.close()
+    return outs
+
+
+@gpu
+@pytest.mark.parametrize("family", ["mode kernel on texel rows", "snap kernel on float rows, texels out", "snap kernel on float rows, floats out",
+                                    "columns kernel on float rows, over the fuse limit", "columns kernel pass by pass, average",
+                                    "columns kernel pass by pass, maximum", "columns kernel pass by pass, hybrid", "i8 pass over float rows"])
+def test_last_launch_of_a_process_call_does_not_depend_on_the_streams_around_it(glvlib, pcm_updates, family):
+    """two updates of 16 417 streams against two updates of its first and its last 65.  n = 256 fuses none of these (16 lanes per row), so every family
+    stays at this size; glv_batch_last_launches is 2 on gl_storage 1 and 3 on gl_storage 2, whose chain runs its state pass as a launch of its own"""
+    G = glvlib
+    kw, table, r16, launches, arithmetic = _second_launch_families(G)[family]
+    large = two_updates(G, kw, table, r16, LARGE_STREAMS, pcm_updates, launches, arithmetic)
+    assert int(large[1].ne(0).sum()) > 0
+    per_stream = 2 * N                                                          # int16 values of a stream's frames
+    for name, s0 in (("first", 0), ("last", LARGE_STREAMS - SMALL_STREAMS)):
+        cut = [pcm[s0 * per_stream:(s0 + SMALL_STREAMS) * per_stream].contiguous() for pcm in pcm_updates]
+        small = two_updates(G, kw, table, r16, SMALL_STREAMS, cut, launches, arithmetic)
+        for u in range(2):
+            assert_same_bits(small[u], large[u][2 * s0:2 * (s0 + SMALL_STREAMS)], (family, name, u))
