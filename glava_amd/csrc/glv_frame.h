@@ -24,6 +24,13 @@ namespace glv {
 enum InMode { IN_S16_STEREO = 0, IN_F32_PLANAR = 1, IN_S16_RING = 2, IN_F32_STEREO = 3, IN_F32_RING = 4,
               IN_S16_TRACK = 5,      // s16 windows cut out of [streams][pitch_frames][2] recordings where they lie (TrackWindows; never a ring)
               IN_F32_TRACK = 6 };    // the same for interleaved stereo f32 recordings, 8 bytes per frame (glv_batch_track_windows_f32)
+// The table kinds of a track call (glv_batch_track_at_s16 / _f32): the kernels of IN_S16_TRACK / IN_F32_TRACK with each window's start read from TrackWindows::starts.
+// Kernel kinds, not input modes of their own -- the host plans them as the hop kinds (the same plan cache row, the same wisdom key) -- numbered behind InMode.
+// Kinds of their own, not a run-time branch on a null table: the branch folded into the hop kinds gave 45 of the 120 IN_S16_TRACK kernels scratch they had not had
+// (N = 1024: 68-80 bytes a lane; N = 16384 / 32768: 180-224), so those stay byte for byte what they were and the table is a template constant.
+constexpr int IN_S16_TRACK_AT = 7, IN_F32_TRACK_AT = 8;
+constexpr int kFrameKinds = 9;       // every IN_MODE glv_frame_kernel is instantiated for: InMode and the table kinds
+GLV_HD constexpr bool in_track_table(int in_mode) { return in_mode == IN_S16_TRACK_AT || in_mode == IN_F32_TRACK_AT; }
 enum Epi { EPI_RAW = 0, EPI_MAG = 1, EPI_MAG_STATE = 2, EPI_RAW_STATE = 3 };
 
 // ops bits as in include/glv_spectrum.h
@@ -101,13 +108,22 @@ GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, u
 // f = s * steps + t -- neighbouring slots and workgroups then hold overlapping windows of ONE stream at the same moment and the overlap meets in L1 / L2 --
 // and frame f reads the n stereo frames (4 bytes each as s16, 8 as f32) from s * pitch_frames + t * hop on (64-bit arithmetic).  Its two channel rows go to row 2 f + ch (stream-major:
 // what glv_track_scan_kernel reads with log_q = 0, hops_per_pitch = steps) or to row (t * streams + s) * 2 + ch (step_major: what d_out and the bars pass take).
+// A table call (glv_batch_track_at_s16 / _f32): `starts` is uint32 [steps] in device memory, shared by all streams, and window t of every stream begins
+// min(starts[t], start_max) frames into its recording, start_max = pitch_frames - n -- the clamp is the kernel's, because the host cannot see the table: whatever
+// the table holds, the window lies inside the recording.  Read by the table kinds (IN_S16_TRACK_AT / IN_F32_TRACK_AT) only: the hop kinds never look at
+// `starts`, which every other entry leaves nullptr -- t * hop, as ever.
 struct TrackWindows {
     uint64_t pitch_frames, hop;
     uint32_t steps, streams;
     uint32_t step_major, pad;
+    const uint32_t* starts;     // appended: every field above keeps its offset
+    uint32_t start_max, pad2;
 };
-// (the host side of the same map, for the emulator and the tests' mirror)
-GLV_HD constexpr uint64_t track_window_start(const TrackWindows& w, uint32_t s, uint32_t t) { return (uint64_t) s * w.pitch_frames + (uint64_t) t * w.hop; }
+// Where window t of stream s begins, in frames; `entry` is starts[t] as the caller read it (unused without a table).  The kernel's rule and the host side of
+// the same map, for the emulator and the tests' mirror.
+GLV_HD constexpr uint64_t track_window_start(const TrackWindows& w, uint32_t s, uint32_t t, uint32_t entry = 0) {
+    return (uint64_t) s * w.pitch_frames + (w.starts ? (uint64_t) (entry < w.start_max ? entry : w.start_max) : (uint64_t) t * w.hop);
+}
 GLV_HD constexpr uint64_t track_window_row(const TrackWindows& w, uint32_t s, uint32_t t) {
     return w.step_major ? ((uint64_t) t * w.streams + s) * 2u : ((uint64_t) s * w.steps + t) * 2u;
 }
@@ -161,7 +177,7 @@ struct FrameArgs {
                                 // (kernel classes FC_GL16_SNAP*: bar_w holds the uint32 weights W' of bar_snap_lane_sum as float bits)
     const ColumnMap* col_map;   // kernel classes FC_GL16_COLS* (glv_batch_set_column_texels): [bars] columns, bars_out float [units][bars]; the work
                                 // lists cover the DISTINCT texels the columns read and BarItem::res indexes those
-    TrackWindows trk;           // IN_S16_TRACK / IN_F32_TRACK kernels only (units = 2 * streams * steps), as `rot` serves the ring kinds; appended: every field above keeps its offset
+    TrackWindows trk;           // IN_S16_TRACK / IN_F32_TRACK kernels and their table kinds only (units = 2 * streams * steps), as `rot` serves the ring kinds; appended: every field above keeps its offset
 };
 
 // ---- GLV_OP_BARS arithmetic (smooth.glsl:25-40; tex clamped to [0,1] like the GL_R16 texture the

@@ -1,11 +1,13 @@
 // glv_inst.hip -- production instantiations of glv_frame_kernel for ONE transform size.
 // Compiled per size with -DGLV_LOG_NN=k (k = log2(nn) = log2(N) - 1, 7..14) and per PART with -DGLV_INST_PART=p so that the
-// 40 translation units build in parallel and balance over the cores (the large sizes compile slowest):
+// 56 translation units build in parallel and balance over the cores (the large sizes compile slowest):
 //   part 0  s16 frames and the s16 ring, configuration 0; the size's dispatcher and geometry functions
 //   part 1  the f32 inputs (planar rows, interleaved stereo, the f32 ring), configuration 0
 //   part 2  configuration 1 (the runner-up plan of the size), every input but the track windows
 //   part 3  s16 windows of a track call where they lie (IN_S16_TRACK), both configurations, the two stateless classes only
 //   part 4  the same for f32 recordings (IN_F32_TRACK)
+//   part 5  part 3 with the windows' starts from a table in device memory (IN_S16_TRACK_AT: glv_batch_track_at_s16)
+//   part 6  part 4 likewise (IN_F32_TRACK_AT)
 // The knob set per size is the measured best of tools/tune.py
 // (profiles/tune_r01_final.txt, earlier sweeps in profiles/tune_r01.txt); see DESIGN.md "Kernel configuration".
 #include "glv_kernel_tmpl.h"
@@ -15,7 +17,7 @@
 #error "compile with -DGLV_LOG_NN=<7..14>"
 #endif
 #ifndef GLV_INST_PART
-#error "compile with -DGLV_INST_PART=<0..4>"
+#error "compile with -DGLV_INST_PART=<0..6>"
 #endif
 
 namespace glv {
@@ -81,6 +83,8 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part1)(int in_mode, int 
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(int in_mode, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part3)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part4)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part5)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part6)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 
 template <int IN_MODE, int V>
 static hipError_t launch_log(int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
@@ -128,10 +132,22 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part3)(int variant, int 
     if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_S16_TRACK, 1>(log_mode, cls, a, grid, st); }
     return hipErrorInvalidValue;
 }
-#else
+#elif GLV_INST_PART == 4
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part4)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     if (variant == 0) return launch_log<IN_F32_TRACK, 0>(log_mode, cls, a, grid, st);
     if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_TRACK, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#elif GLV_INST_PART == 5
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part5)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_S16_TRACK_AT, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_S16_TRACK_AT, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#else
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part6)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_F32_TRACK_AT, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_TRACK_AT, 1>(log_mode, cls, a, grid, st); }
     return hipErrorInvalidValue;
 }
 #endif
@@ -140,6 +156,8 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part4)(int variant, int 
 hipError_t GLV_CAT(launch_frame_, GLV_LOG_NN)(int in_mode, int log_mode, int variant, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     if (in_mode == IN_S16_TRACK) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part3)(variant, log_mode, cls, a, grid, st);
     if (in_mode == IN_F32_TRACK) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part4)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_S16_TRACK_AT) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part5)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_F32_TRACK_AT) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part6)(variant, log_mode, cls, a, grid, st);
     if (variant == 1) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(in_mode, log_mode, cls, a, grid, st);
     if (variant != 0) return hipErrorInvalidValue;
     if (in_mode == IN_S16_STEREO || in_mode == IN_S16_RING) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(in_mode, log_mode, cls, a, grid, st);

@@ -204,8 +204,9 @@ glv_frame_kernel(const FrameArgs a) {
     constexpr int E = FR::E;
     constexpr int T = FR::T, N = FR::N;
     constexpr bool RING = IN_MODE == IN_S16_RING;
-    constexpr bool TRACK = IN_MODE == IN_S16_TRACK;    // windows where they lie in a recording (a.trk): never a ring, stateless classes only (launch_variant)
-    constexpr bool TRACKF = IN_MODE == IN_F32_TRACK;   // the same over interleaved stereo f32 recordings: the f32 stereo pipeline and generic loop, another address per frame
+    constexpr bool TRACK_TABLE = in_track_table(IN_MODE);   // a table call's kinds: the window's start comes from a.trk.starts (track_entry / track_at below)
+    constexpr bool TRACK = IN_MODE == IN_S16_TRACK || IN_MODE == IN_S16_TRACK_AT;    // windows where they lie in a recording (a.trk): never a ring, stateless classes only (launch_variant)
+    constexpr bool TRACKF = IN_MODE == IN_F32_TRACK || IN_MODE == IN_F32_TRACK_AT;   // the same over interleaved stereo f32 recordings: the f32 stereo pipeline and generic loop, another address per frame
     constexpr bool S16 = IN_MODE == IN_S16_STEREO || RING || TRACK;
     constexpr bool WSPLIT = S16 && win_split_of(LOG_NN, STATEFUL);     // s16 samples: the window product without fp64 (glv_core.h apply_window_split)
     // f32 rows may hold -0.0, Inf and NaN: no unit-twiddle shortcut, non-finite values through the bit-faithful log
@@ -447,13 +448,22 @@ glv_frame_kernel(const FrameArgs a) {
     // load_pcm_at reads that window's n frames and not a byte more.  No launch reads outside the windows [s * pitch + t * hop, + n) of the call.
     // IN_F32_TRACK: the same f, so the same windows; load_f32s_raw (pipelined: dwords at 16 c + 4 ch and 16 c + 8 + 4 ch, c < NN, ch < 2) and
     // load_f32_stereo_window_at (generic loop: bytes [16 c, 16 c + 16), c < NN) both stay inside the window's 8 n bytes.
+    // The table kinds (TRACK_TABLE): the window begins min(starts[t], start_max) frames into the stream's recording -- track_window_start clamps whatever
+    // the table holds to pitch_frames - n, so the bound above holds with [s * pitch + min(starts[t], pitch - n), + n) for the windows.  The entry is one more
+    // load, and a load whose value an ADDRESS depends on must not be issued behind stores (the pipelined loops below: one in-order vmcnt): track_entry(f) is
+    // therefore asked for one frame AHEAD of the track_at(f, entry) that uses it, together with the previous frame's PCM loads, and W retires both (where f is
+    // wave-uniform, WAVE_SLOT, the compiler may make it a scalar load, which vmcnt does not count: nothing here relies on that).  t < steps: the entry read is one the call names.  The hop kinds: 0, no load,
+    // and track_at is what it was (the table is a template constant: their code does not change).
     struct TrackAt { const void* win; size_t row0; };
-    auto track_at = [&](uint32_t f) -> TrackAt {
+    auto track_entry = [&](uint32_t f) -> uint32_t { if constexpr (TRACK_TABLE) return a.trk.starts[f % a.trk.steps]; else return 0u; };
+    auto track_at = [&](uint32_t f, uint32_t entry) -> TrackAt {
         const uint32_t s = f / a.trk.steps, t = f - s * a.trk.steps;
-        const uint64_t start = (uint64_t) s * a.trk.pitch_frames + (uint64_t) t * a.trk.hop;
+        uint64_t start;
+        if constexpr (TRACK_TABLE) start = (uint64_t) s * a.trk.pitch_frames + (entry < a.trk.start_max ? entry : a.trk.start_max);      // (track_window_start with a table)
+        else start = (uint64_t) s * a.trk.pitch_frames + (uint64_t) t * a.trk.hop;
         return { static_cast<const char*>(a.in) + start * (TRACKF ? 8u : 4u), a.trk.step_major ? ((size_t) t * a.trk.streams + s) * 2u : (size_t) f * 2u };
     };
-    (void) track_at;
+    (void) track_at; (void) track_entry;
 
     unsigned xcount = 0;
     // A workgroup with a single slot takes both channel rows of a frame back to back (SEQ = 2), so
@@ -489,12 +499,15 @@ glv_frame_kernel(const FrameArgs a) {
         cf v[E];
         typename FR::Raw raw;
         size_t trow = 0, trow_next = 0;      // TRACK: channel-0 row of the slot's current frame / of the frame whose samples `raw` holds
-        (void) trow; (void) trow_next; (void) frame_ptr;
+        uint32_t tent = 0;                   // TRACK, a table call: the table's entry for the frame the NEXT stage A fetches, asked for by the stage A before it
+        (void) trow; (void) trow_next; (void) frame_ptr; (void) tent;
         if (blockIdx.x * SLOTS < nframes) {
             int tid = tid_outer;
             asm volatile("" : "+v"(tid));
-            if constexpr (TRACK) { const TrackAt w = track_at(frame_of(0)); FR::load_pcm_at(raw, w.win, tid); trow = w.row0; }
-            else
+            if constexpr (TRACK) {
+                const TrackAt w = track_at(frame_of(0), track_entry(frame_of(0))); FR::load_pcm_at(raw, w.win, tid); trow = w.row0;
+                if constexpr (TRACK_TABLE) tent = track_entry(frame_of(1));      // (guarded: the mere call cost the hop kinds registers)
+            } else
             FR::template load_pcm<RING>(raw, frame_ptr(frame_of(0)), tid, a.rot);
             FR::template unpack_window<0, WSPLIT>(v, raw, win, tid, 0u, a.mono != 0);
         }
@@ -507,8 +520,9 @@ glv_frame_kernel(const FrameArgs a) {
             const uint32_t fraw = blockIdx.x * SLOTS + m * fstride + slot;
             const bool active = fraw < nframes;
             const uint32_t f = frame_of(m);
-            if constexpr (TRACK) { if (ch) { const TrackAt w = track_at(frame_of(m + 1)); FR::load_pcm_at(raw, w.win, tid); trow_next = w.row0; } }   // A
-            else
+            if constexpr (TRACK) {                                                               // A (and the entry of the frame after: W retires both)
+                if (ch) { const TrackAt w = track_at(frame_of(m + 1), tent); FR::load_pcm_at(raw, w.win, tid); trow_next = w.row0; if constexpr (TRACK_TABLE) tent = track_entry(frame_of(m + 2)); }
+            } else
             if (ch) FR::template load_pcm<RING>(raw, frame_ptr(frame_of(m + 1)), tid, a.rot);   // A
             if constexpr (LIVE_PRE) { FR::live_prefetch(live_pre, (size_t) f * 2 + ch, tid, a); live_pre_ptr = &live_pre; }   // A': the row's old state (W awaits it)
             GLV_SCHED_FENCE();
@@ -577,12 +591,16 @@ glv_frame_kernel(const FrameArgs a) {
             cf v[E];
             typename FR::RawF raw;
             size_t trow = 0, trow_next = 0;      // TRACKF: channel-0 row of the slot's current frame / of the frame whose channel-0 samples `raw` holds or held last
-            (void) trow; (void) trow_next; (void) frame_ptr;
+            uint32_t tent = 0, tent_next = 0;    // TRACKF, a table call: the table's entries for the slot's current frame and its next, each asked for a frame ahead
+            (void) trow; (void) trow_next; (void) frame_ptr; (void) tent; (void) tent_next;
             if (blockIdx.x * SLOTS < nframes) {
                 int tid = tid_outer;
                 asm volatile("" : "+v"(tid));
-                if constexpr (TRACKF) { const TrackAt w = track_at(frame_of(0)); FR::template load_f32s_raw<false>(raw, w.win, tid, 0u); trow = w.row0; }
-                else
+                if constexpr (TRACKF) {
+                    if constexpr (TRACK_TABLE) tent = track_entry(frame_of(0));
+                    const TrackAt w = track_at(frame_of(0), tent); FR::template load_f32s_raw<false>(raw, w.win, tid, 0u); trow = w.row0;
+                    if constexpr (TRACK_TABLE) tent_next = track_entry(frame_of(1));
+                } else
                 FR::template load_f32s_raw<RINGF>(raw, frame_ptr(frame_of(0)), tid, 0u, a.rot);
                 FR::window_f32_raw(v, raw, win, tid);
             }
@@ -595,9 +613,9 @@ glv_frame_kernel(const FrameArgs a) {
                 const bool active = blockIdx.x * SLOTS + m * fstride + slot < nframes;
                 const uint32_t f = frame_of(m);
                 if constexpr (TRACKF) {                                                              // A (unconditional): ch 0 fetches its own window's other channel
-                    const TrackAt w = track_at(frame_of(m + ch));
+                    const TrackAt w = track_at(frame_of(m + ch), ch ? tent_next : tent);
                     FR::template load_f32s_raw<false>(raw, w.win, tid, ch ^ 1u);
-                    if (ch) trow_next = w.row0;
+                    if (ch) { trow_next = w.row0; if constexpr (TRACK_TABLE) { tent = tent_next; tent_next = track_entry(frame_of(m + 2)); } }      // (the entry of the frame after: W retires it)
                 } else
                 FR::template load_f32s_raw<RINGF>(raw, frame_ptr(frame_of(m + ch)), tid, ch ^ 1u, a.rot);   // A (unconditional)
                 GLV_SCHED_FENCE();
@@ -627,7 +645,7 @@ glv_frame_kernel(const FrameArgs a) {
         if constexpr (TRACK) {
             // not pipelined (no production configuration): one slot = one channel row of the window its frame names, one division per row
             typename FR::Raw raw;
-            const TrackAt w = track_at(row >> 1);
+            const TrackAt w = track_at(row >> 1, track_entry(row >> 1));
             FR::load_pcm_at(raw, w.win, tid);
             GLV_SCHED_FENCE();
             FR::template unpack_window<0, WSPLIT>(v, raw, win, tid, row & 1u, a.mono != 0);
@@ -637,7 +655,7 @@ glv_frame_kernel(const FrameArgs a) {
         } else
         if constexpr (TRACKF) {
             // mono at every size, every chain where the configuration is not pipelined for f32 (LOG_E 5): one slot = one channel row of the window its frame names
-            const TrackAt w = track_at(row >> 1);
+            const TrackAt w = track_at(row >> 1, track_entry(row >> 1));
             FR::load_f32_stereo_window_at(v, w.win, win, tid, row & 1u, a.mono != 0);
             BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
             finish_row(v, w.row0 + (row & 1u), tid, active);
@@ -699,7 +717,7 @@ hipError_t launch_variant(FrameClass cls, const FrameArgs& a, int grid, hipStrea
     auto launch_class = [&](auto c) -> hipError_t {
         constexpr int C = decltype(c)::value;
         // (IN_S16_TRACK / IN_F32_TRACK: a track call's transform is always stateless -- the other twelve classes are not instantiated for them)
-        if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2) || ((IN_MODE == IN_S16_TRACK || IN_MODE == IN_F32_TRACK) && fc_has_state(C))) return hipErrorInvalidValue;
+        if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2) || ((IN_MODE == IN_S16_TRACK || IN_MODE == IN_F32_TRACK || in_track_table(IN_MODE)) && fc_has_state(C))) return hipErrorInvalidValue;
         else if constexpr (fc_has_state(C))
             return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE_S>, done[C]);
         else return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TWREG, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE>, done[C]);

@@ -51,10 +51,18 @@ hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool ro
 // out of [streams][pitch_frames][2] recordings: output row r = t * units + 2 s + c is channel c of the n frames from s * pitch_frames + t * hop on,
 // in 64-bit arithmetic.  by_steps (the one-launch form): a workgroup of the bars kernel takes RB consecutive steps of ONE channel row, whose windows
 // overlap and meet in L2, instead of RB consecutive rows r.
+// A table call (glv_batch_track_at_s16 / _f32, glv_wave_kernel only): `starts` is uint32 [steps] in device memory and window t of every stream begins
+// min(starts[t], start_max) frames into its recording, start_max = pitch_frames - n (glv_frame.h TrackWindows: the same table, the same clamp, in the kernel).
+// starts == nullptr: t * hop.
 struct WaveWindows {
     uint32_t units = 0, steps = 0, hop = 0, by_steps = 0;
     uint64_t pitch_frames = 0;
+    const uint32_t* starts = nullptr;
+    uint32_t start_max = 0, pad = 0;
 };
+GLV_HD constexpr uint64_t wave_window_start(const WaveWindows& w, uint32_t s, uint32_t t, uint32_t entry = 0) {
+    return (uint64_t) s * w.pitch_frames + (w.starts ? (uint64_t) (entry < w.start_max ? entry : w.start_max) : (uint64_t) t * w.hop);
+}
 hipError_t launch_bufscale(const float* in, float* out, size_t total_out, uint32_t k, hipStream_t st);
 hipError_t launch_lerp(const float* s0, const float* e0, float* out, size_t total, float mod, hipStream_t st);
 hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin, const int* smax, uint32_t asz, uint32_t reach,
@@ -96,7 +104,7 @@ hipError_t launch_bars_i8_pcm(const void* pcm, uint32_t rot, bool mono, void* ba
 hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint32_t rot, size_t units, void* out, bool r16, uint32_t limit, hipStream_t st);
 // ... and both over every window of a track call (interleaved s16 recordings, any window start): out / bars_out hold w.steps * w.units rows, step-major.
 // launch_wave_track with f32: the recordings are interleaved stereo floats, 8 bytes per frame (pcm 8-byte aligned).
-// launch_bars_i8_pcm_track needs window starts on groups of 8 frames (pcm 32-byte aligned, hop and pitch multiples of 8) and refuses others
+// launch_bars_i8_pcm_track needs window starts on groups of 8 frames (pcm 32-byte aligned, hop and pitch multiples of 8) and refuses others (a table call never reaches it: the host cannot know where a table's windows lie)
 hipError_t launch_wave_track(const void* pcm, bool f32, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st);
 hipError_t launch_bars_i8_pcm_track(const void* pcm, const WaveWindows& w, bool mono, void* bars_out, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st,
                                     bool r16);

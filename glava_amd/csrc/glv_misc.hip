@@ -212,6 +212,8 @@ typedef unsigned int glv_wave_u4 __attribute__((ext_vector_type(4)));
 // KIND 4 (glv_batch_track_wave_f32): KIND 1's unpack over the same windows of float recordings, 8 bytes per frame.  A group's first frame is 8-byte
 // aligned and no more: 16-byte aligned it takes KIND 1's four 16-byte loads, otherwise its 8 frames one naturally aligned 8-byte load at a time.
 // Bounded reads (KIND 3 and 4): s < steps * streams and t + 8 <= limit <= n, so a lane reads frames [t, t + 8) of a window the call names and no others.
+// A table call (WaveWindows::starts): the window of step t' begins min(starts[t'], pitch_frames - n) frames into the recording -- one lookup per lane and group
+// of 8 frames, t' < steps, from a table that sits in L2; the clamp keeps the window inside the recording whatever the table holds.
 template <int KIND, bool R16>
 __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ in, void* __restrict__ out, size_t groups_total, uint32_t n, uint32_t limit,
                                                        uint32_t rot, int mono, const WaveWindows w) {
@@ -246,7 +248,8 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
             emit(s, t, x);
         } else if constexpr (KIND == 3) {
             const uint32_t streams = w.units / 2u;
-            const uint64_t first = (uint64_t) (s % streams) * w.pitch_frames + (uint64_t) (s / streams) * w.hop + t;      // the group's first frame
+            const uint32_t step = (uint32_t) (s / streams);
+            const uint64_t first = wave_window_start(w, (uint32_t) (s % streams), step, w.starts ? w.starts[step] : 0u) + t;      // the group's first frame
             const uint32_t* src = static_cast<const uint32_t*>(in) + first;
             uint32_t f[8];
             if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
@@ -266,7 +269,8 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
             emit(2 * s + 1, t, r);
         } else if constexpr (KIND == 4) {
             const uint32_t streams = w.units / 2u;
-            const uint64_t first = (uint64_t) (s % streams) * w.pitch_frames + (uint64_t) (s / streams) * w.hop + t;      // the group's first frame
+            const uint32_t step = (uint32_t) (s / streams);
+            const uint64_t first = wave_window_start(w, (uint32_t) (s % streams), step, w.starts ? w.starts[step] : 0u) + t;      // the group's first frame
             const cf* src = static_cast<const cf*>(in) + first;
             cf f[8];
             if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
@@ -574,7 +578,7 @@ hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint3
     return hipGetLastError();
 }
 hipError_t launch_wave_track(const void* pcm, bool f32, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st) {
-    if (limit == 0 || limit > n || (limit & 7u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || w.hop == 0) return hipErrorInvalidValue;
+    if (limit == 0 || limit > n || (limit & 7u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || (w.hop == 0 && !w.starts)) return hipErrorInvalidValue;
     const size_t total = (size_t) w.steps * (w.units / 2u) * (limit / 8u);
     const unsigned grid = grid_256(total);
     if (f32) {

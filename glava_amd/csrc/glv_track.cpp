@@ -21,6 +21,8 @@ namespace {
 // scan on: the transform finishes whole rows (live classes for it were built and measured level with the full-row ones at 64 streams,
 // profiles/r15/track_live_rule.txt, and taken out again), the scan walks the kept bins (TrackGeometry::kept), the bars and columns kernels never read
 // beyond them -- the rest of every row of the workspace's second region is not written.
+// A table call (glv_batch_track_at_s16 / _f32, plan_track_at: TrackPlan::at) is whichever of the windows, columns and live forms the batch takes, with the
+// windows where a table in device memory says: the transform runs in the kernel kinds that read it (IN_S16_TRACK_AT / IN_F32_TRACK_AT), nothing else differs.
 struct TrackPlan {
     uint32_t q = 0, log_q = 0;          // residue launches
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
@@ -36,6 +38,8 @@ struct TrackPlan {
     ChainPlan::Bars bars = ChainPlan::NO_BARS;
     uint64_t rows_bytes = 0, work_bytes = 0;   // the transform's region of the workspace (a multiple of 256 bytes), and all of it
     uint64_t out_rows = 0;              // steps * streams * 2
+    bool at = false;                    // the windows lie where a table in device memory says (glv_batch_track_at_s16 / _f32), not every `hop` frames; set before the plan
+    const uint32_t* starts = nullptr;   // ... and the table, uint32 [steps]; set by the entry as f32 is (the sizing query has none), windows form only
     bool live = false;                  // the entry is the live form (glv_batch_track_live_s16 / _f32)
     uint32_t kept = 0;                  // the live form's kept bins K, a multiple of 64 below n (kept_bins); 0: every bin -- the other entries, and the live form's full-row form
 };
@@ -140,7 +144,10 @@ int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t
 // glv_batch_track_windows_s16 / _f32: any hop >= 1, any pitch that holds the windows.  One transform launch over exactly the windows asked for, so its region of the
 // workspace is steps * streams * 2 rows; a stateless chain without bars writes d_out directly and needs none (256: 0 stays "refused").  The scan's region
 // exists where a scan runs AND bars follow it.
-int windows_args(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps) {
+// The hop and pitch rule of every form whose windows are read where they lie, written once.  at: a table call -- the kernels clamp every entry to pitch_frames - n
+// (glv_frame.h TrackWindows), so the recording has to hold ONE window and `hop` is not looked at.
+int windows_args(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps, bool at) {
+    if (at) return pitch_frames >= n ? GLV_OK : fail(GLV_ERR_INVALID, "pitch_frames=%u holds no window of n=%u frames", pitch_frames, n);
     if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
     return pitch_too_short(n, pitch_frames, hop, steps) ? GLV_ERR_INVALID : GLV_OK;
 }
@@ -154,7 +161,7 @@ void windows_geometry(const glv_batch* b, uint32_t steps, unsigned ops, TrackPla
 }
 int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     if (int rc = track_args(ops, steps)) return rc;
-    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps)) return rc;
+    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps, tp.at)) return rc;
     if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
     windows_geometry(b, steps, ops, tp);
     return GLV_OK;
@@ -165,7 +172,7 @@ int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, 
 int plan_track_columns(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     if (int rc = track_args(ops, steps)) return rc;
     if (!(ops & GLV_OP_BARS)) return fail(GLV_ERR_INVALID, "a columns track call samples: GLV_OP_BARS is required (ops 0x%x)", ops);
-    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps)) return rc;
+    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps, tp.at)) return rc;
     if (int rc = track_chain(b, pitch_frames, steps, ops, tp, true)) return rc;
     windows_geometry(b, steps, ops, tp);
     return GLV_OK;
@@ -174,10 +181,18 @@ int plan_track_columns(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, 
 // (TrackPlan::kept).  The workspace keeps the windows and columns queries' layout and size: rows at pitch n, of which the kept bins are written.
 int plan_track_live(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     if (int rc = track_args(ops, steps, true)) return rc;
-    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps)) return rc;
+    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps, tp.at)) return rc;
     if (int rc = track_chain(b, pitch_frames, steps, ops, tp, false, true)) return rc;
     windows_geometry(b, steps, ops, tp);
     return GLV_OK;
+}
+// glv_batch_track_at_s16 / _f32 on an FFT chain: the form a caller of the hop entries would have to pick for the batch -- live, columns or windows -- with the
+// table's rule for hop and pitch (windows_args).  Everything else is that form's plan: what it refuses, its stages, its workspace.  (`hop` is not looked at.)
+int plan_track_at(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    tp.at = true;
+    if (b->ops_mask & GLV_OP_BARS_ONLY) return plan_track_live(b, pitch_frames, hop, steps, ops, tp);
+    if (b->columns()) return plan_track_columns(b, pitch_frames, hop, steps, ops, tp);
+    return plan_track_windows(b, pitch_frames, hop, steps, ops, tp);
 }
 
 int refuse_track_pointers(const void* d_pcm, bool f32, const void* d_out, const void* d_work) {
@@ -209,9 +224,11 @@ int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::Fra
                         float* rows, hipStream_t st) {
     a.in = d_pcm; a.out = rows; a.units = (uint32_t) tp.out_rows;
     a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
-    const int mode = tp.f32 ? glv::IN_F32_TRACK : glv::IN_S16_TRACK;
+    a.trk.pad = 0; a.trk.starts = tp.starts; a.trk.start_max = pitch_frames - b->p.n; a.trk.pad2 = 0;      // (both plans' pitch rule: pitch_frames >= n)
+    const int hop_mode = tp.f32 ? glv::IN_F32_TRACK : glv::IN_S16_TRACK;
+    const int mode = !tp.starts ? hop_mode : tp.f32 ? glv::IN_F32_TRACK_AT : glv::IN_S16_TRACK_AT;      // a table call: the kernel kinds that read it, planned as the hop kinds
     int variant = 0, grid = 0;
-    launch_plan(b, a.units, mode, a.ops, &variant, &grid);
+    launch_plan(b, a.units, hop_mode, a.ops, &variant, &grid);
     b->last_grid = grid; b->last_variant = variant;
     const hipError_t e = glv::launch_frame(b->log_nn, mode, (int) b->p.log_mode, variant, cls, a, grid, st); ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -290,6 +307,7 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
 // (sized for one update).
 struct TrackWavePlan {
     bool f32 = false;               // the recording is interleaved stereo f32, else s16; set before the plan is made (the sizing query's is s16: the same bytes)
+    bool at = false;                // the windows lie where a table in device memory says (glv_batch_track_at_s16 / _f32); set before the plan is made
     ChainPlan pl;                   // the one or two launches of windows that start at any frame
     bool one_launch = false;        // with bars: plan_wave fuses where hop and pitch keep every window on a group of 8 frames -- of a 32-byte aligned d_pcm, which
                                     // only the call sees: on any other it runs `pl`.  Never from floats: the integer pass reads s16 frames, as in a process call
@@ -303,30 +321,32 @@ int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uin
     if (ops & ~(unsigned) (GLV_OP_WAVE | GLV_OP_BARS | GLV_OP_R16))
         return fail(GLV_ERR_INVALID, "a wave track call takes GLV_OP_WAVE with GLV_OP_BARS / GLV_OP_R16 only (ops 0x%x)", ops);
     if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
-    if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
-    if (pitch_too_short(n, pitch_frames, hop, steps)) return GLV_ERR_INVALID;
+    if (int rc = windows_args(n, pitch_frames, hop, steps, tp.at)) return rc;
     if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
     tp.rows = (uint64_t) steps * b->streams * 2u;
     if (tp.rows > 0x100000000ull)                 // (a COUNT of rows, steps * units, which the launchers take as a size_t: exactly 2^32 rows pass)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams);
     if (int rc = check_ops(b, ops, &some_output)) return rc;
     // The sizing query does not see d_pcm, so with bars the workspace is always what the two launches need: plan_wave is asked twice, for windows that
-    // start anywhere (the plan every call can fall back on) and for this call's hop and pitch.
+    // start anywhere (the plan every call can fall back on) and for this call's hop and pitch.  A table call always runs the former: the one-launch pass needs every
+    // window on a group of 8 frames, which the host cannot know of a table in device memory.
     const int in_mode = tp.f32 ? glv::IN_F32_STEREO : glv::IN_S16_STEREO;
     if (int rc = plan_wave(b, in_mode, ops, 0, nullptr, tp.pl, false)) return rc;
     if (ops & GLV_OP_BARS) {
         ChainPlan grouped;
-        if (int rc = plan_wave(b, in_mode, ops, 0, nullptr, grouped, hop % 8u == 0u && pitch_frames % 8u == 0u)) return rc;
+        if (int rc = plan_wave(b, in_mode, ops, 0, nullptr, grouped, !tp.at && hop % 8u == 0u && pitch_frames % 8u == 0u)) return rc;
         tp.one_launch = grouped.wave_fused;
         tp.work_bytes = up256(tp.rows * n * (tp.pl.wave_r16 ? 2u : 4u));
     }
     return GLV_OK;
 }
 
-int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+// d_starts: the table of a table call (its entry has vetted the pointer), and `hop` is not looked at; nullptr: every `hop` frames
+int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
+               const uint32_t* d_starts = nullptr) {
     if (int rc = refuse_track_pointers(d_pcm, f32, d_out, d_work)) return rc;
     TrackWavePlan tp;
-    tp.f32 = f32;
+    tp.f32 = f32; tp.at = d_starts != nullptr;
     if (int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) return rc;
     ChainPlan& pl = tp.pl;
     const bool fused = tp.one_launch && (reinterpret_cast<uintptr_t>(d_pcm) & 31u) == 0u;
@@ -335,6 +355,7 @@ int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames,
     const bool mono = b->p.channels == 1, r16 = (ops & GLV_OP_R16) != 0;
     glv::WaveWindows w;
     w.units = b->streams * 2u; w.steps = steps; w.hop = hop; w.pitch_frames = pitch_frames;
+    w.starts = d_starts; w.start_max = pitch_frames - b->p.n;
     // (a store's 32-bit lane offset spans 4 rows of the workgroup: `units` rows apart by steps)
     w.by_steps = b->track_wave_by_steps && (4ull * w.units + 2u) * b->p.bars * 4u <= 0xffffffffull ? 1u : 0u;
     if (int rc = timed_launch_begin(b, st)) return rc;
@@ -358,14 +379,26 @@ int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames,
 // The sizing query of a track entry: its plan's workspace, or 0 where the plan refuses (no return code to carry it: the message names the code).
 template <class Plan>
 uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, uint32_t, uint32_t, uint32_t, unsigned, Plan&), uint32_t pitch_frames, uint32_t hop, uint32_t steps,
-                            unsigned ops) {
+                            unsigned ops, bool at = false) {
     if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
     Plan tp;
+    tp.at = at;
     if (const int rc = plan(b, pitch_frames, hop, steps, ops, tp)) {
         g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
         return 0;
     }
     return tp.work_bytes;
+}
+// glv_batch_track_at_s16 / _f32: the table's own refusals, then the form the ops and the batch select -- the wave form's executor, or the FFT forms'.
+int track_at(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!d_starts) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_starts) & 3u) return fail(GLV_ERR_INVALID, "d_starts must be 4-byte aligned");
+    if (ops & GLV_OP_WAVE) return track_wave(b, d_pcm, f32, pitch_frames, 0u, steps, d_out, d_work, ops, st, d_starts);
+    TrackPlan tp;
+    if (int rc = plan_track_at(b, pitch_frames, 0u, steps, ops, tp)) return rc;
+    tp.f32 = f32; tp.starts = d_starts;
+    return track(b, tp, d_pcm, pitch_frames, 0u, steps, d_out, d_work, ops, st);
 }
 }  // namespace
 
@@ -463,5 +496,23 @@ int glv_batch_track_wave_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_fr
                              unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     return track_wave(b, d_pcm, true, pitch_frames, hop, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (one query for glv_batch_track_at_s16 and _f32, every form: the workspace of the form's own query for the same steps -- none of them depends on hop or pitch
+// where the windows are read where they lie; asked with the shortest recording a call takes, one window)
+uint64_t glv_batch_track_at_work_bytes(const glv_batch* b, uint32_t steps, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    if (ops & GLV_OP_WAVE) return planned_work_bytes(b, plan_track_wave, b->p.n, 0u, steps, ops, true);
+    return planned_work_bytes(b, plan_track_at, b->p.n, 0u, steps, ops, true);
+}
+
+int glv_batch_track_at_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work,
+                           unsigned ops, void* hip_stream) {
+    return track_at(b, d_pcm, false, pitch_frames, d_starts, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_at_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work,
+                           unsigned ops, void* hip_stream) {
+    return track_at(b, d_pcm, true, pitch_frames, d_starts, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 }  // extern "C"

@@ -103,6 +103,11 @@ def lib() -> C.CDLL:
             L.glv_batch_set_column_texels.argtypes = [vp, vp, C.c_uint32]
         for form in ("track", "track_windows", "track_wave", "track_columns", "track_live"):   # (likewise, each pair by its call's symbol)
             _bind_track_pair(L, form)
+        if hasattr(L, "glv_batch_track_at_s16"):        # (likewise: a table of window starts in place of the hop, a query without hop and pitch)
+            L.glv_batch_track_at_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint]
+            L.glv_batch_track_at_work_bytes.restype = C.c_uint64
+            L.glv_batch_track_at_s16.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_at_f32.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -303,6 +308,28 @@ class Batch:
         what process_f32_stereo on window t would have written; the same workspace query."""
         self._track_call("track_live", d_pcm, pitch_frames, hop, steps, d_out, d_work, ops, stream, "f32")
 
+    def track_at_work_bytes(self, steps: int, ops: int) -> int:
+        """bytes of device workspace track_at_s16 / _f32 need for these arguments (glv_batch_track_at_work_bytes: what the query of the form the call takes
+        reports for the same steps; 256 where the call needs none); raises on arguments the call refuses"""
+        nbytes = int(lib().glv_batch_track_at_work_bytes(self._h, steps, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)
+        return nbytes
+
+    def track_at_s16(self, d_pcm, pitch_frames: int, d_starts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track mode at given window starts (glv_batch_track_at_s16): d_starts uint32 [steps] in device memory, shared by all streams; window t of stream
+        s is the n frames of its recording from track_at_start(pitch_frames, n, d_starts[t]) on -- any order, repeats and backward jumps included.  The
+        form is the one the ops and the batch select (OP_WAVE: wave; an OP_BARS_ONLY batch: live; column texels set: columns; else windows), d_out and
+        d_work as that form takes them, d_work at least track_at_work_bytes(...) bytes.  Output and state bit for bit those of the sequential calls;
+        stream-ordered, kernels only; the table is read when the kernels run."""
+        _check(lib().glv_batch_track_at_s16(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_at_f32(self, d_pcm, pitch_frames: int, d_starts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_at_s16 from a float recording (glv_batch_track_at_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned; step t
+        bit for bit what process_f32_stereo on window t would have written"""
+        _check(lib().glv_batch_track_at_f32(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on
         arguments the call refuses"""
@@ -470,6 +497,14 @@ def track_window(n: int, hop: int, pitch_frames: int, s: int, t: int) -> tuple[i
 def track_window_start(pitch_frames: int, hop: int, s: int, t: int) -> int:
     """first frame (of the whole [streams][pitch_frames] buffer) of window t of stream s of a track call"""
     return s * pitch_frames + t * hop
+
+
+def track_at_start(pitch_frames: int, n: int, start: int) -> int:
+    """Where a window whose table entry is `start` begins in its stream's recording (glava_amd/csrc/glv_frame.h track_window_start with a table; the wave
+    kernel's wave_window_start): the kernels clamp the entry to pitch_frames - n, so the window lies inside the recording whatever the table holds."""
+    if pitch_frames < n or not 0 <= start < 1 << 32:
+        raise ValueError("pitch_frames >= n and a uint32 start")
+    return min(start, pitch_frames - n)
 
 
 def track_windows_rows(streams: int, steps: int, step_major: bool) -> list[int]:

@@ -578,6 +578,50 @@ int glv_batch_track_live_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_
                              unsigned ops, void* hip_stream);
 int glv_batch_track_live_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work,
                              unsigned ops, void* hip_stream);
+/* Track mode at given window starts: every entry above places window t at t * hop, one integer hop per call.  These take a TABLE of positions instead -- a
+ * renderer at a rate the frame rate does not divide (the shipped 22050 Hz at 60 fps: 367.5 frames per step), the windows a live GLava would have shown
+ * (updates every sample_sz / 4 frames, the latest complete one per render frame), variable frame rates, scrubbing, cue lists.  Added within ABI 7; detect
+ * by the symbol.  The ten entries above keep their signatures and behaviour; the residue form (glv_batch_track_s16) has no table twin.
+ *   d_pcm, pitch_frames: as for glv_batch_track_windows_s16 / _f32, with pitch_frames >= n as the only rule (the s16 recording 4-byte aligned, the f32 one 8).
+ *   d_starts  uint32 [steps] in DEVICE memory, 4-byte aligned, shared by all streams.  Window t of stream s is the n frames of that stream's recording
+ *           from min(d_starts[t], pitch_frames - n) on.  Entries may come in any order; repeats and backward jumps are valid.
+ *   d_out, d_work, ops: those of the form the call takes --
+ *           ops with GLV_OP_WAVE: the wave form (glv_batch_track_wave_*); else a GLV_OP_BARS_ONLY batch: the live form (glv_batch_track_live_*); else a batch
+ *           with column texels set: the columns form (glv_batch_track_columns_*); anything else: the windows form (glv_batch_track_windows_*).
+ *           Each form accepts and refuses what its uniform-hop entry does, minus the hop rules.
+ * The clamp is done in the kernels, because the host cannot see the table without a synchronise: whatever the table holds, no launch reads a byte outside the
+ * recordings the call names ([d_pcm + s * pitch_frames, + pitch_frames) frames for s < streams) nor a table entry outside d_starts[0, steps).
+ * Contract: the existing one, word for word -- step t of d_out, and afterwards the batch's state (gravity store, history ring, ring head, gravity form; on a
+ * live batch the state below glv_batch_live_bins), are bit for bit what `steps` consecutive glv_batch_process_s16 / glv_batch_process_f32_stereo calls on
+ * those windows produce and leave behind.  Chunks compose: a call on d_starts + k continues a call that ended at step k.  Calls mix with every other
+ * process, ring and track call.  Stream-ordered: kernels only, nothing allocated or synchronised; the first call can be captured into a hipGraph.
+ * The table is read when the kernels run, not when the call is made: rewriting d_starts (in stream order) between replays re-aims a captured call.
+ * Refused, launching nothing and leaving the batch untouched -- GLV_ERR_INVALID: pitch_frames < n, steps 0, a NULL pointer (d_starts included), a d_starts
+ * not 4-byte aligned, a d_work not 256-byte aligned, an f32 d_pcm not 8-byte aligned, the row-count limits and the ops rules of the form.  GLV_ERR_STATE:
+ * gl_storage 2, a single-row batch, whatever the process call refuses.
+ * Launches: the FFT forms 1 (stateless, no bars), 2 or 3 as for glv_batch_track_windows_*; the wave form 1 without bars and ALWAYS 2 with bars (the
+ * one-launch integer pass needs every window on a group of 8 frames, which the host cannot know of a table in device memory).
+ * Workspace: glv_batch_track_at_work_bytes, which is the form's own query for the same steps (none depends on hop or pitch where windows are read where
+ * they lie); 256 where nothing is parked; 0: refused, glv_last_error starts with the code's name.
+ * Kernels: the transform of glv_batch_track_windows_* with the table's entry in place of t * hop (glv_frame.h TrackWindows).  The entry of a frame is
+ * requested one frame ahead, with the previous frame's samples, so that no load whose value an address depends on is issued behind a row's stores.
+ * Measured (tools/track_at_bench.py, profiles/r16/track_at.txt: one MI355X, N = 4096, the GL chain with F = 5 and the pre-smoothing pass, texels out; a host clock
+ * around the call and the synchronise that ends it, medians of 7 alternating rounds, spread = max - min; 1 / 8 / 64 streams x 2048 steps, 1024 x 256):
+ *   (a) the table t * 735 against glv_batch_track_windows_s16 at hop 735, same library: 1.980 against 1.979 ms (spreads 0.023 / 0.070), 2.538 against 2.529
+ *       (0.014 / 0.019), 5.427 against 5.363 (0.146 / 0.112), 7.959 against 7.741 (0.212 / 0.421) -- 0.1 to 2.8 % behind, inside the spread at every point;
+ *       the float entries 1.980 against 1.986, 2.580 against 2.576, 5.617 against 5.626, 8.398 against 8.346 ms: level.
+ *   (b) glv_batch_track_windows_s16 at hop 735 in this library against the parent commit's: 1.975 / 2.535 / 5.262 / 7.663 against 1.975 / 2.530 / 5.274 /
+ *       7.852 ms, inside the spread at every point (the hop kinds' kernels have the parent's registers and scratch, 152 of 152: profiles/r16/track_at_isa.txt).
+ *   (c) the 22050 Hz / 60 fps table against the same windows through glv_batch_process_s16 one by one: 1.983 against 41.4 ms (20.9 x), 2.542 against 44.6
+ *       (17.6 x), 5.588 against 46.2 (8.3 x), 7.918 against 10.7 (1.35 x).
+ * The table kinds hold 1-2 more VGPRs than the hop kinds at N = 4096 and no scratch.  At other sizes 45 of their 152 kernels have scratch their hop kind lacks
+ * (68-88 bytes a lane at N <= 1024, 12-20 at 2048 and 8192, 168-224 at 16384 and 32768: profiles/r16/track_at_isa.txt) -- the entry carried across the
+ * transform and a second division; those sizes have not been timed. */
+uint64_t glv_batch_track_at_work_bytes(const glv_batch* b, uint32_t steps, unsigned ops);   /* 0: refused, glv_last_error starts with the code's name; sizes both entries */
+int glv_batch_track_at_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps,
+                           void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_at_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps,
+                           void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
