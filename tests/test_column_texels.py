@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from glava_amd.bar_positions import circle_texels, graph_column_texels
+from gpu_lib import bars_mask as _mask, eq as _eq, update_inputs as _inputs
 from oracle_lib import lcg_pcm_fast
-from test_snapped_bars import _eq, _inputs, _mask
 
 pytestmark = pytest.mark.gpu
 F = np.float32

@@ -23,12 +23,13 @@ import pytest
 
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
 from oracle_lib import Oracle, StreamOracle, lcg_pcm_fast
-from test_track_windows import _chains, _compare, _device, _eq, _pcm, _pitch, _seq, _track, _windows
+from gpu_lib import SIZES, bits
+from track_lib import compare_hop, eq as _eq, fft_kernel, hop_windows as _windows, launches_fft, pcm as _pcm, pitch_odd as _pitch
+from track_lib import s16_chains as _chains, seq as _seq, to_device, track
 
 pytestmark = pytest.mark.gpu
 
 GRIDS = (1, 2, 3)
-SIZES = [(256, 0)] + [(n, v) for n in (512, 1024, 2048, 4096, 8192, 16384, 32768) for v in (0, 1)]
 STEPS = 11
 
 
@@ -217,7 +218,6 @@ def test_forced_grid_equals_the_oracle_on_every_stream(glvlib, oracle, n, varian
     streams = _pick_streams(slots, grids, frames_only=True)
     _assert_shape(streams, slots, grids, frames_only=True)
     F = 3 if n >= 16384 else 5
-    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)                       # noqa: E731
     # raw
     x = _frames(500 + n, streams, n)
     want = [StreamOracle(n, gravity=False, average=False).frame(x[s], want_raw=True)[1] for s in range(streams)]
@@ -410,7 +410,7 @@ def _track_shape(G, n, variant, grids):
 def test_track_windows_at_forced_grids(glvlib, n, variant):
     """glv_batch_track_windows_s16 at 1 and 2 workgroups, 11 steps, hop 45 and n + 3, the recording aligned and one frame off: `fft` (step-major rows
     straight into d_out), `fft_r16`, `chain` (stream-major rows, then the scan) and `gl_chain_r16` against sequential glv_batch_process_s16 calls at the
-    automatic grid on a second batch, output and -- through one more update on both -- state (test_track_windows._compare)"""
+    automatic grid on a second batch, output and -- through one more update on both -- state (track_lib.compare)"""
     G = glvlib
     grids = (1, 2)
     streams = _track_shape(G, n, variant, grids)
@@ -423,7 +423,9 @@ def test_track_windows_at_forced_grids(glvlib, n, variant):
                 for g in grids:
                     bt.reset(); bs.reset()
                     bt.set_grid(g)
-                    _compare(G, bt, bs, ops, n, hop, steps=STEPS, odd=odd, seed=41 + g)
+                    pitch = _pitch(n, hop, STEPS + 1)
+                    compare_hop(G, bt, bs, "windows", _pcm(41 + g + n + hop, streams, pitch), odd, pitch, hop, n, STEPS, ops, n, launches_fft(G, ops),
+                                fft_kernel(G, ops))
                     assert bt.last_grid() == g and bt.last_variant() == variant, (chain, hop, odd, bt.last_grid())
         bt.close(); bs.close()
 
@@ -441,7 +443,7 @@ def test_track_windows_at_a_forced_grid_equals_the_oracle(glvlib, oracle, n, var
     x = _pcm(5150 + n, streams, pitch)
     b = _batch(G, G.Params(n=n, avg_frames=F, log_mode=0), streams, GA, variant)
     b.set_grid(1)
-    got = _track(b, _device(x, True), pitch, hop, STEPS, G.OP_FFT | GA, n, torch.float32).cpu().numpy()
+    got = track(b, "windows", to_device(x, True, False), pitch, hop, STEPS, G.OP_FFT | GA, n, torch.float32).cpu().numpy()
     assert b.last_grid() == 1 and b.last_variant() == variant
     s = streams - 1
     so = StreamOracle(n, avg_frames=F)
@@ -470,7 +472,7 @@ def test_track_residue_launches_at_a_forced_grid(glvlib, n):
     assert shape_ok(streams)
     print(f"n {n}: slots {slots} streams {streams}, windows per residue launch {G.track_residues(n, hop, pitch, streams, STEPS)}")
     x = _pcm(77 + n, streams, pitch)
-    d_pcm = _device(x, False)
+    d_pcm = to_device(x, False, False)
     wins = _windows(x, n, hop, 0, STEPS + 1)
     for chain in ("chain", "gl_chain_r16"):
         kw, mask, ops = _chains(G)[chain]
@@ -478,7 +480,7 @@ def test_track_residue_launches_at_a_forced_grid(glvlib, n):
         dt = torch.int16 if ops & G.OP_R16 else torch.float32
         bt, bs = G.Batch(p, streams, mask), G.Batch(p, streams, mask)
         bt.set_grid(1)
-        got = _track(bt, d_pcm, pitch, hop, STEPS, ops, n, dt, old=True)
+        got = track(bt, "residue", d_pcm, pitch, hop, STEPS, ops, n, dt)
         assert bt.last_grid() == 1 and bt.last_launches() == n // hop + 1
         want = _seq(bs, wins[:STEPS], ops, n, dt)
         for t in range(STEPS):

@@ -32,7 +32,7 @@ import pytest
 
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
 from oracle_lib import Oracle, StreamOracle, lcg_pcm_fast
-from test_track_windows import _device, _eq, _pcm, _seq, _track, _windows
+from track_lib import eq as _eq, hop_windows as _windows, pcm as _pcm, seq as _seq, to_device, track, with_table as _with_table
 
 pytestmark = pytest.mark.gpu
 
@@ -263,11 +263,6 @@ def _live_cases(G):
     }
 
 
-def _with_table(b, table):
-    if table: (b.set_bar_texels if table[0] == "bar" else b.set_column_texels)(table[1])
-    return b
-
-
 @pytest.mark.parametrize("F", FS)
 @pytest.mark.parametrize("case", ["7_smallest", "7_shipped", "8", "9", "11", "13"])
 def test_live_classes_are_the_full_chain(glvlib, case, F):
@@ -337,7 +332,7 @@ def test_track_calls_equal_sequential_calls(glvlib, entry, chain, F):
     pitch = n + (most + 3) * hop if old else (n + most * hop + 38) | 1  # (the residue entry takes multiples of the hop only)
     x = _pcm(600 + F + hop, streams, pitch)
     x[:, 2 * hop:2 * hop + n, :] = 0
-    d_pcm = _device(x, not old)                                        # (the windows entry: one frame behind an 8-byte boundary)
+    d_pcm = to_device(x, not old, False)                               # (the windows entry: one frame behind an 8-byte boundary)
     wins = _windows(x, n, hop, 0, most)
     bt, bs = G.Batch(p, streams, GA), G.Batch(p, streams, GA)
     first = F + 1 if F > 1 else 2
@@ -347,7 +342,7 @@ def test_track_calls_equal_sequential_calls(glvlib, entry, chain, F):
         bt.reset(); bs.reset()
         steps, t0, got = sum(chunks), 0, []
         for c in chunks:
-            got.append(_track(bt, d_pcm, pitch, hop, c, ops, n, dt, t0=t0, old=old))
+            got.append(track(bt, "residue" if old else "windows", d_pcm, pitch, hop, c, ops, n, dt, t0=t0))
             assert bt.kernel_name() == "glv_track_scan_kernel" and bt.last_variant() == 0
             t0 += c
         got = torch.cat(got)

@@ -19,16 +19,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_lib import eq as _eq
 from oracle_lib import Oracle, StreamOracle, lcg_pcm_fast
 
 pytestmark = pytest.mark.gpu
-
-
-def _eq(a, b):
-    import torch
-    ia = a.view(torch.int32) if a.dtype == torch.float32 else a
-    ib = b.view(torch.int32) if b.dtype == torch.float32 else b
-    return bool(torch.equal(ia, ib))
 
 
 @pytest.mark.parametrize("n,F,win,log_mode", [(256, 5, True, 1), (512, 5, True, 0), (1024, 5, True, 1), (1024, 6, False, 0), (2048, 2, True, 1),

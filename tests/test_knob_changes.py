@@ -13,23 +13,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_track_columns as tc
-import test_track_f32 as tf
-import test_track_live as tl
-import test_track_windows as tw
-from glava_amd.bar_positions import radial_bar_texels
+from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
+from gpu_lib import SIZES, bits, float_schedule, gl_schedule, oracle_bars as _oracle_bars, updates_of
 from oracle_lib import Oracle, StreamOracle, lcg_pcm_fast
-from test_forced_grid import SIZES
-from test_knob_changes_host import float_schedule, gl_schedule, updates_of
-from test_smooth_shape import _oracle_bars
+from track_lib import eq, hop_windows, pcm, pitch_odd, rec, seq, to_device, track
 
 pytestmark = pytest.mark.gpu
 
 KNOBS = ("ur", "gravity_step", "fft_scale", "fft_cutoff", "avg_window", "channels", "avg_window_kind")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _same(got, want, what):
@@ -530,7 +521,7 @@ TRACK_STEPS = TRACK_F + 2
 
 
 def _track_case(G, entry):
-    """-> (make, base parameters, ops, output width, hop, f32, pieces, call(b, d_pcm, pitch, t0) of one piece, the module whose helpers cut the windows)"""
+    """-> (make, base parameters, ops, output width, hop, f32, pieces, call(b, d_pcm, pitch, t0) of one piece)"""
     n, F = TRACK_N, TRACK_F
     GA = G.OP_GRAVITY | G.OP_AVERAGE
     S = TRACK_STEPS
@@ -538,17 +529,17 @@ def _track_case(G, entry):
         base = dict(n=n, avg_frames=F, log_mode=0)
         ops, hop, f32 = G.OP_FFT | GA, (256 if entry == "track" else 735), entry.endswith("f32")
         make = lambda p: G.Batch(p, TRACK_STREAMS, GA)                                                                    # noqa: E731
-        if f32: call = lambda b, d, pitch, t0: tf._track(b, d, pitch, hop, S, ops, n, _f32dt(), t0=t0)                    # noqa: E731
-        else: call = lambda b, d, pitch, t0: tw._track(b, d, pitch, hop, S, ops, n, _f32dt(), t0=t0, old=entry == "track")  # noqa: E731
+        form = "residue" if entry == "track" else "windows"
+        call = lambda b, d, pitch, t0: track(b, form, d, pitch, hop, S, ops, n, _f32dt(), t0=t0, f32=f32)                  # noqa: E731
         return make, base, ops, n, hop, f32, _pieces(False), call
     if entry == "track_live":
         base = dict(n=n, avg_frames=F, log_mode=0, bars=80)
         ops, hop = G.OP_FFT | GA | G.OP_BARS, 735
         make = lambda p: G.Batch(p, TRACK_STREAMS, GA | G.OP_BARS | G.OP_BARS_ONLY)                                       # noqa: E731
-        call = lambda b, d, pitch, t0: tl._track(b, d, pitch, hop, S, ops, 80, _f32dt(), t0=t0)                            # noqa: E731
+        call = lambda b, d, pitch, t0: track(b, "live", d, pitch, hop, S, ops, 80, _f32dt(), t0=t0)    # noqa: E731
         pieces = [dict(k, smooth_factor=f) for k, f in zip(_pieces(False), (0.025, 0.05, 0.0125))]
         return make, base, ops, 80, hop, False, pieces, call
-    table = tc._table(n, 100)
+    table = np.ascontiguousarray(graph_column_texels(n, 100)[0], np.int64)
     base = dict(n=n, avg_frames=F, avg_window_kind=1, gl_storage=1, log_mode=0, bars=len(table))
     ops, hop = G.OP_FFT | GA | G.OP_BARS, 735
 
@@ -556,7 +547,7 @@ def _track_case(G, entry):
         b = G.Batch(p, TRACK_STREAMS, GA | G.OP_BARS)
         b.set_column_texels(table)
         return b
-    call = lambda b, d, pitch, t0: tc._track(b, d, pitch, hop, S, ops, len(table), t0=t0)                                  # noqa: E731
+    call = lambda b, d, pitch, t0: track(b, "columns", d, pitch, hop, S, ops, len(table), _f32dt(), t0=t0)    # noqa: E731
     pieces = [dict(k, smooth_factor=f) for k, f in zip(_pieces(True), (0.025, 0.05, 0.0125))]
     return make, base, ops, len(table), hop, False, pieces, call
 
@@ -575,29 +566,28 @@ def test_track_calls_cut_at_a_knob_change_equal_the_sequential_calls(glvlib, ora
     G = glvlib
     make, base, ops, w, hop, f32, pieces, call = _track_case(G, entry)
     n, S = TRACK_N, TRACK_STEPS
-    m = tf if f32 else tw
     more = lambda k: {key: k[key] for key in ("smooth_factor",) if key in k}                                             # noqa: E731
     bt, bs = make(_params(G, base, pieces[0], **more(pieces[0]))), make(_params(G, base, pieces[0], **more(pieces[0])))
     if entry == "track_live": assert bt.live_bins() > 0
     # glv_batch_track_s16 wants a pitch that is a multiple of its hop; the other entries take an odd pitch and a recording one frame behind an aligned address
-    pitch = n + (3 * S + 3) * hop if entry == "track" else m._pitch(n, hop, 3 * S + 1)
-    x = np.array(tf._rec(7100, TRACK_STREAMS, pitch), copy=True) if f32 else tw._pcm(7100, TRACK_STREAMS, pitch)
-    d_pcm = m._device(x, entry != "track")
-    wins = m._windows(x, n, hop, 0, 3 * S + 1)
+    pitch = n + (3 * S + 3) * hop if entry == "track" else pitch_odd(n, hop, 3 * S + 1)
+    x = np.array(rec(7100, TRACK_STREAMS, pitch), copy=True) if f32 else pcm(7100, TRACK_STREAMS, pitch)
+    d_pcm = to_device(x, entry != "track", f32)
+    wins = hop_windows(x, n, hop, 0, 3 * S + 1)
     sos = [StreamOracle(n, avg_frames=TRACK_F) for _ in range(TRACK_STREAMS)] if entry == "track_windows" else []
     for i, k in enumerate(pieces):
         for b in (bt, bs): b.set_params(_params(G, base, k, **more(k)))
         got = call(bt, d_pcm, pitch, i * S)
-        want = m._seq(bs, wins[i * S:(i + 1) * S], ops, w, torch.float32)
+        want = seq(bs, wins[i * S:(i + 1) * S], ops, w, torch.float32, f32)
         for t in range(S):
-            assert tw._eq(got[t], want[t]), (entry, i, t, int((got[t].view(torch.int32) != want[t].view(torch.int32)).sum()))
+            assert eq(got[t], want[t]), (entry, i, t, int((got[t].view(torch.int32) != want[t].view(torch.int32)).sum()))
         assert bool((got != 0).any())
         host = got.cpu().numpy()
         for s, so in enumerate(sos):
             for t in range(S):
                 _same(host[t, 2 * s:2 * s + 2], _oracle_frame(so, np.ascontiguousarray(x[s, (i * S + t) * hop:(i * S + t) * hop + n]), k), ("oracle", i, t, s))
         if entry == "track_live": assert bt.live_bins() > 0
-    assert tw._eq(m._seq(bt, wins[3 * S:], ops, w, torch.float32), m._seq(bs, wins[3 * S:], ops, w, torch.float32)), (entry, "state")
+    assert eq(seq(bt, wins[3 * S:], ops, w, torch.float32, f32), seq(bs, wins[3 * S:], ops, w, torch.float32, f32)), (entry, "state")
     bt.close(); bs.close()
 
 
@@ -625,7 +615,7 @@ def test_a_refused_change_leaves_a_batch_with_bar_texels_as_it_was(glvlib):
     def step(u):
         d = torch.from_numpy(_frames(8100, u, streams, n, levels=(16, 4, 64))).cuda()
         b.process_s16(d, o, ops); twin.process_s16(d, o2, ops)
-        assert tw._eq(o, o2), u
+        assert eq(o, o2), u
         assert b.last_launches() == twin.last_launches()
     for u in range(2): step(u)
     other = dict(fft_scale=7.0, fft_cutoff=0.5, smooth_factor=0.06, gravity_step=1.0, ur=50.0, log_mode=0)
@@ -655,7 +645,7 @@ def test_a_refused_change_leaves_a_batch_that_ran_its_live_class_as_it_was(glvli
     def step(u):
         d = torch.from_numpy(_frames(8200, u, streams, n, levels=(16, 4, 64))).cuda()
         b.process_s16(d, o, ops); twin.process_s16(d, o2, ops)
-        assert tw._eq(o, o2), (u, int((o != o2).sum()))
+        assert eq(o, o2), (u, int((o != o2).sum()))
         assert b.last_launches() == twin.last_launches() == 2
     for u in range(F + 1): step(u)
     L = b.live_bins()
@@ -690,6 +680,6 @@ def test_a_forced_grid_survives_set_params(glvlib, oracle):
         o, o2 = _nan(streams * 2, n), _nan(streams * 2, n)
         forced.process_s16(d, o, G.OP_FFT | GA); auto.process_s16(d, o2, G.OP_FFT | GA)
         assert forced.last_grid() == 2 and auto.last_grid() != 2, (u, forced.last_grid(), auto.last_grid())
-        assert tw._eq(o, o2), u
+        assert eq(o, o2), u
         _same(o.cpu().numpy()[:2], _oracle_frame(so, x[0], k), ("oracle", u))
     forced.close(); auto.close()

@@ -6,71 +6,16 @@ mid-sequence behaviour to the reference's compiled operators (their parameters a
 that the GL schedule contains every kind of gravity step the GL_R16 state distinguishes (glv_tables.h gravity_r16_integer_step): the conditions are about
 the inputs, so a schedule that lost one of them fails here, without a device.
 
-Both schedules are defined here and imported by the GPU file."""
+Both schedules are defined in tests/gpu_lib.py, which the GPU file imports them from as well."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from gpu_lib import float_schedule, gl_schedule, updates_of
 from oracle_lib import Oracle, Ref, RefStream, StreamOracle, lcg_pcm_fast
 
 F32 = np.float32
-
-
-def updates_of(F):
-    return 2 * F + 4
-
-
-def float_schedule(updates, seed=2387):
-    """one dict of knobs per update for the float chains.  `ur` and `gravity_step` differ on every update (seeded); fixed positions carry the edge steps --
-    update 1: ur = 0 (the step is +inf, the output -inf; update 2 recovers), 3: gravity_step = 0, 4: a negative step (values rise), 5: a step larger than
-    any magnitude; fft_scale / fft_cutoff change at update 2 and at the last but one; avg_window is switched off at update 3 (and on again at update 9 of
-    schedules that long); channels go 2 -> 1 -> 2 every six updates.  A prefix of a longer schedule is the shorter schedule."""
-    assert updates >= 6
-    rng = np.random.default_rng(seed)
-    out, scale, cutoff, window = [], 10.2, 0.3, True
-    for u in range(updates):
-        ur = float(F32(rng.uniform(40.0, 160.0)))
-        step = float(F32(rng.uniform(0.5, 9.0)))
-        if u == 1: ur = 0.0
-        if u == 3: step = 0.0
-        if u == 4: step = -step
-        if u == 5: step = 1.0e4
-        if u == 2: scale, cutoff = 6.5, 0.55
-        if u == updates - 2: scale, cutoff = 14.0, 0.125
-        if u == 3: window = False
-        if u == 9: window = True
-        out.append(dict(ur=ur, gravity_step=step, fft_scale=scale, fft_cutoff=cutoff, avg_window=window, channels=1 if u % 6 in (2, 3) else 2))
-    return out
-
-
-# the first six updates of the GL schedule: every kind of step, in an order that goes integer -> float -> integer and shows the recovery from ur = 0
-_GL_HEAD = [
-    dict(gravity_step=4.2, ur=86.1328125),                       # the shipped step: integer, D = 3196
-    dict(gravity_step=float(F32(100.5) / F32(65535)), ur=1.0),   # g * 65535 = 100.5: float rounding decides texel by texel
-    dict(gravity_step=1.7, ur=61.0),                             # integer, another D
-    dict(gravity_step=4.2, ur=0.0),                              # +inf: every texel falls to 0
-    dict(gravity_step=-0.9, ur=75.0),                            # g < 0: values rise, evaluated in float
-    dict(gravity_step=150.0, ur=60.0),                           # g = 2.5: larger than any texel
-]
-
-
-def gl_schedule(updates, seed=728):
-    """one dict per update for the GL_R16 chains: (gravity_step, ur) from _GL_HEAD, then seeded -- every third of those at a half-integer of g * 65535;
-    avg_window off at updates 2 and 3 (and 8); the tilt (fft_scale, fft_cutoff) changes at updates 1 and 4 (and 9)"""
-    assert updates >= len(_GL_HEAD)
-    rng = np.random.default_rng(seed)
-    out, scale, cutoff = [], 10.2, 0.3
-    for u in range(updates):
-        if u < len(_GL_HEAD): k = dict(_GL_HEAD[u])
-        else:
-            k = dict(gravity_step=float(F32(rng.uniform(0.3, 9.0))), ur=float(F32(rng.uniform(40.0, 160.0))))
-            if u % 3 == 1: k = dict(gravity_step=float(F32(int(rng.integers(50, 4000)) + 0.5) / F32(65535)), ur=1.0)
-        if u == 1: scale, cutoff = 7.0, 0.5
-        if u == 4: scale, cutoff = 12.5, 0.2
-        if u == 9: scale, cutoff = 10.2, 0.3
-        out.append(dict(k, fft_scale=scale, fft_cutoff=cutoff, avg_window=u not in (2, 3, 8)))
-    return out
 
 
 def step_of(k):

@@ -20,21 +20,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from make_glsl_golden import SHAPES, tex_row  # noqa: E402
+from gpu_lib import oracle_bars as _oracle_bars  # noqa: E402
 from oracle_lib import Oracle, lcg_pcm_fast  # noqa: E402
 
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "glsl_vectors.npz"))
 ULPS = 8 * 2.0 ** -24
-
-
-def _oracle_bars(row, bars, factor, phase, shape, chunked=False):
-    """the oracle's smooth_audio() of one float row under `shape` = (round_formula, sample_mode, hybrid_weight, scale, range)"""
-    formula, mode, hw, scale, rng = shape
-    with Oracle.smooth_shape(formula, scale, rng):
-        if mode:
-            return Oracle.bars_mode(row, bars, mode, hw or 0.65, factor, phase)
-        out = np.empty(bars, np.float32)
-        (Oracle.lib().glvo_bars_chunked_at if chunked else Oracle.lib().glvo_bars_at)(np.ascontiguousarray(row, np.float32), row.size, out, bars, factor, phase)
-        return out
 
 
 @pytest.mark.parametrize("case", SHAPES, ids=[s[0] for s in SHAPES])

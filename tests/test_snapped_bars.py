@@ -9,42 +9,10 @@ import numpy as np
 import pytest
 
 from glava_amd.bar_positions import bars_module_bar_texels, radial_bar_texels
+from gpu_lib import bars_mask as _mask, eq as _eq, update_inputs as _inputs
 from oracle_lib import Oracle, lcg_pcm_fast
 
 pytestmark = pytest.mark.gpu
-
-
-def _eq(a, b):
-    import torch
-    ia = a.view(torch.int32) if a.dtype == torch.float32 else a
-    ib = b.view(torch.int32) if b.dtype == torch.float32 else b
-    return bool(torch.equal(ia, ib))
-
-
-def _inputs(kind, streams, n, fr):
-    """(method, input tensor, extra args) of one update of input kind `kind`"""
-    import torch
-    div = (1, 8, 64)[fr % 3]
-    pcm = (lcg_pcm_fast(9100 + fr + n, streams * 2 * n) // div).astype(np.int16)
-    if kind == "s16":
-        return "process_s16", torch.from_numpy(pcm).cuda(), ()
-    f = torch.from_numpy(pcm.astype(np.float32) / np.float32(32768)).cuda()
-    if kind == "f32":
-        return "process_f32", f.reshape(streams * 2, n).contiguous(), ()
-    if kind == "f32_stereo":
-        return "process_f32_stereo", f, ()
-    new = 256                                                       # ring updates: 256 new stereo frames per stream
-    if kind == "ring_s16":
-        return "ring_update_s16", torch.from_numpy(pcm[: streams * new * 2].copy()).cuda(), (new,)
-    return "ring_update_f32", f[: streams * new * 2].contiguous(), (new,)
-
-
-def _mask(G, kind, bars_only):
-    m = G.OP_GRAVITY | G.OP_AVERAGE | G.OP_BARS
-    if bars_only: m |= G.OP_BARS_ONLY
-    if kind == "ring_s16": m |= G.OP_RING_S16
-    if kind == "ring_f32": m |= G.OP_RING_F32
-    return m
 
 
 def _run_pair(G, n, tex, streams=5, kind="s16", r16=True, bars_only=True, log_mode=1, gl_storage=1, sample_mode=0, updates=3,

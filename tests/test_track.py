@@ -11,104 +11,30 @@ import numpy as np
 import pytest
 
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
-from oracle_lib import StreamOracle, lcg_pcm_fast
+from oracle_lib import StreamOracle
+from track_lib import S16_CHAIN_NAMES as CHAIN_NAMES, compare_hop, eq as _eq, hop_windows as _windows, pcm as _pcm, pitch_residue as _pitch
+from track_lib import s16_chains as _chains, seq as _seq, track
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
 STEPS, STREAMS = 11, 3          # F = 5: the ring wraps twice; 11 is no multiple of n / hop: the residue launches hold unequal window counts
 
 
-def _eq(a, b):
-    import torch
-    ia = a.view(torch.int32) if a.dtype == torch.float32 else a
-    ib = b.view(torch.int32) if b.dtype == torch.float32 else b
-    return bool(torch.equal(ia, ib))
-
-
-def _pitch(n, hop, steps):
-    return n + (steps - 1) * hop + 3 * hop                          # three hops of slack behind the last window
-
-
-def _pcm(seed, streams, pitch):
-    """int16 [streams][pitch][2], every stream at a level of its own"""
-    x = lcg_pcm_fast(seed, streams * pitch * 2).reshape(streams, pitch, 2).copy()
-    for s in range(streams):
-        x[s] //= (1, 8, 64)[s % 3]
-    return x
-
-
-def _windows(x, n, hop, t0, t1):
-    """the sequential side's inputs: window t of every stream, [streams][n][2] contiguous, for t in [t0, t1)"""
-    import torch
-    return [torch.from_numpy(np.ascontiguousarray(x[:, t * hop:t * hop + n, :])).cuda() for t in range(t0, t1)]
-
-
-def _seq(b, wins, ops, w, dt):
-    import torch
-    outs = []
-    for x in wins:
-        o = torch.zeros((b.streams * 2, w), dtype=dt, device="cuda")
-        b.process_s16(x, o, ops)
-        outs.append(o)
-    torch.cuda.synchronize()
-    return torch.stack(outs)
-
-
-def _track(b, d_pcm, pitch, hop, steps, ops, w, dt, t0=0, stream=None):
-    """steps [t0, t0 + steps) of the buffer in one call; the workspace is exactly as large as the library asks, with a guard behind it"""
-    import torch
-    nbytes = b.track_work_bytes(pitch, hop, steps, ops)
-    work = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    assert work.data_ptr() % 256 == 0
-    out = torch.zeros((steps, b.streams * 2, w), dtype=dt, device="cuda")
-    b.track_s16(d_pcm.data_ptr() + t0 * hop * 4, pitch, hop, steps, out, work, ops, stream=stream)
-    torch.cuda.synchronize()
-    assert bool((work[nbytes:] == 0xA5).all()), "the call wrote behind the workspace it asked for"
-    return out
+def _track(b, *args, **kw):
+    """steps [t0, t0 + steps) of the buffer in one call of glv_batch_track_s16 (track_lib.track: exact workspace and output, guards behind both)"""
+    return track(b, "residue", *args, **kw)
 
 
 def _compare(G, p, mask, ops, n, hop, steps=STEPS, streams=STREAMS, w=None, prepare=None, seed=31):
     """one track call against the sequential calls, every step; returns the two batches (track, sequential) for what follows"""
-    import torch
-    w = n if w is None else w
-    dt = torch.int16 if ops & G.OP_R16 else torch.float32
     pitch = _pitch(n, hop, steps)
     x = _pcm(seed + n + hop, streams, pitch)
     bt, bs = G.Batch(p, streams, mask), G.Batch(p, streams, mask)
     if prepare:
         prepare(bt); prepare(bs)
-    got = _track(bt, torch.from_numpy(x).cuda(), pitch, hop, steps, ops, w, dt)
-    assert bt.last_launches() == n // hop + 1 + (1 if ops & G.OP_BARS else 0), bt.last_launches()
-    assert bt.kernel_name() == "glv_track_scan_kernel"
-    want = _seq(bs, _windows(x, n, hop, 0, steps), ops, w, dt)
-    for t in range(steps):
-        assert _eq(got[t], want[t]), (t, int((got[t] != want[t]).sum()))
+    launches = n // hop + 1 + (1 if ops & G.OP_BARS else 0)
+    compare_hop(G, bt, bs, "residue", x, False, pitch, hop, n, steps, ops, n if w is None else w, launches, "glv_track_scan_kernel", state=False)
     return bt, bs, x, pitch
-
-
-def _chains(G):
-    S, GA = G.OP_GRAVITY, G.OP_GRAVITY | G.OP_AVERAGE
-    return {
-        "fft":             (dict(), G.OP_FFT, G.OP_FFT),
-        "fft_r16":         (dict(), G.OP_FFT, G.OP_FFT | G.OP_R16),
-        "gravity":         (dict(), S, G.OP_FFT | S),
-        "chain":           (dict(), GA, G.OP_FFT | GA),
-        "chain_plain_sum": (dict(avg_window=False, avg_frames=3), GA, G.OP_FFT | GA),
-        "chain_r16":       (dict(), GA, G.OP_FFT | GA | G.OP_R16),
-        "chain_mono":      (dict(channels=1), GA, G.OP_FFT | GA),
-        "average":         (dict(), G.OP_AVERAGE, G.OP_FFT | G.OP_AVERAGE),
-        "gl_gravity":      (dict(gl_storage=1), S, G.OP_FFT | S | G.OP_R16),
-        "gl_chain":        (dict(gl_storage=1, avg_window_kind=1), GA, G.OP_FFT | GA),
-        "gl_chain_r16":    (dict(gl_storage=1, avg_window_kind=1), GA, G.OP_FFT | GA | G.OP_R16),
-        "gl_chain_F1":     (dict(gl_storage=1, avg_frames=1), GA, G.OP_FFT | GA | G.OP_R16),
-        "gl_chain_mono":   (dict(gl_storage=1, channels=1), GA, G.OP_FFT | GA | G.OP_R16),
-        "gl_fft":          (dict(gl_storage=1), G.OP_FFT, G.OP_FFT),
-    }
-
-
-CHAIN_NAMES = ["fft", "fft_r16", "gravity", "chain", "chain_plain_sum", "chain_r16", "chain_mono", "average", "gl_gravity", "gl_chain", "gl_chain_r16",
-               "gl_chain_F1", "gl_chain_mono", "gl_fft"]
 
 
 # ---- 1. the contract against sequential calls ---------------------------------------------------------------------------------------

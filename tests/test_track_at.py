@@ -13,19 +13,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_track_windows as tw
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
 from glava_amd.track_starts import live_update_starts
 from oracle_lib import lcg_pcm_fast
+from track_lib import S16_CHAIN_SIZES, compare, eq as _eq, fft_kernel as _fft_name, launches_fft as _fft_launches, out_dtype as _dt, rec, s16_chains, seq as _seq
+from track_lib import to_device, track, windows
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
 STEPS, STREAMS, F = 11, 3, 5          # F = 5: the ring wraps twice
-
-
-def _eq(a, b):
-    return tw._eq(a, b)
 
 
 def _table(name, n):
@@ -47,125 +43,39 @@ def _table(name, n):
     return s, pitch
 
 
-_RECORDINGS = {}
-
-
-def _rec(seed, pitch, f32, streams=STREAMS):
-    """[streams][pitch][2] int16 or float32, every stream at a level of its own (made once per shape and seed, shared, never written)"""
-    key = (seed, pitch, f32, streams)
-    if key not in _RECORDINGS:
-        if f32:
-            x = (np.random.default_rng(seed).standard_normal((streams, pitch, 2)) * 0.3).astype(np.float32)
-            for s in range(streams):
-                x[s] *= np.float32((1.0, 0.125, 0.015625)[s % 3])
-        else:
-            x = tw._pcm(seed, streams, pitch)
-        x.setflags(write=False)
-        if len(_RECORDINGS) > 48:
-            _RECORDINGS.clear()
-        _RECORDINGS[key] = x
-    return _RECORDINGS[key]
-
-
-def _device(x, n, odd, f32):
-    """the recording on the device, at a load boundary (8 bytes for s16, 16 for f32) or one frame behind one, n frames of another pattern behind it"""
-    import torch
-    per = 2                                                            # values per frame
-    tail = (np.arange(n * per) % 251 + 3).astype(x.dtype)
-    if f32:
-        tail = tail / np.float32(300)
-    flat = torch.zeros((x.size + per * n + 2 * per,), dtype=torch.float32 if f32 else torch.int16, device="cuda")
-    unit = 16 if f32 else 8
-    assert flat.data_ptr() % unit == 0
-    off = per if odd else 0
-    flat[off:off + x.size].copy_(torch.from_numpy(np.array(x, copy=True).reshape(-1)))
-    flat[off + x.size:off + x.size + per * n].copy_(torch.from_numpy(tail))
-    view = flat[off:off + x.size]
-    assert view.data_ptr() % unit == (unit // 2 if odd else 0)
-    return view, flat
-
-
 def _starts_dev(starts):
     import torch
     return torch.from_numpy(np.asarray(starts, dtype=np.uint32).view(np.int32).copy()).cuda()
 
 
-def _windows(G, x, n, pitch, starts):
+def _windows_at(G, x, n, pitch, starts):
     """the sequential side's inputs: the window of every stream at each CLAMPED start, [streams][n][2] contiguous"""
-    import torch
-    at = [G.track_at_start(pitch, n, s) for s in starts]
-    return [torch.from_numpy(np.ascontiguousarray(x[:, a:a + n, :])).cuda() for a in at]
+    return windows(x, n, [G.track_at_start(pitch, n, s) for s in starts])
 
 
-def _seq(b, wins, ops, w, dt, f32):
-    import torch
-    outs = []
-    for x in wins:
-        o = torch.zeros((b.streams * 2, w), dtype=dt, device="cuda")
-        (b.process_f32_stereo if f32 else b.process_s16)(x, o, ops)
-        outs.append(o)
-    torch.cuda.synchronize()
-    return torch.stack(outs)
-
-
-def _dt(G, ops):
-    import torch
-    return torch.int16 if ops & G.OP_R16 else torch.float32
-
-
-def _track_at(b, d_pcm, pitch, d_starts, steps, ops, w, dt, f32, t0=0, stream=None):
-    """steps [t0, t0 + steps) of the table in one call; the workspace is exactly as large as the library asks, with a guard behind it"""
-    import torch
-    nbytes = b.track_at_work_bytes(steps, ops)
-    work = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    assert work.data_ptr() % 256 == 0
-    out = torch.zeros((steps, b.streams * 2, w), dtype=dt, device="cuda")
-    (b.track_at_f32 if f32 else b.track_at_s16)(d_pcm, pitch, d_starts.data_ptr() + 4 * t0, steps, out, work, ops, stream=stream)
-    torch.cuda.synchronize()
-    assert bool((work[nbytes:] == 0xA5).all()), "the call wrote behind the workspace it asked for"
-    if b.last_launches() == 1:
-        assert bool((work[:nbytes] == 0xA5).all()), "a call that runs in one launch touched the workspace"
-    return out
+def _track_at(b, d_pcm, pitch, d_starts, steps, ops, w, dt, f32, **kw):
+    """steps [t0, t0 + steps) of the table in one call (track_lib.track: exact workspace and output, guards behind both)"""
+    return track(b, "at", d_pcm, pitch, d_starts, steps, ops, w, dt, f32=f32, **kw)
 
 
 def _compare(G, bt, bs, ops, n, table, f32=False, odd=False, w=None, seed=31, launches=None, name=None):
     """one table call against the sequential calls, every step, and the state through one more update on both batches"""
-    w = n if w is None else w
-    dt = _dt(G, ops)
     starts, pitch = _table(table, n)
-    x = _rec(seed + n, pitch, f32, bt.streams)
-    d_pcm, keep = _device(x, n, odd, f32)
-    got = _track_at(bt, d_pcm, pitch, _starts_dev(starts), STEPS, ops, w, dt, f32)
-    if launches is not None:
-        assert bt.last_launches() == launches, bt.last_launches()
-    if name is not None:
-        assert bt.kernel_name() == name, bt.kernel_name()
-    wins = _windows(G, x, n, pitch, starts + [7])
-    want = _seq(bs, wins[:STEPS], ops, w, dt, f32)
-    for t in range(STEPS):
-        assert _eq(got[t], want[t]), (table, odd, t, starts[t], int((got[t] != want[t]).sum()))
-    assert _eq(_seq(bt, wins[STEPS:], ops, w, dt, f32), _seq(bs, wins[STEPS:], ops, w, dt, f32)), (table, odd, "state")
-    del keep
-    return got
-
-
-def _fft_launches(G, ops):
-    return tw._launches(G, ops)
-
-
-def _fft_name(G, ops):
-    return "glv_track_scan_kernel" if ops & (G.OP_GRAVITY | G.OP_AVERAGE) else "glv_frame_kernel"
+    x = rec(seed + n, bt.streams, pitch, f32)
+    at = [G.track_at_start(pitch, n, s) for s in starts + [7]]
+    return compare(G, bt, bs, "at", x, to_device(x, odd, f32, tail_frames=n), pitch, _starts_dev(starts), at, n, STEPS, ops, n if w is None else w, launches, name,
+                   f32=f32, what=(table, odd, starts))
 
 
 # ---- 1. the windows form against sequential calls ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("f32", [False, True], ids=["s16", "f32"])
 @pytest.mark.parametrize("odd", [False, True])
 @pytest.mark.parametrize("log_mode", [0, 1])
-@pytest.mark.parametrize("chain,n,variant", tw.CHAIN_SIZES)
+@pytest.mark.parametrize("chain,n,variant", S16_CHAIN_SIZES)
 def test_track_at_equals_sequential_calls(glvlib, chain, n, variant, log_mode, odd, f32):
     """table `frac`: consecutive windows change between the load forms; with the recording one frame off they change the other way round"""
     G = glvlib
-    kw, mask, ops = tw._chains(G)[chain]
+    kw, mask, ops = s16_chains(G)[chain]
     p = G.Params(n=n, log_mode=log_mode, **kw)
     bt, bs = G.Batch(p, STREAMS, mask), G.Batch(p, STREAMS, mask)
     assert bt.variants() > variant
@@ -181,7 +91,7 @@ def test_track_at_equals_sequential_calls(glvlib, chain, n, variant, log_mode, o
 @pytest.mark.parametrize("chain", ["fft", "chain", "gl_chain_r16", "chain_mono"])
 def test_track_at_every_table(glvlib, chain, n, variant, table, f32):
     G = glvlib
-    kw, mask, ops = tw._chains(G)[chain]
+    kw, mask, ops = s16_chains(G)[chain]
     p = G.Params(n=n, **kw)
     bt, bs = G.Batch(p, STREAMS, mask), G.Batch(p, STREAMS, mask)
     bt.set_variant(variant)
@@ -197,12 +107,12 @@ def test_uniform_table_equals_the_hop_entry(glvlib, chain, f32):
     import torch
     G = glvlib
     n, hop = 1024, 45
-    kw, mask, ops = tw._chains(G)[chain]
+    kw, mask, ops = s16_chains(G)[chain]
     p = G.Params(n=n, **kw)
     dt = _dt(G, ops)
     starts, pitch = _table("uniform", n)
-    x = _rec(404, pitch, f32)
-    d_pcm, keep = _device(x, n, True, f32)
+    x = rec(404, STREAMS, pitch, f32)
+    d_pcm = to_device(x, True, f32, tail_frames=n)
     ba, bh = G.Batch(p, STREAMS, mask), G.Batch(p, STREAMS, mask)
     got = _track_at(ba, d_pcm, pitch, _starts_dev(starts), STEPS, ops, n, dt, f32)
     nbytes = bh.track_windows_work_bytes(pitch, hop, STEPS, ops)
@@ -213,10 +123,9 @@ def test_uniform_table_equals_the_hop_entry(glvlib, chain, f32):
     torch.cuda.synchronize()
     assert _eq(got, want)
     assert ba.last_launches() == bh.last_launches() and ba.kernel_name() == bh.kernel_name()
-    one_more = _windows(G, x, n, pitch, [7])
+    one_more = _windows_at(G, x, n, pitch, [7])
     assert _eq(_seq(ba, one_more, ops, n, dt, f32), _seq(bh, one_more, ops, n, dt, f32))
     ba.close(); bh.close()
-    del keep
 
 
 # ---- 3. columns, live and wave -----------------------------------------------------------------------------------------------------------------------
@@ -313,19 +222,19 @@ def test_track_at_chunks_compose_and_calls_mix(glvlib, chain, f32):
     import torch
     G = glvlib
     n = 1024
-    kw, mask, ops = tw._chains(G)[chain]
+    kw, mask, ops = s16_chains(G)[chain]
     p = G.Params(n=n, **kw)
     dt = _dt(G, ops)
     starts, pitch = _table("any_order", n)
-    x = _rec(808, pitch, f32)
-    d_pcm, keep = _device(x, n, True, f32)
+    x = rec(808, STREAMS, pitch, f32)
+    d_pcm = to_device(x, True, f32, tail_frames=n)
     d_starts = _starts_dev(starts)
     whole, parts, mixed, bs = (G.Batch(p, STREAMS, mask) for _ in range(4))
     one = _track_at(whole, d_pcm, pitch, d_starts, STEPS, ops, n, dt, f32)
     a = _track_at(parts, d_pcm, pitch, d_starts, 4, ops, n, dt, f32)
     c = _track_at(parts, d_pcm, pitch, d_starts, 7, ops, n, dt, f32, t0=4)
     assert _eq(torch.cat([a, c]), one)
-    one_more = _windows(G, x, n, pitch, [7])
+    one_more = _windows_at(G, x, n, pitch, [7])
     assert _eq(_seq(parts, one_more, ops, n, dt, f32), _seq(whole, one_more, ops, n, dt, f32))
     # table(5), windows entry at hop 45 (4 steps from frame 9 on), two process calls
     hop, first = 45, 9
@@ -334,13 +243,12 @@ def test_track_at_chunks_compose_and_calls_mix(glvlib, chain, f32):
     mid = torch.zeros((4, STREAMS * 2, n), dtype=dt, device="cuda")
     (mixed.track_windows_f32 if f32 else mixed.track_windows_s16)(d_pcm.data_ptr() + first * (8 if f32 else 4), pitch, hop, 4, mid, work, ops)
     got.append(mid)
-    tail = _windows(G, x, n, pitch, [2 * n + 1, 11])
+    tail = _windows_at(G, x, n, pitch, [2 * n + 1, 11])
     got.append(_seq(mixed, tail, ops, n, dt, f32))
     order = starts[:5] + [first + t * hop for t in range(4)] + [2 * n + 1, 11]
-    want = _seq(bs, _windows(G, x, n, pitch, order), ops, n, dt, f32)
+    want = _seq(bs, _windows_at(G, x, n, pitch, order), ops, n, dt, f32)
     assert _eq(torch.cat(got), want)
     for b in (whole, parts, mixed, bs): b.close()
-    del keep
 
 
 # ---- 5. refusals -------------------------------------------------------------------------------------------------------------------------------------
@@ -351,10 +259,10 @@ def test_track_at_refusals_leave_the_batch_untouched(glvlib):
     GA = G.OP_GRAVITY | G.OP_AVERAGE
     ops = G.OP_FFT | GA
     starts, pitch = _table("any_order", n)
-    x = _rec(3, pitch, False)
-    d_pcm, keep = _device(x, n, False, False)
-    xf = _rec(3, pitch, True)
-    d_pcmf, keepf = _device(xf, n, True, True)
+    x = rec(3, STREAMS, pitch, False)
+    d_pcm = to_device(x, False, False, tail_frames=n)
+    xf = rec(3, STREAMS, pitch, True)
+    d_pcmf = to_device(xf, True, True, tail_frames=n)
     d_starts = _starts_dev(starts)
     p = G.Params(n=n)
     b = G.Batch(p, STREAMS, GA | G.OP_BARS)
@@ -399,18 +307,17 @@ def test_track_at_refusals_leave_the_batch_untouched(glvlib):
     live = G.Batch(G.Params(n=n, gl_storage=1), STREAMS, GA | G.OP_BARS | G.OP_BARS_ONLY)
     refused(live, G.ERR_INVALID, query=True)                                       # the live form's own ops rule: bars are part of the call
     mixed = G.Batch(p, STREAMS, GA)
-    mixed.process_s16(_windows(G, x, n, pitch, [0])[0], out[0].clone(), G.OP_FFT | G.OP_GRAVITY)
+    mixed.process_s16(_windows_at(G, x, n, pitch, [0])[0], out[0].clone(), G.OP_FFT | G.OP_GRAVITY)
     refused(mixed, G.ERR_STATE)                                                    # the gravity form mix, as a process call refuses it
     for x_ in (gl2, unannounced, live, mixed): x_.close()
     torch.cuda.synchronize()
     assert _eq(out, before), "a refused call wrote to the output"
     # after all the refused calls the batch continues from untouched state: steps [2, 11) here == sequential all the way on a fresh batch
     bs = G.Batch(p, STREAMS, GA | G.OP_BARS)
-    want = _seq(bs, _windows(G, x, n, pitch, starts), ops, n, torch.float32, False)
+    want = _seq(bs, _windows_at(G, x, n, pitch, starts), ops, n, torch.float32, False)
     got = _track_at(b, d_pcm, pitch, d_starts, STEPS - 2, ops, n, torch.float32, False, t0=2)
     assert _eq(before[:2], want[:2]) and _eq(got, want[2:])
     b.close(); bs.close()
-    del keep, keepf
 
 
 # ---- 6. graph capture: the table is read when the kernels run ----------------------------------------------------------------------------------------
@@ -427,8 +334,8 @@ def test_a_captured_call_is_reaimed_by_rewriting_the_table(glvlib):
     table_a, pitch = _table("any_order", n)
     table_a = table_a[:F]
     table_b = [3 * n, 1, pitch, 17, n + 5]                                         # (pitch: clamped)
-    x = _rec(9, pitch, False)
-    d_pcm, keep = _device(x, n, True, False)
+    x = rec(9, STREAMS, pitch, False)
+    d_pcm = to_device(x, True, False, tail_frames=n)
     bg, be = G.Batch(p, STREAMS, GA), G.Batch(p, STREAMS, GA)
     work = torch.zeros((bg.track_at_work_bytes(F, ops),), dtype=torch.uint8, device="cuda")
     og = torch.zeros((F, STREAMS * 2, n), dtype=torch.int16, device="cuda")
@@ -457,8 +364,7 @@ def test_a_captured_call_is_reaimed_by_rewriting_the_table(glvlib):
         torch.cuda.synchronize()
         assert hip.hipGraphLaunch(exe, sp) == 0
         st.synchronize()
-        want = _seq(be, _windows(G, x, n, pitch, table), ops, n, torch.int16, False)
+        want = _seq(be, _windows_at(G, x, n, pitch, table), ops, n, torch.int16, False)
         assert _eq(og, want), table
     hip.hipGraphExecDestroy(exe); hip.hipGraphDestroy(graph)
     bg.close(); be.close()
-    del keep

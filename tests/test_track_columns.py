@@ -2,8 +2,8 @@
 
 Contract (glv_batch_track_windows_s16's with columns as the output): the columns of step t and the batch's state afterwards are bit for bit what `steps`
 consecutive glv_batch_process_s16 (glv_batch_process_f32_stereo) calls with the same column table produce and leave behind.  The sequential side is a
-second batch driven window by window, the windows cut on the host from the same recording (the helpers of tests/test_track_windows.py and
-tests/test_track_f32.py); floats are compared as int32.  Every call gets a workspace of exactly glv_batch_track_columns_work_bytes bytes and an output of
+second batch driven window by window, the windows cut on the host from the same recording (the helpers of
+tests/track_lib.py); floats are compared as int32.  Every call gets a workspace of exactly glv_batch_track_columns_work_bytes bytes and an output of
 exactly steps * streams * 2 * cols floats, each followed by a guard region that must come back intact.
 
 Two table widths per size: with the narrow one the process call fuses the columns into the transform's launch, with the wide one it runs
@@ -15,18 +15,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_track_f32 as tf
-import test_track_windows as tw
 from glava_amd.bar_positions import graph_column_texels
+from track_lib import compare_hop, eq as _eq, hop_windows, pcm, pitch_odd, rec, seq as _seq, to_device, track
 
 pytestmark = pytest.mark.gpu
 
-GUARD = tw.GUARD
 STEPS, STREAMS = 11, 3          # F = 5: the ring wraps twice
 LANES = {256: 16, 1024: 64, 4096: 128}                      # lanes per row of the sizes' default kernel configuration
 WIDTHS = {256: (40, 200), 1024: (100, 320), 4096: (320, 800)}
 F = np.float32
-_eq = tw._eq
 
 
 def _table(n, W):
@@ -53,37 +50,20 @@ def _pair(G, n, table, kw, state, streams=STREAMS, count=2):
     return bs
 
 
-def _track(b, d_pcm, pitch, hop, steps, ops, cols, t0=0, f32=False, stream=None, fill=0xA5):
-    """steps [t0, t0 + steps) of the recording in one call; workspace and output exactly as large as documented, a guard behind each"""
+def _track(b, d_pcm, pitch, hop, steps, ops, cols, **kw):
+    """steps [t0, t0 + steps) of the recording in one call (track_lib.track: workspace and output exactly as large as documented, a guard behind each)"""
     import torch
-    nbytes = b.track_columns_work_bytes(pitch, hop, steps, ops)
-    work = torch.full((nbytes + GUARD,), fill, dtype=torch.uint8, device="cuda")
-    assert work.data_ptr() % 256 == 0
-    count = steps * b.streams * 2 * cols
-    out = torch.full((count + GUARD,), -7.0, dtype=torch.float32, device="cuda")
-    (b.track_columns_f32 if f32 else b.track_columns_s16)(d_pcm.data_ptr() + t0 * hop * (8 if f32 else 4), pitch, hop, steps, out, work, ops, stream=stream)
-    torch.cuda.synchronize()
-    assert bool((work[nbytes:] == fill).all()), "the call wrote behind the workspace it asked for"
-    assert bool((out[count:] == -7.0).all()), "the call wrote behind its output"
-    return out[:count].view(steps, b.streams * 2, cols)
+    return track(b, "columns", d_pcm, pitch, hop, steps, ops, cols, torch.float32, **kw)
 
 
 def _compare(G, bt, bs, ops, n, hop, cols, seq_launches, steps=STEPS, odd=False, seed=31, f32=False, x=None):
     """one call against the sequential calls, every step, and the state through one more update on both"""
-    import torch
-    m = tf if f32 else tw
-    pitch = m._pitch(n, hop, steps + 1)                                  # odd
+    pitch = pitch_odd(n, hop, steps + 1)
     if x is None:
-        x = tf._rec(seed + n + hop, bt.streams, pitch) if f32 else tw._pcm(seed + n + hop, bt.streams, pitch)
-    got = _track(bt, m._device(x, odd), pitch, hop, steps, ops, cols, f32=f32)
-    assert bt.last_launches() == 3 and bt.kernel_name() == "glv_columns_kernel"
-    wins = m._windows(x, n, hop, 0, steps + 1)
-    want = m._seq(bs, wins[:steps], ops, cols, torch.float32)
+        x = (rec if f32 else pcm)(seed + n + hop, bt.streams, pitch)
+    got = compare_hop(G, bt, bs, "columns", x, odd, pitch, hop, n, steps, ops, cols, 3, "glv_columns_kernel", f32=f32)
     assert bs.last_launches() == seq_launches, (bs.last_launches(), seq_launches)
-    for t in range(steps):
-        assert _eq(got[t], want[t]), (hop, odd, t, int((got[t].view(torch.int32) != want[t].view(torch.int32)).sum()))
     assert bool((got != 0).any())
-    assert _eq(m._seq(bt, wins[steps:], ops, cols, torch.float32), m._seq(bs, wins[steps:], ops, cols, torch.float32)), (hop, odd, "state")
     return got
 
 
@@ -127,11 +107,11 @@ def test_track_columns_equal_the_twins_texels_through_the_contract(glvlib, n):
     G = glvlib
     kw, state = _chains(G)["chain"]
     hop = 37
-    pitch = tw._pitch(n, hop, STEPS)
-    x = tw._pcm(1234 + n, STREAMS, pitch)
-    d_pcm = tw._device(x, True)
+    pitch = pitch_odd(n, hop, STEPS)
+    x = pcm(1234 + n, STREAMS, pitch)
+    d_pcm = to_device(x, True, False)
     twin = G.Batch(G.Params(n=n, bars=n, bar_phase=0.5, gl_storage=1, **kw), STREAMS, state | G.OP_BARS)
-    texels = tw._track(twin, d_pcm, pitch, hop, STEPS, G.OP_FFT | G.OP_BARS | G.OP_R16 | state, n, torch.int16).cpu().numpy().view(np.uint16)
+    texels = track(twin, "windows", d_pcm, pitch, hop, STEPS, G.OP_FFT | G.OP_BARS | G.OP_R16 | state, n, torch.int16).cpu().numpy().view(np.uint16)
     T = (texels.astype(F) / F(65535)).astype(F)
     for W in WIDTHS[n]:
         table = _table(n, W)
@@ -154,8 +134,8 @@ def test_track_columns_f32_equal_sequential_calls(glvlib, n, wide):
     kw, state = _chains(G)["chain"]
     table = _table(n, WIDTHS[n][wide])
     hop = 37
-    pitch = tf._pitch(n, hop, STEPS + 1)
-    x = tf._rec(7000 + n, STREAMS, pitch).copy()
+    pitch = pitch_odd(n, hop, STEPS + 1)
+    x = rec(7000 + n, STREAMS, pitch).copy()
     view = x.reshape(STREAMS, -1)
     for s in range(STREAMS):
         for k, v in enumerate(np.array([-0.0, np.inf, -np.inf, np.nan, 1e-40, -1e-40, 1.4e-45], np.float32)):
@@ -181,24 +161,24 @@ def test_track_columns_chunks_compose_and_mix_with_process_calls(glvlib, chain):
     table = _table(n, 320)
     cols = len(table)
     ops = G.OP_FFT | G.OP_BARS | state
-    pitch = tw._pitch(n, hop, STEPS + 3)
-    x = tw._pcm(77, STREAMS, pitch)
-    d_pcm = tw._device(x, True)
-    wins = tw._windows(x, n, hop, 0, STEPS + 3)
+    pitch = pitch_odd(n, hop, STEPS + 3)
+    x = pcm(77, STREAMS, pitch)
+    d_pcm = to_device(x, True, False)
+    wins = hop_windows(x, n, hop, 0, STEPS + 3)
     bw, bs, bc, bm = _pair(G, n, table, kw, state, count=4)
-    seq = tw._seq(bs, wins, ops, cols, torch.float32)                             # all sequential, STEPS + 3 updates
+    seq = _seq(bs, wins, ops, cols, torch.float32)                             # all sequential, STEPS + 3 updates
     whole = _track(bw, d_pcm, pitch, hop, STEPS, ops, cols)
     assert _eq(whole, seq[:STEPS])
-    assert _eq(tw._seq(bw, wins[STEPS:], ops, cols, torch.float32), seq[STEPS:])  # a track call followed by process calls
+    assert _eq(_seq(bw, wins[STEPS:], ops, cols, torch.float32), seq[STEPS:])  # a track call followed by process calls
     first = _track(bc, d_pcm, pitch, hop, 4, ops, cols)
     rest = _track(bc, d_pcm, pitch, hop, 7, ops, cols, t0=4)
     assert _eq(torch.cat([first, rest]), whole)
-    assert _eq(tw._seq(bc, wins[STEPS:], ops, cols, torch.float32), seq[STEPS:])
+    assert _eq(_seq(bc, wins[STEPS:], ops, cols, torch.float32), seq[STEPS:])
     a = _track(bm, d_pcm, pitch, hop, 3, ops, cols)
-    mid = tw._seq(bm, wins[3:4], ops, cols, torch.float32)
+    mid = _seq(bm, wins[3:4], ops, cols, torch.float32)
     c = _track(bm, d_pcm, pitch, hop, 7, ops, cols, t0=4)
     assert _eq(torch.cat([a, mid, c]), whole)
-    assert _eq(tw._seq(bm, wins[STEPS:], ops, cols, torch.float32), seq[STEPS:])
+    assert _eq(_seq(bm, wins[STEPS:], ops, cols, torch.float32), seq[STEPS:])
     # ... and with the other track calls, the table cleared in between: windows(5) on the bars of glv_params, then the columns of steps [5, 11)
     bx, = _pair(G, n, table, kw, state, count=1)
     bx.set_column_texels(None)
@@ -221,8 +201,8 @@ def test_first_track_columns_call_can_be_captured_and_replayed(glvlib):
     table = _table(n, 320)
     cols = len(table)
     ops = G.OP_FFT | G.OP_BARS | state
-    pitch = tw._pitch(n, hop, Fr)
-    d_pcm = tw._device(tw._pcm(9, STREAMS, pitch), True)
+    pitch = pitch_odd(n, hop, Fr)
+    d_pcm = to_device(pcm(9, STREAMS, pitch), True, False)
     bg, be = _pair(G, n, table, kw, state)
     work = torch.zeros((bg.track_columns_work_bytes(pitch, hop, Fr, ops),), dtype=torch.uint8, device="cuda")
     og = torch.zeros((Fr, STREAMS * 2, cols), dtype=torch.float32, device="cuda")
@@ -271,11 +251,11 @@ def test_track_columns_read_nothing_no_stage_wrote(glvlib, sample_mode):
     table = _table(n, 320)
     cols = len(table)
     ops = G.OP_FFT | G.OP_BARS | state
-    pitch = tw._pitch(n, hop, STEPS)
-    x = tw._pcm(4321, STREAMS, pitch)
-    d_pcm = tw._device(x, False)
+    pitch = pitch_odd(n, hop, STEPS)
+    x = pcm(4321, STREAMS, pitch)
+    d_pcm = to_device(x, False, False)
     (bs,) = _pair(G, n, table, kw, state, count=1)
-    want = tw._seq(bs, tw._windows(x, n, hop, 0, STEPS), ops, cols, torch.float32)
+    want = _seq(bs, hop_windows(x, n, hop, 0, STEPS), ops, cols, torch.float32)
     outs = []
     for fill in (0xFF, 0x00):
         (b,) = _pair(G, n, table, kw, state, count=1)
@@ -294,8 +274,8 @@ def test_track_columns_launches_name_query_and_timing(glvlib):
     kw, state = _chains(G)["chain"]
     table = _table(n, 320)
     ops = G.OP_FFT | G.OP_BARS | state
-    pitch = tw._pitch(n, hop, STEPS)
-    d_pcm = tw._device(tw._pcm(12, STREAMS, pitch), False)
+    pitch = pitch_odd(n, hop, STEPS)
+    d_pcm = to_device(pcm(12, STREAMS, pitch), False, False)
     (b,) = _pair(G, n, table, kw, state, count=1)
     up = lambda v: (v + 255) & ~255                                               # noqa: E731
     for steps in (STEPS, 1):
@@ -318,11 +298,11 @@ def test_track_columns_refusals_leave_the_batch_untouched(glvlib):
     table = _table(n, 320)
     cols = len(table)
     ops = G.OP_FFT | G.OP_BARS | state
-    pitch = tw._pitch(n, hop, STEPS)
-    x = tw._pcm(3, STREAMS, pitch)
-    d_pcm = tw._device(x, False)
-    xf = tf._rec(3, STREAMS, pitch)
-    d_f32 = tf._device(xf, False)
+    pitch = pitch_odd(n, hop, STEPS)
+    x = pcm(3, STREAMS, pitch)
+    d_pcm = to_device(x, False, False)
+    xf = rec(3, STREAMS, pitch)
+    d_f32 = to_device(xf, False, True)
     b, bs = _pair(G, n, table, kw, state)
     work = torch.zeros((b.track_columns_work_bytes(pitch, hop, STEPS, ops),), dtype=torch.uint8, device="cuda")
     out = torch.zeros((STEPS, STREAMS * 2, cols), dtype=torch.float32, device="cuda")
@@ -382,7 +362,7 @@ def test_track_columns_refusals_leave_the_batch_untouched(glvlib):
     unannounced.set_column_texels(table)
     refused(unannounced, G.ERR_STATE)                                            # GLV_OP_AVERAGE without its ring
     mixed, = _pair(G, n, table, kw, state, count=1)
-    mixed.process_s16(tw._windows(x, n, hop, 0, 1)[0], out[0].clone(), G.OP_FFT | G.OP_BARS | G.OP_GRAVITY)
+    mixed.process_s16(hop_windows(x, n, hop, 0, 1)[0], out[0].clone(), G.OP_FFT | G.OP_BARS | G.OP_GRAVITY)
     refused(mixed, G.ERR_STATE, query=False)                                     # the gravity form mix
     others += [live, unannounced, mixed]
     # the three existing track entries still refuse a batch with columns set
@@ -400,7 +380,7 @@ def test_track_columns_refusals_leave_the_batch_untouched(glvlib):
     torch.cuda.synchronize()
     assert _eq(out, before), "a refused call wrote to the output"
     # after all the refused calls the batch continues from untouched state: steps [2, 11) here == sequential all the way on a fresh batch
-    want = tw._seq(bs, tw._windows(x, n, hop, 0, STEPS), ops, cols, torch.float32)
+    want = _seq(bs, hop_windows(x, n, hop, 0, STEPS), ops, cols, torch.float32)
     got = _track(b, d_pcm, pitch, hop, STEPS - 2, ops, cols, t0=2)
     assert _eq(before[:2], want[:2]) and _eq(got, want[2:])
     b.close(); bs.close()

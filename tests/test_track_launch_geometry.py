@@ -3,7 +3,7 @@
 Streams are independent, so stream s of a LARGE track call is, bit for bit, what the same recording gives in a SMALL batch: on every step, and in
 the state the call leaves.  The contract tests (test_track*.py) pin the arithmetic to sequential process calls at 3 streams x 11-14 steps, at most 84
 rows, below every cap of every launcher; here one LARGE call past all of them is compared with SMALL batches fed exactly its first and its last five
-streams and driven through sequential process calls, window by window (tw._seq / tf._seq) -- the path the older tests pin to the oracle:
+streams and driven through sequential process calls, window by window (track_lib.seq) -- the path the older tests pin to the oracle:
 
     large   3457 streams x 19 steps = 65 683 windows, 131 366 rows: more than kGridCap workgroups of one row (glv_columns_kernel, glv_bars_kernel) and of
             two (glv_bars_short_kernel), 2053 >= 512 blocks of 64 rows (split_rounds' unsplit form), more than kGridCap x 256 groups of 8 frames
@@ -25,14 +25,10 @@ The last test is one call whose regions lie beyond 4 GiB, at the shape include/g
 import pytest
 
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
-import test_track_f32 as tf
-import test_track_live as tl
-import test_track_windows as tw
+from track_lib import bars_batch, eq as _eq, out_dtype, pitch_odd, s16_chains, seq as _seq, track, with_table, work_regions
 
 pytestmark = pytest.mark.gpu
 
-GUARD = tw.GUARD
-_eq = tw._eq
 N = 256
 FR = 5
 HOP = 45
@@ -78,7 +74,7 @@ class _Rec:
     def __init__(self, n, hop, f32, layout, streams=STREAMS, steps=STEPS, copies=((SOURCE, COPIES),), seed=0):
         import torch
         self.n, self.hop, self.f32, self.streams = n, hop, f32, streams
-        pitch = tw._pitch(n, hop, steps + 1)                             # odd, holds one more window than the call takes: the state check's
+        pitch = pitch_odd(n, hop, steps + 1)                             # odd, holds one more window than the call takes: the state check's
         if layout == "grouped": pitch = (pitch + 7) // 8 * 8
         if layout == "residue": pitch = (pitch + 63) // 64 * 64
         self.pitch = pitch
@@ -123,26 +119,9 @@ def recordings():
 
 # ---- one call, exactly sized buffers --------------------------------------------------------------------------------------------------------------------------
 def _track(b, entry, rec, ops, w, dt, steps=STEPS, fill=0xA5):
-    """steps [0, steps) of the recording in one call of glv_batch_track_<entry>_s16 / _f32 (`residue`: glv_batch_track_s16).  Workspace and output are exactly
-    as large as the library asks and documents, a guard behind each; returns the output and the workspace"""
-    import torch
-    query, call = ("track_work_bytes", "track_s16") if entry == "residue" else (f"track_{entry}_work_bytes", f"track_{entry}_{'f32' if rec.f32 else 's16'}")
-    nbytes = getattr(b, query)(rec.pitch, rec.hop, steps, ops)
-    work = torch.full((nbytes + GUARD,), fill, dtype=torch.uint8, device="cuda")
-    assert work.data_ptr() % 256 == 0
-    work[nbytes:] = 0xA5
-    count = steps * b.streams * 2 * w
-    flat = torch.zeros((count + GUARD,), dtype=dt, device="cuda")
-    flat[count:] = 23130 if dt == torch.int16 else -7.0
-    getattr(b, call)(rec.view.data_ptr(), rec.pitch, rec.hop, steps, flat, work, ops)
-    torch.cuda.synchronize()
-    assert bool((work[nbytes:] == 0xA5).all()), "the call wrote behind the workspace it asked for"
-    assert bool((flat[count:] == (23130 if dt == torch.int16 else -7.0)).all()), "the call wrote behind its output"
-    return flat[:count].view(steps, b.streams * 2, w), work[:nbytes]
-
-
-def _seq(b, wins, ops, w, dt, f32):
-    return tf._seq(b, wins, ops, w, dt) if f32 else tw._seq(b, wins, ops, w, dt)
+    """steps [0, steps) of the recording in one call (track_lib.track: workspace and output exactly as large as the library asks and documents, a guard
+    behind each); returns the output and the workspace"""
+    return track(b, entry, rec.view, rec.pitch, rec.hop, steps, ops, w, dt, f32=rec.f32, fill=fill, keep_work=True)
 
 
 def _rows(x, s0, count=SMALL):
@@ -153,7 +132,7 @@ def _rows(x, s0, count=SMALL):
 def _check(G, make, entry, rec, ops, w, launches, name, stateful, what, streams=STREAMS, steps=STEPS, ends=ENDS, small=SMALL, copies=((SOURCE, COPIES),)):
     """the LARGE call against SMALL batches through sequential process calls, the copies inside the range, and (stateful) one more process call on all"""
     import torch
-    dt = tl._dt(G, ops)
+    dt = out_dtype(G, ops)
     large = make(streams)
     got, work = _track(large, entry, rec, ops, w, dt, steps=steps)
     assert large.last_launches() == launches and large.kernel_name() == name, (what, large.last_launches(), large.kernel_name())
@@ -190,7 +169,7 @@ def _first_size(G, build, entry, hop=HOP):
             continue
         try:
             query = "track_work_bytes" if entry == "residue" else f"track_{entry}_work_bytes"
-            pitch = tw._pitch(n, hop, STEPS + 1)
+            pitch = pitch_odd(n, hop, STEPS + 1)
             getattr(probe, query)((pitch + 63) // 64 * 64 if entry == "residue" else pitch, hop, STEPS, ops)
             return n, make, ops, w
         except G.GlvError:
@@ -202,7 +181,7 @@ def _first_size(G, build, entry, hop=HOP):
 
 def _maker(G, n, kw, mask, table=None, F=FR):
     def make(streams):
-        return tl._with_table(G.Batch(G.Params(n=n, avg_frames=F, **kw), streams, mask), table)
+        return with_table(G.Batch(G.Params(n=n, avg_frames=F, **kw), streams, mask), table)
     return make
 
 
@@ -256,7 +235,7 @@ def test_track_windows_of_a_stream_do_not_depend_on_the_streams_around_it(glvlib
 def test_residue_track_of_a_stream_does_not_depend_on_the_streams_around_it(glvlib, recordings, chain):
     """hop 64, a pitch that is a multiple of 64: n / hop residue launches over the whole frame sequence, then the scan's log_q / residue_rows map at a large k0"""
     G = glvlib
-    kw, mask, ops = tw._chains(G)[chain]
+    kw, mask, ops = s16_chains(G)[chain]
     hop = 64
     n, make, ops, w = _first_size(G, lambda n: (_maker(G, n, kw, mask), ops, n), "residue", hop=hop)
     rec = recordings(n, hop=hop, layout="residue")
@@ -298,15 +277,15 @@ def _live_candidates(G, case):
 def _scan_keeps_less_than_a_row(G, n, kw, table, ops, rec_of):
     """one stream, F + 1 steps on a workspace of 0xFF bytes: the last 64 bins of every row of the scan's region still hold them (a texel or a float the
     scan had written there would have to be 0xFFFF / a NaN of all ones in every row)"""
-    b = tl._make(G, n, kw, table, streams=1)
+    b = bars_batch(G, n, kw, table, FR, 1)
     if b.live_bins() == 0:
         b.close()
         return False
     rec = rec_of(n)
     steps, elem = FR + 1, 2 if kw.get("gl_storage") == 1 else 4
-    _, work = _track(b, "live", rec, ops, kw["bars"], tl._dt(G, ops), steps=steps, fill=0xFF)
+    _, work = _track(b, "live", rec, ops, kw["bars"], out_dtype(G, ops), steps=steps, fill=0xFF)
     b.close()
-    (_, _), (scan, _) = tl._regions(G, work, steps * 2, n, elem, elem)
+    (_, _), (scan, _) = work_regions(work, steps * 2, n, elem, elem)
     tail = scan[:steps * 2 * n * elem].view(steps * 2, n * elem)[:, -64 * elem:]
     return bool((tail == 0xFF).all())
 
@@ -324,11 +303,11 @@ def test_live_track_of_a_stream_does_not_depend_on_the_streams_around_it(glvlib,
             continue
     else:
         raise AssertionError(f"no candidate size of {case} has live bins")
-    probe = tl._make(G, n, kw, table, streams=1)
+    probe = bars_batch(G, n, kw, table, FR, 1)
     assert probe.live_bins() != 0 and probe.live_bins() < n
     probe.close()
     name = {"gl_smallest": "glv_bars_rows_i8_kernel", "float_80": "glv_bars_kernel", "columns": "glv_columns_kernel"}[case]
-    _check(G, lambda streams: tl._make(G, n, kw, table, streams=streams), "live", recordings(n, f32=f32), ops, kw["bars"], 3, name, True, (case, n, f32))
+    _check(G, lambda streams: bars_batch(G, n, kw, table, FR, streams), "live", recordings(n, f32=f32), ops, kw["bars"], 3, name, True, (case, n, f32))
 
 
 # ---- 5. - 7. glv_batch_track_wave_s16 / _f32: stateless --------------------------------------------------------------------------------------------------
@@ -402,7 +381,7 @@ def test_track_call_with_regions_beyond_4_GiB(glvlib):
         ("float chain", dict(), GA, G.OP_FFT | GA, 2, 4, 4),
     ]
     for what, kw, mask, ops, launches, in_bytes, out_bytes in forms:
-        dt = tl._dt(G, ops)
+        dt = out_dtype(G, ops)
         make = _maker(G, n, kw, mask)
         large, ref = make(streams), make(2 * small)
         up = lambda v: (v + 255) & ~255                                  # noqa: E731
@@ -412,15 +391,15 @@ def test_track_call_with_regions_beyond_4_GiB(glvlib):
         assert got.numel() * out_bytes > 2 ** 32 and got.element_size() == out_bytes
         assert large.last_launches() == launches and large.kernel_name() == "glv_track_scan_kernel", (what, large.last_launches(), large.kernel_name())
         del work
-        want = tw._seq(ref, wins[:steps], ops, n, dt)
+        want = _seq(ref, wins[:steps], ops, n, dt)
         mine = torch.cat([_rows(got, s0, small) for s0 in ends], dim=1)
         assert bool((mine != 0).any())
         for t in range(steps):
             assert _eq(mine[t], want[t]), (what, t, int((mine[t] != want[t]).sum()))
         for c in (511, 512, 1022):
             assert _eq(_rows(got, c, 1), _rows(got, 2, 1)), (what, "copy", c, int((_rows(got, c, 1) != _rows(got, 2, 1)).sum()))
-        after = tw._seq(large, [rec.window(steps)], ops, n, dt)
-        assert _eq(torch.cat([_rows(after, s0, small) for s0 in ends], dim=1), tw._seq(ref, wins[steps:], ops, n, dt)), (what, "state")
+        after = _seq(large, [rec.window(steps)], ops, n, dt)
+        assert _eq(torch.cat([_rows(after, s0, small) for s0 in ends], dim=1), _seq(ref, wins[steps:], ops, n, dt)), (what, "state")
         for c in (511, 512, 1022):
             assert _eq(_rows(after, c, 1), _rows(after, 2, 1)), (what, "state of copy", c)
         large.close(); ref.close()

@@ -14,15 +14,12 @@ import numpy as np
 import pytest
 
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
-import test_track_f32 as tf
-import test_track_windows as tw
+from track_lib import bars_batch, eq as _eq, hop_windows, out_dtype as _dt, pcm, pitch_odd, rec, seq as _seq, to_device, track, work_regions
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
 FR = 5
 STEPS, STREAMS = FR + 9, 3          # past kTrackDepth + F: the ring wraps and the look-ahead refills
-_eq = tw._eq
 
 
 def _hop(n):
@@ -47,19 +44,12 @@ def _cases(G):
     }
 
 
-def _with_table(b, table):
-    if table: (b.set_bar_texels if table[0] == "bar" else b.set_column_texels)(table[1])
-    return b
-
-
 def _mask(G):
     return G.OP_GRAVITY | G.OP_AVERAGE | G.OP_BARS
 
 
 def _make(G, n, kw, table, F=FR, streams=STREAMS, live=True, variant=None):
-    b = _with_table(G.Batch(G.Params(n=n, avg_frames=F, **kw), streams, _mask(G) | (G.OP_BARS_ONLY if live else 0)), table)
-    if variant is not None: b.set_variant(variant)
-    return b
+    return bars_batch(G, n, kw, table, F, streams, live, variant)
 
 
 def _choose(G, case, F=FR):
@@ -72,39 +62,20 @@ def _choose(G, case, F=FR):
     raise AssertionError(f"no candidate size of {case} has live bins")
 
 
-def _track(b, d_pcm, pitch, hop, steps, ops, w, dt, t0=0, f32=False, fill=0xA5, entry="live", stream=None, keep_work=False):
-    """steps [t0, t0 + steps) of the recording in one call; the workspace is exactly as large as the library asks, with a guard behind it"""
-    import torch
-    nbytes = getattr(b, f"track_{entry}_work_bytes")(pitch, hop, steps, ops)
-    work = torch.full((nbytes + GUARD,), fill, dtype=torch.uint8, device="cuda")
-    assert work.data_ptr() % 256 == 0
-    work[nbytes:] = 0xA5
-    out = torch.zeros((steps, b.streams * 2, w), dtype=dt, device="cuda")
-    getattr(b, f"track_{entry}_{'f32' if f32 else 's16'}")(d_pcm.data_ptr() + t0 * hop * (8 if f32 else 4), pitch, hop, steps, out, work, ops, stream=stream)
-    torch.cuda.synchronize()
-    assert bool((work[nbytes:] == 0xA5).all()), "the call wrote behind the workspace it asked for"
-    return (out, work[:nbytes]) if keep_work else out
+def _track(b, *args, entry="live", **kw):
+    """steps [t0, t0 + steps) of the recording in one call (track_lib.track: exact workspace and output, guards behind both)"""
+    return track(b, entry, *args, **kw)
 
 
 def _recording(n, hop, steps, seed, f32, streams=STREAMS, odd=True):
     """(host recording, device recording, pitch): int16 or finite float32 samples, -0 among the floats"""
-    m = tf if f32 else tw
-    pitch = m._pitch(n, hop, steps) + 2                                  # odd, with odd slack
+    pitch = pitch_odd(n, hop, steps) + 2                                 # odd, with odd slack
     if f32:
-        x = np.array(m._rec(seed, streams, pitch), copy=True)
+        x = np.array(rec(seed, streams, pitch), copy=True)
         x.reshape(streams, -1)[:, 7::97] = np.float32(-0.0)
     else:
-        x = m._pcm(seed, streams, pitch)
-    return x, m._device(x, odd), pitch
-
-
-def _seq(b, wins, ops, w, dt, f32):
-    return tf._seq(b, wins, ops, w, dt) if f32 else tw._seq(b, wins, ops, w, dt)
-
-
-def _dt(G, ops):
-    import torch
-    return torch.int16 if ops & G.OP_R16 else torch.float32
+        x = pcm(seed, streams, pitch)
+    return x, to_device(x, odd, f32), pitch
 
 
 # ---- 1. equality with the sequential live calls, and with the unflagged track call -------------------------------------------------------------------
@@ -117,7 +88,7 @@ def test_live_track_equals_sequential_live_calls_and_the_unflagged_track(glvlib,
     n, kw, table, ops = _choose(G, case)
     hop, w, dt = _hop(n), kw["bars"], _dt(G, ops)
     x, d_pcm, pitch = _recording(n, hop, STEPS + 1, 900 + n, f32)
-    wins = (tf if f32 else tw)._windows(x, n, hop, 0, STEPS + 1)
+    wins = hop_windows(x, n, hop, 0, STEPS + 1)
     probe = _make(G, n, kw, table, streams=1)
     nv = probe.variants(); probe.close()
     twin_entry = "columns" if table and table[0] == "col" else "windows"
@@ -161,13 +132,6 @@ def _kept_of(region, zeroed, rows, n, elem):
     return ((last + 1 + 63) // 64 * 64).cpu().numpy()
 
 
-def _regions(G, work, rows, n, e1, e2):
-    up = lambda v_: (v_ + 255) & ~255                                    # noqa: E731
-    r1 = up(rows * n * e1)
-    assert work.numel() == r1 + up(rows * n * e2), (work.numel(), r1, e2)
-    return (work[:r1], e1), (work[r1:], e2)
-
-
 @pytest.mark.parametrize("f32", [False, True], ids=["s16", "f32"])
 @pytest.mark.parametrize("case", ["gl_smallest", "gl_shipped", "float_80"])
 def test_the_scan_writes_the_kept_bins_only_and_nothing_unwritten_is_read(glvlib, case, f32):
@@ -178,7 +142,7 @@ def test_the_scan_writes_the_kept_bins_only_and_nothing_unwritten_is_read(glvlib
     n, kw, table, ops = _choose(G, case)
     hop, w, dt = _hop(n), kw["bars"], _dt(G, ops)
     x, d_pcm, pitch = _recording(n, hop, STEPS, 1200 + n, f32)
-    wins = (tf if f32 else tw)._windows(x, n, hop, 0, STEPS)
+    wins = hop_windows(x, n, hop, 0, STEPS)
     bt, bs = _make(G, n, kw, table), _make(G, n, kw, table)
     L = bt.live_bins()
     want = _seq(bs, wins, ops, w, dt, f32)
@@ -190,7 +154,7 @@ def test_the_scan_writes_the_kept_bins_only_and_nothing_unwritten_is_read(glvlib
     bz.close()
     rows = STEPS * STREAMS * 2
     elem = 2 if kw.get("gl_storage") == 1 else 4                        # texel rows all the way (the integer pass) / float rows
-    (rows_ff, scan_ff), (rows_00, scan_00) = _regions(G, work, rows, n, elem, elem), _regions(G, work0, rows, n, elem, elem)
+    (rows_ff, scan_ff), (rows_00, scan_00) = work_regions(work, rows, n, elem, elem), work_regions(work0, rows, n, elem, elem)
     assert (_kept_of(rows_ff[0], rows_00[0], rows, n, elem) == n).all()
     kept = _kept_of(scan_ff[0], scan_00[0], rows, n, elem)
     K = int(kept.max())
@@ -209,7 +173,7 @@ def test_live_track_at_frame_counts(glvlib, case, F):
     n, kw, table, ops = _choose(G, case, F=F)
     hop, w, dt, steps = _hop(n), kw["bars"], _dt(G, ops), F + 9
     x, d_pcm, pitch = _recording(n, hop, steps + 1, 1500 + n + F, False)
-    wins = tw._windows(x, n, hop, 0, steps + 1)
+    wins = hop_windows(x, n, hop, 0, steps + 1)
     bt, bs = _make(G, n, kw, table, F=F), _make(G, n, kw, table, F=F)
     assert bt.live_bins() != 0
     got = _track(bt, d_pcm, pitch, hop, steps, ops, w, dt)
@@ -244,7 +208,7 @@ def test_flagged_batches_without_live_bins_take_the_full_row_form(glvlib, form):
         kw, ops, e1, e2 = _far_sampling(G, n), G.OP_FFT | _mask(G) | G.OP_R16, 2, 2
     hop, w, dt = _hop(n), kw["bars"], _dt(G, ops)
     x, d_pcm, pitch = _recording(n, hop, STEPS + 1, 2100, False)
-    wins = tw._windows(x, n, hop, 0, STEPS + 1)
+    wins = hop_windows(x, n, hop, 0, STEPS + 1)
     bt, bs, bz = _make(G, n, kw, None), _make(G, n, kw, None), _make(G, n, kw, None)
     assert bt.live_bins() == 0
     got, work = _track(bt, d_pcm, pitch, hop, STEPS, ops, w, dt, fill=0xFF, keep_work=True)
@@ -254,7 +218,7 @@ def test_flagged_batches_without_live_bins_take_the_full_row_form(glvlib, form):
     want = _seq(bs, wins[:STEPS], ops, w, dt, False)
     assert _eq(got, want) and bool((got != 0).any())
     rows = STEPS * STREAMS * 2
-    for (reg, e), (zer, _) in zip(_regions(G, work, rows, n, e1, e2), _regions(G, work0, rows, n, e1, e2)):
+    for (reg, e), (zer, _) in zip(work_regions(work, rows, n, e1, e2), work_regions(work0, rows, n, e1, e2)):
         assert (_kept_of(reg, zer, rows, n, e) == n).all(), form
     assert _eq(_seq(bt, wins[STEPS:], ops, w, dt, False), _seq(bs, wins[STEPS:], ops, w, dt, False))
     bt.close(); bs.close(); bz.close()

@@ -12,26 +12,18 @@ import numpy as np
 import pytest
 
 from glava_amd.bar_positions import graph_column_texels, wave_column_texels
-from oracle_lib import Oracle, lcg_pcm_fast
-from test_track import GUARD, STEPS, STREAMS, _eq, _pcm, _pitch, _seq, _windows
-from test_wave import planar_of_s16, same, texel_floats, upload
+from gpu_lib import planar_of_s16, same, texel_floats, upload
+from oracle_lib import Oracle
+from track_lib import compare, eq as _eq, hop_windows as _windows, pcm as _pcm, pitch_residue as _pitch, seq as _seq, track
 
 pytestmark = pytest.mark.gpu
 
+STEPS, STREAMS = 11, 3          # 66 rows
 
-def _track(b, d_pcm, pitch, hop, steps, ops, w, dt, t0=0, stream=None):
-    """steps [t0, t0 + steps) of the buffer in one call; the workspace is exactly as large as the library asks, with a guard behind it"""
-    import torch
-    nbytes = b.track_wave_work_bytes(pitch, hop, steps, ops)
-    work = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    assert work.data_ptr() % 256 == 0
-    out = torch.zeros((steps, b.streams * 2, w), dtype=dt, device="cuda")
-    b.track_wave_s16(d_pcm.data_ptr() + t0 * hop * 4, pitch, hop, steps, out, work, ops, stream=stream)
-    torch.cuda.synchronize()
-    assert bool((work[nbytes:] == 0xA5).all()), "the call wrote behind the workspace it asked for"
-    if b.last_launches() == 1:
-        assert bool((work[:nbytes] == 0xA5).all()), "a call that runs in one launch touched the workspace"
-    return out
+
+def _track(b, *args, **kw):
+    """steps [t0, t0 + steps) of the buffer in one call of glv_batch_track_wave_s16 (track_lib.track: exact workspace and output, guards behind both)"""
+    return track(b, "wave", *args, **kw)
 
 
 def _launches(G, ops, hop, pitch, fusable=True, address=0):
@@ -45,8 +37,6 @@ def _compare(G, p, ops, n, hop, steps=STEPS, streams=STREAMS, w=None, prepare=No
     """one track call against the sequential calls, every step; returns the two batches (track, sequential) for what follows.  seek: the recordings
     begin that many frames into the device buffer -- d_pcm is 4 * seek bytes off the allocation's alignment"""
     import torch
-    w = n if w is None else w
-    dt = torch.int16 if ops & G.OP_R16 else torch.float32
     pitch = _pitch(n, hop, steps) if pitch is None else pitch
     x = _pcm(seed + n + hop, streams, pitch)
     flat = np.concatenate([np.full((seek, 2), 12345, np.int16), x.reshape(-1, 2)])
@@ -58,13 +48,10 @@ def _compare(G, p, ops, n, hop, steps=STEPS, streams=STREAMS, w=None, prepare=No
     assert d_buf.data_ptr() % 32 == 0
     d_pcm = d_buf[seek:]
     assert d_pcm.data_ptr() == d_buf.data_ptr() + 4 * seek
-    got = _track(bt, d_pcm, pitch, hop, steps, ops, w, dt)
     launches = _launches(G, ops, hop, pitch, fusable, 4 * seek)
-    assert bt.last_launches() == launches, (bt.last_launches(), hop, pitch)
-    assert bt.kernel_name() == ("glv_bars_rows_i8_kernel" if ops & G.OP_BARS and launches == 1 else "glv_wave_kernel")      # the first launch, as the process call reports
-    want = _seq(bs, _windows(x, n, hop, 0, steps), ops, w, dt)
-    for t in range(steps):
-        assert _eq(got[t], want[t]), (t, int((got[t] != want[t]).sum()))
+    name = "glv_bars_rows_i8_kernel" if ops & G.OP_BARS and launches == 1 else "glv_wave_kernel"      # the first launch, as the process call reports
+    got = compare(G, bt, bs, "wave", x, d_pcm, pitch, hop, [t * hop for t in range(steps)], n, steps, ops, n if w is None else w, launches, name,
+                  state=False, what=(hop, pitch))
     assert int(got.ne(0).sum()) > 0
     return bt, bs, x, pitch
 

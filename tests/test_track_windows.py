@@ -13,126 +13,25 @@ import numpy as np
 import pytest
 
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
-from oracle_lib import Oracle, StreamOracle, lcg_pcm_fast
+from oracle_lib import Oracle, StreamOracle
+from track_lib import S16_CHAIN_SIZES as CHAIN_SIZES, compare_hop, eq as _eq, fft_kernel, hop_windows as _windows
+from track_lib import launches_fft as _launches, pcm as _pcm, pitch_odd as _pitch, s16_chains as _chains, seq as _seq, to_device, track
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
 STEPS, STREAMS = 11, 3          # F = 5: the ring wraps twice
 
 
-def _eq(a, b):
-    import torch
-    ia = a.view(torch.int32) if a.dtype == torch.float32 else a
-    ib = b.view(torch.int32) if b.dtype == torch.float32 else b
-    return bool(torch.equal(ia, ib))
-
-
-def _pitch(n, hop, steps):
-    return (n + (steps - 1) * hop + 38) | 1                            # odd, slack behind the last window: nothing but "long enough" is asked of it
-
-
-def _pcm(seed, streams, pitch):
-    """int16 [streams][pitch][2], every stream at a level of its own"""
-    x = lcg_pcm_fast(seed, streams * pitch * 2).reshape(streams, pitch, 2).copy()
-    for s in range(streams):
-        x[s] //= (1, 8, 64)[s % 3]
-    return x
-
-
-def _device(x, odd):
-    """the recording on the device: at an 8-byte boundary, or one frame (4 bytes) behind one"""
-    import torch
-    flat = torch.zeros((x.size + 4,), dtype=torch.int16, device="cuda")
-    assert flat.data_ptr() % 8 == 0
-    view = flat[2:2 + x.size] if odd else flat[:x.size]
-    view.copy_(torch.from_numpy(x.reshape(-1)))
-    assert view.data_ptr() % 8 == (4 if odd else 0)
-    return view
-
-
-def _windows(x, n, hop, t0, t1):
-    """the sequential side's inputs: window t of every stream, [streams][n][2] contiguous, for t in [t0, t1)"""
-    import torch
-    return [torch.from_numpy(np.ascontiguousarray(x[:, t * hop:t * hop + n, :])).cuda() for t in range(t0, t1)]
-
-
-def _seq(b, wins, ops, w, dt):
-    import torch
-    outs = []
-    for x in wins:
-        o = torch.zeros((b.streams * 2, w), dtype=dt, device="cuda")
-        b.process_s16(x, o, ops)
-        outs.append(o)
-    torch.cuda.synchronize()
-    return torch.stack(outs)
-
-
-def _launches(G, ops):
-    state = bool(ops & (G.OP_GRAVITY | G.OP_AVERAGE))
-    return 1 + (1 if state else 0) + (1 if ops & G.OP_BARS else 0)
-
-
-def _track(b, d_pcm, pitch, hop, steps, ops, w, dt, t0=0, stream=None, old=False):
-    """steps [t0, t0 + steps) of the buffer in one call; the workspace is exactly as large as the library asks, with a guard behind it"""
-    import torch
-    nbytes = (b.track_work_bytes if old else b.track_windows_work_bytes)(pitch, hop, steps, ops)
-    work = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    assert work.data_ptr() % 256 == 0
-    out = torch.zeros((steps, b.streams * 2, w), dtype=dt, device="cuda")
-    (b.track_s16 if old else b.track_windows_s16)(d_pcm.data_ptr() + t0 * hop * 4, pitch, hop, steps, out, work, ops, stream=stream)
-    torch.cuda.synchronize()
-    assert bool((work[nbytes:] == 0xA5).all()), "the call wrote behind the workspace it asked for"
-    return out
+def _track(b, *args, old=False, **kw):
+    """steps [t0, t0 + steps) of the buffer in one call (track_lib.track: exact workspace and output, guards behind both); old: through the residue entry"""
+    return track(b, "residue" if old else "windows", *args, **kw)
 
 
 def _compare(G, bt, bs, ops, n, hop, steps=STEPS, w=None, odd=False, seed=31):
     """one call against the sequential calls, every step, and the state through one more update on both; the batches start from reset state"""
-    import torch
-    w = n if w is None else w
-    dt = torch.int16 if ops & G.OP_R16 else torch.float32
     pitch = _pitch(n, hop, steps + 1)
     x = _pcm(seed + n + hop, bt.streams, pitch)
-    got = _track(bt, _device(x, odd), pitch, hop, steps, ops, w, dt)
-    assert bt.last_launches() == _launches(G, ops), bt.last_launches()
-    assert bt.kernel_name() == ("glv_track_scan_kernel" if ops & (G.OP_GRAVITY | G.OP_AVERAGE) else "glv_frame_kernel")
-    wins = _windows(x, n, hop, 0, steps + 1)
-    want = _seq(bs, wins[:steps], ops, w, dt)
-    for t in range(steps):
-        assert _eq(got[t], want[t]), (hop, odd, t, int((got[t] != want[t]).sum()))
-    assert _eq(_seq(bt, wins[steps:], ops, w, dt), _seq(bs, wins[steps:], ops, w, dt)), (hop, odd, "state")
-
-
-def _chains(G):
-    S, GA = G.OP_GRAVITY, G.OP_GRAVITY | G.OP_AVERAGE
-    return {
-        "fft":             (dict(), G.OP_FFT, G.OP_FFT),
-        "fft_r16":         (dict(), G.OP_FFT, G.OP_FFT | G.OP_R16),
-        "gravity":         (dict(), S, G.OP_FFT | S),
-        "chain":           (dict(), GA, G.OP_FFT | GA),
-        "chain_plain_sum": (dict(avg_window=False, avg_frames=3), GA, G.OP_FFT | GA),
-        "chain_r16":       (dict(), GA, G.OP_FFT | GA | G.OP_R16),
-        "chain_mono":      (dict(channels=1), GA, G.OP_FFT | GA),
-        "average":         (dict(), G.OP_AVERAGE, G.OP_FFT | G.OP_AVERAGE),
-        "gl_gravity":      (dict(gl_storage=1), S, G.OP_FFT | S | G.OP_R16),
-        "gl_chain":        (dict(gl_storage=1, avg_window_kind=1), GA, G.OP_FFT | GA),
-        "gl_chain_r16":    (dict(gl_storage=1, avg_window_kind=1), GA, G.OP_FFT | GA | G.OP_R16),
-        "gl_chain_F1":     (dict(gl_storage=1, avg_frames=1), GA, G.OP_FFT | GA | G.OP_R16),
-        "gl_chain_mono":   (dict(gl_storage=1, channels=1), GA, G.OP_FFT | GA | G.OP_R16),
-        "gl_fft":          (dict(gl_storage=1), G.OP_FFT, G.OP_FFT),
-    }
-
-
-CHAIN_NAMES = ["fft", "fft_r16", "gravity", "chain", "chain_plain_sum", "chain_r16", "chain_mono", "average", "gl_gravity", "gl_chain", "gl_chain_r16",
-               "gl_chain_F1", "gl_chain_mono", "gl_fft"]
-# (n, kernel configuration): every size and every configuration IN_S16_TRACK is built for.  At 256 / 512 several slots share a wave (the load form's
-# branch may diverge; 512 configuration 1 puts four windows in one wave), 1024 is the smallest size where none does.  The three entries that carry the
-# full chain list came first; the others run the chains that differ in the transform launch: step-major rows straight into d_out (fft, fft_r16),
-# stream-major rows for the scan (chain, gl_chain_r16) and the mono mix
-FULL_SIZES = [(256, 0), (1024, 0), (1024, 1)]
-SIZES = [(256, 0)] + [(n, v) for n in (512, 1024, 2048, 4096, 8192, 16384, 32768) for v in (0, 1)]
-REDUCED_CHAINS = ["fft", "fft_r16", "chain", "gl_chain_r16", "chain_mono"]
-CHAIN_SIZES = [(c, n, v) for c in CHAIN_NAMES for n, v in SIZES if (n, v) in FULL_SIZES or c in REDUCED_CHAINS]
+    compare_hop(G, bt, bs, "windows", x, odd, pitch, hop, n, steps, ops, n if w is None else w, _launches(G, ops), fft_kernel(G, ops))
 
 
 def _hops(n):
@@ -212,7 +111,7 @@ def test_track_windows_equals_the_residue_entry_and_composes(glvlib, chain):
     dt = torch.int16 if ops & G.OP_R16 else torch.float32
     pitch = (STEPS + 4) * hop + n                                                   # a multiple of the hop: the old entry asks for it
     x = _pcm(77, STREAMS, pitch)
-    d_pcm = _device(x, False)
+    d_pcm = to_device(x, False, False)
     wins = _windows(x, n, hop, 0, STEPS + 1)
     bo, bn = G.Batch(p, STREAMS, mask), G.Batch(p, STREAMS, mask)
     old = _track(bo, d_pcm, pitch, hop, STEPS, ops, n, dt, old=True)
@@ -252,7 +151,7 @@ def test_track_windows_float_chain_equals_the_oracle(glvlib, oracle):
     pitch = _pitch(n, hop, STEPS)
     x = _pcm(5150, STREAMS, pitch)
     b = G.Batch(G.Params(n=n, avg_frames=F, log_mode=0), STREAMS, GA)
-    got = _track(b, _device(x, True), pitch, hop, STEPS, G.OP_FFT | GA, n, torch.float32).cpu().numpy()
+    got = _track(b, to_device(x, True, False), pitch, hop, STEPS, G.OP_FFT | GA, n, torch.float32).cpu().numpy()
     s = 1
     so = StreamOracle(n, avg_frames=F)
     for t in range(STEPS):
@@ -271,7 +170,7 @@ def test_track_windows_gl_chain_equals_the_oracle(glvlib, oracle):
     pitch = _pitch(n, hop, STEPS)
     x = _pcm(616, STREAMS, pitch) // 16
     b = G.Batch(G.Params(n=n, avg_frames=F, avg_window_kind=1, gl_storage=1, log_mode=0), STREAMS, GA)
-    got = _track(b, _device(x, False), pitch, hop, STEPS, G.OP_FFT | GA | G.OP_R16, n, torch.int16).cpu().numpy().view(np.uint16)
+    got = _track(b, to_device(x, False, False), pitch, hop, STEPS, G.OP_FFT | GA | G.OP_R16, n, torch.int16).cpu().numpy().view(np.uint16)
     store = np.zeros((STREAMS * 2, n), np.float32); hist = np.zeros((STREAMS * 2, F, n), np.float32)
     heads = [C.c_size_t(0) for _ in range(STREAMS * 2)]
     for t in range(STEPS):
@@ -292,7 +191,7 @@ def test_track_windows_launch_counts_and_workspace(glvlib):
     GA = G.OP_GRAVITY | G.OP_AVERAGE
     pitch = _pitch(n, hop, steps)
     x = _pcm(12, STREAMS, pitch)
-    d_pcm = _device(x, False)
+    d_pcm = to_device(x, False, False)
     R = steps * STREAMS * 2
     up = lambda v: (v + 255) & ~255                                               # noqa: E731
     cases = [   # params, mask, ops, launches, workspace, out width, dtype
@@ -309,14 +208,10 @@ def test_track_windows_launch_counts_and_workspace(glvlib):
         if nbytes is None:      # a GL chain's texel rows; the scan's results as texels where the integer pass takes them, as floats else (as glv_batch_track_s16)
             nbytes = up(R * n * 2) + up(R * n * (2 if b.bars_arithmetic() == G.BARS_I8_EXACT else 4))
         assert b.track_windows_work_bytes(pitch, hop, steps, ops) == nbytes, (kw, ops)
-        work = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-        out = torch.zeros((steps, STREAMS * 2, w), dtype=dt, device="cuda")
-        b.track_windows_s16(d_pcm, pitch, hop, steps, out, work, ops)
-        torch.cuda.synchronize()
+        out = _track(b, d_pcm, pitch, hop, steps, ops, w, dt)                     # (asserts that a one-launch call leaves workspace and guard untouched)
         assert b.last_launches() == launches, (kw, ops, b.last_launches())
         assert b.kernel_name() == ("glv_track_scan_kernel" if ops & GA else "glv_frame_kernel")
         if launches == 1:
-            assert bool((work == 0xA5).all()), "the one-launch call touched the workspace"
             assert bool((out != 0).any())
         b.close()
 
@@ -333,7 +228,7 @@ def test_first_track_windows_call_can_be_captured_and_replayed(glvlib):
     ops = G.OP_FFT | GA | G.OP_R16
     p = G.Params(n=n, gl_storage=1, avg_window_kind=1, avg_frames=F)
     pitch = _pitch(n, hop, F)
-    d_pcm = _device(_pcm(9, STREAMS, pitch), True)
+    d_pcm = to_device(_pcm(9, STREAMS, pitch), True, False)
     bg, be = G.Batch(p, STREAMS, GA), G.Batch(p, STREAMS, GA)
     work = torch.zeros((bg.track_windows_work_bytes(pitch, hop, F, ops),), dtype=torch.uint8, device="cuda")
     og = torch.zeros((F, STREAMS * 2, n), dtype=torch.int16, device="cuda")
@@ -367,7 +262,7 @@ def test_track_windows_refusals_leave_the_batch_untouched(glvlib):
     ops = G.OP_FFT | GA
     pitch = _pitch(n, hop, STEPS)
     x = _pcm(3, STREAMS, pitch)
-    d_pcm = _device(x, False)
+    d_pcm = to_device(x, False, False)
     p = G.Params(n=n)
     b = G.Batch(p, STREAMS, GA | G.OP_BARS)
     work = torch.zeros((b.track_windows_work_bytes(pitch, hop, STEPS, ops | G.OP_BARS),), dtype=torch.uint8, device="cuda")

@@ -4,48 +4,17 @@ Every expectation is bit equality against the models of tests/oracle_lib.py: the
 (glvo_wrange, and the compiled reference's transform_wrange where it is available), the upload rounding (glvo_texels_r16), the pre-smoothing
 pass in its exact integer form (glvo_bars_int_at) and, for sample_mode maximum / hybrid, the shader's float loop (glvo_bars_mode_at).  No
 tolerances.  The GPU tests need GLV_OP_WAVE; the CPU tests at the end need the helper, the constant and the exported symbol."""
-import ctypes as C
 import os
 import re
 
 import numpy as np
 import pytest
 
+from gpu_lib import planar_of_s16, same, texel_floats, upload, wrange
 from oracle_lib import Oracle, Ref, lcg_pcm, lcg_pcm_fast
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
-
-
-def wrange(x, use_ref=False):
-    """transform_wrange (render.c:773-781) of every row of x through the oracle, or through the compiled reference"""
-    x = np.array(x, dtype=np.float32, copy=True)
-    flat = x.reshape(-1, x.shape[-1])
-    for i in range(flat.shape[0]):
-        row = np.ascontiguousarray(flat[i])
-        if use_ref:
-            p = Ref.params()
-            Ref.lib().glvref_wrange(C.byref(p), row, row.size)
-        else:
-            Oracle.lib().glvo_wrange(row, row.size)
-        flat[i] = row
-    return x
-
-
-def upload(planar):
-    """the GL_R16 texels of the wave bind for planar rows [rows][n] (already unpacked): wrange, then the upload rounding"""
-    return Oracle.texels_r16(wrange(planar))
-
-
-def texel_floats(c):
-    return (c.astype(np.float64) / 65535).astype(np.float32)
-
-
-def planar_of_s16(pcm, streams, n, channels=2):
-    rows = np.empty((streams * 2, n), np.float32)
-    for s in range(streams):
-        rows[2 * s], rows[2 * s + 1] = Oracle.unpack_s16(pcm[s * 2 * n:(s + 1) * 2 * n], channels)
-    return rows
 
 
 def planar_of_f32(frames, streams, n, channels=2):
@@ -55,15 +24,6 @@ def planar_of_f32(frames, streams, n, channels=2):
         Oracle.lib().glvo_unpack_f32(np.ascontiguousarray(frames[s * 2 * n:(s + 1) * 2 * n]), n, channels, l, r)
         rows[2 * s], rows[2 * s + 1] = l, r
     return rows
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint16)
-
-
-def same(got, want):
-    return bits(got).shape == bits(want).shape and bool((bits(got) == bits(want)).all())
 
 
 def dev_u16(t):
