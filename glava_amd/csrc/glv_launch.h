@@ -44,6 +44,8 @@ struct TrackGeometry {
     uint32_t residue_rows;     // channel rows between the first rows of two residue launches
     uint32_t out_texels;       // results as GL_R16 texels (uint16 rows) instead of floats
     uint32_t kept;             // bins [0, kept) of every row are walked, loaded and stored, state included: n, or a live track call's kept bins (a multiple of 64)
+    float gravity_step;        // a rates call (glv_batch_track_rates_s16 / _f32): step t applies gravity with gravity_step * (1.0F / ur[t]), render.c:728 evaluated in the
+    const float* ur;           //   kernel's rates kind -- float [steps] in device memory, read in [0, steps) only; nullptr: every other call, FrameArgs::g / grav_sub as they are
 };
 hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool rows_texels, hipStream_t st);
 // Where the windows of the track sources of GLV_OP_WAVE lie (glv_wave_kernel, glv_bars_rows_i8_kernel).  A process call's windows lie back to back -- the

@@ -65,7 +65,14 @@ __global__ void __launch_bounds__(256) glv_post_kernel(const FrameArgs a, const 
 // k = h >> log_q of the residue launch r = h & (q - 1), whose rows start at r * residue_rows.
 constexpr int kTrackLanes = 64;          // one wave per workgroup: with few streams the lanes of a row spread over n / 128 CUs
 constexpr int kTrackDepth = 8;
-template <bool IN16>
+// The rates kind (RATES; glv_batch_track_rates_s16 / _f32): gravity's step changes from update to update, as a live GLava's measured gl->ur does -- step tt
+// applies g = gravity_step * (1.0F / ur[tt]) (render.c:728: a correctly rounded division, then a separate multiply; the units are compiled without contraction),
+// evaluated here because the host cannot see a table in device memory without a synchronise.  The entry of step tt + kTrackDepth is requested with that step's
+// row, in a register ring beside ahead[]: uniform across the workgroup, in [0, steps) only, and like the row never in the dependent chain of a step.  Texel
+// state takes the float expression the pass is defined by at every step (gravity_r16_flt): the host accepts the packed integer step only after checking it
+// against this very expression for all 65 536 texel values (glv_tables.h gravity_r16_integer_step), so the bits are those of the sequential calls whichever
+// arm each of them took.  The other kinds' code has no table in it.
+template <bool IN16, bool RATES = false>
 __global__ void __launch_bounds__(kTrackLanes) glv_track_scan_kernel(const FrameArgs a, const TrackGeometry t) {
     using V = typename std::conditional<IN16, uint32_t, cf>::type;         // one lane's element of a row: a texel pair / a float pair
     extern __shared__ __attribute__((aligned(8))) unsigned char track_lds[];
@@ -98,13 +105,14 @@ __global__ void __launch_bounds__(kTrackLanes) glv_track_scan_kernel(const Frame
     char* const out = reinterpret_cast<char*>(a.out);
     const size_t out_row_bytes = (size_t) t.n * (out16 ? 2u : 4u);
     const uint32_t out_off = pair * (out16 ? 4u : 8u);
-    auto step = [&](V x, uint32_t tt) {
+    auto step = [&](V x, uint32_t tt, float g) {
         char* const o = out + ((size_t) tt * a.units + row) * out_row_bytes;
         if constexpr (IN16) {
             uint32_t tex = x;                                               // apply_state_r16
             if (grav) {
                 const uint32_t store = avg ? ring[(F == 1 ? head : ring_slot(head, F - 2, F)) * kTrackLanes] : gs;
-                tex = gravity_r16(tex, store, a.g, a.grav_sub, a.grav_int);
+                if constexpr (RATES) tex = gravity_r16_flt(tex, store, g);
+                else tex = gravity_r16(tex, store, a.g, a.grav_sub, a.grav_int);
                 if (!avg) gs = tex;
             }
             if (avg) {
@@ -128,13 +136,13 @@ __global__ void __launch_bounds__(kTrackLanes) glv_track_scan_kernel(const Frame
                     prev = ring[ring_slot(head, f, F) * kTrackLanes];
                     average_add(acc, prev, a.wts[f], windowed);
                 }
-                if (grav) { val.x = gravity(val.x, prev.x, a.g); val.y = gravity(val.y, prev.y, a.g); }
+                if (grav) { val.x = gravity(val.x, prev.x, g); val.y = gravity(val.y, prev.y, g); }
                 ring[head * kTrackLanes] = val;
                 average_add(acc, val, a.wts[F - 1], windowed);
                 val = average_end(acc, a.F_as_float);
                 head = head + 1u == F ? 0u : head + 1u;
             } else if (grav) {
-                val.x = gravity(val.x, gs.x, a.g); val.y = gravity(val.y, gs.y, a.g);
+                val.x = gravity(val.x, gs.x, g); val.y = gravity(val.y, gs.y, g);
                 gs = val;
             }
             if (out16) st<uint32_t>(o, out_off, pack_unorm16(val.x, val.y));    // render.c:521-524
@@ -143,16 +151,25 @@ __global__ void __launch_bounds__(kTrackLanes) glv_track_scan_kernel(const Frame
     };
     // ---- the walk
     V ahead[kTrackDepth];
+    float rate[RATES ? kTrackDepth : 1];                                    // the rates kind: ur of the steps whose rows are in flight
 #pragma unroll
-    for (int j = 0; j < kTrackDepth; ++j) ahead[j] = (uint32_t) j < t.steps ? fetch((uint32_t) j) : V();
+    for (int j = 0; j < kTrackDepth; ++j) {
+        ahead[j] = (uint32_t) j < t.steps ? fetch((uint32_t) j) : V();
+        if constexpr (RATES) rate[j] = (uint32_t) j < t.steps ? t.ur[j] : 1.0f;
+    }
     for (uint32_t t0 = 0; t0 < t.steps; t0 += (uint32_t) kTrackDepth) {
 #pragma unroll
         for (int j = 0; j < kTrackDepth; ++j) {
             const uint32_t tt = t0 + (uint32_t) j;
             if (tt >= t.steps) break;
             const V x = ahead[j];
-            if (tt + (uint32_t) kTrackDepth < t.steps) ahead[j] = fetch(tt + (uint32_t) kTrackDepth);
-            step(x, tt);
+            float g = a.g;
+            if constexpr (RATES) g = t.gravity_step * (1.0F / rate[j]);    // render.c:728
+            if (tt + (uint32_t) kTrackDepth < t.steps) {
+                ahead[j] = fetch(tt + (uint32_t) kTrackDepth);
+                if constexpr (RATES) rate[j] = t.ur[tt + (uint32_t) kTrackDepth];
+            }
+            step(x, tt, g);
         }
     }
     // ---- the state the sequential calls would have left
@@ -545,6 +562,12 @@ hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool ro
     const uint64_t blocks = (uint64_t) a.units * ((t.kept + 2u * (uint32_t) kTrackLanes - 1u) / (2u * (uint32_t) kTrackLanes));
     if (t.n < 2u * (uint32_t) kTrackLanes || t.kept == 0 || t.kept > t.n || t.kept % 64u != 0 || t.steps == 0 || blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const size_t lds = (a.ops & OP_AVERAGE) ? (size_t) a.F * kTrackLanes * (rows_texels ? sizeof(uint32_t) : sizeof(cf)) : 0;   // <= 32 KiB (F <= 64)
+    if (t.ur) {                                                             // the rates kind: a table without gravity has no reader
+        if (!(a.ops & OP_GRAVITY)) return hipErrorInvalidValue;
+        if (rows_texels) hipLaunchKernelGGL((glv_track_scan_kernel<true, true>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);
+        else hipLaunchKernelGGL((glv_track_scan_kernel<false, true>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);
+        return hipGetLastError();
+    }
     if (rows_texels) hipLaunchKernelGGL((glv_track_scan_kernel<true>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);
     else hipLaunchKernelGGL((glv_track_scan_kernel<false>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t);
     return hipGetLastError();

@@ -23,6 +23,8 @@ namespace {
 // beyond them -- the rest of every row of the workspace's second region is not written.
 // A table call (glv_batch_track_at_s16 / _f32, plan_track_at: TrackPlan::at) is whichever of the windows, columns and live forms the batch takes, with the
 // windows where a table in device memory says: the transform runs in the kernel kinds that read it (IN_S16_TRACK_AT / IN_F32_TRACK_AT), nothing else differs.
+// A rates call (glv_batch_track_rates_s16 / _f32, track_rates: TrackPlan::ur) is a table call whose scan runs in the kernel's rates kind: gravity's step of
+// update t comes from a second table in device memory, gravity_step * (1.0F / ur[t]) -- the plan, the workspace, the launches and the batch's own ur are the table call's.
 struct TrackPlan {
     uint32_t q = 0, log_q = 0;          // residue launches
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
@@ -40,6 +42,7 @@ struct TrackPlan {
     uint64_t out_rows = 0;              // steps * streams * 2
     bool at = false;                    // the windows lie where a table in device memory says (glv_batch_track_at_s16 / _f32), not every `hop` frames; set before the plan
     const uint32_t* starts = nullptr;   // ... and the table, uint32 [steps]; set by the entry as f32 is (the sizing query has none), windows form only
+    const float* ur = nullptr;          // a rates call's table of update rates, float [steps]; set by track_at as starts is, read by the scan alone
     bool live = false;                  // the entry is the live form (glv_batch_track_live_s16 / _f32)
     uint32_t kept = 0;                  // the live form's kept bins K, a multiple of 64 below n (kept_bins); 0: every bin -- the other entries, and the live form's full-row form
 };
@@ -244,6 +247,7 @@ int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t st
     glv::TrackGeometry g;
     g.n = b->p.n; g.steps = steps; g.hops_per_pitch = tp.hops_per_pitch; g.log_q = tp.log_q; g.residue_rows = tp.residue_rows; g.out_texels = tp.out16 ? 1u : 0u;
     g.kept = tp.kept != 0 ? tp.kept : b->p.n;
+    g.gravity_step = b->p.gravity_step; g.ur = tp.ur;
     const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
     b->kernel_name = "glv_track_scan_kernel";
@@ -390,15 +394,28 @@ uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, ui
     return tp.work_bytes;
 }
 // glv_batch_track_at_s16 / _f32: the table's own refusals, then the form the ops and the batch select -- the wave form's executor, or the FFT forms'.
-int track_at(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+// d_ur: the second table of a rates call (track_rates has vetted it, and that the ops have the gravity that reads it); nullptr: the batch's own ur
+int track_at(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
+             const float* d_ur = nullptr) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_starts) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (reinterpret_cast<uintptr_t>(d_starts) & 3u) return fail(GLV_ERR_INVALID, "d_starts must be 4-byte aligned");
     if (ops & GLV_OP_WAVE) return track_wave(b, d_pcm, f32, pitch_frames, 0u, steps, d_out, d_work, ops, st, d_starts);
     TrackPlan tp;
     if (int rc = plan_track_at(b, pitch_frames, 0u, steps, ops, tp)) return rc;
-    tp.f32 = f32; tp.starts = d_starts;
+    tp.f32 = f32; tp.starts = d_starts; tp.ur = d_ur;
     return track(b, tp, d_pcm, pitch_frames, 0u, steps, d_out, d_work, ops, st);
+}
+// glv_batch_track_rates_s16 / _f32: the rate table's own refusals, then the table call.  The wave form keeps no state and applies no gravity, and a chain
+// without gravity would leave the table unread: both are the caller's mistake, not a call that quietly ignores an argument.
+int track_rates(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
+                unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!d_ur) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_ur) & 3u) return fail(GLV_ERR_INVALID, "d_ur must be 4-byte aligned");
+    if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE is stateless: no gravity reads the rate table (glv_batch_track_at_s16 / _f32; ops 0x%x)", ops);
+    if (!(ops & GLV_OP_GRAVITY)) return fail(GLV_ERR_INVALID, "a rates track call needs GLV_OP_GRAVITY, which reads the rate table (ops 0x%x)", ops);
+    return track_at(b, d_pcm, f32, pitch_frames, d_where, steps, d_out, d_work, ops, st, d_ur);
 }
 }  // namespace
 
@@ -514,5 +531,17 @@ int glv_batch_track_at_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_fr
 int glv_batch_track_at_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work,
                            unsigned ops, void* hip_stream) {
     return track_at(b, d_pcm, true, pitch_frames, d_starts, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (sized by glv_batch_track_at_work_bytes: the rate table adds no region.  d_where is the header's d_starts, handed on whole: tests/test_track_at_host.py pins
+// every entry named glv_batch_track_<form>_s16 / _f32 other than the `at` pair to a body that names no table of starts)
+int glv_batch_track_rates_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
+                              unsigned ops, void* hip_stream) {
+    return track_rates(b, d_pcm, false, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_rates_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
+                              unsigned ops, void* hip_stream) {
+    return track_rates(b, d_pcm, true, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 }  // extern "C"

@@ -108,6 +108,9 @@ def lib() -> C.CDLL:
             L.glv_batch_track_at_work_bytes.restype = C.c_uint64
             L.glv_batch_track_at_s16.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_track_at_f32.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_rates_s16"):     # (likewise: a table call with a second table, the update rate gravity runs at per step)
+            L.glv_batch_track_rates_s16.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_rates_f32.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -329,6 +332,17 @@ class Batch:
         """track_at_s16 from a float recording (glv_batch_track_at_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned; step t
         bit for bit what process_f32_stereo on window t would have written"""
         _check(lib().glv_batch_track_at_f32(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_rates_s16(self, d_pcm, pitch_frames: int, d_starts, d_ur, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_at_s16 with a per-step update rate (glv_batch_track_rates_s16): d_ur float32 [steps] in device memory, shared by all streams; step t
+        applies gravity with gravity_step * (1.0F / d_ur[t]), as a process call preceded by set_params(ur=d_ur[t]) does -- output and state bit for bit
+        those calls'; the batch's own ur is not changed.  ops must have OP_GRAVITY and no OP_WAVE; d_work at least track_at_work_bytes(steps, ops) bytes.
+        Tables of a live session: glava_amd.track_starts.live_session_rates.  Stream-ordered, kernels only; both tables are read when the kernels run."""
+        _check(lib().glv_batch_track_rates_s16(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), _ptr(d_ur), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_rates_f32(self, d_pcm, pitch_frames: int, d_starts, d_ur, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_rates_s16 from a float recording (glv_batch_track_rates_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
+        _check(lib().glv_batch_track_rates_f32(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), _ptr(d_ur), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

@@ -1,7 +1,9 @@
 """Tables of window starts for track mode at given positions (include/glv_spectrum.h glv_batch_track_at_s16 / _f32; Batch.track_at_s16 / _f32).
 
 Integer arithmetic only: a table is a list of frame positions, and a position that went through a float would drift or tie differently from one
-machine to the next.  A frame rate is the fraction fps_num / fps_den (60 / 1, 24 / 1, 60000 / 1001), a sample rate an integer of frames per second.
+machine to the next.  The one exception is live_session_rates' table of update rates: the reference accumulates frame durations in a double
+(render.c:2384) and closes its measuring second when the sum reaches 1.0, so whether 60 additions of 1 / 60 reach 1.0 decides which frame closes the
+second -- they do: the sum is 1.0000000000000013 -- and only the same IEEE double additions give the same answer.  They give it on every machine.  A frame rate is the fraction fps_num / fps_den (60 / 1, 24 / 1, 60000 / 1001), a sample rate an integer of frames per second.
 The functions return Python ints; a caller uploads them as uint32 (numpy.asarray(starts, dtype=numpy.uint32))."""
 from __future__ import annotations
 
@@ -52,3 +54,36 @@ def live_update_starts(rate: int, fps_num: int, fps_den: int, frames: int, updat
             last = updates
         step_of_frame.append(len(starts) - 1)
     return starts, step_of_frame
+
+
+def live_session_rates(rate: int, fps: int, frames: int, update_frames: int) -> tuple[list[int], list[int], list[float]]:
+    """The windows a live GLava shows over `frames` render frames at `fps` per second (an integer >= 1, as gl->rate is) AND the update rate gravity runs
+    at for each of them.  Returns (starts, step_of_frame, ur): the first two are exactly live_update_starts(rate, fps, 1, frames, update_frames); ur[t]
+    is the value gl->ur holds while the render frame that runs step t runs it, as a Python float that is an exact float32 -- the second table of
+    glv_batch_track_rates_s16 / _f32 (numpy.asarray(ur, dtype=numpy.float32)).
+
+    What it restates (render.c:2358-2399).  gl->ur starts at 1.0 (render.c:906) and both gravity paths read it at every update (render.c:728, :2224).
+    After every render frame the loop adds the frame's duration to tcounter, a double, and counts the frame in ucounter if it ran an update; when
+    tcounter >= 1.0 it sets ur = (float) (ucounter / tcounter) and resets both.  Frames before the first update count like any other.  Render frame j
+    therefore uses the value as it stands before frame j's own counters are added.  At 22050 Hz, 60 fps and updates of 256 frames: 59 steps at 1.0 (the
+    step is the whole gravity_step and every value falls to 0), 60 steps at 59.0, then 60.0 -- never the 22050 / 256 = 86.13 updates the audio thread
+    publishes, because a render frame shows the latest one only.
+
+    What is modelled: every frame meets its target -- its duration is exactly 1.0 / fps (render.c:2362-2370, the frame that sleeps up to its target) --
+    and updates arrive on the audio clock, as in live_update_starts.  What is not: wall-clock jitter.  A frame that overruns its target adds its real
+    duration, the second then closes on another frame and ur takes values near, not at, these; a recorded session's durations are not reproducible."""
+    _positive(fps=fps)
+    starts, step_of_frame = live_update_starts(rate, fps, 1, frames, update_frames)
+    from struct import pack, unpack
+    duration = 1.0 / float(fps)                     # render.c:2362
+    ur, cur, tcounter, ucounter = [], 1.0, 0.0, 0
+    for j in range(frames):
+        ran = step_of_frame[j] >= 0 and (j == 0 or step_of_frame[j] != step_of_frame[j - 1])      # `modified`
+        if ran:
+            ur.append(cur)
+            ucounter += 1                           # render.c:2380-2381
+        tcounter += duration                        # render.c:2384
+        if tcounter >= 1.0:
+            cur = unpack("f", pack("f", ucounter / tcounter))[0]      # render.c:2387: a double quotient stored in a float
+            tcounter, ucounter = 0.0, 0
+    return starts, step_of_frame, ur

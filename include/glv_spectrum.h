@@ -171,7 +171,10 @@ typedef struct glv_params {
     float gravity_step;     /* render.c:728, default 4.2  (render.c:911) */
     float ur;               /* updates per second used by gravity (render.c:728); the reference measures it
                                (render.c:2387); ideal value rate/(sample_sz/4).  Like the reference, any value is
-                               taken: 0 (an interval without updates) makes the step infinite and the output -inf */
+                               taken: 0 (an interval without updates) makes the step infinite and the output -inf.
+                               The reference starts at 1.0F (render.c:906) and replaces it by ucounter / tcounter each time a
+                               second of frame durations has passed (render.c:2379-2399): a live GLava never runs at the
+                               ideal value.  A track call that follows it: glv_batch_track_rates_s16 / _f32 */
     uint32_t avg_frames;    /* F, render.c:743; 1..GLV_MAX_AVG_FRAMES */
     uint32_t avg_window;    /* bool, render.c:745/765 */
     uint32_t avg_window_kind; /* 0: CPU twin 0.6/0.4, oldest-first (render.c:661,751-766)
@@ -580,8 +583,8 @@ int glv_batch_track_live_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_fr
                              unsigned ops, void* hip_stream);
 /* Track mode at given window starts: every entry above places window t at t * hop, one integer hop per call.  These take a TABLE of positions instead -- a
  * renderer at a rate the frame rate does not divide (the shipped 22050 Hz at 60 fps: 367.5 frames per step), the windows a live GLava would have shown
- * (updates every sample_sz / 4 frames, the latest complete one per render frame), variable frame rates, scrubbing, cue lists.  Added within ABI 7; detect
- * by the symbol.  The ten entries above keep their signatures and behaviour; the residue form (glv_batch_track_s16) has no table twin.
+ * (updates every sample_sz / 4 frames, the latest complete one per render frame), variable frame rates (with the gravity those run at:
+ * glv_batch_track_rates_s16 / _f32 below), scrubbing, cue lists.  Added within ABI 7; detect by the symbol.  The ten entries above keep their signatures and behaviour; the residue form (glv_batch_track_s16) has no table twin.
  *   d_pcm, pitch_frames: as for glv_batch_track_windows_s16 / _f32, with pitch_frames >= n as the only rule (the s16 recording 4-byte aligned, the f32 one 8).
  *   d_starts  uint32 [steps] in DEVICE memory, 4-byte aligned, shared by all streams.  Window t of stream s is the n frames of that stream's recording
  *           from min(d_starts[t], pitch_frames - n) on.  Entries may come in any order; repeats and backward jumps are valid.
@@ -622,6 +625,46 @@ int glv_batch_track_at_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_fr
                            void* d_out, void* d_work, unsigned ops, void* hip_stream);
 int glv_batch_track_at_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps,
                            void* d_out, void* d_work, unsigned ops, void* hip_stream);
+/* Track mode with a per-step update rate: every track entry above applies gravity with ONE step for the whole call, g = gravity_step * (1.0F / ur) from the
+ * batch's glv_params.  The reference measures ur as it runs (render.c:906, :2379-2399) and both gravity paths read it at every update (render.c:728, :2224): at
+ * 22050 Hz, 60 fps and updates of 256 frames a live GLava's first 59 updates run at ur = 1.0, the next 60 at 59.0, the rest at 60.0 -- never at 22050 / 256.  These
+ * entries take that sequence as a second table.  Added within ABI 7; detect by the symbol.
+ *   Everything except d_ur is glv_batch_track_at_s16 / _f32, word for word: the form the batch selects (a GLV_OP_BARS_ONLY batch: live; column texels set: columns;
+ *   anything else: windows), the clamp of d_starts[t], d_out, the launches, the kernel glv_batch_kernel_name reports, and the workspace -- sized by
+ *   glv_batch_track_at_work_bytes(b, steps, ops): the rate table adds no region.  A uniform hop is the table t * hop.
+ *   d_ur    float [steps] in DEVICE memory, 4-byte aligned, shared by all streams.  Step t applies gravity with g_t = gravity_step * (1.0F / d_ur[t]): the host's
+ *           expression (render.c:728), a correctly rounded division and then a separate multiply, evaluated in the scan kernel because the host cannot see the
+ *           table without a synchronise.  No entry outside d_ur[0, steps) is read.  0, -0, negative, tiny and huge entries are taken as the reference takes them.
+ * Contract: step t of d_out, and afterwards the batch's state (gravity store, history ring, ring head, gravity form; on a live batch the state below
+ * glv_batch_live_bins), are bit for bit what `steps` consecutive glv_batch_process_s16 / glv_batch_process_f32_stereo calls produce and leave behind when each is
+ * preceded by glv_batch_set_params with ur = d_ur[t].  The batch's own ur is NOT changed: the next process or track call uses it.  Chunks compose (a call on
+ * d_starts + k, d_ur + k continues one that ended at step k); calls mix with every other process, ring and track call.  Stream-ordered: kernels only, nothing
+ * allocated or synchronised, the first call can be captured; both tables are read when the kernels run, so rewriting d_ur in stream order re-aims a captured call.
+ * A NaN entry is outside the contract (glv_batch_set_params refuses a NaN ur): that step and those after it are unspecified, but no launch reads or writes out
+ * of bounds whatever the table holds.
+ * Refused, launching nothing and leaving the batch untouched -- GLV_ERR_INVALID: a NULL d_ur or one not 4-byte aligned, ops without GLV_OP_GRAVITY (nothing
+ * would read the table), ops with GLV_OP_WAVE (stateless), and everything glv_batch_track_at_* refuses with this code; GLV_ERR_STATE: as glv_batch_track_at_*.
+ * Kernel: the rates kind of glv_track_scan_kernel (glv_misc.hip).  The entry of step t + 8 is requested with that step's row, so no load a step depends on sits
+ * in its dependent chain.  Texel state (a GL chain) evaluates the float expression the gravity pass is defined by at every step: the host's packed integer step
+ * is accepted only after being checked against that expression for all 65 536 texel values, so the bits are the sequential calls' either way.  The two existing
+ * kinds of the scan kept their registers and scratch (profiles/r17/track_rates_isa.txt).
+ * Python: glava_amd.track_starts.live_session_rates(rate, fps, frames, update_frames) gives (starts, step_of_frame, ur) of a live session whose every frame
+ * meets its target and whose updates arrive on the audio clock; wall-clock jitter is not modelled.
+ * Measured (tools/track_rates_bench.py, profiles/r17/track_rates.txt; the protocol of profiles/r16/track_at.txt: one MI355X, N = 4096, the GL chain with F = 5 and
+ * the pre-smoothing pass, texels out, medians of 7 alternating rounds, spread = max - min; 1 / 8 / 64 streams x 2048 steps, 1024 x 256):
+ *   (a) the rates entry with every d_ur[t] = the batch's ur against glv_batch_track_at_s16 on the same table t * 735, same library: 2.044 against 1.979 ms (spreads
+ *       0.006 / 0.060), 2.602 against 2.527 (0.022 / 0.028), 5.669 against 5.388 (0.145 / 0.174), 8.164 against 7.887 (0.392 / 0.437) -- 3.0 to 5.2 % BEHIND, and
+ *       beyond the spread at 1, 8 and 64 streams (0.065, 0.075 and 0.281 ms), inside it at 1024.  That is what the division and the float form of the texel step
+ *       cost in every wave and step: 21 more VALU instructions a step than the packed integer step (profiles/r17/track_rates_isa.txt).  A per-step integer form on
+ *       the device was not built; a caller whose rate never changes takes glv_batch_track_at_*.
+ *   (b) glv_batch_track_at_s16 in this library against the parent commit's: 1.975 / 2.538 / 5.391 / 7.928 against 1.976 / 2.533 / 5.340 / 7.908 ms (spreads 0.011 /
+ *       0.021 / 0.218 / 0.288 and 0.019 / 0.014 / 0.169 / 0.532), inside the spread at every point; bench.py level (101.4 / 101.1 against 100.4 M frames/s).
+ *   (c) the tables of live_session_rates(22050, 60, ..., 256) against the same windows through glv_batch_process_s16 one by one with glv_batch_set_params between
+ *       the calls: 2.054 against 68.4 ms (33.3 x), 2.621 against 72.2 (27.5 x), 5.910 against 73.0 (12.3 x), 8.358 against 14.4 (1.72 x). */
+int glv_batch_track_rates_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, const float* d_ur, uint32_t steps,
+                              void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_rates_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, const float* d_ur, uint32_t steps,
+                              void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
