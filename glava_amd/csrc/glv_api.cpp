@@ -35,7 +35,8 @@ int validate(const glv_params* p) {
         return fail(GLV_ERR_INVALID, "avg_frames=%u: must be in [1, %d]", p->avg_frames, GLV_MAX_AVG_FRAMES);
     if (p->avg_window_kind > 1) return fail(GLV_ERR_INVALID, "avg_window_kind=%u: must be 0 or 1", p->avg_window_kind);
     if (p->log_mode > 2) return fail(GLV_ERR_INVALID, "log_mode=%u: must be 0, 1 or 2", p->log_mode);
-    if (p->gl_storage > 2) return fail(GLV_ERR_INVALID, "gl_storage=%u: must be 0, 1 (GL_R16 state, one launch) or 2 (pass by pass, f32 state)", p->gl_storage);
+    if (p->gl_storage > 3)
+        return fail(GLV_ERR_INVALID, "gl_storage=%u: must be 0, 1 (GL_R16 state, one launch), 2 (pass by pass, f32 state) or 3 (float state, bars sample the GL_R16 upload)", p->gl_storage);
     if (p->ur != p->ur) return fail(GLV_ERR_INVALID, "ur is NaN");   // 0 is legal: render.c:2387 yields it after an interval without updates
     if (p->round_formula > GLV_ROUND_LINEAR) return fail(GLV_ERR_INVALID, "round_formula=%u: 0 sinusoidal, 1 circular, 2 linear", p->round_formula);
     if (p->sample_mode > GLV_SAMPLE_HYBRID) return fail(GLV_ERR_INVALID, "sample_mode=%u: 0 average, 1 maximum, 2 hybrid", p->sample_mode);
@@ -186,7 +187,7 @@ int glv_batch_set_params(glv_batch* b, const glv_params* p) {
     if (p->n != b->p.n || p->avg_frames != b->p.avg_frames)
         return fail(GLV_ERR_STATE, "params (n=%u, F=%u) do not match the batch (n=%u, F=%u): fixed at creation", p->n, p->avg_frames, b->p.n, b->p.avg_frames);
     if ((p->gl_storage == 1) != b->state16)
-        return fail(GLV_ERR_STATE, "gl_storage=%u: the state of this batch was created as %s", p->gl_storage, b->state16 ? "GL_R16 texels (gl_storage 1)" : "floats (gl_storage 0 / 2)");
+        return fail(GLV_ERR_STATE, "gl_storage=%u: the state of this batch was created as %s", p->gl_storage, b->state16 ? "GL_R16 texels (gl_storage 1)" : "floats (gl_storage 0 / 2 / 3)");
     if (b->snapped() && (p->bars != b->p.bars || p->gl_storage == 0))
         return fail(GLV_ERR_STATE, "bar texels are set (glv_batch_set_bar_texels): bars (%u -> %u) must keep the table's length and gl_storage must stay non-zero "
                                    "(a float chain has no pre-smoothed texture); clear the table first", b->p.bars, p->bars);
@@ -354,6 +355,7 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
     HIP_TRY(hipSetDevice(b->device));
     if (!b->bar.desc) return fail(GLV_ERR_STATE, "the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created)");
     if (b->snapped()) return fail(GLV_ERR_STATE, "glv_batch_bars takes float spectra, not a GL chain's texels: refused while bar texels or column texels are set (glv_batch_set_bar_texels / glv_batch_set_column_texels)");
+    if (upload_storage(b->p)) return fail(GLV_ERR_STATE, "glv_batch_bars takes float spectra: on gl_storage 3 GLV_OP_BARS samples the upload's texels (caller's float rows: a gl_storage 0 batch)");
     const glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->bar);
     hipError_t e = glv::launch_bars(d_spec, d_bars, (size_t) b->streams * 2, b->p.n, b->p.bars, b->bar_x.nsteps, b->bar_x.items, b->bar.desc, b->bar.w,
                                     (hipStream_t) hip_stream, false, &rt);
@@ -461,7 +463,7 @@ int glv_state_create(const glv_params* p, int device, glv_state** out) {
     glv_state* s = new (std::nothrow) glv_state();
     if (!s) return fail(GLV_ERR_NOMEM, "out of host memory");
     // (GL_R16 state -- the accel path of handle_audio, glv_gl_texture -- also announces the pre-smoothing pass: one scratch row)
-    const unsigned mask = GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_WAVE | (p && p->gl_storage == 1 && p->bars >= 1 && p->bars <= p->n ? (unsigned) GLV_OP_BARS : 0u);
+    const unsigned mask = GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_SMOOTH | GLV_OP_WAVE | (p && (p->gl_storage == 1 || p->gl_storage == 3) && p->bars >= 1 && p->bars <= p->n ? (unsigned) GLV_OP_BARS : 0u);
     int rc = batch_create_rows(p, 1, mask, device, true, &s->b);
     if (rc == GLV_OK) {
         const char* mode = std::getenv("GLV_STAGING");
@@ -548,8 +550,8 @@ int glv_wave_texture(const glv_params* p, glv_state* s, const float* buf, int sm
     glv_batch* b = s->b;
     if (p->n != b->p.n || p->avg_frames != b->p.avg_frames)
         return fail(GLV_ERR_STATE, "params (n=%u, F=%u) do not match the state (n=%u, F=%u)", p->n, p->avg_frames, b->p.n, b->p.avg_frames);
-    if (smooth_pass && (p->gl_storage != 1 || !b->state16 || !(b->ops_mask & GLV_OP_BARS)))
-        return fail(GLV_ERR_STATE, "glv_wave_texture with the pre-smoothing pass needs a state created with gl_storage = 1 and bars = n (the pass samples GL_R16 texels)");
+    if (smooth_pass && (!(p->gl_storage == 1 ? b->state16 : p->gl_storage == 3 && !b->state16) || !(b->ops_mask & GLV_OP_BARS)))
+        return fail(GLV_ERR_STATE, "glv_wave_texture with the pre-smoothing pass needs a state created with gl_storage = 1 (or 3) and bars = n (the pass samples GL_R16 texels)");
     if (smooth_pass && p->bars != p->n)
         return fail(GLV_ERR_INVALID, "glv_wave_texture with the pre-smoothing pass: bars must equal n (bar_phase 0.5: the pass's texel centres)");
     if (int rc = sync_params(b, p)) return rc;

@@ -278,14 +278,17 @@ int ensure_snap_tables(glv_batch* b) {
 // a chain with state and no smoothing pass, whose kernel class takes them -- the float chain's bars as GL_R16 texels leave through
 // glv_bars_kernel, the GL_R16 chain stores them itself, the GL passes one by one (gl_storage 2, the audit log) never fuse; GLV_UNFUSED_BARS
 // (diagnostics) forces two launches.  process() adds that the chain transforms (GLV_OP_FFT) and is not run pass by pass (GLV_OP_RAW).
+// gl_storage 3: snapped tables only (bar texels and columns, kernel classes FC_STATE_SNAP / FC_STATE_COLS: the finished float row in LDS is sampled through
+// the upload's quantiser, results as texels or floats); its unsnapped bars are the integer pass or glv_bars_mode_kernel, always a second launch.
 bool bars_fusable(const glv_batch* b, unsigned ops) {
     return (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !(ops & GLV_OP_SMOOTH) && !b->unfused_bars
-           && (b->p.gl_storage == 0 ? !(ops & GLV_OP_R16) : b->p.gl_storage == 1 && b->p.log_mode != 2);
+           && (b->p.gl_storage == 0 ? !(ops & GLV_OP_R16) : upload_storage(b->p) ? b->snapped() : b->p.gl_storage == 1 && b->p.log_mode != 2);
 }
 // Do the bars of table set `s` need the internal rows -- true unless every chain the creation mask announces fuses them in every kernel
 // configuration.  One difference from process(): under the audit log (log_mode 2) a float chain fuses its bars and gets the rows all the
 // same -- which batches hold them is kept as it was.
 bool bars_need_rows(const glv_batch* b, const BarTableSet& s) {
+    if (upload_storage(b->p)) return true;            // (its unsnapped bars and its stateless chains always take two launches)
     bool all_fused = bars_fusable(b, b->ops_mask) && b->p.log_mode != 2;
     for (int v = 0; v < glv::frame_variants(b->log_nn) && v < kMaxVariants; ++v) all_fused = all_fused && s.fusable[v];
     return !all_fused;

@@ -352,20 +352,28 @@ __global__ void __launch_bounds__(256) glv_bars_seq_kernel(const float* __restri
 // block-transposed (glv_tables.h make_bar_mode_blocks: [tap][lane], one coalesced 256-byte load per tap) and padded with +0 up to the block's longest
 // bar -- x * +0 = +0 changes neither the maximum (vmax >= +0) nor the sum.  MODE 1: bar = vmax;  MODE 2: bar = vmax * (1 - H) + (avg / weight) * H,
 // every operation rounded on its own (no fused multiply-add: the shader's expression as written).
-template <int MODE, int RR, bool LDS>
-__global__ void __launch_bounds__(256) glv_bars_mode_kernel(const float* __restrict__ spec, void* __restrict__ bars_out, size_t nrows, uint32_t n, uint32_t bars,
+// TEXROWS (the texel-row kind: gl_storage 3, the upload of a finished float row; a track call's scan results): `rows` is uint16 [nrows][n], GL_R16 texels c, and
+// x = c / 65535 correctly rounded (unorm16_to_float: what texelFetch returns, what a GL chain's float rows hold) -- then the walk as it is.
+template <int MODE, int RR, bool LDS, bool TEXROWS = false>
+__global__ void __launch_bounds__(256) glv_bars_mode_kernel(const void* __restrict__ rows, void* __restrict__ bars_out, size_t nrows, uint32_t n, uint32_t bars,
                                                            const BarDesc* __restrict__ desc, const BarModeBlock* __restrict__ blocks, uint32_t nblocks,
                                                            const float* __restrict__ mw, uint32_t bins, float hyb, float one_minus_hyb, int r16) {
     extern __shared__ __attribute__((aligned(16))) float glv_mode_rows[];        // [bins][RR]: a tap's RR rows are one 16-byte read per four rows
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     auto clamp01 = [](float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; };   // NaN -> 0
+    using Row = typename std::conditional<TEXROWS, uint16_t, float>::type;
+    const Row* spec = static_cast<const Row*>(rows);
+    auto sample = [&](size_t at) -> float {                                           // at < nrows * n
+        if constexpr (TEXROWS) return unorm16_to_float(spec[at]);                     // (in [0, 1] already)
+        else return clamp01(spec[at]);
+    };
     for (size_t row0 = (size_t) blockIdx.x * RR; row0 < nrows; row0 += (size_t) gridDim.x * RR) {
         if constexpr (LDS) {
             __syncthreads();                                                      // the previous rows have been read
             for (uint32_t i = threadIdx.x; i < (uint32_t) RR * bins; i += 256u) {
                 const uint32_t r = i / bins, bin = i - r * bins;                  // (coalesced row reads; the transposing writes are the small side)
                 const size_t row = row0 + r < nrows ? row0 + r : nrows - 1;
-                glv_mode_rows[bin * (uint32_t) RR + r] = clamp01(spec[row * (size_t) n + bin]);
+                glv_mode_rows[bin * (uint32_t) RR + r] = sample(row * (size_t) n + bin);
             }
             __syncthreads();
         }
@@ -400,7 +408,7 @@ __global__ void __launch_bounds__(256) glv_bars_mode_kernel(const float* __restr
                         for (int r = 0; r < RR; ++r) x[r] = glv_mode_rows[bin * (uint32_t) RR + (uint32_t) r];
                     } else {
 #pragma unroll
-                        for (int r = 0; r < RR; ++r) x[r] = clamp01(spec[(row0 + r < nrows ? row0 + r : nrows - 1) * (size_t) n + bin]);
+                        for (int r = 0; r < RR; ++r) x[r] = sample((row0 + r < nrows ? row0 + r : nrows - 1) * (size_t) n + bin);
                     }
 #pragma unroll
                     for (int r = 0; r < RR; ++r) {
@@ -423,13 +431,13 @@ __global__ void __launch_bounds__(256) glv_bars_mode_kernel(const float* __restr
         }
     }
 }
-template <int MODE>
-static hipError_t launch_bars_mode(const float* spec, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const BarRowsTables& rt, hipStream_t st, int r16) {
+template <int MODE, bool TEXROWS = false>
+static hipError_t launch_bars_mode(const void* spec, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const BarRowsTables& rt, hipStream_t st, int r16) {
     if (rt.mblocks == nullptr || rt.mw == nullptr || rt.nmblocks == 0 || rt.mode_bins == 0 || rt.mode_bins > n) return hipErrorInvalidValue;
     const uint32_t bins = rt.mode_bins;
     const float h = rt.hybrid_weight, omh = 1.0f - rt.hybrid_weight;
     auto grid_of = [&](int rr) { const unsigned g = capped_grid(nrows, (size_t) rr, kGridCap); return dim3(g ? g : 1u); };
-#define GLV_MODE_LAUNCH(RR, LDSF, BYTES) hipLaunchKernelGGL((glv_bars_mode_kernel<MODE, RR, LDSF>), grid_of(RR), dim3(256), BYTES, st, spec, bars_out, nrows, n, bars, desc, rt.mblocks, rt.nmblocks, rt.mw, bins, h, omh, r16)
+#define GLV_MODE_LAUNCH(RR, LDSF, BYTES) hipLaunchKernelGGL((glv_bars_mode_kernel<MODE, RR, LDSF, TEXROWS>), grid_of(RR), dim3(256), BYTES, st, spec, bars_out, nrows, n, bars, desc, rt.mblocks, rt.nmblocks, rt.mw, bins, h, omh, r16)
     // rows per workgroup by what their sampled bins take of the 64 KiB a launch may ask for without an attribute: 8 (n <= 4096 as shipped), 4, 1; else through L1
     if ((size_t) bins * 32u <= 64u * 1024u && nrows >= 8) GLV_MODE_LAUNCH(8, true, (size_t) bins * 32u);
     else if ((size_t) bins * 16u <= 64u * 1024u) GLV_MODE_LAUNCH(4, true, (size_t) bins * 16u);
@@ -1040,8 +1048,9 @@ hipError_t launch_bars(const float* spec, float* bars_out, size_t nrows, uint32_
                        const BarItem* items, const BarDesc* desc, const float* tap_w, hipStream_t st, bool r16, const BarRowsTables* rt) {
     const int r = r16 ? 1 : 0;
     // SAMPLE_MODE maximum / hybrid: one lane per bar and row, any number of bars
-    if (rt != nullptr && rt->mode == 1u) return launch_bars_mode<1>(spec, bars_out, nrows, n, bars, desc, *rt, st, r);
-    if (rt != nullptr && rt->mode == 2u) return launch_bars_mode<2>(spec, bars_out, nrows, n, bars, desc, *rt, st, r);
+    if (rt != nullptr && rt->mode == 1u) return rt->rows_texels ? launch_bars_mode<1, true>(spec, bars_out, nrows, n, bars, desc, *rt, st, r) : launch_bars_mode<1>(spec, bars_out, nrows, n, bars, desc, *rt, st, r);
+    if (rt != nullptr && rt->mode == 2u) return rt->rows_texels ? launch_bars_mode<2, true>(spec, bars_out, nrows, n, bars, desc, *rt, st, r) : launch_bars_mode<2>(spec, bars_out, nrows, n, bars, desc, *rt, st, r);
+    if (rt != nullptr && rt->rows_texels) return hipErrorInvalidValue;      // (texel rows under sample_mode average: launch_bars_i8 / launch_bars_snap)
     // many bars: one fma chain per bar (glv_tables.h make_bar_mtiles) -- on the matrix cores when the host could cut the tiles into
     // rounds for the LDS ring, one lane per bar otherwise
     if (bars >= 256) {

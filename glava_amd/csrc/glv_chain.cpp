@@ -12,9 +12,9 @@ bool gl_fused_chain(const glv_batch* b, unsigned ops) {
 }
 }  // namespace glvh
 namespace {
-// ... or the GL passes one by one (gl_storage 2; RAW / SMOOTH / the audit log of 1)?
+// ... or the GL passes one by one (gl_storage 2; RAW / SMOOTH / the audit log of 1)?  (gl_storage 3 is the float chain: no GL pass)
 bool gl_passes_chain(const glv_batch* b, unsigned ops) {
-    return b->p.gl_storage != 0 && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !gl_fused_chain(b, ops);
+    return b->p.gl_storage != 0 && !upload_storage(b->p) && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) && !gl_fused_chain(b, ops);
 }
 }  // namespace
 namespace glvh __attribute__((visibility("hidden"))) {
@@ -141,7 +141,7 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
     if (stateful & ~b->ops_mask)
         return fail(GLV_ERR_STATE, "ops 0x%x need state the batch was not created with (ops_mask 0x%x)", ops, b->ops_mask);
     if (stateful && b->state16 != (b->p.gl_storage == 1))
-        return fail(GLV_ERR_STATE, "gl_storage=%u: the state of this batch was created as %s", b->p.gl_storage, b->state16 ? "GL_R16 texels (gl_storage 1)" : "floats (gl_storage 0 / 2)");
+        return fail(GLV_ERR_STATE, "gl_storage=%u: the state of this batch was created as %s", b->p.gl_storage, b->state16 ? "GL_R16 texels (gl_storage 1)" : "floats (gl_storage 0 / 2 / 3)");
     if ((b->ops_mask & GLV_OP_BARS_ONLY) && stateful && !(ops & GLV_OP_BARS))
         return fail(GLV_ERR_STATE, "the batch was created with GLV_OP_BARS_ONLY: its state lives only below the bins the bars sample, a stateful call must ask for GLV_OP_BARS (ops 0x%x)", ops);
     if ((ops & GLV_OP_WRANGE) && (ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "GLV_OP_WRANGE excludes GLV_OP_FFT");
@@ -150,16 +150,26 @@ int check_ops(const glv_batch* b, unsigned ops, const float* d_out) {
     if (!(ops & (GLV_OP_FFT | GLV_OP_GRAVITY | GLV_OP_AVERAGE | GLV_OP_WRANGE | GLV_OP_SMOOTH | GLV_OP_MAGNITUDE | GLV_OP_R16 | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "empty ops");
     if ((ops & GLV_OP_R16) && (ops & (GLV_OP_RAW | GLV_OP_SMOOTH))) return fail(GLV_ERR_INVALID, "GLV_OP_R16 excludes GLV_OP_RAW and GLV_OP_SMOOTH");
     if ((ops & GLV_OP_R16) && !d_out) return fail(GLV_ERR_INVALID, "GLV_OP_R16 needs an output buffer");
-    if ((ops & GLV_OP_OUTPUT_IS_STATE) && (!state_is_output || !d_out || (ops & (GLV_OP_BARS | GLV_OP_R16)) || b->p.gl_storage))
+    if ((ops & GLV_OP_OUTPUT_IS_STATE) && (!state_is_output || !d_out || (ops & (GLV_OP_BARS | GLV_OP_R16)) || (b->p.gl_storage && !upload_storage(b->p))))
         return fail(GLV_ERR_INVALID, "GLV_OP_OUTPUT_IS_STATE needs a chain that ends in gravity with f32 rows out (no AVERAGE / SMOOTH / RAW / BARS / R16, gl_storage 0)");
     if ((ops & GLV_OP_BARS) && !b->bar.desc)
         return fail(GLV_ERR_STATE, "GLV_OP_BARS: the batch has no bar tables (bars / smooth_factor / bar_phase were unusable when it was created; tables are built at creation and by glv_batch_set_params, process calls never allocate)");
     if ((ops & GLV_OP_BARS) && (b->bar_x.count != b->p.bars || b->bar_x.factor != b->p.smooth_factor || b->bar_x.phase != b->p.bar_phase || !same_shape(b->bar_x.shape_of, b->p)))
         return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
+    if ((ops & GLV_OP_BARS) && !(ops & GLV_OP_WAVE) && upload_storage(b->p)) {
+        // gl_storage 3: the bars sample the GL_R16 upload of the finished float buffer (render.c:2185, :2276-2303) -- an FFT chain's, with or without state;
+        // what is offered is what the shipped `setsmoothpass true` configuration runs, in the exact forms the GL chains have
+        if (!(ops & GLV_OP_FFT) || (ops & (GLV_OP_SMOOTH | GLV_OP_RAW)))
+            return fail(GLV_ERR_STATE, "GLV_OP_BARS on gl_storage 3 samples the upload of an FFT chain's finished rows: GLV_OP_FFT is required, GLV_OP_SMOOTH / GLV_OP_RAW are "
+                                       "not offered with it (ops 0x%x)", ops);
+        if (!b->snapped() && b->p.sample_mode == GLV_SAMPLE_AVERAGE && !(b->p.bars >= glv::kBarSeqMin && b->bar_x.i8()))
+            return fail(GLV_ERR_STATE, "GLV_OP_BARS on gl_storage 3: unsnapped averaging bars run as the exact integer pass only (bars=%u: 256 or more, with integer tables); the "
+                                       "modules' bars come from glv_batch_set_bar_texels / glv_batch_set_column_texels", b->p.bars);
+    }
     if ((ops & GLV_OP_BARS) && b->snapped()) {
         // bars at texels of the pre-smoothing pass: the chain's rows must be what that pass samples -- a GL chain's texels, not smoothed
-        // (... or the wave texture's: GLV_OP_WAVE | GLV_OP_BARS, vetted above)
-        if (!(ops & GLV_OP_WAVE) && (!(ops & GLV_OP_FFT) || !(gl_fused_chain(b, ops) || gl_passes_chain(b, ops)) || (ops & GLV_OP_SMOOTH)))
+        // (... or the wave texture's: GLV_OP_WAVE | GLV_OP_BARS, vetted above; or the upload of gl_storage 3, vetted above)
+        if (!(ops & GLV_OP_WAVE) && !upload_storage(b->p) && (!(ops & GLV_OP_FFT) || !(gl_fused_chain(b, ops) || gl_passes_chain(b, ops)) || (ops & GLV_OP_SMOOTH)))
             return fail(GLV_ERR_STATE, "GLV_OP_BARS with bar texels set (glv_batch_set_bar_texels) needs a GL chain's texel rows: GLV_OP_FFT with gravity / average on "
                                        "gl_storage 1 or 2, without GLV_OP_SMOOTH (ops 0x%x)", ops);
         if (!snap_current(b)) return fail(GLV_ERR_STATE, "GLV_OP_BARS: bar parameters changed without glv_batch_set_params");
@@ -200,16 +210,21 @@ int plan_wave(const glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float
 int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, size_t units, bool r16, hipStream_t st) {
     hipError_t e;
     if (pl.bars == ChainPlan::NO_BARS) return GLV_OK;
-    if (pl.bars == ChainPlan::BARS_F32) {
-        const glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->bar);
+    if (pl.bars == ChainPlan::BARS_F32 || pl.bars == ChainPlan::BARS_MODE_TEXELS) {
+        glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->bar);
+        rt.rows_texels = pl.bars == ChainPlan::BARS_MODE_TEXELS ? 1u : 0u;
         e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, b->bar_x.nsteps, b->bar_x.items, b->bar.desc, b->bar.w, st, r16, &rt);
     } else if (pl.bars == ChainPlan::BARS_SNAP || pl.bars == ChainPlan::BARS_SNAP_FLOATS) {
         e = glv::launch_bars_snap(pl.rows, pl.bars == ChainPlan::BARS_SNAP_FLOATS, d_bars, units, b->p.n, b->p.bars, b->snap.desc, reinterpret_cast<const uint32_t*>(b->snap.w.get()), st, r16);
     } else if (pl.bars == ChainPlan::BARS_COLUMNS) {
         e = glv::launch_columns(pl.rows, d_bars, units, b->p.n, (uint32_t) b->snap_x.tex.size(), b->p.bars, b->snap_x.col_nsteps, b->snap_x.col_items, b->snap.desc,
                                 b->snap.w, b->snap_x.col_map, b->p.sample_mode, shape_hybrid(b->p), st);
-    } else if (pl.bars == ChainPlan::BARS_SNAP_MODE) {
-        const glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->snap);
+    } else if (pl.bars == ChainPlan::BARS_COLUMNS_TEXELS) {
+        e = glv::launch_columns_texels(reinterpret_cast<const uint16_t*>(pl.rows), d_bars, units, b->p.n, (uint32_t) b->snap_x.tex.size(), b->p.bars, b->snap_x.col_nsteps,
+                                       b->snap_x.col_items, b->snap.desc, b->snap.w, b->snap_x.col_map, b->p.sample_mode, shape_hybrid(b->p), st);
+    } else if (pl.bars == ChainPlan::BARS_SNAP_MODE || pl.bars == ChainPlan::BARS_SNAP_MODE_TEXELS) {
+        glv::BarRowsTables rt = rows_tables(b->p, b->bar_x, b->snap);
+        rt.rows_texels = pl.bars == ChainPlan::BARS_SNAP_MODE_TEXELS ? 1u : 0u;
         e = glv::launch_bars(pl.rows, d_bars, units, b->p.n, b->p.bars, 0, nullptr, b->snap.desc, nullptr, st, r16, &rt);
     } else {
         const glv::BarIRowsTables irt = b->bar_x.irows_tables();
@@ -251,7 +266,12 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t
         pl.rows = (ops & GLV_OP_BARS) ? pl.out : d_out;
     } else pl.rows = pl.out ? pl.out : b->d_grav;           // no rows out: a chain that ends in gravity, whose state is its output
     // many bars of texel rows: the integer matrix-core pass -- on the GL_R16 chain's texels, or on the texel values of the GL passes
+    // gl_storage 3: the float chain writes the upload's texels (FC_R16 / FC_STATE_R16) and every second launch runs its texel-row kind (check_ops vetted the bars)
+    const bool upload = (ops & GLV_OP_BARS) && upload_storage(b->p);
+    const bool averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;
     if (!(ops & GLV_OP_BARS) || pl.fused_bars) pl.bars = ChainPlan::NO_BARS;
+    else if (upload) pl.bars = snap ? (b->columns() ? ChainPlan::BARS_COLUMNS_TEXELS : averaging ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_MODE_TEXELS)
+                                    : (averaging ? ChainPlan::BARS_I8 : ChainPlan::BARS_MODE_TEXELS);
     else if (snap && b->columns()) pl.bars = ChainPlan::BARS_COLUMNS;
     else if (snap) pl.bars = b->p.sample_mode != GLV_SAMPLE_AVERAGE ? ChainPlan::BARS_SNAP_MODE : pl.route == ChainPlan::GL_FUSED ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_FLOATS;
     else if (b->p.bars >= glv::kBarSeqMin && b->bar_x.i8() && (pl.route == ChainPlan::GL_FUSED || (gl_passes && !(ops & GLV_OP_SMOOTH))))
@@ -262,10 +282,12 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t
         pl.ops = ops & ~(unsigned) (GLV_OP_PRIVATE_STATE | GLV_OP_OUTPUT_IS_STATE);
         if (ops & GLV_OP_BARS) pl.ops &= ~(unsigned) GLV_OP_R16;     // with bars the texel conversion applies to the bars, the spectra stay f32
         if (pl.bars == ChainPlan::BARS_I8 || pl.bars == ChainPlan::BARS_SNAP) pl.ops |= glv::OP_R16;   // ... but the GL_R16 chain hands the integer pass its rows as 16-bit texels
+        if (upload && pl.bars != ChainPlan::NO_BARS) pl.ops |= glv::OP_R16;                            // ... and gl_storage 3 every second launch: the upload's texels
     }
     // the GL_R16 chain's rows go to the bars of a second launch and nowhere else (the scratch rows): what those bars do not sample is not stored
+    // (gl_storage 3 likewise: the texel rows of the float-state classes)
     const uint32_t bins_needed = snap ? b->snap.bins : b->bar_x.bins_needed;
-    if (pl.route == ChainPlan::GL_FUSED && pl.bars != ChainPlan::NO_BARS && bins_needed != 0 && bins_needed < b->p.n)
+    if ((pl.route == ChainPlan::GL_FUSED || upload) && pl.bars != ChainPlan::NO_BARS && bins_needed != 0 && bins_needed < b->p.n)
         pl.out_limit = bins_needed * 4u;
     // GLV_OP_BARS_ONLY: ... and what they do not sample is not computed, nor is its state kept -- the GL_R16 chain, and a float chain with
     // the bars fused (check_ops vetted the call)
@@ -320,7 +342,7 @@ int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, 
         a.bars = b->p.bars; a.bars_out = d_out; a.col_map = b->snap_x.col_map;      // (NULL unless column texels are set)
     }
     if (pl.route == ChainPlan::GL_FUSED) a.gl_storage = 1;
-    if (pl.route == ChainPlan::POST && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) a.gl_storage = b->p.gl_storage;   // the post kernel models it directly
+    if (pl.route == ChainPlan::POST && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) a.gl_storage = upload_storage(b->p) ? 0u : b->p.gl_storage;   // the post kernel models it directly (3: the float operators)
     if (pl.route == ChainPlan::GL_PASSES && !pl.out)
         return fail(GLV_ERR_STATE, "this gl_storage chain needs the internal spectra rows (created for gl_storage 2 batches with state, and with GLV_OP_BARS in the ops_mask)");
     if (pl.live_points != 0) { a.live_points = pl.live_points; b->ran_live = true; }

@@ -84,12 +84,18 @@ enum FrameClass : int {
                              //   1.3 % (68.2 vs 69.1 M frames/s, N = 4096, 64 K streams, same box alternating: profiles/r07/snapped_bars.txt)
     FC_GL16_COLS = 12,       // FC_GL16_SNAP / FC_GL16_SNAP_LIVE whose snapped texels stay in LDS, as 16-bit values; lane x then stores the mean of three
     FC_GL16_COLS_LIVE = 13,  //   of them: column x of the graph module (glv_batch_set_column_texels, column_mean).  Own classes for the same reason
+    FC_STATE_SNAP = 14,      // FC_STATE_BARS' epilogue (float state, the finished FLOAT row into the slot's LDS region) followed by FC_GL16_SNAP's loop: the
+    FC_STATE_COLS = 15,      //   taps are read through pack_unorm16, the upload's quantiser, so the row is sampled as its GL_R16 upload (gl_storage 3:
+                             //   GLava with setaccelfft false); FC_STATE_COLS likewise with FC_GL16_COLS' loop and column store.  Own classes again
 };
-constexpr int kFrameClasses = 14;
-GLV_HD constexpr bool fc_cols(int c) { return c == FC_GL16_COLS || c == FC_GL16_COLS_LIVE; }
-GLV_HD constexpr bool fc_snap(int c) { return c == FC_GL16_SNAP || c == FC_GL16_SNAP_LIVE || fc_cols(c); }
+constexpr int kFrameClasses = 16;
+GLV_HD constexpr bool fc_cols(int c) { return c == FC_GL16_COLS || c == FC_GL16_COLS_LIVE || c == FC_STATE_COLS; }
+GLV_HD constexpr bool fc_snap(int c) { return c == FC_GL16_SNAP || c == FC_GL16_SNAP_LIVE || c == FC_STATE_SNAP || fc_cols(c); }
 GLV_HD constexpr bool fc_fused_bars(int c) { return c == FC_STATE_BARS || c == FC_GL16_BARS || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE || fc_snap(c); }
-GLV_HD constexpr bool fc_gl16(int c) { return c == FC_GL16 || c == FC_GL16_BARS || c == FC_GL16_LIVE || c == FC_GL16_BARS_LIVE || fc_snap(c); }
+GLV_HD constexpr bool fc_gl16(int c) {
+    return c == FC_GL16 || c == FC_GL16_BARS || c == FC_GL16_LIVE || c == FC_GL16_BARS_LIVE || c == FC_GL16_SNAP || c == FC_GL16_SNAP_LIVE || c == FC_GL16_COLS
+           || c == FC_GL16_COLS_LIVE;
+}
 GLV_HD constexpr bool fc_live(int c) { return c == FC_GL16_LIVE || c == FC_STATE_BARS_LIVE || c == FC_GL16_BARS_LIVE || c == FC_GL16_SNAP_LIVE || c == FC_GL16_COLS_LIVE; }
 GLV_HD constexpr bool fc_has_state(int c) { return c != FC_PLAIN && c != FC_R16; }
 GLV_HD constexpr bool fc_texel_out(int c) { return c == FC_R16 || c == FC_STATE_R16; }     // rows out as uint16 texels, always
@@ -99,6 +105,7 @@ GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, u
     if (gl16 && fused_bars && snap && cols) return live ? FC_GL16_COLS_LIVE : FC_GL16_COLS;
     if (gl16 && fused_bars && snap) return live ? FC_GL16_SNAP_LIVE : FC_GL16_SNAP;
     if (gl16) return fused_bars ? (live ? FC_GL16_BARS_LIVE : FC_GL16_BARS) : (live ? FC_GL16_LIVE : FC_GL16);
+    if (fused_bars && snap) return cols ? FC_STATE_COLS : FC_STATE_SNAP;      // (gl_storage 3 has no live bins: no live class)
     if (fused_bars) return live ? FC_STATE_BARS_LIVE : FC_STATE_BARS;
     if (ops & (OP_GRAVITY | OP_AVERAGE)) return (ops & OP_R16) ? FC_STATE_R16 : FC_STATE;
     return (ops & OP_R16) ? FC_R16 : FC_PLAIN;
@@ -160,7 +167,9 @@ struct FrameArgs {
     float F_rcp;           // RN(1 / F): the GL_R16 chain's final division (glv_core.h div_frames)
     uint32_t out_limit;    // gl_storage 1, rows handed to a later kernel only (the bars of a second launch): bytes of a float row that are
                            // written at all -- the pre-smoothing pass samples bins below 0.31 n, the rest of the row is not stored (0: no limit);
-                           // texel rows (OP_R16: what the i8 matrix-core pass reads) stop at the same bin, i.e. at half as many bytes
+                           // texel rows (OP_R16: what the i8 matrix-core pass reads) stop at the same bin, i.e. at half as many bytes.
+                           // Likewise the texel rows of the float-state classes FC_R16 / FC_STATE_R16 in front of a second launch (gl_storage 3: the
+                           // upload of the finished float buffer); the float state is written whole
     uint32_t live_points;  // gl_storage 1, GLV_OP_BARS_ONLY batches (0: every point): complex points [0, live_points) of a row are all the chain's consumer (the
                            // bars of a second launch) ever samples -- the LIVE kernel class keeps the gravity store and the ring, and computes magnitude,
                            // upload, gravity and average, for the last pass's blocks of L0 points that hold them, and touches nothing beyond
@@ -1232,15 +1241,20 @@ struct Frame {
             return val;
         };
         // one finished pair / point -> the output row (f32 or GL_R16 texels)
+        // (R16 with a.out_limit: texel rows handed to the bars of a second launch only -- gl_storage 3 -- end where those bars stop sampling; `off` is the
+        // offset in a FLOAT row, as out_limit counts.  The state is stored whole all the same.)
         auto store_pair = [&](uint32_t off, const cf2& two) {
             if constexpr (R16) {
+                if (a.out_limit != 0u && off >= a.out_limit) return;
                 const u32x2 q = { pack_unorm16(two.a.x, two.a.y), pack_unorm16(two.b.x, two.b.y) };
                 st<u32x2>(out_row, off / 2u, q);
             } else st<cf2>(out_row, off, two);
         };
         auto store_point = [&](uint32_t off, const cf& one) {
-            if constexpr (R16) st<uint32_t>(out_row, off / 2u, pack_unorm16(one.x, one.y));
-            else st<cf>(out_row, off, one);
+            if constexpr (R16) {
+                if (a.out_limit != 0u && off >= a.out_limit) return;
+                st<uint32_t>(out_row, off / 2u, pack_unorm16(one.x, one.y));
+            } else st<cf>(out_row, off, one);
         };
         if constexpr (!STATE) {
             // stateless: value -> store, pair by pair (nothing but the pair in flight)

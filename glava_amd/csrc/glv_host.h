@@ -38,6 +38,10 @@ inline bool same_shape(const glv_params& a, const glv_params& b) {
            && same_bits(a.sample_scale, b.sample_scale) && same_bits(a.sample_range, b.sample_range);
 }
 
+// glv_params.gl_storage 3: the CPU operators on float state as with 0, and GLV_OP_BARS samples the GL_R16 upload of the finished float rows (GLava with
+// `setaccelfft false`: render.c:2149-2155, :2185, :2276-2303).  State, float rows and texels out are gl_storage 0's in every bit.
+inline bool upload_storage(const glv_params& p) { return p.gl_storage == 3u; }
+
 constexpr int kOpsClasses = 7, kInKinds = 7;     // wisdom classes (wisdom_class): glv::FrameClass 0..6
 constexpr int kMaxVariants = 4;
 // glv_batch_track_wave_s16, bars in one launch: a workgroup's rows are consecutive output rows (false) or consecutive steps of one channel row (true).
@@ -262,7 +266,9 @@ struct ChainPlan {
                 BARS_SNAP, BARS_SNAP_FLOATS, BARS_SNAP_MODE,                    // bars at texels of the pre-smoothing pass: over texel rows, over
                                                                                // c / 65535, and sample_mode maximum / hybrid (glv_bars_mode_kernel)
                 BARS_COLUMNS,                                                   // means of three such texels (glv_columns_kernel; rows c / 65535)
-                BARS_COLUMNS_TEXELS } bars = NO_BARS;                           // ... over texel rows (a columns track call's scan results)
+                BARS_COLUMNS_TEXELS,                                            // ... over texel rows (a columns track call's scan results; gl_storage 3)
+                BARS_MODE_TEXELS, BARS_SNAP_MODE_TEXELS } bars = NO_BARS;       // BARS_F32 / BARS_SNAP_MODE under maximum / hybrid over texel rows (gl_storage 3:
+                                                                               // glv_bars_mode_kernel's texel-row kind)
     int variant = 0, grid = 0;                  // the frame kernel's configuration and workgroups (FFT chains)
     glv::FrameClass cls = glv::FC_PLAIN;        // ... and its class
     unsigned ops = 0;                           // what the first kernel runs (FrameArgs::ops)

@@ -414,7 +414,7 @@ glv_frame_kernel(const FrameArgs a) {
                 }
             } else
             if (active) {
-                if (GL16 && a.bars_r16 && snap) {          // snapped texels: the integer results as they are
+                if (a.bars_r16 && snap) {                  // snapped texels: the integer results as they are (the GL_R16 chain's, or FC_STATE_SNAP's)
                     uint16_t* bo = reinterpret_cast<uint16_t*>(a.bars_out) + row * a.bars;
                     const uint32_t* lout = reinterpret_cast<const uint32_t*>(lres);
                     for (uint32_t k = (uint32_t) tid; k < a.bars; k += T) bo[k] = (uint16_t) lout[k];
@@ -716,13 +716,15 @@ hipError_t launch_variant(FrameClass cls, const FrameArgs& a, int grid, hipStrea
     // region (NBUF 1); the GL_R16 chain is built for log modes 0 and 1
     auto launch_class = [&](auto c) -> hipError_t {
         constexpr int C = decltype(c)::value;
-        // (IN_S16_TRACK / IN_F32_TRACK: a track call's transform is always stateless -- the other twelve classes are not instantiated for them)
+        // (IN_S16_TRACK / IN_F32_TRACK: a track call's transform is always stateless -- the other fourteen classes are not instantiated for them)
         if constexpr ((fc_fused_bars(C) && !(FR::T % 64 == 0 && NBUF == 1)) || (fc_gl16(C) && LOG_MODE == 2) || ((IN_MODE == IN_S16_TRACK || IN_MODE == IN_F32_TRACK || in_track_table(IN_MODE)) && fc_has_state(C))) return hipErrorInvalidValue;
         else if constexpr (fc_has_state(C))
             return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TW_STATEFUL, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE_S>, done[C]);
         else return launch(glv_frame_kernel<LOG_NN, IN_MODE, LOG_MODE, SLOTS, NBUF, TWREG, WINLDS, OCC, PREFETCH, TILTREG, LOG_E, C, WPRE>, done[C]);
     };
     switch (cls) {     // (in the order of the kernels in the code object)
+        case FC_STATE_COLS:      return launch_class(std::integral_constant<int, FC_STATE_COLS>{});
+        case FC_STATE_SNAP:      return launch_class(std::integral_constant<int, FC_STATE_SNAP>{});
         case FC_GL16_LIVE:       return launch_class(std::integral_constant<int, FC_GL16_LIVE>{});
         case FC_GL16_COLS_LIVE:  return launch_class(std::integral_constant<int, FC_GL16_COLS_LIVE>{});
         case FC_GL16_COLS:       return launch_class(std::integral_constant<int, FC_GL16_COLS>{});

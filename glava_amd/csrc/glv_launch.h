@@ -81,11 +81,13 @@ constexpr uint32_t kRowsI8Rings[] = {160, 288, 448, 832, 1600};
 // rt: the tables of the many-bars kernels (>= 256 bars; glv_tables.h make_bar_mtiles): tiles of 32 bars with their weights, the bars'
 // weight sums, and -- when they could be cut -- the rounds of the matrix-core kernel for an LDS ring of ring_bins bins (one of kRowsRings)
 // mode != 0 (glv_params.sample_mode maximum / hybrid): the block-transposed weights of glv_bars_mode_kernel (glv_tables.h make_bar_mode_blocks) and the
-// bins of a row its bars sample; the other tables are then unused
+// bins of a row its bars sample; the other tables are then unused.  rows_texels (mode != 0 only): `spec` is uint16 [nrows][n], GL_R16 texels c -- the kernel's
+// texel-row kind takes x = c / 65535 correctly rounded (unorm16_to_float: what texelFetch returns) and walks as over floats
 struct BarRowsTables {
     const BarMTile* mtiles; uint32_t ntiles; const float* wt; const float* wsum;
     const BarTile* rounds; uint32_t nrounds, ring_bins;
     uint32_t mode = 0; float hybrid_weight = 0.65f; const BarModeBlock* mblocks = nullptr; uint32_t nmblocks = 0; const float* mw = nullptr; uint32_t mode_bins = 0;
+    uint32_t rows_texels = 0;
 };
 hipError_t launch_bars(const float* spec, float* bars_out, size_t nrows, uint32_t n, uint32_t bars, uint32_t nsteps,
                        const BarItem* items, const BarDesc* desc, const float* tap_w, hipStream_t st, bool r16 = false, const BarRowsTables* rt = nullptr);

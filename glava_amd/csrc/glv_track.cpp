@@ -101,6 +101,17 @@ int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsig
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams at pitch_frames=%u: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams, pitch_frames);
     tp.state = (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)) != 0;
     tp.live = live;
+    if (upload_storage(b->p)) {
+        // gl_storage 3: the float chain (float rows into the scan, float state) whose results leave as the upload's texels wherever bars follow -- from the
+        // scan's float-state form, or from a stateless transform directly; the bars of a second launch as plan_chain picks them (check_ops vetted them)
+        const bool with_bars = (ops & GLV_OP_BARS) != 0, averaging = b->p.sample_mode == GLV_SAMPLE_AVERAGE;
+        tp.bars = !with_bars ? ChainPlan::NO_BARS
+                  : b->snapped() ? (b->columns() ? ChainPlan::BARS_COLUMNS_TEXELS : averaging ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_MODE_TEXELS)
+                                 : (averaging ? ChainPlan::BARS_I8 : ChainPlan::BARS_MODE_TEXELS);
+        tp.out16 = with_bars || (ops & GLV_OP_R16) != 0;
+        tp.in16 = !tp.state && tp.out16;
+        return GLV_OK;                  // (live: such a batch has no live bins -- tp.kept stays 0, the full-row form)
+    }
     if (columns) {      // (check_ops: GLV_OP_BARS on a GL chain with state, no GLV_OP_R16; gl_storage 2 went above -- texel state, texel rows all the way)
         tp.bars = ChainPlan::BARS_COLUMNS_TEXELS; tp.in16 = tp.out16 = true;
         if (live) tp.kept = kept_bins(b, tp);
@@ -271,7 +282,7 @@ const char* bars_kernel_name(const glv_batch* b, ChainPlan::Bars bars) {
     switch (bars) {
         case ChainPlan::BARS_I8: case ChainPlan::BARS_I8_FLOATS: return "glv_bars_rows_i8_kernel";
         case ChainPlan::BARS_SNAP: case ChainPlan::BARS_SNAP_FLOATS: return "glv_bars_snap_kernel";
-        case ChainPlan::BARS_SNAP_MODE: return "glv_bars_mode_kernel";
+        case ChainPlan::BARS_SNAP_MODE: case ChainPlan::BARS_SNAP_MODE_TEXELS: case ChainPlan::BARS_MODE_TEXELS: return "glv_bars_mode_kernel";
         default: return b->p.sample_mode != GLV_SAMPLE_AVERAGE ? "glv_bars_mode_kernel" : b->p.bars >= glv::kBarSeqMin ? "glv_bars_rows_kernel" : "glv_bars_kernel";
     }
 }

@@ -27,6 +27,10 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_STATE = 0, 1, 2, 3, 4, 5
 BARS_NONE, BARS_F32_CHAIN, BARS_F32_MATRIX, BARS_I8_EXACT, BARS_F32_SEQ = 0, 1, 2, 3, 4
 ROUND_SINUSOIDAL, ROUND_CIRCULAR, ROUND_LINEAR = 0, 1, 2          # glv_params.round_formula
 SAMPLE_AVERAGE, SAMPLE_MAXIMUM, SAMPLE_HYBRID = 0, 1, 2            # glv_params.sample_mode
+# glv_params.gl_storage: float state and float rows (the CPU operators) / GL_R16 state, one launch (GLava as shipped) / the GL passes one by one on
+# float state / the CPU operators on float state as with 0, and OP_BARS samples the GL_R16 upload of the finished buffer (GLava with `setaccelfft false`;
+# added within ABI 7: a library that has it accepts the value in glv_batch_create)
+GL_STORAGE_FLOAT, GL_STORAGE_R16, GL_STORAGE_PASSES, GL_STORAGE_UPLOAD = 0, 1, 2, 3
 
 
 class GlvError(RuntimeError):
@@ -167,7 +171,12 @@ def _check(rc: int) -> None:
 
 @dataclass
 class Params:
-    """Mirror of glv_params; defaults are the shipped GLava configuration."""
+    """Mirror of glv_params; defaults are the shipped GLava configuration.
+
+    gl_storage: GL_STORAGE_FLOAT (0, the CPU operators on float state), GL_STORAGE_R16 (1, the GL passes on GL_R16 state in one launch),
+    GL_STORAGE_PASSES (2, the GL passes one by one) or GL_STORAGE_UPLOAD (3, GLava with `setaccelfft false`: everything as with 0, and OP_BARS -- the
+    pre-smoothing pass, bar texels, column texels, maximum / hybrid -- samples the GL_R16 upload of the finished float rows; OP_WAVE | OP_BARS as with 1).
+    A batch moves between 0, 2 and 3 through set_params; 1 is a state class of its own."""
     n: int = 4096
     channels: int = 2
     fft_scale: float = 10.2

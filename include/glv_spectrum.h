@@ -139,7 +139,7 @@ enum {
                                                                   needs no rows between launches.  glv_batch_track_wave_s16 inherits it.
                                    A new bit: every call without it is what it was.  Refused: with GLV_OP_FFT / GRAVITY / AVERAGE / RAW / WRANGE / MAGNITUDE /
                                    SMOOTH / OUTPUT_IS_STATE (GLV_ERR_INVALID); GLV_OP_WAVE | GLV_OP_BARS on a gl_storage 0 batch (GLV_ERR_STATE: a float chain has
-                                   no texel rows), on a batch whose ops_mask lacked either bit (GLV_ERR_STATE: the rows between the two launches are made at
+                                   no texel rows -- true of 0, the operators alone; gl_storage 3 adds the upload and takes the call exactly as 1 does), on a batch whose ops_mask lacked either bit (GLV_ERR_STATE: the rows between the two launches are made at
                                    creation); any GLV_OP_WAVE call, with or without bars, while column texels are set (GLV_ERR_STATE: the wave shader does not average three texels).  With bar texels set
                                    (glv_batch_set_bar_texels) GLV_OP_WAVE | GLV_OP_BARS gives the texels of the pass at the table's positions */
     GLV_OP_OUTPUT_IS_STATE = 1u << 12 /* opt-in, with a chain that ENDS in gravity (GLV_OP_GRAVITY without AVERAGE / SMOOTH / RAW, f32
@@ -206,8 +206,29 @@ typedef struct glv_params {
                                GL_R16 texels (GLV_OP_R16) or their floats c / 65535.  28 n bytes per frame at avg_frames = 5.
                                2: the same values, pass by pass as the reference runs them: the transform writes f32 spectra, a
                                second kernel applies gravity / average on f32 state (every value a float c / 65535).  Bit-identical
-                               to 1 on every input; kept as the checker of 1 and for the chains 1 does not fuse.  The storage
-                               class (1 vs 0 / 2) is fixed when a batch or state is created. */
+                               to 1 on every input; kept as the checker of 1 and for the chains 1 does not fuse.
+                               3 (added within ABI 7; detect it by glv_batch_create accepting the value): GLava with `setaccelfft false`.
+                               The CPU operators on float state exactly as with 0 -- float rows out, GLV_OP_R16 texels out and the
+                               state afterwards are gl_storage 0's in every bit (render.c:2149-2155) -- and then the GL_R16 upload of
+                               the finished buffer (render.c:2185, :521-524), which is what GLV_OP_BARS samples: with c[i] =
+                               unorm16(row[i]) the texels of the finished float row of an FFT chain (with or without gravity /
+                               average), the call's output is what the GL chains define over texel rows c in the arithmetic
+                               glv_batch_bars_arithmetic reports -- sample_mode average at 256 bars or more: GLV_BARS_I8_EXACT
+                               (with bars = n, bar_phase 0.5 the pre-smoothing pass of render.c:2276-2303); bar texels
+                               (glv_batch_set_bar_texels) and column texels (glv_batch_set_column_texels): the texels / the
+                               column_mean of three texels of that pass over the same rows; sample_mode maximum / hybrid:
+                               GLV_BARS_F32_SEQ over x = c / 65535, with or without a table, at any bar count.  GLV_OP_WAVE |
+                               GLV_OP_BARS as with 1.  Not offered (the non-shipped `setsmoothpass false` / `setsmooth` corners,
+                               GLV_ERR_STATE): unsnapped averaging bars below 256 (or without integer tables), GLV_OP_SMOOTH or
+                               GLV_OP_RAW together with GLV_OP_BARS, GLV_OP_BARS without GLV_OP_FFT, and glv_batch_bars on
+                               caller's rows; without GLV_OP_BARS, GLV_OP_SMOOTH is what it is on 0.  A GLV_OP_BARS_ONLY batch has
+                               no live bins (glv_batch_live_bins 0) and runs the full chain with the same results.  Routes
+                               (glv_batch_last_launches): bar texels and columns in ONE launch where the GL_R16 chain fuses them
+                               (kernel classes FC_STATE_SNAP / FC_STATE_COLS: the finished float row in LDS is sampled through the
+                               upload's quantiser), else two: the float-state kernel writes the upload's texels of the bins the
+                               bars sample into the internal rows, then glv_bars_rows_i8_kernel / glv_bars_snap_kernel /
+                               glv_columns_kernel / glv_bars_mode_kernel (texel-row kinds) run on them.
+                               The storage class (1 vs 0 / 2 / 3) is fixed when a batch or state is created. */
     float bar_phase;        /* GLV_OP_BARS evaluates smooth_audio() at idx = (k + bar_phase) / bars, k = 0 .. bars-1.
                                0 (default): the bar positions of the modules (radial/1.frag:58-70: pos = k / (NBARS / 2)) with the
                                `setsmoothpass false` semantics -- smooth_audio() averaging the spectrum at those positions.  With
@@ -336,9 +357,9 @@ typedef struct glv_batch glv_batch;
 
 int glv_batch_create(const glv_params* p, uint32_t streams, unsigned ops_mask, int device, glv_batch** out);
 /* Change the scalar knobs of a batch (fft_scale, fft_cutoff, gravity_step, ur, avg_window*, log_mode, channels, bars,
- * smooth_*, bar_phase, gl_storage 0 <-> 2): regenerates and uploads whatever tables depend on them -- synchronously; this is the
+ * smooth_*, bar_phase, gl_storage among 0, 2 and 3): regenerates and uploads whatever tables depend on them -- synchronously; this is the
  * only place besides creation that allocates or copies.  n, avg_frames and the state's storage class (gl_storage == 1 or not)
- * are fixed at creation (GLV_ERR_STATE).  State (gravity, history, rings) is kept. */
+ * are fixed at creation (GLV_ERR_STATE: moving to or from 1).  State (gravity, history, rings) is kept. */
 int glv_batch_set_params(glv_batch* b, const glv_params* p);
 int glv_batch_reset(glv_batch* b);
 int glv_batch_destroy(glv_batch* b);
@@ -364,6 +385,10 @@ int glv_batch_process_s16(glv_batch* b, const int16_t* d_pcm, float* d_out, unsi
  * whatever the batch holds.
  * Accepted: GLV_OP_FFT (required; alone it is a spectrogram) with GLV_OP_GRAVITY / AVERAGE / BARS / R16 in the combinations glv_batch_process_s16 takes,
  * on gl_storage 0 and 1, channels 1 and 2, every log_mode, GLV_OP_BARS with and without a bar-texel table (glv_batch_set_bar_texels).
+ * gl_storage 3 (added within ABI 7): every track entry -- this one, glv_batch_track_windows_*, _columns_*, _live_* (the full-row form: such a batch has no live
+ * bins), _at_*, _rates_* and the wave entries -- takes such a batch under its own contract, word for word: the stateless transform writes float rows (texel
+ * rows where no state follows and bars do), the scan runs its float-state form and writes the upload's texels for GLV_OP_BARS, and the texel-row bars /
+ * snap / columns / mode kernel follows; the workspace queries follow those element sizes (float rows in the first region, texel rows in the second).
  * Refused: GLV_ERR_INVALID -- GLV_OP_RAW / SMOOTH / WAVE / WRANGE / MAGNITUDE / OUTPUT_IS_STATE, steps == 0, hop not a power of two in [4, n],
  * pitch_frames % hop != 0, pitch_frames < n + (steps - 1) * hop, a NULL pointer, a workspace that is not 256-byte aligned, more than 2^32 rows in one
  * call; GLV_ERR_STATE -- gl_storage 2 (the checker form), a batch created with GLV_OP_BARS_ONLY (its state beyond the live bins does not exist),
@@ -700,7 +725,8 @@ int glv_batch_ring_append_f32(glv_batch* b, const float* d_new, uint32_t new_fra
 int glv_batch_ring_planar(glv_batch* b, int f32_ring, float* d_planar, void* hip_stream);
 
 /* smooth_audio() bar sampling of spectra already in HBM (d_spec float [streams][2][n]) into
- * d_bars float [streams][2][bars]; what GLV_OP_BARS runs after the transform. */
+ * d_bars float [streams][2][bars]; what GLV_OP_BARS runs after the transform.  Refused on a gl_storage 3 batch (GLV_ERR_STATE): there GLV_OP_BARS samples the
+ * upload's texels, and caller's float rows go through a gl_storage 0 batch. */
 int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_stream);
 
 /* GLV_OP_BARS at texels of the pre-smoothed texture: bar k = texel t[k] of the pre-smoothing pass (bars = n, bar_phase 0.5), which is what the
@@ -713,9 +739,11 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
  * takes the bars (the GL_R16 chain, gl_storage 1, sample_mode average, whenever the unsnapped bars of the configuration fuse), else as a second launch.
  *   texels == NULL or count == 0: off -- the unsnapped bars again, bit for bit.  Synchronous, may allocate (like glv_batch_set_params).
  *   Refused: count != bars or any t[k] >= n (GLV_ERR_INVALID); a batch created without GLV_OP_BARS or with gl_storage 0 (GLV_ERR_STATE: a float chain
- *   has no pre-smoothed texture); a twin whose arithmetic would be GLV_BARS_F32_MATRIX (GLV_ERR_INVALID, glv_last_error says why).
- *   While a table is set: glv_batch_set_params that changes bars or sets gl_storage 0, glv_batch_bars, and GLV_OP_BARS calls that are not a GL chain
- *   (GLV_OP_FFT with gravity / average, no GLV_OP_SMOOTH) or GLV_OP_WAVE | GLV_OP_BARS (the same contract over the wave texture: the twin is the same
+ *   has no pre-smoothed texture -- true of 0, the operators alone; gl_storage 3, the same chain followed by the upload, takes the table: the twin's rows are
+ *   then the upload's texels of the finished float rows, stateless FFT chains included, in one launch where the GL_R16 chain would fuse the same table); a twin whose arithmetic would be GLV_BARS_F32_MATRIX (GLV_ERR_INVALID, glv_last_error says why).
+ *   While a table is set: glv_batch_set_params that changes bars or sets gl_storage 0 (a float chain has no pre-smoothed texture: true of 0, not of 3),
+ *   glv_batch_bars, and GLV_OP_BARS calls that are not a GL chain
+ *   (GLV_OP_FFT with gravity / average, no GLV_OP_SMOOTH; gl_storage 3: any GLV_OP_FFT chain without GLV_OP_SMOOTH / GLV_OP_RAW) or GLV_OP_WAVE | GLV_OP_BARS (the same contract over the wave texture: the twin is the same
  *   GLV_OP_WAVE | GLV_OP_BARS call with bars = n, bar_phase 0.5; always a second launch) are refused with GLV_ERR_STATE; a change of smooth_factor or of the shape rebuilds the
  *   table's taps.  glv_batch_reset keeps the table, glv_batch_destroy frees it.
  * glv_batch_live_bins: every snapped position lies in [0, 1), which the live bins already cover whenever smooth_factor >= 1 / bars (the unsnapped
@@ -755,7 +783,8 @@ int glv_batch_timing_end(glv_batch* b, double* kernel_ms, uint64_t* launches);
 /* Algorithmic HBM bytes one process call moves for the given ops: what the CHAIN must move -- input, state
  * read and written, output.  Rows that one launch of a multi-launch chain hands to the next (the uint16 `av` rows in front of the
  * pre-smoothing pass, bars that are not computed inside the transform's launch) are traffic of the organisation, not of the problem, and
- * are not counted -- except gl_storage 2, whose pass-by-pass f32 round trip (+16 n) is its definition.  A chain that ends in gravity is
+ * are not counted -- except gl_storage 2, whose pass-by-pass f32 round trip (+16 n) is its definition; gl_storage 3 counts as the float chain of
+ * gl_storage 0 (the texel rows between its two launches are not counted).  A chain that ends in gravity is
  * counted with its output copy (28 n) unless GLV_OP_OUTPUT_IS_STATE is in `ops` (20 n; a NULL d_out moves those 20 n too).
  * GLV_OP_WAVE: the input bytes the result depends on plus the output bytes, per stereo frame -- without GLV_OP_BARS the whole window (4 n for s16, 8 n
  * for f32) and 4 n texels or 8 n floats out; with GLV_OP_BARS the frames the bars sample (4 or 8 bytes x the sampled reach: the bins below the last tap of
@@ -827,7 +856,9 @@ const char* glv_batch_kernel_name(const glv_batch* b);
  *   GLV_BARS_F32_SEQ       (ABI 7) sample_mode maximum / hybrid: one lane per bar and row, the shader's loop in float as glv_params.sample_mode documents
  *                          (oracle glvo_bars_mode_at), float and texel rows alike
  * With bar texels set (glv_batch_set_bar_texels) it reports the twin's arithmetic: GLV_BARS_I8_EXACT or GLV_BARS_F32_SEQ.
- * Float rows (gl_storage 0) always take the float forms.  Callers and parity tests that depend on the exact form check this. */
+ * Float rows (gl_storage 0) always take the float forms.  gl_storage 3 reports what GLV_OP_BARS runs over the upload's texels of its float rows: the same
+ * values as 1 and 2 (GLV_BARS_F32_CHAIN and GLV_BARS_F32_MATRIX then name bars a GLV_OP_BARS call on such a batch refuses).  Callers and parity tests that
+ * depend on the exact form check this. */
 enum { GLV_BARS_NONE = 0, GLV_BARS_F32_CHAIN = 1, GLV_BARS_F32_MATRIX = 2, GLV_BARS_I8_EXACT = 3, GLV_BARS_F32_SEQ = 4 };
 int glv_batch_bars_arithmetic(const glv_batch* b);
 
