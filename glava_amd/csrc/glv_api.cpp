@@ -77,6 +77,7 @@ int batch_create_rows(const glv_params* p, uint32_t streams, unsigned ops_mask, 
     b->unfused_bars = std::getenv("GLV_UNFUSED_BARS") != nullptr;
     b->unfused_wave = std::getenv("GLV_UNFUSED_WAVE") != nullptr;
     if (const char* o = std::getenv("GLV_TRACK_WAVE_ORDER")) b->track_wave_by_steps = std::strcmp(o, "steps") == 0;
+    if (const char* o = std::getenv("GLV_TRACK_FRAMES_SEGMENT")) b->track_frames_segment = (uint32_t) std::strtoul(o, nullptr, 10);
     b->bar_i8_off = std::getenv("GLV_NO_BARS_I8") != nullptr;
     b->log_nn = log2_exact(p->n) - 1;
     hipDeviceProp_t prop;

@@ -184,6 +184,7 @@ struct glv_batch {
     bool unfused_bars = false;   // GLV_UNFUSED_BARS in the environment at creation (diagnostics: bars always as a second launch)
     bool unfused_wave = false;   // GLV_UNFUSED_WAVE likewise: GLV_OP_WAVE | GLV_OP_BARS always as the waveform kernel + the bars kernel
     bool track_wave_by_steps = kTrackWaveBySteps;   // row order of glv_batch_track_wave_s16's one-launch form (GLV_TRACK_WAVE_ORDER=rows|steps at creation: diagnostics)
+    uint32_t track_frames_segment = 0;              // frames per segment of glv_batch_track_frames_s16 / _f32's frames kernel (GLV_TRACK_FRAMES_SEGMENT=<frames> at creation: diagnostics; 0: glv::track_frames_segment)
     bool state16 = false;        // gl_storage == 1 at creation: d_grav / d_hist hold uint16 texels (2 bytes per value)
     float grav_g = 0.f; uint32_t grav_sub = 0; bool grav_int = false, grav_known = false;   // the gravity step on texels (glv_tables.h gravity_r16_integer_step)
     DeviceArray<float> d_scratch;    // [streams*2][n] spectra feeding GLV_OP_BARS

@@ -48,6 +48,22 @@ struct TrackGeometry {
     const float* ur;           //   kernel's rates kind -- float [steps] in device memory, read in [0, steps) only; nullptr: every other call, FrameArgs::g / grav_sub as they are
 };
 hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool rows_texels, hipStream_t st);
+// The render frames of a track call on gl_storage 3 (glv_track_frames.hip; glv_batch_track_frames_s16 / _f32).  Keyframe k of the call is block k of `keys`
+// (float [2][units][n]) for k < 2 and the finished float rows of step k - 2 in `rows` (float [steps][units][n]) beyond; frame j of row r is the GL_R16 upload
+// of keyframe from[j] itself where from[j] == to[j], of s + ((e - s) * mod[j]) of keyframes from[j] and to[j] else (render.c:1806, :2185).  The tables are
+// device memory, read in [0, frames) only, every index clamped to steps + 1 in the kernel.  out: uint16 [frames][units][n], rows at pitch n of which bins
+// [0, limit) are written (limit a multiple of 4); segment: the frames one lane walks with its keyframes in registers (track_frames_segment: the default).
+struct TrackFrames {
+    const uint32_t* from; const uint32_t* to; const float* mod;
+    const float* keys; const float* rows;
+    void* out;
+    uint32_t frames, steps, units, n, limit, segment;
+};
+uint32_t track_frames_segment(uint32_t frames, uint32_t units, uint32_t limit);
+hipError_t launch_track_frames(const TrackFrames& t, hipStream_t st);
+// ... and the keyframes the next call starts from: keys[0] <- keyframe keep_from, keys[1] <- keyframe keep_to, element by element, both read before either is
+// written (the pairs (0, 1), (1, k >= 2) and (k, k') with 2 <= k < k': the host vets them)
+hipError_t launch_track_keys(float* keys, const float* rows, uint32_t units, uint32_t n, uint32_t keep_from, uint32_t keep_to, hipStream_t st);
 // Where the windows of the track sources of GLV_OP_WAVE lie (glv_wave_kernel, glv_bars_rows_i8_kernel).  A process call's windows lie back to back -- the
 // identity geometry, which those kernels' existing kinds have built in and never read from here.  A track call (glv_batch_track_wave_s16) cuts them
 // out of [streams][pitch_frames][2] recordings: output row r = t * units + 2 s + c is channel c of the n frames from s * pitch_frames + t * hop on,

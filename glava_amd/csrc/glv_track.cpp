@@ -45,6 +45,9 @@ struct TrackPlan {
     const float* ur = nullptr;          // a rates call's table of update rates, float [steps]; set by track_at as starts is, read by the scan alone
     bool live = false;                  // the entry is the live form (glv_batch_track_live_s16 / _f32)
     uint32_t kept = 0;                  // the live form's kept bins K, a multiple of 64 below n (kept_bins); 0: every bin -- the other entries, and the live form's full-row form
+    const glv_track_frames* fr = nullptr;   // a frames call (glv_batch_track_frames_s16 / _f32): its render frames; set before the plan (the sizing query's holds `frames` alone)
+    uint64_t frame_rows = 0;            // ... fr->frames * streams * 2: the rows the frames kernel writes and the bars run over
+    uint64_t frames_off = 0;            // ... and where its texel rows lie in the workspace when bars follow: behind the transform's region and the scan's
 };
 // What the two track entries (glv_batch_track_s16, glv_batch_track_windows_s16) share, written once so that they cannot disagree: the refusals that are
 // not about hop or pitch, and what the chain's stages carry.  In the order the checks have always run: (1) the arguments ...
@@ -108,7 +111,8 @@ int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsig
         tp.bars = !with_bars ? ChainPlan::NO_BARS
                   : b->snapped() ? (b->columns() ? ChainPlan::BARS_COLUMNS_TEXELS : averaging ? ChainPlan::BARS_SNAP : ChainPlan::BARS_SNAP_MODE_TEXELS)
                                  : (averaging ? ChainPlan::BARS_I8 : ChainPlan::BARS_MODE_TEXELS);
-        tp.out16 = with_bars || (ops & GLV_OP_R16) != 0;
+        // (a frames call: every step's finished rows stay floats -- they are the keyframes; the upload is the frames kernel's)
+        tp.out16 = !tp.fr && (with_bars || (ops & GLV_OP_R16) != 0);
         tp.in16 = !tp.state && tp.out16;
         return GLV_OK;                  // (live: such a batch has no live bins -- tp.kept stays 0, the full-row form)
     }
@@ -168,10 +172,11 @@ int windows_args(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps
 void windows_geometry(const glv_batch* b, uint32_t steps, unsigned ops, TrackPlan& tp) {
     const uint32_t n = b->p.n;
     tp.windows = true; tp.scan = tp.state; tp.hops_per_pitch = steps;      // (one residue: log_q and residue_rows stay 0)
-    tp.to_out = !tp.state && !(ops & GLV_OP_BARS);
+    tp.to_out = !tp.state && !(ops & GLV_OP_BARS) && !tp.fr;
     if (tp.to_out) { tp.rows_bytes = 0; tp.work_bytes = 256; return; }
     tp.rows_bytes = up256(tp.out_rows * n * (tp.in16 ? 2u : 4u));
-    tp.work_bytes = tp.rows_bytes + (tp.state && (ops & GLV_OP_BARS) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+    tp.frames_off = tp.rows_bytes + (tp.state && ((ops & GLV_OP_BARS) || tp.fr) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
+    tp.work_bytes = tp.frames_off + (tp.fr && (ops & GLV_OP_BARS) ? up256(tp.frame_rows * n * 2u) : 0u);      // a frames call with bars: the frames' texel rows
 }
 int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     if (int rc = track_args(ops, steps)) return rc;
@@ -207,6 +212,22 @@ int plan_track_at(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint3
     if (b->ops_mask & GLV_OP_BARS_ONLY) return plan_track_live(b, pitch_frames, hop, steps, ops, tp);
     if (b->columns()) return plan_track_columns(b, pitch_frames, hop, steps, ops, tp);
     return plan_track_windows(b, pitch_frames, hop, steps, ops, tp);
+}
+// glv_batch_track_frames_s16 / _f32: what the frames ask of the ops and the batch, then the table call's plan with tp.fr set -- float rows out of its last float
+// stage (track_chain), parked in the workspace (windows_geometry), the frames' texel rows behind them where bars follow.
+int plan_track_frames(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsigned ops, TrackPlan& tp) {
+    if (tp.fr->frames == 0) return fail(GLV_ERR_INVALID, "frames must be > 0");
+    if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no keyframes: a frames track call takes an FFT chain (ops 0x%x)", ops);
+    if (!(ops & (GLV_OP_R16 | GLV_OP_BARS)))
+        return fail(GLV_ERR_INVALID, "a frames track call's result is a texture: GLV_OP_R16 (the upload's texels) and / or GLV_OP_BARS (ops 0x%x)", ops);
+    if (!upload_storage(b->p))
+        return fail(GLV_ERR_STATE, "gl_storage=%u: keyframes are interpolated in front of the GL_R16 upload of gl_storage 3 (0 has no upload, on 1 the reference forces interpolation off)",
+                    b->p.gl_storage);
+    if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
+    tp.frame_rows = (uint64_t) tp.fr->frames * b->streams * 2u;
+    if (tp.frame_rows > 0xffffffffull)
+        return fail(GLV_ERR_INVALID, "frames=%u of %u streams: more than 2^32 - 1 rows in one call, cut the frames into chunks", tp.fr->frames, b->streams);
+    return plan_track_at(b, pitch_frames, 0u, steps, ops, tp);
 }
 
 int refuse_track_pointers(const void* d_pcm, bool f32, const void* d_out, const void* d_work) {
@@ -268,13 +289,33 @@ int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t st
     return GLV_OK;
 }
 // (3) for a batch with column texels: the columns of every step's row, from the scan's texels
-int track_columns(glv_batch* b, const TrackPlan& tp, const float* rows, float* out, hipStream_t st) {
-    const hipError_t e = glv::launch_columns_texels(reinterpret_cast<const uint16_t*>(rows), out, (size_t) tp.out_rows, b->p.n,
+int track_columns(glv_batch* b, const float* rows, size_t units, float* out, hipStream_t st) {
+    const hipError_t e = glv::launch_columns_texels(reinterpret_cast<const uint16_t*>(rows), out, units, b->p.n,
                                                     (uint32_t) b->snap_x.tex.size(), b->p.bars, b->snap_x.col_nsteps, b->snap_x.col_items, b->snap.desc, b->snap.w,
                                                     b->snap_x.col_map, b->p.sample_mode, shape_hybrid(b->p), st);
     ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "columns launch failed: %s", hipGetErrorString(e));
     b->kernel_name = "glv_columns_kernel";
+    return GLV_OK;
+}
+// A frames call, between (2) and (3): every render frame's buffer as the upload's texels (glv_track_frames_kernel), from the keyframes the caller carries and the
+// steps' finished float rows -- into d_out, or with bars behind those rows in the workspace, where only the bins the bars kernel reads are written (plan_chain's
+// limit for the same kernels on this storage).  Then the keyframes the next call starts from.  `rows`: the steps' rows in, the rows stage (3) reads out.
+int track_frames(glv_batch* b, const TrackPlan& tp, float*& rows, uint32_t steps, char* work, float* out, unsigned ops, hipStream_t st) {
+    const glv_track_frames& fr = *tp.fr;
+    const bool bars = (ops & GLV_OP_BARS) != 0;
+    glv::TrackFrames t;
+    t.from = fr.d_from; t.to = fr.d_to; t.mod = fr.d_mod; t.keys = fr.d_keys; t.rows = rows;
+    t.out = bars ? static_cast<void*>(work + tp.frames_off) : static_cast<void*>(out);
+    t.frames = fr.frames; t.steps = steps; t.units = b->streams * 2u; t.n = b->p.n; t.limit = b->p.n;
+    const uint32_t bins = b->snapped() ? b->snap.bins : b->bar_x.bins_needed;
+    if (bars && bins != 0 && bins < b->p.n) t.limit = (bins + 3u) & ~3u;
+    t.segment = b->track_frames_segment != 0 ? b->track_frames_segment : glv::track_frames_segment(t.frames, t.units, t.limit);
+    hipError_t e = glv::launch_track_frames(t, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "frames launch failed: %s", hipGetErrorString(e));
+    e = glv::launch_track_keys(fr.d_keys, rows, t.units, t.n, fr.keep_from, fr.keep_to, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "keyframe write-back launch failed: %s", hipGetErrorString(e));
+    if (bars) rows = static_cast<float*>(t.out);
     return GLV_OK;
 }
 // the kernel (family) of stage (3), which a live track call names (the other entries have always named the scan)
@@ -307,11 +348,15 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     ChainPlan pl;
     pl.bars = tp.bars;
     pl.rows = reinterpret_cast<float*>(work + (tp.scan ? tp.rows_bytes : 0u));       // what the bars read: the scan's results, or a stateless transform's rows
-    if (tp.scan) if (int rc = track_scan(b, tp, a, steps, work, (ops & GLV_OP_BARS) ? pl.rows : out, ops, st)) return rc;
-    // (3) the bars of every step's rows, or the columns
-    if (tp.bars == ChainPlan::BARS_COLUMNS_TEXELS) { if (int rc = track_columns(b, tp, pl.rows, out, st)) return rc; }
-    else if (int rc = launch_bars_pass(b, pl, out, (size_t) steps * b->streams * 2u, (ops & GLV_OP_R16) != 0, st)) return rc;
+    const bool parked = (ops & GLV_OP_BARS) || tp.fr;      // the steps' finished rows stay in the workspace: the bars read them, or a frames call's frames kernel
+    if (tp.scan) if (int rc = track_scan(b, tp, a, steps, work, parked ? pl.rows : out, ops, st)) return rc;
+    size_t units = (size_t) tp.out_rows;
+    if (tp.fr) { if (int rc = track_frames(b, tp, pl.rows, steps, work, out, ops, st)) return rc; units = (size_t) tp.frame_rows; }
+    // (3) the bars of every step's rows (a frames call: of every frame's), or the columns
+    if (tp.bars == ChainPlan::BARS_COLUMNS_TEXELS) { if (int rc = track_columns(b, pl.rows, units, out, st)) return rc; }
+    else if (int rc = launch_bars_pass(b, pl, out, units, (ops & GLV_OP_R16) != 0, st)) return rc;
     else if (tp.live) b->kernel_name = bars_kernel_name(b, tp.bars);
+    if (tp.fr) b->kernel_name = "glv_track_frames_kernel";      // (a frames call names its own kernel, whatever follows it)
     return timed_launch_end(b, st);
 }
 
@@ -406,27 +451,47 @@ uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, ui
 }
 // glv_batch_track_at_s16 / _f32: the table's own refusals, then the form the ops and the batch select -- the wave form's executor, or the FFT forms'.
 // d_ur: the second table of a rates call (track_rates has vetted it, and that the ops have the gravity that reads it); nullptr: the batch's own ur
+// fr: the render frames of a frames call (track_frames_call has vetted them and the ops); nullptr: every other call
 int track_at(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
-             const float* d_ur = nullptr) {
+             const glv_track_frames* fr = nullptr, const float* d_ur = nullptr) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_starts) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (reinterpret_cast<uintptr_t>(d_starts) & 3u) return fail(GLV_ERR_INVALID, "d_starts must be 4-byte aligned");
     if (ops & GLV_OP_WAVE) return track_wave(b, d_pcm, f32, pitch_frames, 0u, steps, d_out, d_work, ops, st, d_starts);
     TrackPlan tp;
-    if (int rc = plan_track_at(b, pitch_frames, 0u, steps, ops, tp)) return rc;
+    tp.fr = fr;
+    if (int rc = fr ? plan_track_frames(b, pitch_frames, steps, ops, tp) : plan_track_at(b, pitch_frames, 0u, steps, ops, tp)) return rc;
     tp.f32 = f32; tp.starts = d_starts; tp.ur = d_ur;
     return track(b, tp, d_pcm, pitch_frames, 0u, steps, d_out, d_work, ops, st);
 }
 // glv_batch_track_rates_s16 / _f32: the rate table's own refusals, then the table call.  The wave form keeps no state and applies no gravity, and a chain
 // without gravity would leave the table unread: both are the caller's mistake, not a call that quietly ignores an argument.
 int track_rates(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
-                unsigned ops, hipStream_t st) {
+                unsigned ops, hipStream_t st, const glv_track_frames* fr = nullptr) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_ur) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (reinterpret_cast<uintptr_t>(d_ur) & 3u) return fail(GLV_ERR_INVALID, "d_ur must be 4-byte aligned");
     if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE is stateless: no gravity reads the rate table (glv_batch_track_at_s16 / _f32; ops 0x%x)", ops);
     if (!(ops & GLV_OP_GRAVITY)) return fail(GLV_ERR_INVALID, "a rates track call needs GLV_OP_GRAVITY, which reads the rate table (ops 0x%x)", ops);
-    return track_at(b, d_pcm, f32, pitch_frames, d_where, steps, d_out, d_work, ops, st, d_ur);
+    return track_at(b, d_pcm, f32, pitch_frames, d_where, steps, d_out, d_work, ops, st, fr, d_ur);
+}
+// glv_batch_track_frames_s16 / _f32: what can be said of the frames without the batch's plan -- the pointers and the pair of keyframes kept -- then the rates call
+// or the table call with the frames handed on.  Nothing here launches; a refusal below (plan_track_frames, the table call's own) leaves the batch as untouched.
+int track_frames_call(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, const glv_track_frames* fr,
+                      void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!fr) return fail(GLV_ERR_INVALID, "fr is NULL");
+    if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no keyframes: a frames track call takes an FFT chain (ops 0x%x)", ops);
+    if (!fr->d_from || !fr->d_to || !fr->d_mod || !fr->d_keys) return fail(GLV_ERR_INVALID, "NULL device pointer in glv_track_frames");
+    if ((reinterpret_cast<uintptr_t>(fr->d_from) | reinterpret_cast<uintptr_t>(fr->d_to) | reinterpret_cast<uintptr_t>(fr->d_mod)) & 3u)
+        return fail(GLV_ERR_INVALID, "d_from, d_to and d_mod must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(fr->d_keys) & 15u) return fail(GLV_ERR_INVALID, "d_keys must be 16-byte aligned");
+    const uint32_t kf = fr->keep_from, kt = fr->keep_to;
+    if (!((kf == 0u && kt == 1u) || (kf == 1u && kt >= 2u) || (kf >= 2u && kt > kf)) || (uint64_t) kt >= (uint64_t) steps + 2u)
+        return fail(GLV_ERR_INVALID, "keep_from=%u, keep_to=%u: the keyframes kept are (0, 1), (1, k) or (k, k') with 2 <= k < k' < steps + 2 = %llu", kf, kt,
+                    (unsigned long long) steps + 2u);
+    if (d_ur) return track_rates(b, d_pcm, f32, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, st, fr);
+    return track_at(b, d_pcm, f32, pitch_frames, d_where, steps, d_out, d_work, ops, st, fr);
 }
 }  // namespace
 
@@ -554,5 +619,30 @@ int glv_batch_track_rates_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch
 int glv_batch_track_rates_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
                               unsigned ops, void* hip_stream) {
     return track_rates(b, d_pcm, true, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (one query for glv_batch_track_frames_s16 and _f32: the table call's regions with float rows in both, and with bars the frames' texel rows behind them; asked, like
+// glv_batch_track_at_work_bytes, with the shortest recording a call takes)
+uint64_t glv_batch_track_frames_work_bytes(const glv_batch* b, uint32_t steps, uint32_t frames, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    glv_track_frames shape = {};
+    shape.frames = frames;
+    TrackPlan tp;
+    tp.fr = &shape;
+    if (const int rc = plan_track_frames(b, b->p.n, steps, ops, tp)) {
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return tp.work_bytes;
+}
+
+int glv_batch_track_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, const glv_track_frames* fr,
+                               void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_frames_call(b, d_pcm, false, pitch_frames, d_where, d_ur, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, const glv_track_frames* fr,
+                               void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_frames_call(b, d_pcm, true, pitch_frames, d_where, d_ur, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 }  // extern "C"

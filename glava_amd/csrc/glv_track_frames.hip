@@ -1,0 +1,125 @@
+// glv_track_frames.hip -- the render frames of a track call on gl_storage 3 (glv_batch_track_frames_s16 / _f32): keyframe interpolation and the GL_R16
+// upload of every frame's buffer in one launch, and the keyframes a next call starts from in another.
+//
+//   glv_track_frames_kernel   frame j of row r = unorm16(s + ((e - s) * mod[j])) of keyframes from[j] and to[j] (render.c:1792-1809, :2185, :521-524)
+//   glv_track_keys_kernel     d_keys[0] <- keyframe keep_from, d_keys[1] <- keyframe keep_to (render.c:2347-2353 as it stands after the last frame)
+#include <hip/hip_runtime.h>
+
+#include "glv_core.h"
+#include "glv_launch.h"
+#include "glv_launch_util.h"
+
+namespace glv {
+
+typedef float glv_f4 __attribute__((ext_vector_type(4)));
+typedef uint32_t glv_u2 __attribute__((ext_vector_type(2)));
+
+// Keyframe k of a call is row block k of `keys` for k < 2 and the finished float rows of step k - 2 beyond: every index a table holds is clamped to
+// steps + 1 here, so whatever the tables hold nothing outside the two arrays is read.
+// One lane owns four consecutive bins of one channel row (a 16-byte keyframe load, an 8-byte texel store) and walks the frames of one segment with both
+// keyframes in registers: a keyframe is loaded when its index changes and taken from the other register where a push moved it there (`from` of a frame is
+// `to` of its predecessor whenever an update was pushed between them), so a segment of a live session's tables reads each keyframe row about once instead of
+// twice per frame.  The tables hold absolute indices: no frame depends on another, a segment starts anywhere, and the work items are
+// [segment][row][group of 256 bins] -- a workgroup is one wave and takes the items blockIdx.x, blockIdx.x + gridDim.x, ... of however many there are.
+// The table entries of the frame kFramesDepth ahead are requested with the frame being computed (uniform across the workgroup, inside [0, frames) only), as
+// glv_track_scan_kernel requests its rates.
+// `limit`: the bins of a row that are written, a multiple of 4 -- the row where the texels are the result, what the bars kernel of the next launch reads else.
+// The lerp is the three float operations of render.c:1806 in its order, compiled without contraction; from == to is the keyframe's own bits, no arithmetic
+// (render.c:2185 with interpolation off).  The quantiser is pack_unorm16, the upload every gl_storage 3 class applies.
+constexpr int kFramesLanes = 64;
+constexpr int kFramesDepth = 4;
+constexpr size_t kFramesGridCap = 256 * 32;           // 256 CUs x 32 resident waves
+
+__global__ void __launch_bounds__(kFramesLanes) glv_track_frames_kernel(const TrackFrames t, const uint32_t groups, const uint64_t items) {
+    const uint32_t last_key = t.steps + 1u;
+    uint16_t* const out = static_cast<uint16_t*>(t.out);
+    for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const uint32_t group = (uint32_t) (item % groups);
+        const uint64_t rest = item / groups;
+        const uint32_t row = (uint32_t) (rest % t.units);
+        const uint32_t seg = (uint32_t) (rest / t.units);
+        const uint32_t bin = (group * (uint32_t) kFramesLanes + threadIdx.x) * 4u;
+        if (bin >= t.limit) continue;                                       // the last group of a row: nothing of these lanes is read or written
+        const uint32_t j0 = seg * t.segment;                                // (< frames: the host counted the segments)
+        const uint32_t j1 = t.frames - j0 > t.segment ? j0 + t.segment : t.frames;
+        auto key = [&](uint32_t k) -> glv_f4 {
+            const float* const base = k < 2u ? t.keys + ((size_t) k * t.units + row) * t.n : t.rows + ((size_t) (k - 2u) * t.units + row) * t.n;
+            return *reinterpret_cast<const glv_f4*>(base + bin);
+        };
+        uint32_t from[kFramesDepth], to[kFramesDepth];
+        float mod[kFramesDepth];
+#pragma unroll
+        for (int d = 0; d < kFramesDepth; ++d) {
+            const bool in = (uint32_t) d < j1 - j0;
+            from[d] = in ? t.from[j0 + (uint32_t) d] : 0u; to[d] = in ? t.to[j0 + (uint32_t) d] : 0u; mod[d] = in ? t.mod[j0 + (uint32_t) d] : 0.0f;
+        }
+        uint32_t ks = 0xffffffffu, ke = 0xffffffffu;                         // the keyframes in s and e: none yet (no clamped index is this)
+        glv_f4 s = { 0.0f, 0.0f, 0.0f, 0.0f }, e = s;
+        for (uint32_t jb = j0; jb < j1; jb += (uint32_t) kFramesDepth) {
+#pragma unroll
+            for (int d = 0; d < kFramesDepth; ++d) {
+                const uint32_t j = jb + (uint32_t) d;
+                if (j >= j1) break;
+                const uint32_t kf = from[d] < last_key ? from[d] : last_key, kt = to[d] < last_key ? to[d] : last_key;
+                const float m = mod[d];
+                if (j1 - j > (uint32_t) kFramesDepth) {
+                    from[d] = t.from[j + (uint32_t) kFramesDepth]; to[d] = t.to[j + (uint32_t) kFramesDepth]; mod[d] = t.mod[j + (uint32_t) kFramesDepth];
+                }
+                glv_f4 ns = s;
+                if (kf != ks) ns = kf == ke ? e : key(kf);
+                if (kt != ke) e = kt == ks ? s : key(kt);
+                s = ns; ks = kf; ke = kt;
+                glv_f4 w = s;
+                if (kf != kt) w = s + ((e - s) * m);                        // render.c:1806
+                const glv_u2 c = { pack_unorm16(w.x, w.y), pack_unorm16(w.z, w.w) };    // render.c:521-524
+                *reinterpret_cast<glv_u2*>(out + ((size_t) j * t.units + row) * t.n + bin) = c;
+            }
+        }
+    }
+}
+
+// Element i of both kept keyframes is read before element i of either destination is written, and no other lane touches element i: the pairs the host
+// accepts -- (0, 1), (1, k), (k, k') with 2 <= k < k' -- never read what another lane has written.
+__global__ void __launch_bounds__(256) glv_track_keys_kernel(float* keys, const float* rows, const size_t quads, const uint32_t keep_from, const uint32_t keep_to) {
+    glv_f4* const k0 = reinterpret_cast<glv_f4*>(keys);
+    glv_f4* const k1 = k0 + quads;
+    const glv_f4* const steps = reinterpret_cast<const glv_f4*>(rows);
+    const glv_f4* const a = keep_from < 2u ? k0 + (size_t) keep_from * quads : steps + (size_t) (keep_from - 2u) * quads;
+    const glv_f4* const b = keep_to < 2u ? k0 + (size_t) keep_to * quads : steps + (size_t) (keep_to - 2u) * quads;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < quads; i += (size_t) gridDim.x * blockDim.x) {
+        const glv_f4 va = a[i], vb = b[i];
+        k0[i] = va; k1[i] = vb;
+    }
+}
+
+// The frames of a segment where the caller names none: long enough that a keyframe serves several frames, short enough that a single stream's call still
+// fills the chip -- two rounds of the 8192 resident waves where frames * units * groups allow them (a wave's walk is a chain of 512-byte stores: with one
+// segment, 64 streams x 3426 frames of N = 4096 ran on 2048 waves and wrote 2.3 TB/s, profiles/r19/track_frames.txt).
+constexpr uint64_t kFramesWaves = 2u * kFramesGridCap;
+uint32_t track_frames_segment(uint32_t frames, uint32_t units, uint32_t limit) {
+    const uint64_t per_segment = (uint64_t) units * ((limit / 4u + (uint32_t) kFramesLanes - 1u) / (uint32_t) kFramesLanes);
+    const uint64_t wanted = per_segment >= kFramesWaves ? 1u : (kFramesWaves + per_segment - 1u) / per_segment;
+    const uint64_t len = ((uint64_t) frames + wanted - 1u) / wanted;
+    return (uint32_t) (len < 8u ? 8u : len);
+}
+
+hipError_t launch_track_frames(const TrackFrames& t, hipStream_t st) {
+    if (!t.from || !t.to || !t.mod || !t.keys || !t.rows || !t.out) return hipErrorInvalidValue;
+    if (t.frames == 0 || t.steps == 0 || t.units == 0 || t.segment == 0 || t.limit == 0 || t.limit > t.n || (t.limit & 3u) || (t.n & 3u) || t.steps > 0xfffffffdu)
+        return hipErrorInvalidValue;
+    const uint32_t groups = (t.limit / 4u + (uint32_t) kFramesLanes - 1u) / (uint32_t) kFramesLanes;
+    const uint64_t segments = ((uint64_t) t.frames + t.segment - 1u) / t.segment;
+    const uint64_t items = segments * t.units * groups;                      // (< 2^32 * 2^32 / 4: no overflow)
+    const unsigned grid = capped_grid((size_t) items, 1, kFramesGridCap);
+    hipLaunchKernelGGL(glv_track_frames_kernel, dim3(grid), dim3(kFramesLanes), 0, st, t, groups, items);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_keys(float* keys, const float* rows, uint32_t units, uint32_t n, uint32_t keep_from, uint32_t keep_to, hipStream_t st) {
+    if (!keys || !rows || units == 0 || n == 0 || (n & 3u)) return hipErrorInvalidValue;
+    const size_t quads = (size_t) units * (n / 4u);
+    hipLaunchKernelGGL(glv_track_keys_kernel, dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, keys, rows, quads, keep_from, keep_to);
+    return hipGetLastError();
+}
+
+}  // namespace glv

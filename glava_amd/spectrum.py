@@ -56,6 +56,13 @@ class MultiStats(C.Structure):
     _fields_ = [("frames", C.c_uint64), ("seconds", C.c_double), ("bytes", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class TrackFrames(C.Structure):
+    """glv_track_frames: the render frames of a glv_batch_track_frames_s16 / _f32 call -- three device tables of `frames` entries, the caller-owned keyframes
+    and the pair of keyframe indices written back to them"""
+    _fields_ = [("d_from", C.c_void_p), ("d_to", C.c_void_p), ("d_mod", C.c_void_p), ("frames", C.c_uint32), ("d_keys", C.c_void_p),
+                ("keep_from", C.c_uint32), ("keep_to", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -115,6 +122,12 @@ def lib() -> C.CDLL:
         if hasattr(L, "glv_batch_track_rates_s16"):     # (likewise: a table call with a second table, the update rate gravity runs at per step)
             L.glv_batch_track_rates_s16.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_track_rates_f32.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_frames_s16"):    # (likewise: a table or rates call on gl_storage 3 whose output is every render frame's texture, keyframes interpolated)
+            FR = C.POINTER(TrackFrames)
+            L.glv_batch_track_frames_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint]
+            L.glv_batch_track_frames_work_bytes.restype = C.c_uint64
+            L.glv_batch_track_frames_s16.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_frames_f32.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -352,6 +365,37 @@ class Batch:
     def track_rates_f32(self, d_pcm, pitch_frames: int, d_starts, d_ur, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
         """track_rates_s16 from a float recording (glv_batch_track_rates_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
         _check(lib().glv_batch_track_rates_f32(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), _ptr(d_ur), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_frames_work_bytes(self, steps: int, frames: int, ops: int) -> int:
+        """bytes of device workspace track_frames_s16 / _f32 need for these arguments (glv_batch_track_frames_work_bytes: the steps' float rows, the scan's where
+        the chain keeps state, and with OP_BARS the frames' texel rows); raises on arguments the call refuses"""
+        nbytes = int(lib().glv_batch_track_frames_work_bytes(self._h, steps, frames, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)
+        return nbytes
+
+    def _track_frames(self, kind: str, d_pcm, pitch_frames, d_starts, d_ur, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream) -> None:
+        fr = TrackFrames(_ptr(d_from), _ptr(d_to), _ptr(d_mod), frames, _ptr(d_keys), keep[0], keep[1])
+        _check(getattr(lib(), f"glv_batch_track_frames_{kind}")(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), _ptr(d_ur), steps, C.byref(fr), _ptr(d_out),
+                                                                 _ptr(d_work), ops, _ptr(stream)))
+
+    def track_frames_s16(self, d_pcm, pitch_frames: int, d_starts, d_ur, steps: int, d_from, d_to, d_mod, frames: int, d_keys, keep: tuple[int, int], d_out, d_work,
+                         ops: int, stream: int | None = None) -> None:
+        """track mode at render frames on a gl_storage 3 batch (glv_batch_track_frames_s16): the `steps` updates of track_at_s16 (d_ur None) or track_rates_s16
+        run and leave the batch exactly as those calls do; d_out then holds, frame-major, what a process call with `ops` would write for each of `frames`
+        render frames if its finished float row were the frame's buffer -- keyframe d_from[j] itself where d_from[j] == d_to[j], else
+        s + ((e - s) * d_mod[j]) of keyframes d_from[j] and d_to[j] in float32 (`setinterpolate true`).  Keyframes 0 and 1 are d_keys float32
+        [2][streams][2][n] (zeros before a session's first call), keyframe 2 + t the finished float row of step t; afterwards d_keys holds keyframes
+        keep[0] and keep[1], what the next call of the session starts from.  d_from / d_to uint32 [frames], d_mod float32 [frames], all in device memory;
+        ops OP_FFT with OP_R16 and / or OP_BARS; d_work at least track_frames_work_bytes(steps, frames, ops) bytes, 256-byte aligned.  Tables:
+        glava_amd.track_starts.keyframe_tables / live_session_frames.  Stream-ordered, kernels only; every table is read when the kernels run."""
+        self._track_frames("s16", d_pcm, pitch_frames, d_starts, d_ur, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
+
+    def track_frames_f32(self, d_pcm, pitch_frames: int, d_starts, d_ur, steps: int, d_from, d_to, d_mod, frames: int, d_keys, keep: tuple[int, int], d_out, d_work,
+                         ops: int, stream: int | None = None) -> None:
+        """track_frames_s16 from a float recording (glv_batch_track_frames_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
+        self._track_frames("f32", d_pcm, pitch_frames, d_starts, d_ur, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

@@ -87,3 +87,91 @@ def live_session_rates(rate: int, fps: int, frames: int, update_frames: int) -> 
             cur = unpack("f", pack("f", ucounter / tcounter))[0]      # render.c:2387: a double quotient stored in a float
             tcounter, ucounter = 0.0, 0
     return starts, step_of_frame, ur
+
+
+def _f32(x: float) -> float:
+    from struct import pack, unpack
+    return unpack("f", pack("f", x))[0]
+
+
+def _f32_mul(a: float, b: float) -> float:
+    """the float32 product of two float32 values: their double product is exact (48 significant bits), so one rounding gives it"""
+    return _f32(a * b)
+
+
+def keyframe_tables(modified, on, uratio, kcounter: int = 0) -> tuple[list[int], list[int], list[float], int, int]:
+    """The keyframe tables of glv_batch_track_frames_s16 / _f32 for one call's render frames.  Per frame: modified[j] -- the frame runs an update (the next
+    step of the call, in order); on[j] -- keyframe interpolation is configured on (`setinterpolate true`); uratio[j] -- gl->ur / gl->fr as the frame computes
+    it (render.c:1761), any number that float32 holds.  Returns (from, to, mod, keep_from, keep_to) in the call's keyframe indices: 0 and 1 are the `start` and
+    `end` keyframes the call is handed in d_keys, 2 + t is the finished row of the call's step t.
+
+    What it restates.  A frame interpolates when on[j] and uratio[j] <= 0.9F (render.c:1763).  It then uploads start + (end - start) * mod of the keyframes as
+    they stand BEFORE its own update is pushed, mod = min(uratio * kcounter, 1.0F) in float32 (render.c:1804-1806, :2185): from = start, to = end.  A frame
+    that does not interpolate uploads its buffer (render.c:2185), which holds the spectrum its own update just finished or, without one, the last one
+    finished: from = to = that row.  Before the call's first update that row is keyframe 1 -- exact where the previous call's last update was pushed, and the
+    zeros of a fresh d_keys at the start of a session (GLava's buffers are zeroed too); a call cut while interpolation is off is best cut at a frame that runs
+    an update.  After the upload, a frame with an update pushes start <- end, end <- its row only if it interpolated (render.c:2348: keyframes go stale while
+    interpolation is off) and resets kcounter; any other frame increments it (render.c:2380-2383).  keep_from / keep_to are start and end after the last
+    frame: what the next call finds in d_keys.  kcounter: the frames without an update directly in front of the call's first frame (gl->kcounter as the call
+    finds it; 0 at the start of a session and wherever a call begins right after a frame with an update) -- with it the tables of a session cut into calls are
+    the uncut session's."""
+    modified, on, uratio = list(modified), list(on), list(uratio)
+    if not (len(modified) == len(on) == len(uratio)) or not modified:
+        raise ValueError("modified, on and uratio must be equally long lists of at least one render frame")
+    if not isinstance(kcounter, int) or isinstance(kcounter, bool) or kcounter < 0:
+        raise ValueError(f"kcounter must be an integer >= 0, not {kcounter!r}")
+    start, end, shown, step = 0, 1, 1, 0
+    frm: list[int] = []
+    to: list[int] = []
+    mod: list[float] = []
+    for m, o, u in zip(modified, on, uratio):
+        u = _f32(float(u))
+        lerp = bool(o) and u <= _f32(0.9)                    # render.c:1763
+        if m:
+            shown = 2 + step
+            step += 1
+        if lerp:
+            frm.append(start); to.append(end)
+            mod.append(min(_f32_mul(u, float(kcounter)), 1.0))     # render.c:1804-1805 (kcounter < 2^24: exact as a float)
+        else:
+            frm.append(shown); to.append(shown)
+            mod.append(0.0)
+        if m:
+            if lerp: start, end = end, shown                 # render.c:2347-2353
+            kcounter = 0
+        else:
+            kcounter += 1
+    return frm, to, mod, start, end
+
+
+def live_session_frames(rate: int, fps: int, frames: int, update_frames: int) -> tuple[list[int], list[float], list[int], list[int], list[float], int, int]:
+    """live_session_rates extended by the measured frame rate gl->fr: a `setinterpolate true` session on `setaccelfft false` (gl_storage 3) over `frames`
+    render frames.  Returns (starts, ur, from, to, mod, keep_from, keep_to): the first two are live_session_rates' tables, the rest keyframe_tables' for the
+    session's frames -- everything glv_batch_track_frames_s16 / _f32 takes besides the recording.
+
+    What it restates.  gl->fr starts at 1.0 like gl->ur (render.c:905-906); when tcounter reaches 1.0 both are set from the same counters, fr = (float)
+    (fcounter / tcounter) (render.c:2386), and frame j computes uratio = ur / fr in float from the values as they stand before its own counters are added.
+    At 22050 Hz and updates of 256 frames a 60 fps session never interpolates (uratio 1.0, then 59 / 60); a 144 fps session does from its second second on
+    (85.4 / 144).  The double additions are live_session_rates' own, and so is the disclaimer: every frame meets its target, wall-clock jitter is not modelled."""
+    _positive(fps=fps)
+    starts, step_of_frame = live_update_starts(rate, fps, 1, frames, update_frames)
+    duration = 1.0 / float(fps)                     # render.c:2362
+    ur: list[float] = []
+    modified: list[bool] = []
+    uratio: list[float] = []
+    cur_ur, cur_fr, tcounter, ucounter, fcounter = 1.0, 1.0, 0.0, 0, 0
+    for j in range(frames):
+        ran = step_of_frame[j] >= 0 and (j == 0 or step_of_frame[j] != step_of_frame[j - 1])      # `modified`
+        modified.append(ran)
+        uratio.append(_f32(cur_ur / cur_fr))        # render.c:1761: a float quotient (the double quotient of two floats rounds to it)
+        fcounter += 1                               # render.c:2379
+        if ran:
+            ur.append(cur_ur)
+            ucounter += 1                           # render.c:2380-2381
+        tcounter += duration                        # render.c:2384
+        if tcounter >= 1.0:
+            cur_fr = _f32(fcounter / tcounter)      # render.c:2386
+            cur_ur = _f32(ucounter / tcounter)      # render.c:2387
+            tcounter, ucounter, fcounter = 0.0, 0, 0
+    frm, to, mod, keep_from, keep_to = keyframe_tables(modified, [True] * frames, uratio)
+    return starts, ur, frm, to, mod, keep_from, keep_to

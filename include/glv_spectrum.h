@@ -690,6 +690,71 @@ int glv_batch_track_rates_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch
                               void* d_out, void* d_work, unsigned ops, void* hip_stream);
 int glv_batch_track_rates_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, const float* d_ur, uint32_t steps,
                               void* d_out, void* d_work, unsigned ops, void* hip_stream);
+/* Track mode at render frames: the entries above give one result per UPDATE.  With `setinterpolate true` on `setaccelfft false` (gl_storage 3) the texture a
+ * module samples on a render frame is not the latest finished spectrum but start + (end - start) * min(uratio * kcounter, 1) of the last two finished rows
+ * (render.c:1760-1763, :1792-1809; the upload picks that buffer, :2185; the pre-smoothing pass runs over the upload, :2276-2303; the keyframes are pushed at
+ * :2347-2353, the counters kept at :2379-2383) -- whenever the update rate is below 0.9 of the frame rate: a 144 Hz display, `setsamplesize 4096`.  These
+ * entries run the updates of a recording AND give every render frame's texture, bars, bar texels or columns in one call.  Added within ABI 7; detect by the symbol.
+ *   Updates: d_where / d_ur / steps are glv_batch_track_at_* 's d_starts and glv_batch_track_rates_* 's d_ur, word for word (d_ur NULL: the batch's own ur, the
+ *   table call; else the rates call with its refusals).  The `steps` updates run through those calls' executor, and afterwards the batch's state (gravity store,
+ *   history ring, ring head, gravity form) is bit for bit what they leave.
+ *   Keyframes: keyframe k of a call is d_keys[k] for k < 2 -- `start` and `end` as the previous call left them -- and for k >= 2 the finished FLOAT row of step
+ *   k - 2, what the same call on a gl_storage 0 batch writes as floats.  Every index a table holds is clamped to steps + 1 in the kernel: whatever the tables
+ *   hold, no launch reads outside d_keys, the steps' rows, or the tables' [0, frames).
+ *   Frame j, per row and bin: d_from[j] == d_to[j] -- that keyframe's own bits, no arithmetic (a frame whose uratio > 0.9 or with interpolation off: render.c:2185
+ *   uploads the buffer); else w = s + ((e - s) * d_mod[j]) of keyframes s = d_from[j], e = d_to[j]: three separate IEEE float operations in the order of
+ *   render.c:1806, no fused multiply-add, d_mod[j] applied as given (the host's min(uratio * kcounter, 1.0F)).  Then the upload's quantiser c = unorm16(w), the
+ *   function every gl_storage 3 class applies (NaN and -0 give 0).
+ *   d_out, frame-major: block j is what a gl_storage 3 process call with these ops would write if its finished float row were w_j.  GLV_OP_R16 without
+ *   GLV_OP_BARS: the upload's texels, uint16 [frames][streams][2][n].  With GLV_OP_BARS the bars kernel follows over frames * streams * 2 texel rows -- the integer
+ *   pass at 256 bars or more, bar texels, column texels (floats), maximum / hybrid, each in the arithmetic glv_batch_bars_arithmetic reports, as texels with
+ *   GLV_OP_R16 -- [frames][streams][2][bars].
+ *   Write-back: after the last frame d_keys[0] <- keyframe keep_from and d_keys[1] <- keyframe keep_to, both read before either is written; the pairs are (0, 1),
+ *   (1, k >= 2) and (k, k') with 2 <= k < k'.  So chunks compose: a session cut into calls, each starting from the d_keys its predecessor left, gives the frames of
+ *   the uncut session.  d_keys is zero-filled before a session's first call: the reference mallocs its keyframe buffers (render.c:1682) and shows garbage until two
+ *   updates have passed; zero is this library's definition (integration/nullgl_harness.c does the same).
+ *   Workspace: glv_batch_track_frames_work_bytes(b, steps, frames, ops) bytes, 256-byte aligned: the steps' float rows from the transform, the scan's where the
+ *   chain keeps state, and with GLV_OP_BARS the frames' texel rows (each region rounded up to 256 bytes).
+ * Launches (glv_batch_last_launches): the table call's for the float chain without bars (1 stateless, 2 with state), + 1 (glv_track_frames_kernel), + 1 (the
+ * write-back), + 1 with GLV_OP_BARS.  Stream-ordered: kernels only, nothing allocated or synchronised, the first call can be captured; all tables are read when
+ * the kernels run, so rewriting d_mod in stream order re-aims a captured call.  glv_batch_kernel_name reports "glv_track_frames_kernel", whatever follows it.
+ * Refused, launching nothing and leaving the batch untouched -- GLV_ERR_STATE: any gl_storage but 3 (on 1 the reference forces interpolation off,
+ * render.c:2161-2168; 0 has no upload), a single-row batch, and everything the underlying table call refuses with this code; GLV_ERR_INVALID: fr NULL or any of
+ * its pointers NULL, frames == 0, d_keys not 16-byte aligned or a table not 4-byte aligned, a keep pair outside the list above or >= steps + 2, ops without
+ * GLV_OP_R16 or GLV_OP_BARS (the result is a texture), GLV_OP_WAVE, frames * streams * 2 > 2^32 - 1, and everything the table call refuses with this code.
+ * Kernel (glv_track_frames.hip): one lane owns four consecutive bins of a row (16-byte keyframe loads, 8-byte texel stores) and walks a segment of frames with
+ * both keyframes in registers, reloading one only when its index changes -- a live session's tables advance monotonically, so a keyframe row is read about once per
+ * segment, not twice per frame; table entries are requested 4 frames ahead; the grid is segments x rows x groups of 256 bins, looped over beyond 8192 workgroups,
+ * the segment at least 8 frames and as long as still leaves 16384 workgroups.  With GLV_OP_BARS only the bins the bars kernel reads are written, the limit of
+ * gl_storage 3's two-launch process route.  The scan, frame and bars kernels kept their code.
+ * Python: glava_amd.track_starts.keyframe_tables(modified, on, uratio) gives (from, to, mod, keep_from, keep_to) from a session's per-frame record;
+ * live_session_frames(rate, fps, frames, update_frames) the whole session's tables with gl->fr measured as the reference measures it (wall-clock jitter is not
+ * modelled).
+ * Measured (tools/track_frames_bench.py, profiles/r19/track_frames.txt; the protocol of profiles/r17/track_rates.txt: one MI355X, N = 4096, gl_storage 3, F = 5, the
+ * pre-smoothing pass, texels out, the tables of live_session_frames(22050, 144, ..., 256), medians of 7 alternating rounds, spread = max - min; 1 / 8 / 64 streams x
+ * 2048 steps = 3426 frames, 1024 streams x 256 steps = 430 frames):
+ *   (a) the frames call against glv_batch_track_rates_s16 on the same batch and steps: 1.569 against 1.529 ms, 2.133 against 1.934, 7.019 against 5.584, 11.561
+ *       against 8.694 (spreads 0.01 / 0.02 / 0.18 / 0.13) -- 1.67 times the rows through the bars kernel, and the frames stage;
+ *   (b) the frames stage alone (frames kernel and write-back, texels out, by difference of HIP-event times): 0.030 / 0.210 / 1.556 / 3.219 ms, i.e. 4.8 / 4.8 / 5.1 /
+ *       5.0 TB/s of texels written and keyframe rows read, beside the 5.47 TB/s of profiles/stream_ceiling.json's read-write mix (4.0-6.2 TB/s for pure writes).
+ *       With one segment at 64 streams (the default as first built: 2048 workgroups) the same stage took 3.460 ms, 2.3 TB/s;
+ *   (c) glv_batch_track_at_s16 on the shipped GL chain in this library against the parent commit's: 1.967 / 2.532 / 5.419 / 8.152 against 1.971 / 2.527 / 5.444 /
+ *       7.997 ms (spreads 0.020 / 0.026 / 0.227 / 0.385 and 0.055 / 0.032 / 0.112 / 0.337), inside the spread at every point; bench.py 103.8 / 102.1 against
+ *       103.9 / 103.3 M frames/s alternating (profiles/r19/bench_compare.txt), inside the run-to-run spread.  The device code of every object both trees have is the
+ *       parent's byte for byte (tools/track_frames_isa.py, profiles/r19/track_frames_isa.txt). */
+typedef struct glv_track_frames {
+    const uint32_t* d_from;   /* uint32 [frames], device: keyframe index of `start` for render frame j            */
+    const uint32_t* d_to;     /* uint32 [frames], device: keyframe index of `end`                                   */
+    const float*    d_mod;    /* float  [frames], device: the host's min(uratio * kcounter, 1.0F), applied as given */
+    uint32_t        frames;   /* render frames of this call, >= 1                                                   */
+    float*          d_keys;   /* float [2][streams][2][n], device, caller-owned, 16-byte aligned: keyframes 0 and 1 */
+    uint32_t        keep_from, keep_to;   /* keyframe indices written back to d_keys[0] / d_keys[1] after the call  */
+} glv_track_frames;
+uint64_t glv_batch_track_frames_work_bytes(const glv_batch* b, uint32_t steps, uint32_t frames, unsigned ops);   /* 0: refused, glv_last_error starts with the code's name; sizes both entries */
+int glv_batch_track_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur /* NULL: the batch's ur */,
+                               uint32_t steps, const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur /* NULL: the batch's ur */,
+                               uint32_t steps, const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
