@@ -128,6 +128,20 @@ hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint3
 hipError_t launch_wave_track(const void* pcm, bool f32, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st);
 hipError_t launch_bars_i8_pcm_track(const void* pcm, const WaveWindows& w, bool mono, void* bars_out, uint32_t n, uint32_t bars, const BarIRowsTables* rt, hipStream_t st,
                                     bool r16);
+// The render frames of a wave track call (glv_track_frames.hip; glv_batch_track_wave_frames_s16 / _f32): TrackFrames' tables and arithmetic with the keyframes
+// beyond the caller's two read from the recording where they lie.  Keyframe k < 2 is block k of `keys` (float [2][w.units][n]); keyframe 2 + t of row 2 s + c and
+// sample i is (u + 1.0F) / 2.0F of the unpack u of frame wave_window_start(w, s, t, w.starts[t]) + i (w.starts is required: a table call's windows), every index
+// clamped to w.steps + 1 in the kernel.  out: rows [frames][w.units] at pitch n of which samples [0, limit) are written (limit a multiple of 4) -- the upload's
+// texels (r16) or their floats c / 65535; segment: as TrackFrames', with the streams as its rows (a lane owns both channel rows of its four frames).
+struct WaveFrames {
+    const uint32_t* from; const uint32_t* to; const float* mod;
+    float* keys;
+    void* out;
+    uint32_t frames, n, limit, segment;
+};
+hipError_t launch_wave_frames(const void* pcm, bool f32, const WaveWindows& w, bool mono, const WaveFrames& t, bool r16, hipStream_t st);
+// ... and the keyframes the next call starts from, as floats: keys[0] <- keyframe keep_from, keys[1] <- keyframe keep_to (launch_track_keys' pairs, vetted by the host)
+hipError_t launch_wave_keys(const void* pcm, bool f32, const WaveWindows& w, bool mono, float* keys, uint32_t n, uint32_t keep_from, uint32_t keep_to, hipStream_t st);
 // bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels) over texel rows: uint16, or floats c / 65535 (rows_f32); one lane per bar and row
 hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const uint32_t* wi,
                             hipStream_t st, bool r16);

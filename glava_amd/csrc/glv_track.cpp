@@ -373,6 +373,8 @@ struct TrackWavePlan {
                                     // only the call sees: on any other it runs `pl`.  Never from floats: the integer pass reads s16 frames, as in a process call
     uint64_t rows = 0;              // steps * streams * 2
     uint64_t work_bytes = 256;      // (without bars there is no second launch and nothing to park: the convention keeps 0 for "refused")
+    const glv_track_frames* render = nullptr;   // a frames call (glv_batch_track_wave_frames_s16 / _f32): its render frames; set before the plan (the sizing query's holds `frames` alone)
+    uint64_t frame_rows = 0;        // ... render->frames * streams * 2: the rows the frames kernel writes and the bars run over -- nothing is computed per step
 };
 int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackWavePlan& tp) {
     static const float some_output = 0.0f;       // (check_ops asks whether an output exists: the caller's is vetted by track_wave)
@@ -398,15 +400,40 @@ int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uin
         tp.one_launch = grouped.wave_fused;
         tp.work_bytes = up256(tp.rows * n * (tp.pl.wave_r16 ? 2u : 4u));
     }
+    if (!tp.render) return GLV_OK;
+    // A frames call: a table call whose rows are the render frames' -- the lerp sits between the unpack and the upload, so the pass never runs from the s16 frames
+    // in one launch, and what is parked for the bars is the frames' rows in plan_wave's format.
+    if (tp.render->frames == 0) return fail(GLV_ERR_INVALID, "frames must be > 0");
+    tp.frame_rows = (uint64_t) tp.render->frames * b->streams * 2u;
+    if (tp.frame_rows > 0xffffffffull)
+        return fail(GLV_ERR_INVALID, "frames=%u of %u streams: more than 2^32 - 1 rows in one call, cut the frames into chunks", tp.render->frames, b->streams);
+    tp.one_launch = false;
+    if (ops & GLV_OP_BARS) tp.work_bytes = up256(tp.frame_rows * n * (tp.pl.wave_r16 ? 2u : 4u));
     return GLV_OK;
 }
 
+// The two launches of a frames call in place of the waveform kernel's one: every render frame's rows (glv_wave_frames_kernel) -- into d_out, or with bars into the
+// workspace in the format and up to the limit plan_wave chose for the waveform kernel's rows -- then the keyframes the next call starts from.
+int track_wave_frames(glv_batch* b, const TrackWavePlan& tp, const void* d_pcm, const glv::WaveWindows& w, void* rows, hipStream_t st) {
+    const glv_track_frames& fr = *tp.render;
+    const bool mono = b->p.channels == 1;
+    glv::WaveFrames t;
+    t.from = fr.d_from; t.to = fr.d_to; t.mod = fr.d_mod; t.keys = fr.d_keys; t.out = rows;
+    t.frames = fr.frames; t.n = b->p.n; t.limit = (tp.pl.wave_limit + 3u) & ~3u;      // (a lane owns four frames; n is a multiple of 4)
+    t.segment = b->track_frames_segment != 0 ? b->track_frames_segment : glv::track_frames_segment(t.frames, b->streams, t.limit);
+    hipError_t e = glv::launch_wave_frames(d_pcm, tp.f32, w, mono, t, tp.pl.wave_r16, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "frames launch failed: %s", hipGetErrorString(e));
+    e = glv::launch_wave_keys(d_pcm, tp.f32, w, mono, fr.d_keys, t.n, fr.keep_from, fr.keep_to, st); ++b->last_launches;
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "keyframe write-back launch failed: %s", hipGetErrorString(e));
+    return GLV_OK;
+}
+// fr: the render frames of a frames call (track_frames_call has vetted them; a table call, so d_starts is set); nullptr: every other call
 // d_starts: the table of a table call (its entry has vetted the pointer), and `hop` is not looked at; nullptr: every `hop` frames
 int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
-               const uint32_t* d_starts = nullptr) {
+               const glv_track_frames* fr = nullptr, const uint32_t* d_starts = nullptr) {
     if (int rc = refuse_track_pointers(d_pcm, f32, d_out, d_work)) return rc;
     TrackWavePlan tp;
-    tp.f32 = f32; tp.at = d_starts != nullptr;
+    tp.f32 = f32; tp.at = d_starts != nullptr; tp.render = fr;
     if (int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) return rc;
     ChainPlan& pl = tp.pl;
     const bool fused = tp.one_launch && (reinterpret_cast<uintptr_t>(d_pcm) & 31u) == 0u;
@@ -420,6 +447,14 @@ int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames,
     w.by_steps = b->track_wave_by_steps && (4ull * w.units + 2u) * b->p.bars * 4u <= 0xffffffffull ? 1u : 0u;
     if (int rc = timed_launch_begin(b, st)) return rc;
     hipError_t e;
+    if (fr) {
+        if (ops & GLV_OP_BARS) pl.out = pl.rows = static_cast<float*>(d_work);
+        else pl.out = static_cast<float*>(d_out);
+        if (int rc = track_wave_frames(b, tp, d_pcm, w, pl.out, st)) return rc;
+        if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) tp.frame_rows, r16, st)) return rc;
+        b->kernel_name = "glv_wave_frames_kernel";      // (a frames call names its own kernel, whatever follows it)
+        return timed_launch_end(b, st);
+    }
     if (fused) {
         const glv::BarIRowsTables irt = b->bar_x.irows_tables();
         e = glv::launch_bars_i8_pcm_track(d_pcm, w, mono, d_out, b->p.n, b->p.bars, &irt, st, r16);
@@ -457,7 +492,7 @@ int track_at(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, c
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_starts) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (reinterpret_cast<uintptr_t>(d_starts) & 3u) return fail(GLV_ERR_INVALID, "d_starts must be 4-byte aligned");
-    if (ops & GLV_OP_WAVE) return track_wave(b, d_pcm, f32, pitch_frames, 0u, steps, d_out, d_work, ops, st, d_starts);
+    if (ops & GLV_OP_WAVE) return track_wave(b, d_pcm, f32, pitch_frames, 0u, steps, d_out, d_work, ops, st, fr, d_starts);
     TrackPlan tp;
     tp.fr = fr;
     if (int rc = fr ? plan_track_frames(b, pitch_frames, steps, ops, tp) : plan_track_at(b, pitch_frames, 0u, steps, ops, tp)) return rc;
@@ -477,11 +512,13 @@ int track_rates(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames
 }
 // glv_batch_track_frames_s16 / _f32: what can be said of the frames without the batch's plan -- the pointers and the pair of keyframes kept -- then the rates call
 // or the table call with the frames handed on.  Nothing here launches; a refusal below (plan_track_frames, the table call's own) leaves the batch as untouched.
+// wave: the entry is the wave form (glv_batch_track_wave_frames_s16 / _f32), whose keyframes are read from the recording -- the table call's wave executor, no rates
 int track_frames_call(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, const glv_track_frames* fr,
-                      void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+                      void* d_out, void* d_work, unsigned ops, hipStream_t st, bool wave = false) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!fr) return fail(GLV_ERR_INVALID, "fr is NULL");
-    if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no keyframes: a frames track call takes an FFT chain (ops 0x%x)", ops);
+    if (!wave && (ops & GLV_OP_WAVE)) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no keyframes: a frames track call takes an FFT chain (ops 0x%x)", ops);
+    if (wave && !(ops & GLV_OP_WAVE)) return fail(GLV_ERR_INVALID, "a wave frames track call needs GLV_OP_WAVE (ops 0x%x; GLV_OP_FFT chains: glv_batch_track_frames_s16)", ops);
     if (!fr->d_from || !fr->d_to || !fr->d_mod || !fr->d_keys) return fail(GLV_ERR_INVALID, "NULL device pointer in glv_track_frames");
     if ((reinterpret_cast<uintptr_t>(fr->d_from) | reinterpret_cast<uintptr_t>(fr->d_to) | reinterpret_cast<uintptr_t>(fr->d_mod)) & 3u)
         return fail(GLV_ERR_INVALID, "d_from, d_to and d_mod must be 4-byte aligned");
@@ -644,5 +681,30 @@ int glv_batch_track_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitc
 int glv_batch_track_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, const glv_track_frames* fr,
                                void* d_out, void* d_work, unsigned ops, void* hip_stream) {
     return track_frames_call(b, d_pcm, true, pitch_frames, d_where, d_ur, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (one query for glv_batch_track_wave_frames_s16 and _f32: 256 without bars, else the frames' rows in the format plan_wave gives the bars kernel; asked, like
+// glv_batch_track_at_work_bytes, with the shortest recording a call takes)
+uint64_t glv_batch_track_wave_frames_work_bytes(const glv_batch* b, uint32_t steps, uint32_t frames, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    glv_track_frames shape = {};
+    shape.frames = frames;
+    TrackWavePlan tp;
+    tp.at = true; tp.render = &shape;
+    if (const int rc = plan_track_wave(b, b->p.n, 0u, steps, ops, tp)) {
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return tp.work_bytes;
+}
+
+int glv_batch_track_wave_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
+                                    void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_frames_call(b, d_pcm, false, pitch_frames, d_where, nullptr, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream, true);
+}
+
+int glv_batch_track_wave_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
+                                    void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_frames_call(b, d_pcm, true, pitch_frames, d_where, nullptr, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream, true);
 }
 }  // extern "C"

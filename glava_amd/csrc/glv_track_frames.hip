@@ -3,6 +3,9 @@
 //
 //   glv_track_frames_kernel   frame j of row r = unorm16(s + ((e - s) * mod[j])) of keyframes from[j] and to[j] (render.c:1792-1809, :2185, :521-524)
 //   glv_track_keys_kernel     d_keys[0] <- keyframe keep_from, d_keys[1] <- keyframe keep_to (render.c:2347-2353 as it stands after the last frame)
+// ... and of a wave track call on any gl_storage (glv_batch_track_wave_frames_s16 / _f32), whose keyframes are read from the recording:
+//   glv_wave_frames_kernel    the same frame from keyframes (u + 1.0F) / 2.0F of the unpacked window of step k - 2 (render.c:777-778), as texels or their floats
+//   glv_wave_keys_kernel      the same write-back, as floats
 #include <hip/hip_runtime.h>
 
 #include "glv_core.h"
@@ -119,6 +122,168 @@ hipError_t launch_track_keys(float* keys, const float* rows, uint32_t units, uin
     if (!keys || !rows || units == 0 || n == 0 || (n & 3u)) return hipErrorInvalidValue;
     const size_t quads = (size_t) units * (n / 4u);
     hipLaunchKernelGGL(glv_track_keys_kernel, dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, keys, rows, quads, keep_from, keep_to);
+    return hipGetLastError();
+}
+
+// ---- the wave module's render frames (glv_batch_track_wave_frames_s16 / _f32) -----------------------------------------------------------------------------
+// A wave keyframe is a trivial function of the recording -- the backend's unpack, wrange's + 1.0F and / 2.0F (render.c:777-778) -- so the steps' float rows never
+// exist: keyframe 2 + t is read from the window of step t where it lies, as glv_wave_kernel's kinds 3 and 4 read it (the same helpers, the same clamp of the
+// table's entry, the same rule for a group that is not 16-byte aligned), and keyframes 0 and 1 from the caller's d_keys.
+// One lane owns FOUR consecutive frames of one stream, both channel rows: 16 bytes of s16 or 32 bytes of floats from the recording, two 16-byte loads from d_keys.
+// Bounded reads: i + 4 <= limit <= n and the start is clamped to pitch_frames - n, so a lane reads frames [i, i + 4) of a window inside the recording of a
+// stream < streams; a table index is clamped to steps + 1 before it is used, and the starts are read in [0, steps) only.
+typedef float glv_f2 __attribute__((ext_vector_type(2)));
+typedef uint32_t glv_u4 __attribute__((ext_vector_type(4)));
+
+template <bool F32_IN>
+__device__ __forceinline__ void wave_key(const void* pcm, const WaveWindows& w, const int mono, const float* keys, const uint32_t n, const uint32_t k,
+                                         const uint32_t stream, const uint32_t i, glv_f4& l, glv_f4& r) {
+    if (k < 2u) {
+        const float* const base = keys + ((size_t) k * w.units + 2u * stream) * n + i;
+        l = *reinterpret_cast<const glv_f4*>(base);
+        r = *reinterpret_cast<const glv_f4*>(base + n);
+        return;
+    }
+    const uint32_t step = k - 2u;                                               // (< steps: k was clamped to steps + 1)
+    const uint64_t first = wave_window_start(w, stream, step, w.starts[step]) + i;      // the lane's first frame, in 64-bit arithmetic
+    float a[4], b[4];
+    if constexpr (F32_IN) {
+        const glv_f2* const src = static_cast<const glv_f2*>(pcm) + first;
+        glv_f2 f[4];
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+            const glv_f4 lo = *reinterpret_cast<const glv_f4*>(src), hi = *reinterpret_cast<const glv_f4*>(src + 2);
+            f[0] = glv_f2{lo.x, lo.y}; f[1] = glv_f2{lo.z, lo.w}; f[2] = glv_f2{hi.x, hi.y}; f[3] = glv_f2{hi.z, hi.w};
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) f[q] = src[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (mono) { a[q] = (f[q].x + f[q].y) / 2; b[q] = a[q]; } else { a[q] = f[q].x; b[q] = f[q].y; }     // pulse_input.c:167
+        }
+    } else {
+        const uint32_t* const src = static_cast<const uint32_t*>(pcm) + first;
+        uint32_t f[4];
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+            const glv_u4 v = *reinterpret_cast<const glv_u4*>(src);
+            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) f[q] = src[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int x = (int16_t) (f[q] & 0xffffu), y = (int16_t) (f[q] >> 16);
+            if (mono) { a[q] = unpack_s16_mono(x, y); b[q] = a[q]; } else { a[q] = unpack_s16(x); b[q] = unpack_s16(y); }
+        }
+    }
+    l = glv_f4{(a[0] + 1.0f) / 2.0f, (a[1] + 1.0f) / 2.0f, (a[2] + 1.0f) / 2.0f, (a[3] + 1.0f) / 2.0f};       // render.c:777-778
+    r = glv_f4{(b[0] + 1.0f) / 2.0f, (b[1] + 1.0f) / 2.0f, (b[2] + 1.0f) / 2.0f, (b[3] + 1.0f) / 2.0f};
+}
+
+// glv_track_frames_kernel's walk with a stream's two channel rows in one lane: `s` and `e` are four float4, a keyframe is loaded when its index changes and taken
+// from the other pair of registers where a push moved it there, table entries are requested kFramesDepth ahead.  The work items are
+// [segment][stream][group of 256 frames], one wave each, looped beyond the grid.  R16_OUT: the upload's texels, 8 bytes per channel row and frame; else their
+// floats c / 65535 (what texelFetch returns: glv_wave_kernel's float form), 16 bytes.
+template <bool F32_IN, bool R16_OUT>
+__global__ void __launch_bounds__(kFramesLanes) glv_wave_frames_kernel(const void* pcm, const WaveWindows w, const int mono, const WaveFrames t, const uint32_t groups,
+                                                                       const uint64_t items) {
+    const uint32_t last_key = w.steps + 1u;
+    const uint32_t streams = w.units / 2u;
+    for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const uint32_t group = (uint32_t) (item % groups);
+        const uint64_t rest = item / groups;
+        const uint32_t stream = (uint32_t) (rest % streams);
+        const uint32_t seg = (uint32_t) (rest / streams);
+        const uint32_t i = (group * (uint32_t) kFramesLanes + threadIdx.x) * 4u;
+        if (i >= t.limit) continue;                                         // the last group of a row: nothing of these lanes is read or written
+        const uint32_t j0 = seg * t.segment;                                // (< frames: the host counted the segments)
+        const uint32_t j1 = t.frames - j0 > t.segment ? j0 + t.segment : t.frames;
+        auto emit = [&](uint32_t j, uint32_t c, const glv_f4 v) {
+            const uint32_t lo = pack_unorm16(v.x, v.y), hi = pack_unorm16(v.z, v.w);      // render.c:521-524
+            const size_t at = ((size_t) j * w.units + 2u * stream + c) * t.n + i;
+            if constexpr (R16_OUT) *reinterpret_cast<glv_u2*>(static_cast<uint16_t*>(t.out) + at) = glv_u2{lo, hi};
+            else *reinterpret_cast<glv_f4*>(static_cast<float*>(t.out) + at) =
+                     glv_f4{unorm16_to_float(lo & 0xffffu), unorm16_to_float(lo >> 16), unorm16_to_float(hi & 0xffffu), unorm16_to_float(hi >> 16)};
+        };
+        uint32_t from[kFramesDepth], to[kFramesDepth];
+        float mod[kFramesDepth];
+#pragma unroll
+        for (int d = 0; d < kFramesDepth; ++d) {
+            const bool in = (uint32_t) d < j1 - j0;
+            from[d] = in ? t.from[j0 + (uint32_t) d] : 0u; to[d] = in ? t.to[j0 + (uint32_t) d] : 0u; mod[d] = in ? t.mod[j0 + (uint32_t) d] : 0.0f;
+        }
+        uint32_t ks = 0xffffffffu, ke = 0xffffffffu;                         // the keyframes in s and e: none yet (no clamped index is this)
+        glv_f4 sl = { 0.0f, 0.0f, 0.0f, 0.0f }, sr = sl, el = sl, er = sl;
+        for (uint32_t jb = j0; jb < j1; jb += (uint32_t) kFramesDepth) {
+#pragma unroll
+            for (int d = 0; d < kFramesDepth; ++d) {
+                const uint32_t j = jb + (uint32_t) d;
+                if (j >= j1) break;
+                const uint32_t kf = from[d] < last_key ? from[d] : last_key, kt = to[d] < last_key ? to[d] : last_key;
+                const float m = mod[d];
+                if (j1 - j > (uint32_t) kFramesDepth) {
+                    from[d] = t.from[j + (uint32_t) kFramesDepth]; to[d] = t.to[j + (uint32_t) kFramesDepth]; mod[d] = t.mod[j + (uint32_t) kFramesDepth];
+                }
+                glv_f4 nl = sl, nr = sr;
+                if (kf != ks) { if (kf == ke) { nl = el; nr = er; } else wave_key<F32_IN>(pcm, w, mono, t.keys, t.n, kf, stream, i, nl, nr); }
+                if (kt != ke) { if (kt == ks) { el = sl; er = sr; } else wave_key<F32_IN>(pcm, w, mono, t.keys, t.n, kt, stream, i, el, er); }
+                sl = nl; sr = nr; ks = kf; ke = kt;
+                glv_f4 wl = sl, wr = sr;
+                if (kf != kt) { wl = sl + ((el - sl) * m); wr = sr + ((er - sr) * m); }      // render.c:1806
+                emit(j, 0u, wl);
+                emit(j, 1u, wr);
+            }
+        }
+    }
+}
+
+// Element i of both kept keyframes is read before element i of either destination is written, and no other lane touches element i (glv_track_keys_kernel's
+// rule); a keyframe beyond the caller's two comes from the recording, which no lane writes.
+template <bool F32_IN>
+__global__ void __launch_bounds__(256) glv_wave_keys_kernel(const void* pcm, const WaveWindows w, const int mono, float* keys, const uint32_t n, const size_t quads,
+                                                            const uint32_t keep_from, const uint32_t keep_to) {
+    const uint32_t per_stream = n / 4u;
+    for (size_t q = (size_t) blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t) gridDim.x * blockDim.x) {
+        const uint32_t stream = (uint32_t) (q / per_stream), i = (uint32_t) (q % per_stream) * 4u;
+        glv_f4 al, ar, bl, br;
+        wave_key<F32_IN>(pcm, w, mono, keys, n, keep_from, stream, i, al, ar);
+        wave_key<F32_IN>(pcm, w, mono, keys, n, keep_to, stream, i, bl, br);
+        float* const k0 = keys + (size_t) 2u * stream * n + i;
+        float* const k1 = k0 + (size_t) w.units * n;
+        *reinterpret_cast<glv_f4*>(k0) = al; *reinterpret_cast<glv_f4*>(k0 + n) = ar;
+        *reinterpret_cast<glv_f4*>(k1) = bl; *reinterpret_cast<glv_f4*>(k1 + n) = br;
+    }
+}
+
+hipError_t launch_wave_frames(const void* pcm, bool f32, const WaveWindows& w, bool mono, const WaveFrames& t, bool r16, hipStream_t st) {
+    if (!pcm || !w.starts || !t.from || !t.to || !t.mod || !t.keys || !t.out) return hipErrorInvalidValue;
+    if (t.frames == 0 || w.steps == 0 || w.steps > 0xfffffffdu || w.units == 0 || (w.units & 1u) || t.segment == 0 || t.limit == 0 || t.limit > t.n || (t.limit & 3u) ||
+        (t.n & 3u) || w.pitch_frames < t.n || w.start_max != w.pitch_frames - t.n)
+        return hipErrorInvalidValue;
+    const uint32_t groups = (t.limit / 4u + (uint32_t) kFramesLanes - 1u) / (uint32_t) kFramesLanes;
+    const uint64_t segments = ((uint64_t) t.frames + t.segment - 1u) / t.segment;
+    const uint64_t items = segments * (w.units / 2u) * groups;              // (< 2^32 * 2^31 / 4: no overflow)
+    const unsigned grid = capped_grid((size_t) items, 1, kFramesGridCap);
+    const int m = mono ? 1 : 0;
+    if (f32) {
+        if (r16) hipLaunchKernelGGL((glv_wave_frames_kernel<true, true>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, groups, items);
+        else hipLaunchKernelGGL((glv_wave_frames_kernel<true, false>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, groups, items);
+    } else {
+        if (r16) hipLaunchKernelGGL((glv_wave_frames_kernel<false, true>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, groups, items);
+        else hipLaunchKernelGGL((glv_wave_frames_kernel<false, false>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, groups, items);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_wave_keys(const void* pcm, bool f32, const WaveWindows& w, bool mono, float* keys, uint32_t n, uint32_t keep_from, uint32_t keep_to, hipStream_t st) {
+    if (!pcm || !w.starts || !keys || n == 0 || (n & 3u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || w.pitch_frames < n || w.start_max != w.pitch_frames - n)
+        return hipErrorInvalidValue;
+    if ((uint64_t) keep_from >= (uint64_t) w.steps + 2u || (uint64_t) keep_to >= (uint64_t) w.steps + 2u) return hipErrorInvalidValue;
+    const size_t quads = (size_t) (w.units / 2u) * (n / 4u);
+    const int m = mono ? 1 : 0;
+    if (f32) hipLaunchKernelGGL((glv_wave_keys_kernel<true>), dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, pcm, w, m, keys, n, quads, keep_from, keep_to);
+    else hipLaunchKernelGGL((glv_wave_keys_kernel<false>), dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, pcm, w, m, keys, n, quads, keep_from, keep_to);
     return hipGetLastError();
 }
 

@@ -128,6 +128,12 @@ def lib() -> C.CDLL:
             L.glv_batch_track_frames_work_bytes.restype = C.c_uint64
             L.glv_batch_track_frames_s16.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
             L.glv_batch_track_frames_f32.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_wave_frames_s16"):   # (likewise: the wave module's render frames, keyframes read from the recording)
+            FR = C.POINTER(TrackFrames)
+            L.glv_batch_track_wave_frames_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint]
+            L.glv_batch_track_wave_frames_work_bytes.restype = C.c_uint64
+            L.glv_batch_track_wave_frames_s16.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_wave_frames_f32.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -396,6 +402,36 @@ class Batch:
                          ops: int, stream: int | None = None) -> None:
         """track_frames_s16 from a float recording (glv_batch_track_frames_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
         self._track_frames("f32", d_pcm, pitch_frames, d_starts, d_ur, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
+
+    def track_wave_frames_work_bytes(self, steps: int, frames: int, ops: int) -> int:
+        """bytes of device workspace track_wave_frames_s16 / _f32 need for these arguments (glv_batch_track_wave_frames_work_bytes: 256 without OP_BARS, else the
+        frames' rows as the bars kernel takes them); raises on arguments the call refuses"""
+        nbytes = int(lib().glv_batch_track_wave_frames_work_bytes(self._h, steps, frames, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)
+        return nbytes
+
+    def _track_wave_frames(self, kind: str, d_pcm, pitch_frames, d_starts, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream) -> None:
+        fr = TrackFrames(_ptr(d_from), _ptr(d_to), _ptr(d_mod), frames, _ptr(d_keys), keep[0], keep[1])
+        _check(getattr(lib(), f"glv_batch_track_wave_frames_{kind}")(self._h, _ptr(d_pcm), pitch_frames, _ptr(d_starts), steps, C.byref(fr), _ptr(d_out), _ptr(d_work),
+                                                                      ops, _ptr(stream)))
+
+    def track_wave_frames_s16(self, d_pcm, pitch_frames: int, d_starts, steps: int, d_from, d_to, d_mod, frames: int, d_keys, keep: tuple[int, int], d_out, d_work,
+                              ops: int, stream: int | None = None) -> None:
+        """track mode at render frames for the wave module, on any gl_storage (glv_batch_track_wave_frames_s16): d_out holds, frame-major, what a process call with
+        `ops` (OP_WAVE [| OP_BARS] [| OP_R16]) would write for each of `frames` render frames if its wrange'd buffer were the frame's -- keyframe d_from[j] itself
+        where d_from[j] == d_to[j], else s + ((e - s) * d_mod[j]) in float32 (`setinterpolate true`).  Keyframes 0 and 1 are d_keys float32 [2][streams][2][n]
+        (zeros before a session's first call); keyframe 2 + t is (u + 1.0F) / 2.0F of the unpacked window that begins track_at_start(pitch_frames, n, d_starts[t])
+        frames into each recording, read where it lies: `steps` keyframes, nothing computed per step.  Afterwards d_keys holds keyframes keep[0] and keep[1] as
+        floats.  d_starts, d_from, d_to uint32, d_mod float32, all in device memory; d_work at least track_wave_frames_work_bytes(steps, frames, ops) bytes, 256-byte
+        aligned.  Tables: glava_amd.track_starts.keyframe_tables / live_session_frames.  Stream-ordered, two kernels, three with OP_BARS."""
+        self._track_wave_frames("s16", d_pcm, pitch_frames, d_starts, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
+
+    def track_wave_frames_f32(self, d_pcm, pitch_frames: int, d_starts, steps: int, d_from, d_to, d_mod, frames: int, d_keys, keep: tuple[int, int], d_out, d_work,
+                              ops: int, stream: int | None = None) -> None:
+        """track_wave_frames_s16 from a float recording (glv_batch_track_wave_frames_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
+        self._track_wave_frames("f32", d_pcm, pitch_frames, d_starts, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

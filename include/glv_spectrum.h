@@ -755,6 +755,40 @@ int glv_batch_track_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitc
                                uint32_t steps, const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream);
 int glv_batch_track_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur /* NULL: the batch's ur */,
                                uint32_t steps, const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+/* Track mode at render frames for the wave module.  The reference forces interpolation off only when a bind with an `fft` transform is pushed to the GL
+ * (render.c:2131-2135, :2161-2168); the wave module's bind requests `window` and `wrange` and nothing else (wave/1.frag:7-9), so with `setinterpolate true` every
+ * render frame whose uratio <= 0.9 uploads s + ((e - s) * min(uratio * kcounter, 1)) of the last two wrange'd buffers (render.c:1792-1809; a wave bind uploads
+ * `ilb`, :2185), runs the pre-smoothing pass over that upload (:2276-2303) and pushes the keyframes (:2347-2353) -- on ANY gl_storage, under the shipped
+ * `setaccelfft true` too.  The entries above refuse GLV_OP_WAVE; these give every render frame's wave texture.  Added within ABI 7; detect by the symbol.
+ *   Steps: d_where is glv_batch_track_at_* 's d_starts -- uint32 [steps] in device memory, shared by all streams, window t begins min(d_where[t], pitch_frames - n)
+ *   frames into each recording (a fixed hop is the table t * hop).  `steps` is the number of keyframes the recording contributes: nothing is computed per step.
+ *   Keyframes: keyframe k < 2 is d_keys[k], float [streams][2][n]; keyframe 2 + t of row 2 s + c and sample i is (u + 1.0F) / 2.0F (render.c:777-778), u the
+ *   backend's unpack of frame min(d_where[t], pitch_frames - n) + i of stream s: s16 v / 65535, mono ((l + r) / 2) / 65535 in C int arithmetic (fifo.c:94-110);
+ *   floats the sample itself, mono (l + r) / 2 (pulse_input.c:155-178) -- glv_wave_kernel's helpers.  The float keyframes exist nowhere else: no entry returns
+ *   them (GLV_OP_WAVE without GLV_OP_R16 gives c / 65535).  Every index a table holds is clamped to steps + 1 in the kernel: whatever the tables hold, nothing
+ *   outside d_pcm's recordings, d_keys and the tables' [0, frames) / [0, steps) is read.  d_keys is zero-filled before a session's first call.
+ *   Frame j: d_from[j] == d_to[j] -- that keyframe's own bits; else w = s + ((e - s) * d_mod[j]), three float operations in the order of render.c:1806.  Then the
+ *   upload's quantiser c = unorm16(w), then what a GLV_OP_WAVE process call with the same ops does on this batch: texels c (GLV_OP_R16), floats c / 65535
+ *   (neither GLV_OP_R16 nor GLV_OP_BARS), or with GLV_OP_BARS the pre-smoothing pass / bar texels / maximum / hybrid over frames * streams * 2 rows.
+ *   ops: GLV_OP_WAVE [| GLV_OP_BARS] [| GLV_OP_R16], exactly what glv_batch_track_wave_* takes, on every batch it takes them on (channels 1 and 2, bar texels,
+ *   fewer than 256 bars, maximum / hybrid) and refused where it refuses, with its codes (column texels set, gl_storage 0 with bars, a creation mask without both
+ *   bits, a single-row batch).  fr: glv_track_frames as above, with every refusal glv_batch_track_frames_* makes about it.
+ *   d_out, frame-major: [frames][streams][2][w], w = n or bars.  Write-back: d_keys[0] <- keyframe keep_from, d_keys[1] <- keyframe keep_to as floats, both read
+ *   before either is written; chunks compose as above.
+ *   Workspace: glv_batch_track_wave_frames_work_bytes(b, steps, frames, ops): 256 without bars; with bars the frames' rows, frames * streams * 2 * n texels or
+ *   floats (as the bars kernel takes them), rounded up to 256 bytes.  256-byte aligned.
+ * Launches: 2 (glv_wave_frames_kernel, the write-back glv_wave_keys_kernel), 3 with GLV_OP_BARS.  There is no transform launch and there are no step rows.  Kernels
+ * only: nothing allocated or synchronised, the first call can be captured, the tables are read when the kernels run.  glv_batch_kernel_name reports
+ * "glv_wave_frames_kernel".  The batch's state is not touched.
+ * Kernel (glv_track_frames.hip): one lane owns four consecutive frames of one stream, both channel rows -- a keyframe is 16 bytes of s16 or 32 bytes of floats from
+ * the recording (wide loads where the group is 16-byte aligned, naturally aligned dword / 8-byte loads else: a window starts at any frame), or two 16-byte loads
+ * from d_keys -- and walks a segment of frames with both keyframes in registers, as glv_track_frames_kernel does; the work items are segments x streams x groups
+ * of 256 frames, one wave each, looped beyond 8192 workgroups. */
+uint64_t glv_batch_track_wave_frames_work_bytes(const glv_batch* b, uint32_t steps, uint32_t frames, unsigned ops);   /* 0: refused, glv_last_error starts with the code's name; sizes both entries */
+int glv_batch_track_wave_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
+                                    void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_wave_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
+                                    void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
