@@ -235,18 +235,18 @@ int glv_batch_destroy(glv_batch* b) {
 int glv_batch_process_s16(glv_batch* b, const int16_t* d_pcm, float* d_out, unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "s16 input requires GLV_OP_FFT or GLV_OP_WAVE");
-    return process(b, d_pcm, glv::IN_S16_STEREO, d_out, ops, b->streams * 2, 0, (hipStream_t) hip_stream);
+    return process_windows(b, d_pcm, glv::IN_S16_STEREO, glv::DEC_S16, d_out, ops, (hipStream_t) hip_stream);
 }
 
 int glv_batch_process_f32(glv_batch* b, const float* d_f32, float* d_out, unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
-    return process(b, d_f32, glv::IN_F32_PLANAR, d_out, ops, b->streams * 2, 0, (hipStream_t) hip_stream);
+    return process_windows(b, d_f32, glv::IN_F32_PLANAR, glv::DEC_F32_PLANAR, d_out, ops, (hipStream_t) hip_stream);
 }
 
 int glv_batch_process_f32_stereo(glv_batch* b, const float* d_pcm, float* d_out, unsigned ops, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "interleaved input requires GLV_OP_FFT or GLV_OP_WAVE");
-    return process(b, d_pcm, glv::IN_F32_STEREO, d_out, ops, b->streams * 2, 0, (hipStream_t) hip_stream);
+    return process_windows(b, d_pcm, glv::IN_F32_STEREO, glv::DEC_F32, d_out, ops, (hipStream_t) hip_stream);
 }
 
 // append `new_frames` frames of `fb` bytes each per stream at ring position `pos` (frames) of rings with a pitch of n frames:
@@ -269,6 +269,7 @@ static int ring_append(char* d_ring, const char* d_new, uint32_t pos, uint32_t n
 // allocated (GLV_OP_RING_S16 / _F32) and advance it.  *old_pos receives the position before the append.
 static int ring_push(glv_batch* b, bool f32, const void* d_new, uint32_t new_frames, hipStream_t st, uint32_t* old_pos) {
     const uint32_t n = b->p.n;
+    if (int rc = refuse_bufscale(b, f32 ? "the f32 ring entries" : "the s16 ring entries")) return rc;
     if (new_frames == 0 || new_frames > n)
         return fail(GLV_ERR_INVALID, "new_frames=%u: must be in [1, n=%u] (sample_sz/4 of %s)", new_frames, n, f32 ? "pulse_input.c:155-178" : "fifo.c:38,91");
     const size_t fb = f32 ? 8 : 4;
@@ -328,6 +329,7 @@ int glv_batch_ring_append_f32(glv_batch* b, const float* d_new, uint32_t new_fra
 int glv_batch_ring_planar(glv_batch* b, int f32_ring, float* d_planar, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_planar) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (int rc = refuse_bufscale(b, "glv_batch_ring_planar")) return rc;
     const void* ring = f32_ring ? static_cast<const void*>(b->d_ring_f32.get()) : static_cast<const void*>(b->d_ring.get());
     if (!ring) return fail(GLV_ERR_STATE, "the batch has no %s ring yet (create it with GLV_OP_RING_%s or append to it first)", f32_ring ? "f32" : "s16", f32_ring ? "F32" : "S16");
     HIP_TRY(hipSetDevice(b->device));

@@ -296,10 +296,22 @@ int plan_chain(glv_batch* b, int in_mode, unsigned ops, uint32_t units, uint32_t
     return GLV_OK;
 }
 
+// bufscale > 1, the first launch of a process call: the caller's windows of k * n frames into the batch's staging rows (ChainPlan::dec_in; glv_decimate_kernel),
+// which the chain then reads as planar rows.  A process call's windows lie back to back: one step, pitch k * n.
+int decimate_stage(glv_batch* b, const ChainPlan& pl, hipStream_t st) {
+    if (!pl.dec_in) return GLV_OK;
+    glv::Decimate d = {};
+    d.in = pl.dec_in; d.out = b->d_decim; d.n = b->p.n; d.k = b->bufscale; d.mono = b->p.channels == 1 ? 1u : 0u;
+    d.w.pitch_frames = (uint64_t) b->bufscale * b->p.n; d.w.steps = 1; d.w.streams = b->streams;
+    const hipError_t e = glv::launch_decimate(pl.dec_kind, d, st); ++b->last_launches;
+    return e == hipSuccess ? GLV_OK : fail(GLV_ERR_HIP, "bufscale launch failed: %s", hipGetErrorString(e));
+}
+
 // Carries out a WAVE plan: one HIP-event window around its one or two launches; stream-ordered, nothing is allocated.
 int run_wave(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units, uint32_t rot, hipStream_t st) {
     const bool mono = b->p.channels == 1;
     if (int rc = timed_launch_begin(b, st)) return rc;
+    if (int rc = decimate_stage(b, pl, st)) return rc;
     hipError_t e;
     if (pl.wave_fused) {
         const glv::BarIRowsTables irt = b->bar_x.irows_tables();
@@ -348,6 +360,7 @@ int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, 
     if (pl.live_points != 0) { a.live_points = pl.live_points; b->ran_live = true; }
 
     if (int rc = timed_launch_begin(b, st)) return rc;
+    if (int rc = decimate_stage(b, pl, st)) return rc;
     hipError_t e = hipSuccess;
     if (pl.route == ChainPlan::POST || pl.route == ChainPlan::COPY) {
         if (in_mode != glv::IN_F32_PLANAR) return fail(GLV_ERR_INVALID, "operators without GLV_OP_FFT take planar f32 input");
@@ -404,8 +417,9 @@ int refuse_stale_tilt(const glv_batch* b) {
 }
 
 // One update of `units` channel rows through the fused kernel (or the post kernel when no FFT is asked).
+// dec_in: bufscale > 1 -- d_in is the batch's staging rows, which the chain's first launch makes from the windows at dec_in (process_windows)
 int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units,
-            uint32_t rot, hipStream_t st) {
+            uint32_t rot, hipStream_t st, const void* dec_in, int dec_kind) {
     if (!d_in) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (int rc = check_ops(b, ops, d_out)) return rc;
     if (int rc = refuse_gravity_mix(b, ops)) return rc;
@@ -414,8 +428,25 @@ int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned 
     ChainPlan pl;
     if (int rc = plan_chain(b, in_mode, ops, units, rot, d_out, pl)) return rc;
     if (int rc = refuse_stale_tilt(b)) return rc;
+    pl.dec_in = dec_in; pl.dec_kind = dec_kind;
     commit_gravity_form(b, ops);
     if (pl.route == ChainPlan::WAVE) return run_wave(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
     return run_chain(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
+}
+
+// The three process entries: the call as it has always run, or with bufscale > 1 the chain glv_batch_process_f32 plans on this batch for the same ops, over the
+// staging rows its first launch decimates the caller's windows of k * n frames into.  Whatever the planar entry refuses is refused in its words, before anything
+// is launched.
+int process_windows(glv_batch* b, const void* d_in, int in_mode, int dec_kind, float* d_out, unsigned ops, hipStream_t st) {
+    if (b->bufscale == 1u) return process(b, d_in, in_mode, d_out, ops, b->streams * 2, 0, st);
+    if (!d_in) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_in) & (dec_kind == glv::DEC_F32 ? 7u : 3u))
+        return fail(GLV_ERR_INVALID, "the input must be aligned like its frames: %d bytes", dec_kind == glv::DEC_F32 ? 8 : 4);
+    return process(b, b->d_decim, glv::IN_F32_PLANAR, d_out, ops, b->streams * 2, 0, st, d_in, dec_kind);
+}
+// What does not honour `setbufscale`: refused while k > 1, in the setter's name
+int refuse_bufscale(const glv_batch* b, const char* entry) {
+    if (b->bufscale == 1u) return GLV_OK;
+    return fail(GLV_ERR_STATE, "%s does not take a batch with bufscale k=%u (glv_batch_set_bufscale): set k = 1, or use a batch of its own", entry, b->bufscale);
 }
 }  // namespace glvh

@@ -186,6 +186,27 @@ int batch_alloc(glv_batch* b) {
 }  // namespace glvh
 
 extern "C" {
+// `setbufscale k` for a batch (include/glv_spectrum.h): the factor, and the staging rows a process call decimates into -- made here, by this call alone, so that
+// the process and track calls stay launches only.  Like glv_batch_set_params it waits for the device first: a queued call may still read the array that goes.
+// State, head, tables, bar and column texels are not touched; glv_batch_set_params and glv_batch_reset do not touch k.
+int glv_batch_set_bufscale(glv_batch* b, uint32_t k) {
+    if (k == 0 || k > GLV_MAX_BUFSCALE) return fail(GLV_ERR_INVALID, "glv_batch_set_bufscale: k=%u: must be in [1, %d] (1: off)", k, GLV_MAX_BUFSCALE);
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if ((uint64_t) k * b->p.n > ((uint64_t) 1 << 21))
+        return fail(GLV_ERR_INVALID, "glv_batch_set_bufscale: k=%u at n=%u: a window of k * n frames holds at most 2^21", k, b->p.n);
+    if (b->single_row) return fail(GLV_ERR_STATE, "glv_batch_set_bufscale: a single-row batch (the drop-ins') takes rows as they are: glv_prelude_bufscale decimates them");
+    if (b->ops_mask & (GLV_OP_RING_S16 | GLV_OP_RING_F32))
+        return fail(GLV_ERR_STATE, "glv_batch_set_bufscale: the batch was created with GLV_OP_RING_S16 / GLV_OP_RING_F32, whose rings hold n frames");
+    if (k == b->bufscale) return GLV_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (k == 1u) b->d_decim.reset();
+    else if (!b->d_decim) HIP_TRY(b->d_decim.alloc((size_t) b->rows * b->p.n, false));      // (on failure the owner holds what it held: nothing, and k stays 1)
+    b->bufscale = k;
+    return GLV_OK;
+}
+uint32_t glv_batch_bufscale(const glv_batch* b) { return b ? b->bufscale : 0u; }
+
 // Placement wisdom (round 6; profiles/r06/modes.txt).  A stateful chain runs at one of two or three speeds, 7 - 14 % apart, and which one is a property of
 // WHERE ITS STATE ARRAYS LIE in physical memory relative to the caller's output buffer: K batches of one process, created one after the other, each keep
 // their own speed against the same buffers, and one batch changes speed with the output buffer it is given -- not with the allocator (hipMalloc, virtual
@@ -196,6 +217,7 @@ extern "C" {
 int glv_batch_tune_placement(glv_batch* b, const int16_t* d_pcm, void* d_out, unsigned ops, int candidates, void* hip_stream, float* first_ms, float* best_ms) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!(ops & GLV_OP_FFT) || !(ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) return fail(GLV_ERR_INVALID, "glv_batch_tune_placement tunes a stateful chain: ops needs GLV_OP_FFT and GLV_OP_GRAVITY / GLV_OP_AVERAGE");
+    if (int rc = refuse_bufscale(b, "glv_batch_tune_placement")) return rc;
     if (int rc = check_ops(b, ops, static_cast<float*>(d_out))) return rc;
     if (!d_pcm || !d_out) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (candidates < 1) candidates = 1;

@@ -189,6 +189,8 @@ struct glv_batch {
     float grav_g = 0.f; uint32_t grav_sub = 0; bool grav_int = false, grav_known = false;   // the gravity step on texels (glv_tables.h gravity_r16_integer_step)
     DeviceArray<float> d_scratch;    // [streams*2][n] spectra feeding GLV_OP_BARS
     DeviceArray<float> d_ring_f32;   // [streams][n][2] interleaved f32 ring (glv_batch_ring_update_f32)
+    uint32_t bufscale = 1;           // `setbufscale k` (glv_batch_set_bufscale): a window of every process and track call is k * n frames, decimated to n (render.c:1765-1790); 1: off
+    DeviceArray<float> d_decim;      // [streams*2][n] the decimated rows of a process call, which the chain then reads as IN_F32_PLANAR; held while bufscale > 1
     uint32_t ring_pos_f32 = 0;
     DeviceArray<int> d_smin, d_smax; // transform_smooth window bounds (host generated)
     uint32_t smooth_asz = 0;
@@ -280,6 +282,8 @@ struct ChainPlan {
     bool wave_fused = false;                    // WAVE: the bars in ONE launch (glv_bars_rows_i8_kernel parks texels made from the s16 frames)
     bool wave_r16 = false;                      // WAVE: the waveform kernel writes texels (else their floats c / 65535)
     uint32_t wave_limit = 0;                    // WAVE: samples of a row the waveform kernel produces (what the bars sample, or n)
+    const void* dec_in = nullptr;               // bufscale > 1: the caller's windows of k * n frames, which the first launch of the chain decimates into the batch's
+    int dec_kind = 0;                           // staging rows (glv::DecimateKind) -- the chain is then the planar entry's on those rows
 };
 
 // ---- what crosses a unit boundary, in the order glv_wisdom / glv_device_state / glv_bar_tables / glv_chain.cpp (indented: tests/src_scan.py finds a DEFINITION by its return type at the start of a line) ----
@@ -302,5 +306,8 @@ struct ChainPlan {
     int plan_wave(const glv_batch* b, int in_mode, unsigned ops, uint32_t rot, float* d_out, ChainPlan& pl, bool whole_groups);
     int launch_bars_pass(glv_batch* b, const ChainPlan& pl, float* d_bars, size_t units, bool r16, hipStream_t st);
     int refuse_gravity_mix(const glv_batch* b, unsigned ops); void commit_gravity_form(glv_batch* b, unsigned ops); int refuse_stale_tilt(const glv_batch* b);
-    int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units, uint32_t rot, hipStream_t st);
+    int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units, uint32_t rot, hipStream_t st, const void* dec_in = nullptr,
+                int dec_kind = 0);
+    int process_windows(glv_batch* b, const void* d_in, int in_mode, int dec_kind, float* d_out, unsigned ops, hipStream_t st);
+    int refuse_bufscale(const glv_batch* b, const char* entry);
 }  // namespace glvh

@@ -82,6 +82,20 @@ GLV_HD constexpr uint64_t wave_window_start(const WaveWindows& w, uint32_t s, ui
     return (uint64_t) s * w.pitch_frames + (w.starts ? (uint64_t) (entry < w.start_max ? entry : w.start_max) : (uint64_t) t * w.hop);
 }
 hipError_t launch_bufscale(const float* in, float* out, size_t total_out, uint32_t k, hipStream_t st);
+// `setbufscale k` on the batched layer (glv_decimate.hip; glv_batch_set_bufscale): every window of a call is k * n frames and becomes a pair of planar float rows
+// of n samples, out[t] = (x[t k] + ... + x[t k + k - 1]) / (float) k summed from +0.0F in index order (render.c:1765-1790).  Kinds: interleaved s16 frames,
+// interleaved float frames (both unpacked as the backend does, `mono`: channels == 1), and a process call's planar rows float [streams][2][k n] (no mix).
+// The interleaved kinds cut their windows out of [streams][pitch_frames][2] recordings by TrackWindows' rules with k n in the place of n: window t of stream s
+// begins track_window_start(w, s, t, starts[t]) frames in, w.start_max = w.pitch_frames - k n where a table is set, and its rows go to row
+// track_window_row(w, s, t) of `out` -- where the transform that reads them as IN_F32_PLANAR writes its own.  A process call: steps 1, hop 0, pitch k n.
+enum DecimateKind { DEC_S16 = 0, DEC_F32 = 1, DEC_F32_PLANAR = 2 };
+struct Decimate {
+    const void* in; float* out;
+    uint32_t n, k, mono, pad;
+    TrackWindows w;
+};
+constexpr size_t kDecimateGridCap = 256 * 8;       // 256 CUs x 8 resident 256-lane workgroups; the kernel's loop takes what lies beyond
+hipError_t launch_decimate(int kind, const Decimate& d, hipStream_t st);
 hipError_t launch_lerp(const float* s0, const float* e0, float* out, size_t total, float mod, hipStream_t st);
 hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin, const int* smax, uint32_t asz, uint32_t reach,
                          uint32_t max_window, hipStream_t st);

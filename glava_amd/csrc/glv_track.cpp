@@ -25,6 +25,10 @@ namespace {
 // windows where a table in device memory says: the transform runs in the kernel kinds that read it (IN_S16_TRACK_AT / IN_F32_TRACK_AT), nothing else differs.
 // A rates call (glv_batch_track_rates_s16 / _f32, track_rates: TrackPlan::ur) is a table call whose scan runs in the kernel's rates kind: gravity's step of
 // update t comes from a second table in device memory, gravity_step * (1.0F / ur[t]) -- the plan, the workspace, the launches and the batch's own ur are the table call's.
+// A batch with bufscale k > 1 (glv_batch_set_bufscale) runs the windows form and everything built on it with windows of k * n frames: stage (1) is then two launches --
+// glv_decimate_kernel writes every window's decimated rows, steps * streams * 2 rows of n floats, into a region in FRONT of the workspace's others (TrackPlan::dec_bytes),
+// each at the row index the transform's result takes, and the stateless transform runs once over them as IN_F32_PLANAR -- and the stages behind it see no difference.
+// The residue form (whose trick rests on back-to-back windows of n frames) and the wave forms refuse such a batch.
 struct TrackPlan {
     uint32_t q = 0, log_q = 0;          // residue launches
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
@@ -48,7 +52,10 @@ struct TrackPlan {
     const glv_track_frames* fr = nullptr;   // a frames call (glv_batch_track_frames_s16 / _f32): its render frames; set before the plan (the sizing query's holds `frames` alone)
     uint64_t frame_rows = 0;            // ... fr->frames * streams * 2: the rows the frames kernel writes and the bars run over
     uint64_t frames_off = 0;            // ... and where its texel rows lie in the workspace when bars follow: behind the transform's region and the scan's
+    uint64_t dec_bytes = 0;             // bufscale > 1: the decimated rows' region at the very start of the workspace (a multiple of 256 bytes); every other region lies behind it
 };
+// frames of a window: n, or the k * n that bufscale k decimates to n
+uint64_t window_frames(const glv_batch* b) { return (uint64_t) b->bufscale * b->p.n; }
 // What the two track entries (glv_batch_track_s16, glv_batch_track_windows_s16) share, written once so that they cannot disagree: the refusals that are
 // not about hop or pitch, and what the chain's stages carry.  In the order the checks have always run: (1) the arguments ...
 // live: the entry is the live form, whose batches keep state only where bars sample -- bars and a state operator are part of the call
@@ -135,14 +142,15 @@ int track_chain(const glv_batch* b, uint32_t pitch_frames, uint32_t steps, unsig
     return GLV_OK;
 }
 uint64_t up256(uint64_t v) { return (v + 255u) & ~(uint64_t) 255u; }
-bool pitch_too_short(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps) {
-    if ((uint64_t) pitch_frames >= (uint64_t) n + (uint64_t) (steps - 1) * hop) return false;
-    (void) fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%u frames every hop=%u", pitch_frames, steps, n, hop);
+bool pitch_too_short(uint64_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps) {
+    if ((uint64_t) pitch_frames >= n + (uint64_t) (steps - 1) * hop) return false;
+    (void) fail(GLV_ERR_INVALID, "pitch_frames=%u holds fewer than steps=%u windows of n=%llu frames every hop=%u", pitch_frames, steps, (unsigned long long) n, hop);
     return true;
 }
 // Everything about a track call that does not depend on its pointers or on what the batch did before: refusals, geometry, workspace.
 int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     const uint32_t n = b->p.n;
+    if (int rc = refuse_bufscale(b, "glv_batch_track_s16 (its residue launches rest on back-to-back windows of n frames; glv_batch_track_windows_s16 takes any hop)")) return rc;
     if (int rc = track_args(ops, steps)) return rc;
     const int lh = log2_exact(hop);
     if (lh < 2 || hop > n) return fail(GLV_ERR_INVALID, "hop=%u: must be a power of two in [4, n=%u]", hop, n);
@@ -164,8 +172,9 @@ int plan_track(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t
 // exists where a scan runs AND bars follow it.
 // The hop and pitch rule of every form whose windows are read where they lie, written once.  at: a table call -- the kernels clamp every entry to pitch_frames - n
 // (glv_frame.h TrackWindows), so the recording has to hold ONE window and `hop` is not looked at.
-int windows_args(uint32_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps, bool at) {
-    if (at) return pitch_frames >= n ? GLV_OK : fail(GLV_ERR_INVALID, "pitch_frames=%u holds no window of n=%u frames", pitch_frames, n);
+// n: the frames of a window (window_frames: k * n on a batch with bufscale k)
+int windows_args(uint64_t n, uint32_t pitch_frames, uint32_t hop, uint32_t steps, bool at) {
+    if (at) return pitch_frames >= n ? GLV_OK : fail(GLV_ERR_INVALID, "pitch_frames=%u holds no window of n=%llu frames", pitch_frames, (unsigned long long) n);
     if (hop == 0) return fail(GLV_ERR_INVALID, "hop must be > 0");
     return pitch_too_short(n, pitch_frames, hop, steps) ? GLV_ERR_INVALID : GLV_OK;
 }
@@ -173,14 +182,15 @@ void windows_geometry(const glv_batch* b, uint32_t steps, unsigned ops, TrackPla
     const uint32_t n = b->p.n;
     tp.windows = true; tp.scan = tp.state; tp.hops_per_pitch = steps;      // (one residue: log_q and residue_rows stay 0)
     tp.to_out = !tp.state && !(ops & GLV_OP_BARS) && !tp.fr;
-    if (tp.to_out) { tp.rows_bytes = 0; tp.work_bytes = 256; return; }
+    tp.dec_bytes = b->bufscale > 1u ? up256(tp.out_rows * n * 4u) : 0u;      // (offsets below are counted from behind it: `track` moves its base)
+    if (tp.to_out) { tp.rows_bytes = 0; tp.work_bytes = tp.dec_bytes != 0 ? tp.dec_bytes : 256; return; }
     tp.rows_bytes = up256(tp.out_rows * n * (tp.in16 ? 2u : 4u));
     tp.frames_off = tp.rows_bytes + (tp.state && ((ops & GLV_OP_BARS) || tp.fr) ? up256(tp.out_rows * n * (tp.out16 ? 2u : 4u)) : 0u);
-    tp.work_bytes = tp.frames_off + (tp.fr && (ops & GLV_OP_BARS) ? up256(tp.frame_rows * n * 2u) : 0u);      // a frames call with bars: the frames' texel rows
+    tp.work_bytes = tp.dec_bytes + tp.frames_off + (tp.fr && (ops & GLV_OP_BARS) ? up256(tp.frame_rows * n * 2u) : 0u);      // a frames call with bars: the frames' texel rows
 }
 int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     if (int rc = track_args(ops, steps)) return rc;
-    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps, tp.at)) return rc;
+    if (int rc = windows_args(window_frames(b), pitch_frames, hop, steps, tp.at)) return rc;
     if (int rc = track_chain(b, pitch_frames, steps, ops, tp)) return rc;
     windows_geometry(b, steps, ops, tp);
     return GLV_OK;
@@ -191,7 +201,7 @@ int plan_track_windows(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, 
 int plan_track_columns(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     if (int rc = track_args(ops, steps)) return rc;
     if (!(ops & GLV_OP_BARS)) return fail(GLV_ERR_INVALID, "a columns track call samples: GLV_OP_BARS is required (ops 0x%x)", ops);
-    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps, tp.at)) return rc;
+    if (int rc = windows_args(window_frames(b), pitch_frames, hop, steps, tp.at)) return rc;
     if (int rc = track_chain(b, pitch_frames, steps, ops, tp, true)) return rc;
     windows_geometry(b, steps, ops, tp);
     return GLV_OK;
@@ -200,7 +210,7 @@ int plan_track_columns(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, 
 // (TrackPlan::kept).  The workspace keeps the windows and columns queries' layout and size: rows at pitch n, of which the kept bins are written.
 int plan_track_live(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uint32_t steps, unsigned ops, TrackPlan& tp) {
     if (int rc = track_args(ops, steps, true)) return rc;
-    if (int rc = windows_args(b->p.n, pitch_frames, hop, steps, tp.at)) return rc;
+    if (int rc = windows_args(window_frames(b), pitch_frames, hop, steps, tp.at)) return rc;
     if (int rc = track_chain(b, pitch_frames, steps, ops, tp, false, true)) return rc;
     windows_geometry(b, steps, ops, tp);
     return GLV_OK;
@@ -255,13 +265,21 @@ int track_residues(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::Fr
     return GLV_OK;
 }
 // (1) as windows: every window of the call where it lies, one launch, into `rows`
+// dec: bufscale > 1 -- the decimated rows' region, which glv_decimate_kernel fills from the windows of k * n frames and the transform then reads as planar rows
 int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::FrameClass cls, const void* d_pcm, uint32_t pitch_frames, uint32_t hop, uint32_t steps,
-                        float* rows, hipStream_t st) {
+                        float* rows, float* dec, hipStream_t st) {
     a.in = d_pcm; a.out = rows; a.units = (uint32_t) tp.out_rows;
     a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
-    a.trk.pad = 0; a.trk.starts = tp.starts; a.trk.start_max = pitch_frames - b->p.n; a.trk.pad2 = 0;      // (both plans' pitch rule: pitch_frames >= n)
-    const int hop_mode = tp.f32 ? glv::IN_F32_TRACK : glv::IN_S16_TRACK;
-    const int mode = !tp.starts ? hop_mode : tp.f32 ? glv::IN_F32_TRACK_AT : glv::IN_S16_TRACK_AT;      // a table call: the kernel kinds that read it, planned as the hop kinds
+    a.trk.pad = 0; a.trk.starts = tp.starts; a.trk.start_max = pitch_frames - b->p.n * b->bufscale; a.trk.pad2 = 0;      // (both plans' pitch rule: pitch_frames >= a window)
+    int hop_mode = tp.f32 ? glv::IN_F32_TRACK : glv::IN_S16_TRACK;
+    int mode = !tp.starts ? hop_mode : tp.f32 ? glv::IN_F32_TRACK_AT : glv::IN_S16_TRACK_AT;      // a table call: the kernel kinds that read it, planned as the hop kinds
+    if (dec) {
+        glv::Decimate d = {};
+        d.in = d_pcm; d.out = dec; d.n = b->p.n; d.k = b->bufscale; d.mono = b->p.channels == 1 ? 1u : 0u; d.w = a.trk;
+        const hipError_t e = glv::launch_decimate(tp.f32 ? glv::DEC_F32 : glv::DEC_S16, d, st); ++b->last_launches;
+        if (e != hipSuccess) return fail(GLV_ERR_HIP, "bufscale launch failed: %s", hipGetErrorString(e));
+        a.in = dec; hop_mode = mode = glv::IN_F32_PLANAR;      // row r of the region becomes row r of `rows`: the index the windows kinds give window (s, t)
+    }
     int variant = 0, grid = 0;
     launch_plan(b, a.units, hop_mode, a.ops, &variant, &grid);
     b->last_grid = grid; b->last_variant = variant;
@@ -335,7 +353,7 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     b->last_launches = 0;
     HIP_TRY(hipSetDevice(b->device));
     commit_gravity_form(b, ops);
-    char* const work = static_cast<char*>(d_work);
+    char* const work = static_cast<char*>(d_work) + tp.dec_bytes;      // (bufscale > 1: the decimated rows come first, every other region behind them)
     float* const out = static_cast<float*>(d_out);
     if (int rc = timed_launch_begin(b, st)) return rc;
     glv::FrameArgs a;
@@ -343,7 +361,8 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     a.ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u); a.log_mode = b->p.log_mode;
     const glv::FrameClass cls = glv::frame_class(false, false, false, a.ops);
     if (tp.kept != 0) b->ran_live = true;      // the live form over the kept bins: the scan leaves the state at and beyond bin `kept` as it finds it
-    if (int rc = tp.windows ? track_windows(b, tp, a, cls, d_pcm, pitch_frames, hop, steps, tp.to_out ? out : reinterpret_cast<float*>(work), st)
+    if (int rc = tp.windows ? track_windows(b, tp, a, cls, d_pcm, pitch_frames, hop, steps, tp.to_out ? out : reinterpret_cast<float*>(work),
+                                            tp.dec_bytes != 0 ? static_cast<float*>(d_work) : nullptr, st)
                             : track_residues(b, tp, a, cls, static_cast<const int16_t*>(d_pcm), hop, work, st)) return rc;
     ChainPlan pl;
     pl.bars = tp.bars;
@@ -385,6 +404,7 @@ int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uin
     if (steps == 0) return fail(GLV_ERR_INVALID, "steps must be > 0");
     if (int rc = windows_args(n, pitch_frames, hop, steps, tp.at)) return rc;
     if (b->single_row) return fail(GLV_ERR_STATE, "a track call needs a batch of stereo streams");
+    if (int rc = refuse_bufscale(b, tp.render ? "glv_batch_track_wave_frames_s16 / _f32" : "a wave track call (glv_batch_track_wave_s16 / _f32, GLV_OP_WAVE in a table call)")) return rc;
     tp.rows = (uint64_t) steps * b->streams * 2u;
     if (tp.rows > 0x100000000ull)                 // (a COUNT of rows, steps * units, which the launchers take as a size_t: exactly 2^32 rows pass)
         return fail(GLV_ERR_INVALID, "steps=%u of %u streams: more than 2^32 rows in one call, cut the track into chunks", steps, b->streams);
@@ -633,7 +653,7 @@ int glv_batch_track_wave_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_fr
 uint64_t glv_batch_track_at_work_bytes(const glv_batch* b, uint32_t steps, unsigned ops) {
     if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
     if (ops & GLV_OP_WAVE) return planned_work_bytes(b, plan_track_wave, b->p.n, 0u, steps, ops, true);
-    return planned_work_bytes(b, plan_track_at, b->p.n, 0u, steps, ops, true);
+    return planned_work_bytes(b, plan_track_at, (uint32_t) window_frames(b), 0u, steps, ops, true);
 }
 
 int glv_batch_track_at_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work,
@@ -666,7 +686,7 @@ uint64_t glv_batch_track_frames_work_bytes(const glv_batch* b, uint32_t steps, u
     shape.frames = frames;
     TrackPlan tp;
     tp.fr = &shape;
-    if (const int rc = plan_track_frames(b, b->p.n, steps, ops, tp)) {
+    if (const int rc = plan_track_frames(b, (uint32_t) window_frames(b), steps, ops, tp)) {
         g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
         return 0;
     }

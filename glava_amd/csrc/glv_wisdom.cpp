@@ -198,6 +198,7 @@ int glv_wisdom_save(const char* path) {
 int glv_batch_autotune(glv_batch* b, const int16_t* d_pcm, float* d_out, unsigned ops, void* hip_stream, int* best_grid, float* best_ms) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!(ops & GLV_OP_FFT)) return fail(GLV_ERR_INVALID, "autotune needs GLV_OP_FFT (it tunes the frame kernel)");
+    if (int rc = refuse_bufscale(b, "glv_batch_autotune")) return rc;
     if (int rc = check_ops(b, ops, d_out)) return rc;
     if (!d_pcm) return fail(GLV_ERR_INVALID, "NULL device pointer");
     hipStream_t st = (hipStream_t) hip_stream;

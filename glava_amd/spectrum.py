@@ -31,6 +31,7 @@ SAMPLE_AVERAGE, SAMPLE_MAXIMUM, SAMPLE_HYBRID = 0, 1, 2            # glv_params.
 # float state / the CPU operators on float state as with 0, and OP_BARS samples the GL_R16 upload of the finished buffer (GLava with `setaccelfft false`;
 # added within ABI 7: a library that has it accepts the value in glv_batch_create)
 GL_STORAGE_FLOAT, GL_STORAGE_R16, GL_STORAGE_PASSES, GL_STORAGE_UPLOAD = 0, 1, 2, 3
+MAX_BUFSCALE = 16                  # GLV_MAX_BUFSCALE: the largest k of Batch.set_bufscale
 
 
 class GlvError(RuntimeError):
@@ -134,6 +135,10 @@ def lib() -> C.CDLL:
             L.glv_batch_track_wave_frames_work_bytes.restype = C.c_uint64
             L.glv_batch_track_wave_frames_s16.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
             L.glv_batch_track_wave_frames_f32.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_set_bufscale"):        # (likewise: `setbufscale k` for a batch -- windows of k * n frames, decimated on the device)
+            L.glv_batch_set_bufscale.argtypes = [vp, C.c_uint32]
+            L.glv_batch_bufscale.argtypes = [vp]
+            L.glv_batch_bufscale.restype = C.c_uint32
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -253,6 +258,19 @@ class Batch:
         cp = params.c()
         _check(lib().glv_batch_set_params(self._h, C.byref(cp)))
         self.params = params
+
+    def set_bufscale(self, k: int) -> None:
+        """glv_batch_set_bufscale: `setbufscale k` of rc.glsl (1: off, the default; up to MAX_BUFSCALE).  While k > 1 a window of every process call and of the
+        FFT track entries (windows, columns, live, at, rates, frames) is k * n frames -- [streams][k * n][2] interleaved, [streams][2][k * n] for process_f32 --
+        and is decimated on the device to the n samples per channel the chain transforms: means of k consecutive samples, summed in float32 in index order
+        and divided once (render.c:1765-1790).  Synchronous, and the only call of the feature that allocates; state, head, tables and texel tables are kept,
+        set_params and reset keep k.  track_s16, the wave track entries, the ring entries, autotune and tune_placement refuse while k > 1."""
+        _check(lib().glv_batch_set_bufscale(self._h, k))
+
+    @property
+    def bufscale(self) -> int:
+        """the batch's bufscale k (glv_batch_bufscale)"""
+        return int(lib().glv_batch_bufscale(self._h))
 
     def process_s16(self, d_pcm, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         """one update of every stream; stream-ordered (never allocates, never copies synchronously).  Chains ending in gravity

@@ -802,6 +802,32 @@ int glv_batch_process_f32(glv_batch* b, const float* d_f32, float* d_out, unsign
  * receives (glava/pulse_input.c:155-178); channels == 1 mixes (L + R) / 2 in float (pulse_input.c:167) */
 int glv_batch_process_f32_stereo(glv_batch* b, const float* d_pcm, float* d_out, unsigned ops, void* hip_stream);
 
+/* `setbufscale k` of rc.glsl (rd_update's box decimation, render.c:1765-1790) for a batch.  Added within ABI 7: detect it by the symbol.  With transform
+ * size n and bufscale k a window of every call below is k * n frames (GLava's bufsize), and channel sample t of it is
+ *     acc = 0.0F; for a in 0..k-1: acc = acc + x[t*k + a]; acc = acc / (float) k
+ * of the backend's unpack x of the frames (s16: v / 65535.0F, channels == 1: ((l + r) / 2) / 65535.0F in C integer arithmetic, fifo.c:94-110; f32: the sample,
+ * channels == 1: (l + r) / 2.0F) -- every addition and the one division rounded float32 operations in that order, no fused multiply-add, no reciprocal, no
+ * integer pre-sum; a window whose first sample is -0.0F gives +0.0F.  Everything behind it is what the library computes from planar float rows of n samples.
+ *   glv_batch_set_bufscale   k = 1: off, the default; 2..GLV_MAX_BUFSCALE.  Like glv_batch_set_params it is synchronous and the only place the feature
+ *       allocates: a batch-owned staging array of streams * 2 * n floats (k = 1 frees it; on failure the batch stays as it was).  State, head, tables, bar and
+ *       column texels are kept; glv_batch_set_params and glv_batch_reset keep k.  GLV_ERR_INVALID: k = 0, k > GLV_MAX_BUFSCALE, k * n > 2^21.  GLV_ERR_STATE: a
+ *       single-row batch (the drop-ins'), a batch created with GLV_OP_RING_S16 / GLV_OP_RING_F32.  With k = 1 every entry runs the code path it has always run.
+ *   Process calls while k > 1: glv_batch_process_s16 and glv_batch_process_f32_stereo read [streams][k*n][2], glv_batch_process_f32 reads planar
+ *       [streams][2][k*n] (the lb / rb rd_update itself decimates: no mix).  One launch (glv_decimate_kernel) writes the staging rows, then the chain
+ *       glv_batch_process_f32 plans on this batch for the same ops runs on them; what that entry refuses is refused in its words.  glv_batch_last_launches and
+ *       the timing pair count the extra launch.  The calls never allocate and can be captured into a hipGraph from the first one on.
+ *   Track calls on FFT chains while k > 1 (glv_batch_track_windows_*, _columns_*, _live_*, _at_*, _rates_*, _frames_*, s16 and f32): window t of a stream is
+ *       the k * n frames from t * hop, or from min(starts[t], pitch_frames - k * n) for a table call -- the pitch rules and the kernel's clamp use k * n, no launch
+ *       reads outside the recordings whatever a table holds.  One launch writes every window's decimated rows, steps * streams * 2 * n floats, into a new FIRST
+ *       region of the workspace (the *_work_bytes queries answer for the batch as it is; a stateless chain without bars needs the workspace for these rows
+ *       alone), the stateless transform runs once over them, and the scan, bars, columns, frames and key write-back stages run unchanged.  Keyframes of a frames
+ *       call are rows of n, as the reference's interpolate_buf of bufsize / bufscale is (render.c:1681); the tables and d_keys do not change.
+ *   GLV_ERR_STATE while k > 1, each naming glv_batch_set_bufscale: glv_batch_track_s16 (its residues rest on back-to-back windows of n frames),
+ *       glv_batch_track_wave_* and glv_batch_track_wave_frames_*, the ring entries, glv_batch_autotune and glv_batch_tune_placement. */
+#define GLV_MAX_BUFSCALE 16
+int      glv_batch_set_bufscale(glv_batch* b, uint32_t k);
+uint32_t glv_batch_bufscale(const glv_batch* b);
+
 /* FIFO ring mode (glava/fifo.c:91-112): the batch keeps an n-frame s16 ring per stream in
  * HBM; each call appends `new_frames` (= sample_sz/4, fifo.c:38,91) stereo frames per
  * stream (d_new int16 [streams][new_frames][2]; NULL => poll-timeout zero fill,

@@ -1,0 +1,65 @@
+"""Have the existing kernels moved?  The comparison of tools/track_frames_isa.py -- the gfx950 device code of every product object both trees have, .text and
+kernel descriptors byte for byte -- between this tree's build and the parent commit's, and the registers and scratch of the new unit's kernels
+(glv_decimate.hip: VGPRs, SGPRs, scratch bytes, and tools/isa_stats.py's instruction mix).
+
+    python tools/bufscale_isa.py --parent-build DIR/glava_amd/csrc/build [--out profiles/r21/bufscale_isa.txt]
+
+Both trees must be built (python -m glava_amd.build).  Needs no GPU.  Exit status 1 if an object both trees have differs."""
+import argparse
+import glob
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from glava_amd.build import CSRC, HIPFLAGS, OBJ, SMALL, _hipcc  # noqa: E402
+from track_frames_isa import device_sections  # noqa: E402
+
+NEW_UNIT = "glv_decimate"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-build", required=True, help="glava_amd/csrc/build of the tree to compare with, built")
+    ap.add_argument("--out", default=os.path.join("profiles", "r21", "bufscale_isa.txt"))
+    a = ap.parse_args()
+    lines = ["# device code of the product objects, gfx950: this tree against the parent commit's build.  Per object and section: bytes, sha256[:16] of this tree's, and",
+             "# whether the parent's are the same bytes.  .text: the machine code of every kernel of the object; .rodata: the kernel descriptors (VGPRs, SGPRs, scratch, LDS)"]
+    moved, seen = 0, 0
+    with tempfile.TemporaryDirectory() as tmp:
+        for obj in sorted(glob.glob(os.path.join(OBJ, "*.o"))):
+            name = os.path.basename(obj)
+            if not name.startswith(("glv_inst_", *SMALL)): continue              # (the host units hold no kernels)
+            here = device_sections(obj, tmp)
+            other = os.path.join(a.parent_build, name)
+            head = f"{name:<22} .text {here['.text'][0]:>8} {here['.text'][1]}  .rodata {here['.rodata'][0]:>6} {here['.rodata'][1]}  "
+            if not os.path.exists(other):
+                lines.append(head + "new in this tree")
+                continue
+            there = device_sections(other, tmp)
+            seen += 1
+            moved += here != there
+            lines.append(head + ("identical to the parent's" if here == there else f"DIFFERS: parent .text {there['.text']} .rodata {there['.rodata']}"))
+        lines.append(f"# objects both trees have: {seen}; moved against the parent: {moved}")
+        asm = os.path.join(tmp, "decimate.s")
+        subprocess.run([_hipcc(), *HIPFLAGS, "--cuda-device-only", "-S", os.path.join(CSRC, NEW_UNIT + ".hip"), "-o", asm], check=True)
+        text = open(asm).read()
+        lines.append(f"# the new unit's kernels ({NEW_UNIT}.hip): registers and scratch from the kernel descriptors")
+        for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
+            g = lambda k: (re.search(r"\.amdhsa_" + k + r" (\d+)", m.group(2)) or [None, "?"])[1]    # noqa: E731
+            lines.append(f"    {m.group(1)}: VGPRs {g('next_free_vgpr')}  SGPRs {g('next_free_sgpr')}  scratch {g('private_segment_fixed_size')} B  LDS {g('group_segment_fixed_size')} B")
+        lines.append("# ... and their instruction mix (tools/isa_stats.py):")
+        lines += ["    " + x for x in subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_stats.py"), asm], check=True, capture_output=True, text=True).stdout.split("\n") if x.strip()]
+    print("\n".join(lines))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    sys.exit(1 if moved else 0)
+
+
+if __name__ == "__main__":
+    main()
