@@ -185,7 +185,105 @@ int batch_alloc(glv_batch* b) {
 }
 }  // namespace glvh
 
+namespace {
+// ---- stream slots (glv_batch_reset_streams / _save_streams / _load_streams) ----------------------------------------------------------------------
+// What a blob of this batch is now: the state arrays it owns, the element they hold, and what the calls it has run made of them.
+void stream_desc(const glv_batch* b, glv_stream_state_desc* d) {
+    const uint64_t n = b->p.n, elem = b->state16 ? 2u : 4u;
+    std::memset(d, 0, sizeof(*d));
+    d->n = b->p.n; d->avg_frames = b->p.avg_frames; d->elem_bytes = (uint32_t) elem; d->gravity_form = (uint32_t) b->grav_mode;
+    d->regions = (b->d_grav ? 1u : 0u) | (b->d_hist ? 2u : 0u) | (b->d_ring ? 4u : 0u) | (b->d_ring_f32 ? 8u : 0u);
+    d->kept_bins = (b->ops_mask & GLV_OP_BARS_ONLY) && b->ran_live && b->live_bins() != 0 ? b->live_bins() : b->p.n;
+    d->bytes = (b->d_grav ? 2u * n * elem : 0u) + (b->d_hist ? 2u * n * elem * b->p.avg_frames : 0u) + (b->d_ring ? 4u * n : 0u) + (b->d_ring_f32 ? 8u * n : 0u);
+}
+// The region table of the launch: the stream's part of each array in the portable order, rotated by the batch's positions as they are now (`rotated`;
+// a reset writes zeros, which read the same at every rotation).
+void stream_regions(const glv_batch* b, bool rotated, glv::SlotTable& t) {
+    const uint32_t n = b->p.n, row = n * (b->state16 ? 2u : 4u), F = b->p.avg_frames;
+    uint32_t k = 0, start = 0;
+    auto add = [&](void* base, uint32_t stream_bytes, uint32_t chan_bytes, uint32_t unit, uint32_t pos, uint32_t mod) {
+        t.r[k++] = glv::SlotRegion{static_cast<char*>(base), start, stream_bytes, chan_bytes, (uint32_t) log2_exact(unit), rotated ? pos % mod : 0u, mod};
+        start += stream_bytes;
+    };
+    if (b->d_grav) add(b->d_grav, 2u * row, row, row, 0u, 1u);
+    if (b->d_hist) add(b->d_hist, 2u * row * F, row * F, row, b->head, F);
+    if (b->d_ring) add(b->d_ring.get(), 4u * n, 4u * n, 4u, b->ring_pos, n);
+    if (b->d_ring_f32) add(b->d_ring_f32.get(), 8u * n, 8u * n, 8u, b->ring_pos_f32, n);
+    t.nregions = k; t.bytes = start; t.streams = b->streams;
+}
+// what all three calls refuse; `blob`: the call moves blobs
+int slots_check(const glv_batch* b, const char* entry, const uint32_t* d_idx, uint32_t count, const void* d_blob, bool blob) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!d_idx || (reinterpret_cast<uintptr_t>(d_idx) & 3u)) return fail(GLV_ERR_INVALID, "%s: d_idx is NULL or not 4-byte aligned", entry);
+    if (blob && (!d_blob || (reinterpret_cast<uintptr_t>(d_blob) & 15u))) return fail(GLV_ERR_INVALID, "%s: d_blob is NULL or not 16-byte aligned", entry);
+    if (count == 0) return fail(GLV_ERR_INVALID, "%s: count must be > 0", entry);
+    if (b->single_row) return fail(GLV_ERR_STATE, "%s: a single-row batch (the drop-ins') has no streams to choose among", entry);
+    if (b->grav_cur != b->d_grav)
+        return fail(GLV_ERR_STATE, "%s: the latest gravity output of this batch lives in the caller's buffer (GLV_OP_OUTPUT_IS_STATE): the library does not own that memory", entry);
+    return GLV_OK;
+}
+int slots_launch(glv_batch* b, int kind, const uint32_t* d_idx, uint32_t count, void* d_blob, hipStream_t st) {
+    glv::SlotTable t = {};
+    stream_regions(b, kind != glv::SLOT_ZERO, t);
+    t.idx = d_idx; t.blob = d_blob; t.count = count;
+    HIP_TRY(hipSetDevice(b->device));
+    const hipError_t e = glv::launch_slots(kind, t, st);
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "stream slots launch failed: %s", hipGetErrorString(e));
+    b->last_launches = 1; b->kernel_name = "glv_slots_kernel";
+    return GLV_OK;
+}
+}  // namespace
+
 extern "C" {
+int glv_batch_stream_state_desc(const glv_batch* b, glv_stream_state_desc* d) {
+    if (!b || !d) return fail(GLV_ERR_INVALID, "glv_batch_stream_state_desc: NULL argument");
+    if (b->single_row) return fail(GLV_ERR_STATE, "glv_batch_stream_state_desc: a single-row batch (the drop-ins') has no streams to choose among");
+    stream_desc(b, d);
+    return GLV_OK;
+}
+
+int glv_batch_reset_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, void* hip_stream) {
+    if (int rc = slots_check(b, "glv_batch_reset_streams", d_idx, count, nullptr, false)) return rc;
+    b->last_launches = 0;
+    if (!b->d_grav && !b->d_hist && !b->d_ring && !b->d_ring_f32) return GLV_OK;      // nothing is kept per stream: every stream is a fresh one already
+    return slots_launch(b, glv::SLOT_ZERO, d_idx, count, nullptr, (hipStream_t) hip_stream);
+}
+
+int glv_batch_save_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, void* d_blob, glv_stream_state_desc* d, void* hip_stream) {
+    if (int rc = slots_check(b, "glv_batch_save_streams", d_idx, count, d_blob, true)) return rc;
+    if (!d) return fail(GLV_ERR_INVALID, "glv_batch_save_streams: d is NULL");
+    glv_stream_state_desc now;
+    stream_desc(b, &now);
+    if (now.regions == 0) return fail(GLV_ERR_STATE, "glv_batch_save_streams: the batch keeps neither state nor a ring (ops_mask 0x%x): a stream has nothing to save", b->ops_mask);
+    if (int rc = slots_launch(b, glv::SLOT_GATHER, d_idx, count, d_blob, (hipStream_t) hip_stream)) return rc;
+    *d = now;
+    return GLV_OK;
+}
+
+int glv_batch_load_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, const void* d_blob, const glv_stream_state_desc* d, void* hip_stream) {
+    if (int rc = slots_check(b, "glv_batch_load_streams", d_idx, count, d_blob, true)) return rc;
+    if (!d) return fail(GLV_ERR_INVALID, "glv_batch_load_streams: d is NULL");
+    glv_stream_state_desc now;
+    stream_desc(b, &now);
+    if (now.regions == 0) return fail(GLV_ERR_STATE, "glv_batch_load_streams: the batch keeps neither state nor a ring (ops_mask 0x%x): a stream has nothing to load", b->ops_mask);
+    if (d->n != now.n || d->avg_frames != now.avg_frames || d->elem_bytes != now.elem_bytes || d->regions != now.regions || d->bytes != now.bytes)
+        return fail(GLV_ERR_STATE, "glv_batch_load_streams: the blob (n=%u, F=%u, %u-byte elements, regions 0x%x) is not of this batch's kind (n=%u, F=%u, %u-byte elements, "
+                                   "regions 0x%x)", d->n, d->avg_frames, d->elem_bytes, d->regions, now.n, now.avg_frames, now.elem_bytes, now.regions);
+    if (d->gravity_form > 2u) return fail(GLV_ERR_INVALID, "glv_batch_load_streams: gravity_form=%u: 0, 1 or 2", d->gravity_form);
+    // the form gravity's state is kept in: a batch keeps one (refuse_gravity_mix says why, and its words refuse the blob of the other)
+    const unsigned form_ops = d->gravity_form == 0u ? 0u : d->gravity_form == 2u ? (unsigned) (GLV_OP_GRAVITY | GLV_OP_AVERAGE) : (unsigned) GLV_OP_GRAVITY;
+    if (int rc = refuse_gravity_mix(b, form_ops)) return rc;
+    const bool live_blob = d->kept_bins != now.n;
+    if (live_blob && (!(b->ops_mask & GLV_OP_BARS_ONLY) || b->live_bins() == 0 || b->live_bins() != d->kept_bins))
+        return fail(GLV_ERR_STATE, "glv_batch_load_streams: the blob keeps bins [0, %u) of n=%u only (a GLV_OP_BARS_ONLY batch that has run its live class): it loads into a "
+                                   "GLV_OP_BARS_ONLY batch whose glv_batch_live_bins() equals that (this batch: %u)", d->kept_bins, now.n,
+                    (b->ops_mask & GLV_OP_BARS_ONLY) ? b->live_bins() : 0u);
+    if (int rc = slots_launch(b, glv::SLOT_SCATTER, d_idx, count, const_cast<void*>(d_blob), (hipStream_t) hip_stream)) return rc;
+    commit_gravity_form(b, form_ops);        // (form 0: nothing to adopt)
+    if (live_blob) b->ran_live = true;
+    return GLV_OK;
+}
+
 // `setbufscale k` for a batch (include/glv_spectrum.h): the factor, and the staging rows a process call decimates into -- made here, by this call alone, so that
 // the process and track calls stay launches only.  Like glv_batch_set_params it waits for the device first: a queued call may still read the array that goes.
 // State, head, tables, bar and column texels are not touched; glv_batch_set_params and glv_batch_reset do not touch k.

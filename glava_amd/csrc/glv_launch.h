@@ -96,6 +96,24 @@ struct Decimate {
 };
 constexpr size_t kDecimateGridCap = 256 * 8;       // 256 CUs x 8 resident 256-lane workgroups; the kernel's loop takes what lies beyond
 hipError_t launch_decimate(int kind, const Decimate& d, hipStream_t st);
+// Chosen streams of a batch (glv_slots.hip; glv_batch_reset_streams / _save_streams / _load_streams): zero their state, gather it into blobs in the portable
+// form, or scatter blobs back -- one launch each.  A stream's portable bytes are the regions below back to back (`start` = the sum of the stream_bytes before);
+// a region is the stream's stream_bytes of one device array, one or two blocks of chan_bytes = mod << log_unit bytes, and portable unit u of a block is array
+// unit (u + pos) mod `mod` of that block (pos < mod; units below 16 bytes are a PCM ring's frames).  idx: uint32 [count] in device memory, read when the kernel
+// runs, an entry >= streams skipped with its blob; blob: count * bytes bytes, 16-byte aligned (SLOT_ZERO: unused).
+enum SlotKind { SLOT_ZERO = 0, SLOT_GATHER = 1, SLOT_SCATTER = 2 };
+constexpr int kSlotRegions = 4;
+struct SlotRegion {
+    char* base;
+    uint32_t start, stream_bytes, chan_bytes, log_unit, pos, mod;
+};
+struct SlotTable {
+    SlotRegion r[kSlotRegions];
+    const uint32_t* idx; void* blob;
+    uint32_t nregions, streams, count, bytes;      // bytes: of one stream's portable form (a multiple of 16)
+};
+constexpr size_t kSlotsGridCap = 256 * 8;          // 256 CUs x 8 resident 256-lane workgroups of 256 pieces each; the kernel's loop takes what lies beyond
+hipError_t launch_slots(int kind, const SlotTable& t, hipStream_t st);
 hipError_t launch_lerp(const float* s0, const float* e0, float* out, size_t total, float mod, hipStream_t st);
 hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin, const int* smax, uint32_t asz, uint32_t reach,
                          uint32_t max_window, hipStream_t st);

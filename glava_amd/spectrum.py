@@ -64,6 +64,14 @@ class TrackFrames(C.Structure):
                 ("keep_from", C.c_uint32), ("keep_to", C.c_uint32)]
 
 
+class StreamStateDesc(C.Structure):
+    """glv_stream_state_desc: what a blob of Batch.save_streams is -- the batch's n, F and element size, the form gravity's state was kept in, the regions
+    present (bit 0 gravity rows, 1 average ring, 2 s16 PCM ring, 3 f32 PCM ring), the bins kept and the bytes of one stream (glava_amd/stream_slots.py
+    restates the layout)"""
+    _fields_ = [("n", C.c_uint32), ("avg_frames", C.c_uint32), ("elem_bytes", C.c_uint32), ("gravity_form", C.c_uint32), ("regions", C.c_uint32),
+                ("kept_bins", C.c_uint32), ("bytes", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -139,6 +147,12 @@ def lib() -> C.CDLL:
             L.glv_batch_set_bufscale.argtypes = [vp, C.c_uint32]
             L.glv_batch_bufscale.argtypes = [vp]
             L.glv_batch_bufscale.restype = C.c_uint32
+        if hasattr(L, "glv_batch_reset_streams"):       # (likewise: reset, save and load chosen streams of a batch)
+            SD = C.POINTER(StreamStateDesc)
+            L.glv_batch_stream_state_desc.argtypes = [vp, SD]
+            L.glv_batch_reset_streams.argtypes = [vp, vp, C.c_uint32, vp]
+            L.glv_batch_save_streams.argtypes = [vp, vp, C.c_uint32, vp, SD, vp]
+            L.glv_batch_load_streams.argtypes = [vp, vp, C.c_uint32, vp, SD, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -271,6 +285,33 @@ class Batch:
     def bufscale(self) -> int:
         """the batch's bufscale k (glv_batch_bufscale)"""
         return int(lib().glv_batch_bufscale(self._h))
+
+    def stream_state_desc(self) -> StreamStateDesc:
+        """what a blob of this batch is now (glv_batch_stream_state_desc): .bytes per stream, the regions present, the gravity form and kept bins as the
+        calls the batch has run left them"""
+        d = StreamStateDesc()
+        _check(lib().glv_batch_stream_state_desc(self._h, C.byref(d)))
+        return d
+
+    def reset_streams(self, d_idx, count: int, stream: int | None = None) -> None:
+        """glv_batch_reset_streams: the streams listed in d_idx (uint32 [count] in device memory, read when the kernel runs; entries >= streams are skipped)
+        become streams of a batch reset() has just cleared, every other stream is untouched; head, ring positions and gravity form stay.  One launch,
+        stream-ordered, capturable; a captured reset is re-aimed by rewriting d_idx.  Reset a slot when a listener attaches to it."""
+        _check(lib().glv_batch_reset_streams(self._h, _ptr(d_idx), count, _ptr(stream)))
+
+    def save_streams(self, d_idx, count: int, d_blob, stream: int | None = None) -> StreamStateDesc:
+        """glv_batch_save_streams: the state of the listed streams into d_blob (count * stream_state_desc().bytes bytes, 16-byte aligned; blob j belongs to
+        d_idx[j]) in the portable form -- gravity rows, the average ring oldest frame first, the PCM rings oldest frame first: no position of this batch
+        survives.  Returns the descriptor load_streams checks.  One launch, stream-ordered."""
+        d = StreamStateDesc()
+        _check(lib().glv_batch_save_streams(self._h, _ptr(d_idx), count, _ptr(d_blob), C.byref(d), _ptr(stream)))
+        return d
+
+    def load_streams(self, d_idx, count: int, d_blob, desc: StreamStateDesc, stream: int | None = None) -> None:
+        """glv_batch_load_streams: blobs of save_streams into the listed streams, rotated by THIS batch's positions -- the stream then continues bit for
+        bit as the saved one would have.  desc must match the batch (n, F, element size, regions: ERR_STATE), the gravity forms must agree unless one is
+        still 0, a live blob (kept_bins < n) loads only into an OP_BARS_ONLY batch with the same live_bins().  Duplicates in d_idx are the caller's error."""
+        _check(lib().glv_batch_load_streams(self._h, _ptr(d_idx), count, _ptr(d_blob), C.byref(desc), _ptr(stream)))
 
     def process_s16(self, d_pcm, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         """one update of every stream; stream-ordered (never allocates, never copies synchronously).  Chains ending in gravity

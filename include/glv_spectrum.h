@@ -849,6 +849,57 @@ int glv_batch_ring_append_s16(glv_batch* b, const int16_t* d_new /* NULL = zero 
 int glv_batch_ring_append_f32(glv_batch* b, const float* d_new, uint32_t new_frames, void* hip_stream);
 int glv_batch_ring_planar(glv_batch* b, int f32_ring, float* d_planar, void* hip_stream);
 
+/* Stream slots: reset, save and load CHOSEN streams of a batch.  Added within ABI 7: detect them by the symbol.  In the reference every listener is a GLava of
+ * its own that starts from calloc'd buffers and leaves when it likes; these calls give one stream of a batch that lifecycle (a listener that takes over a freed
+ * slot: reset it), checkpoints for seeking under the track entries, moves between batches and compaction -- without touching the other streams.
+ *
+ * Common to the three calls: d_idx is uint32 [count] in device memory and is read when the kernel runs (like the tables of glv_batch_track_at_*); an entry
+ * >= streams is skipped where it is read, its blob is then neither read nor written, and no launch touches memory outside the batch or the blobs whatever the
+ * table holds.  d_blob is count * d->bytes bytes, 16-byte aligned; blob j belongs to d_idx[j].  Each call is ONE launch (glv_slots_kernel, reported by
+ * glv_batch_last_launches), stream-ordered, allocates nothing and copies nothing synchronously: it can be captured into a hipGraph, and a captured reset can
+ * be replayed at any time and re-aimed by rewriting d_idx.  Save and load take head and the ring positions when they are enqueued, as a process call does.
+ * Duplicates in d_idx are harmless for reset and save; for load they are the caller's error: which blob wins is unspecified.
+ *
+ * The portable form of one stream (a blob) is the regions below in this order, present regions only (glv_stream_state_desc.regions), each a multiple of 16
+ * bytes; elements are floats, or GL_R16 texels (uint16) on a gl_storage 1 batch:
+ *   bit 0  gravity rows    [2][n] elements          the stream's rows of the batch's gravity store
+ *   bit 1  average ring    [2][F][n] elements       oldest frame first: blob row q of a channel is ring slot (head + q) mod F, head being the slot that
+ *                                                   receives the next frame (so blob row F - 1 is the newest, which is gravity's state in form 2)
+ *   bit 2  s16 PCM ring    [n][2] int16             oldest frame first: blob frame q is ring frame (ring position + q) mod n
+ *   bit 3  f32 PCM ring    [n][2] float             likewise with the f32 ring's position
+ * No position of the source batch survives into a blob, and the batch that loads one rotates by its own positions.
+ *
+ *   glv_batch_stream_state_desc   what a blob of this batch is NOW (gravity_form and kept_bins follow the calls the batch has run).
+ *   glv_batch_reset_streams       afterwards the listed streams are streams of a batch glv_batch_reset has just cleared, for every later process, ring and
+ *       track call, in output and state, bit for bit; every other stream is untouched.  head, the ring positions, the gravity form and the live flag stay: zero
+ *       state reads the same at every rotation and in both forms.  A batch with neither state nor ring: GLV_OK, no launch.
+ *   glv_batch_save_streams        gathers the listed streams into d_blob and fills *d (the descriptor a later load checks).
+ *   glv_batch_load_streams        scatters blobs into the listed streams: after save(A, i) and load(B, j), stream j of B continues exactly as stream i of A
+ *       would have -- given the same input every later call writes the same output and leaves the same state, bit for bit, whatever head / ring positions
+ *       the two batches are at, also with A == B (source and destination may overlap in the lists: a save completes before the load is enqueued).  Parameters
+ *       (fft_scale, ur, bars, ...) are the caller's business, exactly as state is kept across glv_batch_set_params.  Checked on the host before anything
+ *       runs, a refused call leaves the batch as it was: n, avg_frames, elem_bytes and regions must equal the batch's own (GLV_ERR_STATE); a blob of
+ *       gravity_form 0 loads anywhere; a batch whose form is still 0 adopts the blob's (all its streams are zero, and zero is the same state in both
+ *       forms); otherwise the forms must be equal (a batch keeps one form: see glv_batch_gravity_state); a blob with kept_bins == n loads into any such
+ *       batch, a GLV_OP_BARS_ONLY one included (whole rows are a superset of what it keeps); a blob with kept_bins < n loads only into a GLV_OP_BARS_ONLY
+ *       batch whose glv_batch_live_bins() equals it, which then counts as having run its live class.
+ * All three: GLV_ERR_INVALID for a NULL or misaligned pointer (d_idx 4 bytes, d_blob 16) and count == 0; GLV_ERR_STATE for a single-row batch (the glv_state
+ * drop-ins') and while the batch's latest gravity output lives in the caller's buffer (GLV_OP_OUTPUT_IS_STATE in force: the library does not own that
+ * memory); save and load also for a batch with neither state nor ring.  `setbufscale` plays no part: its staging rows are not state.
+ * Blobs are plain device memory: moving one to another device (a stream that changes its glv_multi shard) is the caller's own peer copy. */
+typedef struct glv_stream_state_desc {   /* host side; what a blob is, filled by the library */
+    uint32_t n, avg_frames;
+    uint32_t elem_bytes;      /* 4: float state (gl_storage 0 / 2 / 3), 2: GL_R16 texels (gl_storage 1) */
+    uint32_t gravity_form;    /* the batch's form when asked: 0 none yet, 1 the gravity store, 2 the newest ring slot (gravity fused with average) */
+    uint32_t regions;         /* bit 0 gravity rows, 1 average ring, 2 s16 PCM ring, 3 f32 PCM ring */
+    uint32_t kept_bins;       /* n, or glv_batch_live_bins() of a GLV_OP_BARS_ONLY batch that has run its live class */
+    uint64_t bytes;           /* per stream */
+} glv_stream_state_desc;
+int glv_batch_stream_state_desc(const glv_batch* b, glv_stream_state_desc* d);
+int glv_batch_reset_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, void* hip_stream);
+int glv_batch_save_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, void* d_blob, glv_stream_state_desc* d, void* hip_stream);
+int glv_batch_load_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, const void* d_blob, const glv_stream_state_desc* d, void* hip_stream);
+
 /* smooth_audio() bar sampling of spectra already in HBM (d_spec float [streams][2][n]) into
  * d_bars float [streams][2][bars]; what GLV_OP_BARS runs after the transform.  Refused on a gl_storage 3 batch (GLV_ERR_STATE): there GLV_OP_BARS samples the
  * upload's texels, and caller's float rows go through a gl_storage 0 batch. */

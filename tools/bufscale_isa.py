@@ -1,8 +1,9 @@
 """Have the existing kernels moved?  The comparison of tools/track_frames_isa.py -- the gfx950 device code of every product object both trees have, .text and
 kernel descriptors byte for byte -- between this tree's build and the parent commit's, and the registers and scratch of the new unit's kernels
-(glv_decimate.hip: VGPRs, SGPRs, scratch bytes, and tools/isa_stats.py's instruction mix).
+(--unit, glv_decimate.hip unless given: VGPRs, SGPRs, scratch bytes, and tools/isa_stats.py's instruction mix).
 
-    python tools/bufscale_isa.py --parent-build DIR/glava_amd/csrc/build [--out profiles/r21/bufscale_isa.txt]
+    python tools/bufscale_isa.py --parent-build DIR/glava_amd/csrc/build [--unit glv_decimate] [--out profiles/r21/bufscale_isa.txt]
+    python tools/bufscale_isa.py --parent-build DIR/glava_amd/csrc/build --unit glv_slots --out profiles/r22/stream_slots_isa.txt
 
 Both trees must be built (python -m glava_amd.build).  Needs no GPU.  Exit status 1 if an object both trees have differs."""
 import argparse
@@ -19,12 +20,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from glava_amd.build import CSRC, HIPFLAGS, OBJ, SMALL, _hipcc  # noqa: E402
 from track_frames_isa import device_sections  # noqa: E402
 
-NEW_UNIT = "glv_decimate"
-
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-build", required=True, help="glava_amd/csrc/build of the tree to compare with, built")
+    ap.add_argument("--unit", default="glv_decimate", help="the unit new in this tree, whose kernels' registers and scratch are listed")
     ap.add_argument("--out", default=os.path.join("profiles", "r21", "bufscale_isa.txt"))
     a = ap.parse_args()
     lines = ["# device code of the product objects, gfx950: this tree against the parent commit's build.  Per object and section: bytes, sha256[:16] of this tree's, and",
@@ -45,10 +45,10 @@ def main():
             moved += here != there
             lines.append(head + ("identical to the parent's" if here == there else f"DIFFERS: parent .text {there['.text']} .rodata {there['.rodata']}"))
         lines.append(f"# objects both trees have: {seen}; moved against the parent: {moved}")
-        asm = os.path.join(tmp, "decimate.s")
-        subprocess.run([_hipcc(), *HIPFLAGS, "--cuda-device-only", "-S", os.path.join(CSRC, NEW_UNIT + ".hip"), "-o", asm], check=True)
+        asm = os.path.join(tmp, a.unit + ".s")
+        subprocess.run([_hipcc(), *HIPFLAGS, "--cuda-device-only", "-S", os.path.join(CSRC, a.unit + ".hip"), "-o", asm], check=True)
         text = open(asm).read()
-        lines.append(f"# the new unit's kernels ({NEW_UNIT}.hip): registers and scratch from the kernel descriptors")
+        lines.append(f"# the new unit's kernels ({a.unit}.hip): registers and scratch from the kernel descriptors")
         for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
             g = lambda k: (re.search(r"\.amdhsa_" + k + r" (\d+)", m.group(2)) or [None, "?"])[1]    # noqa: E731
             lines.append(f"    {m.group(1)}: VGPRs {g('next_free_vgpr')}  SGPRs {g('next_free_sgpr')}  scratch {g('private_segment_fixed_size')} B  LDS {g('group_segment_fixed_size')} B")
