@@ -266,8 +266,9 @@ static int ring_append(char* d_ring, const char* d_new, uint32_t pos, uint32_t n
 }
 
 // the append half of a ring update: copy / zero-fill the new frames at the write position of the ring glv_batch_create
-// allocated (GLV_OP_RING_S16 / _F32) and advance it.  *old_pos receives the position before the append.
-static int ring_push(glv_batch* b, bool f32, const void* d_new, uint32_t new_frames, hipStream_t st, uint32_t* old_pos) {
+// allocated (GLV_OP_RING_S16 / _F32) and advance it.  *old_pos receives the position before the append.  streams: the rings [0, streams) receive frames
+// (the batch's, or the prefix of a glv_batch_ring_update_first_* call).
+static int ring_push(glv_batch* b, bool f32, const void* d_new, uint32_t new_frames, hipStream_t st, uint32_t* old_pos, uint32_t streams) {
     const uint32_t n = b->p.n;
     if (int rc = refuse_bufscale(b, f32 ? "the f32 ring entries" : "the s16 ring entries")) return rc;
     if (new_frames == 0 || new_frames > n)
@@ -277,7 +278,7 @@ static int ring_push(glv_batch* b, bool f32, const void* d_new, uint32_t new_fra
     uint32_t* pos = f32 ? &b->ring_pos_f32 : &b->ring_pos;
     if (!ring)
         return fail(GLV_ERR_STATE, "the batch was created without GLV_OP_RING_%s in its ops_mask (rings are allocated at creation, ring updates never allocate)", f32 ? "F32" : "S16");
-    if (int rc = ring_append(ring, static_cast<const char*>(d_new), *pos, new_frames, n, fb, b->streams, st)) return rc;
+    if (int rc = ring_append(ring, static_cast<const char*>(d_new), *pos, new_frames, n, fb, streams, st)) return rc;
     *old_pos = *pos;
     *pos = (*pos + new_frames) % n;                              // the oldest frame now sits here: the window starts there
     return GLV_OK;
@@ -291,7 +292,7 @@ int glv_batch_ring_update_s16(glv_batch* b, const int16_t* d_new, uint32_t new_f
     HIP_TRY(hipSetDevice(b->device));
     if (int rc = check_ops(b, ops, d_out)) return rc;            // nothing is appended when the call cannot be processed
     uint32_t old_pos = 0;
-    if (int rc = ring_push(b, false, d_new, new_frames, st, &old_pos)) return rc;
+    if (int rc = ring_push(b, false, d_new, new_frames, st, &old_pos, b->streams)) return rc;
     const int rc = process(b, b->d_ring, glv::IN_S16_RING, d_out, ops, b->streams * 2, b->ring_pos, st);
     if (rc != GLV_OK) b->ring_pos = old_pos;                      // a failed launch leaves the ring where the caller saw it
     return rc;
@@ -305,17 +306,65 @@ int glv_batch_ring_update_f32(glv_batch* b, const float* d_new, uint32_t new_fra
     HIP_TRY(hipSetDevice(b->device));
     if (int rc = check_ops(b, ops, d_out)) return rc;
     uint32_t old_pos = 0;
-    if (int rc = ring_push(b, true, d_new, new_frames, st, &old_pos)) return rc;
+    if (int rc = ring_push(b, true, d_new, new_frames, st, &old_pos, b->streams)) return rc;
     const int rc = process(b, b->d_ring_f32, glv::IN_F32_RING, d_out, ops, b->streams * 2, b->ring_pos_f32, st);
     if (rc != GLV_OK) b->ring_pos_f32 = old_pos;
     return rc;
+}
+
+// Elastic batches (include/glv_spectrum.h): the process and ring-update calls on streams [0, count) of the batch -- the un-suffixed call with 2 * count channel rows
+// and count rings, refused in its words; the batch's positions advance as for a full call.
+int glv_batch_process_first_s16(glv_batch* b, uint32_t count, const int16_t* d_pcm, float* d_out, unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (int rc = refuse_prefix(b, "glv_batch_process_first_s16", count)) return rc;
+    if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "s16 input requires GLV_OP_FFT or GLV_OP_WAVE");
+    return process_first(b, count, d_pcm, glv::IN_S16_STEREO, glv::DEC_S16, d_out, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_process_first_f32(glv_batch* b, uint32_t count, const float* d_f32, float* d_out, unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (int rc = refuse_prefix(b, "glv_batch_process_first_f32", count)) return rc;
+    return process_first(b, count, d_f32, glv::IN_F32_PLANAR, glv::DEC_F32_PLANAR, d_out, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_process_first_f32_stereo(glv_batch* b, uint32_t count, const float* d_pcm, float* d_out, unsigned ops, void* hip_stream) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (int rc = refuse_prefix(b, "glv_batch_process_first_f32_stereo", count)) return rc;
+    if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE))) return fail(GLV_ERR_INVALID, "interleaved input requires GLV_OP_FFT or GLV_OP_WAVE");
+    return process_first(b, count, d_pcm, glv::IN_F32_STEREO, glv::DEC_F32, d_out, ops, (hipStream_t) hip_stream);
+}
+
+// both ring entries' prefix form: glv_batch_ring_update_s16 / _f32 with `count` in the place of the batch's streams
+static int ring_update_first(glv_batch* b, bool f32, uint32_t count, const void* d_new, uint32_t new_frames, float* d_out, unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (int rc = refuse_prefix(b, f32 ? "glv_batch_ring_update_first_f32" : "glv_batch_ring_update_first_s16", count)) return rc;
+    if (!(ops & (GLV_OP_FFT | GLV_OP_WAVE)))
+        return fail(GLV_ERR_INVALID, "ring mode requires GLV_OP_FFT or GLV_OP_WAVE (glv_batch_ring_append_%s appends without transforming)", f32 ? "f32" : "s16");
+    if (f32 && !d_new) return fail(GLV_ERR_INVALID, "d_new is NULL (the PulseAudio backend has no zero-fill path)");
+    HIP_TRY(hipSetDevice(b->device));
+    if (int rc = check_ops(b, ops, d_out)) return rc;            // nothing is appended when the call cannot be processed
+    uint32_t old_pos = 0;
+    if (int rc = ring_push(b, f32, d_new, new_frames, st, &old_pos, count)) return rc;
+    uint32_t* const pos = f32 ? &b->ring_pos_f32 : &b->ring_pos;
+    const void* const ring = f32 ? static_cast<const void*>(b->d_ring_f32.get()) : static_cast<const void*>(b->d_ring.get());
+    const int rc = process(b, ring, f32 ? glv::IN_F32_RING : glv::IN_S16_RING, d_out, ops, 2 * count, *pos, st);
+    if (rc != GLV_OK) *pos = old_pos;                            // a failed launch leaves the ring where the caller saw it
+    return rc;
+}
+
+int glv_batch_ring_update_first_s16(glv_batch* b, uint32_t count, const int16_t* d_new, uint32_t new_frames, float* d_out, unsigned ops, void* hip_stream) {
+    return ring_update_first(b, false, count, d_new, new_frames, d_out, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_ring_update_first_f32(glv_batch* b, uint32_t count, const float* d_new, uint32_t new_frames, float* d_out, unsigned ops, void* hip_stream) {
+    return ring_update_first(b, true, count, d_new, new_frames, d_out, ops, (hipStream_t) hip_stream);
 }
 
 int glv_batch_ring_append_s16(glv_batch* b, const int16_t* d_new, uint32_t new_frames, void* hip_stream) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     HIP_TRY(hipSetDevice(b->device));
     uint32_t old_pos = 0;
-    return ring_push(b, false, d_new, new_frames, (hipStream_t) hip_stream, &old_pos);
+    return ring_push(b, false, d_new, new_frames, (hipStream_t) hip_stream, &old_pos, b->streams);
 }
 
 int glv_batch_ring_append_f32(glv_batch* b, const float* d_new, uint32_t new_frames, void* hip_stream) {
@@ -323,7 +372,7 @@ int glv_batch_ring_append_f32(glv_batch* b, const float* d_new, uint32_t new_fra
     if (!d_new) return fail(GLV_ERR_INVALID, "d_new is NULL (the PulseAudio backend has no zero-fill path)");
     HIP_TRY(hipSetDevice(b->device));
     uint32_t old_pos = 0;
-    return ring_push(b, true, d_new, new_frames, (hipStream_t) hip_stream, &old_pos);
+    return ring_push(b, true, d_new, new_frames, (hipStream_t) hip_stream, &old_pos, b->streams);
 }
 
 int glv_batch_ring_planar(glv_batch* b, int f32_ring, float* d_planar, void* hip_stream) {

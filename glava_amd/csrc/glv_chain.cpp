@@ -302,7 +302,7 @@ int decimate_stage(glv_batch* b, const ChainPlan& pl, hipStream_t st) {
     if (!pl.dec_in) return GLV_OK;
     glv::Decimate d = {};
     d.in = pl.dec_in; d.out = b->d_decim; d.n = b->p.n; d.k = b->bufscale; d.mono = b->p.channels == 1 ? 1u : 0u;
-    d.w.pitch_frames = (uint64_t) b->bufscale * b->p.n; d.w.steps = 1; d.w.streams = b->streams;
+    d.w.pitch_frames = (uint64_t) b->bufscale * b->p.n; d.w.steps = 1; d.w.streams = pl.dec_streams;
     const hipError_t e = glv::launch_decimate(pl.dec_kind, d, st); ++b->last_launches;
     return e == hipSuccess ? GLV_OK : fail(GLV_ERR_HIP, "bufscale launch failed: %s", hipGetErrorString(e));
 }
@@ -428,7 +428,7 @@ int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned 
     ChainPlan pl;
     if (int rc = plan_chain(b, in_mode, ops, units, rot, d_out, pl)) return rc;
     if (int rc = refuse_stale_tilt(b)) return rc;
-    pl.dec_in = dec_in; pl.dec_kind = dec_kind;
+    pl.dec_in = dec_in; pl.dec_kind = dec_kind; pl.dec_streams = units / 2u;
     commit_gravity_form(b, ops);
     if (pl.route == ChainPlan::WAVE) return run_wave(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
     return run_chain(b, pl, d_in, in_mode, d_out, ops, units, rot, st);
@@ -443,6 +443,21 @@ int process_windows(glv_batch* b, const void* d_in, int in_mode, int dec_kind, f
     if (reinterpret_cast<uintptr_t>(d_in) & (dec_kind == glv::DEC_F32 ? 7u : 3u))
         return fail(GLV_ERR_INVALID, "the input must be aligned like its frames: %d bytes", dec_kind == glv::DEC_F32 ? 8 : 4);
     return process(b, b->d_decim, glv::IN_F32_PLANAR, d_out, ops, b->streams * 2, 0, st, d_in, dec_kind);
+}
+// ... and the three glv_batch_process_first_* entries: the same call on streams [0, count) -- 2 * count channel rows where process_windows passes all of the batch's.
+// Every kernel takes its rows from the call (the grid is planned for them, a tuned grid clamped to them), so the rows behind are neither read nor written; head,
+// the gravity form and the live flag are the batch's own and advance as for a full call.
+int refuse_prefix(const glv_batch* b, const char* entry, uint32_t count) {
+    if (count == 0 || count > b->streams) return fail(GLV_ERR_INVALID, "%s: count=%u: must be in [1, streams=%u]", entry, count, b->streams);
+    if (b->single_row) return fail(GLV_ERR_STATE, "%s: a single-row batch (the drop-ins') has no streams to choose among", entry);
+    return GLV_OK;
+}
+int process_first(glv_batch* b, uint32_t count, const void* d_in, int in_mode, int dec_kind, float* d_out, unsigned ops, hipStream_t st) {
+    if (b->bufscale == 1u) return process(b, d_in, in_mode, d_out, ops, 2 * count, 0, st);
+    if (!d_in) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_in) & (dec_kind == glv::DEC_F32 ? 7u : 3u))
+        return fail(GLV_ERR_INVALID, "the input must be aligned like its frames: %d bytes", dec_kind == glv::DEC_F32 ? 8 : 4);
+    return process(b, b->d_decim, glv::IN_F32_PLANAR, d_out, ops, 2 * count, 0, st, d_in, dec_kind);
 }
 // What does not honour `setbufscale`: refused while k > 1, in the setter's name
 int refuse_bufscale(const glv_batch* b, const char* entry) {

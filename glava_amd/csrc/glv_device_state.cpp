@@ -232,6 +232,28 @@ int slots_launch(glv_batch* b, int kind, const uint32_t* d_idx, uint32_t count, 
     b->last_launches = 1; b->kernel_name = "glv_slots_kernel";
     return GLV_OK;
 }
+// Whether streams described by *d -- `what`: the blob of a load, the source batch of a copy -- can become streams of batch b, whose own descriptor is `now`;
+// checked on the host before anything runs, refused in the entry's name.  *fit: what the batch adopts once the launch went through (adopt_streams).
+struct StreamsFit { unsigned form_ops = 0; bool live = false; };
+int streams_fit(const glv_batch* b, const char* entry, const char* what, const glv_stream_state_desc* d, const glv_stream_state_desc& now, StreamsFit* fit) {
+    if (d->n != now.n || d->avg_frames != now.avg_frames || d->elem_bytes != now.elem_bytes || d->regions != now.regions || d->bytes != now.bytes)
+        return fail(GLV_ERR_STATE, "%s: %s (n=%u, F=%u, %u-byte elements, regions 0x%x) is not of this batch's kind (n=%u, F=%u, %u-byte elements, "
+                                   "regions 0x%x)", entry, what, d->n, d->avg_frames, d->elem_bytes, d->regions, now.n, now.avg_frames, now.elem_bytes, now.regions);
+    if (d->gravity_form > 2u) return fail(GLV_ERR_INVALID, "%s: gravity_form=%u: 0, 1 or 2", entry, d->gravity_form);
+    // the form gravity's state is kept in: a batch keeps one (refuse_gravity_mix says why, and its words refuse the streams of the other)
+    fit->form_ops = d->gravity_form == 0u ? 0u : d->gravity_form == 2u ? (unsigned) (GLV_OP_GRAVITY | GLV_OP_AVERAGE) : (unsigned) GLV_OP_GRAVITY;
+    if (int rc = refuse_gravity_mix(b, fit->form_ops)) return rc;
+    fit->live = d->kept_bins != now.n;
+    if (fit->live && (!(b->ops_mask & GLV_OP_BARS_ONLY) || b->live_bins() == 0 || b->live_bins() != d->kept_bins))
+        return fail(GLV_ERR_STATE, "%s: %s keeps bins [0, %u) of n=%u only (a GLV_OP_BARS_ONLY batch that has run its live class): it loads into a "
+                                   "GLV_OP_BARS_ONLY batch whose glv_batch_live_bins() equals that (this batch: %u)", entry, what, d->kept_bins, now.n,
+                    (b->ops_mask & GLV_OP_BARS_ONLY) ? b->live_bins() : 0u);
+    return GLV_OK;
+}
+void adopt_streams(glv_batch* b, const StreamsFit& fit) {
+    commit_gravity_form(b, fit.form_ops);    // (form 0: nothing to adopt)
+    if (fit.live) b->ran_live = true;
+}
 }  // namespace
 
 extern "C" {
@@ -266,21 +288,39 @@ int glv_batch_load_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, 
     glv_stream_state_desc now;
     stream_desc(b, &now);
     if (now.regions == 0) return fail(GLV_ERR_STATE, "glv_batch_load_streams: the batch keeps neither state nor a ring (ops_mask 0x%x): a stream has nothing to load", b->ops_mask);
-    if (d->n != now.n || d->avg_frames != now.avg_frames || d->elem_bytes != now.elem_bytes || d->regions != now.regions || d->bytes != now.bytes)
-        return fail(GLV_ERR_STATE, "glv_batch_load_streams: the blob (n=%u, F=%u, %u-byte elements, regions 0x%x) is not of this batch's kind (n=%u, F=%u, %u-byte elements, "
-                                   "regions 0x%x)", d->n, d->avg_frames, d->elem_bytes, d->regions, now.n, now.avg_frames, now.elem_bytes, now.regions);
-    if (d->gravity_form > 2u) return fail(GLV_ERR_INVALID, "glv_batch_load_streams: gravity_form=%u: 0, 1 or 2", d->gravity_form);
-    // the form gravity's state is kept in: a batch keeps one (refuse_gravity_mix says why, and its words refuse the blob of the other)
-    const unsigned form_ops = d->gravity_form == 0u ? 0u : d->gravity_form == 2u ? (unsigned) (GLV_OP_GRAVITY | GLV_OP_AVERAGE) : (unsigned) GLV_OP_GRAVITY;
-    if (int rc = refuse_gravity_mix(b, form_ops)) return rc;
-    const bool live_blob = d->kept_bins != now.n;
-    if (live_blob && (!(b->ops_mask & GLV_OP_BARS_ONLY) || b->live_bins() == 0 || b->live_bins() != d->kept_bins))
-        return fail(GLV_ERR_STATE, "glv_batch_load_streams: the blob keeps bins [0, %u) of n=%u only (a GLV_OP_BARS_ONLY batch that has run its live class): it loads into a "
-                                   "GLV_OP_BARS_ONLY batch whose glv_batch_live_bins() equals that (this batch: %u)", d->kept_bins, now.n,
-                    (b->ops_mask & GLV_OP_BARS_ONLY) ? b->live_bins() : 0u);
+    StreamsFit fit;
+    if (int rc = streams_fit(b, "glv_batch_load_streams", "the blob", d, now, &fit)) return rc;
     if (int rc = slots_launch(b, glv::SLOT_SCATTER, d_idx, count, const_cast<void*>(d_blob), (hipStream_t) hip_stream)) return rc;
-    commit_gravity_form(b, form_ops);        // (form 0: nothing to adopt)
-    if (live_blob) b->ran_live = true;
+    adopt_streams(b, fit);
+    return GLV_OK;
+}
+
+// Chosen streams from slot to slot, inside a batch or between two (include/glv_spectrum.h): the contract of save(src) + load(dst) in one launch and without the
+// blob -- load's checks with the source batch's descriptor as it is now in the blob's place, then one kernel that reads every piece where src's positions put it
+// and writes it where dst's do.
+int glv_batch_copy_streams(glv_batch* dst, const uint32_t* d_dst_idx, glv_batch* src, const uint32_t* d_src_idx, uint32_t count, void* hip_stream) {
+    static const char* const entry = "glv_batch_copy_streams";
+    if (int rc = slots_check(dst, entry, d_dst_idx, count, nullptr, false)) return rc;
+    if (int rc = slots_check(src, entry, d_src_idx, count, nullptr, false)) return rc;
+    if (dst->device != src->device)
+        return fail(GLV_ERR_INVALID, "%s: the batches live on devices %d and %d: between devices a stream travels as a blob (glv_batch_save_streams, the caller's peer copy, "
+                                     "glv_batch_load_streams)", entry, src->device, dst->device);
+    glv_stream_state_desc now, from;
+    stream_desc(dst, &now);
+    stream_desc(src, &from);
+    if (now.regions == 0 && from.regions == 0)
+        return fail(GLV_ERR_STATE, "%s: the batches keep neither state nor a ring (ops_mask 0x%x, 0x%x): a stream has nothing to copy", entry, src->ops_mask, dst->ops_mask);
+    StreamsFit fit;
+    if (int rc = streams_fit(dst, entry, "the source batch", &from, now, &fit)) return rc;
+    glv::SlotTable ts = {}, td = {};
+    stream_regions(src, true, ts);
+    stream_regions(dst, true, td);
+    ts.idx = d_src_idx; ts.count = count; td.idx = d_dst_idx; td.count = count;
+    HIP_TRY(hipSetDevice(dst->device));
+    const hipError_t e = glv::launch_slot_copy(ts, td, (hipStream_t) hip_stream);
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "stream copy launch failed: %s", hipGetErrorString(e));
+    dst->last_launches = 1; dst->kernel_name = "glv_slot_copy_kernel";
+    adopt_streams(dst, fit);
     return GLV_OK;
 }
 

@@ -284,6 +284,7 @@ struct ChainPlan {
     uint32_t wave_limit = 0;                    // WAVE: samples of a row the waveform kernel produces (what the bars sample, or n)
     const void* dec_in = nullptr;               // bufscale > 1: the caller's windows of k * n frames, which the first launch of the chain decimates into the batch's
     int dec_kind = 0;                           // staging rows (glv::DecimateKind) -- the chain is then the planar entry's on those rows
+    uint32_t dec_streams = 0;                   // ... for the streams of the call: units / 2 (all of the batch, or the prefix of a glv_batch_process_first_* call)
 };
 
 // ---- what crosses a unit boundary, in the order glv_wisdom / glv_device_state / glv_bar_tables / glv_chain.cpp (indented: tests/src_scan.py finds a DEFINITION by its return type at the start of a line) ----
@@ -309,5 +310,7 @@ struct ChainPlan {
     int process(glv_batch* b, const void* d_in, int in_mode, float* d_out, unsigned ops, uint32_t units, uint32_t rot, hipStream_t st, const void* dec_in = nullptr,
                 int dec_kind = 0);
     int process_windows(glv_batch* b, const void* d_in, int in_mode, int dec_kind, float* d_out, unsigned ops, hipStream_t st);
+    int process_first(glv_batch* b, uint32_t count, const void* d_in, int in_mode, int dec_kind, float* d_out, unsigned ops, hipStream_t st);
+    int refuse_prefix(const glv_batch* b, const char* entry, uint32_t count);
     int refuse_bufscale(const glv_batch* b, const char* entry);
 }  // namespace glvh

@@ -114,6 +114,10 @@ struct SlotTable {
 };
 constexpr size_t kSlotsGridCap = 256 * 8;          // 256 CUs x 8 resident 256-lane workgroups of 256 pieces each; the kernel's loop takes what lies beyond
 hipError_t launch_slots(int kind, const SlotTable& t, hipStream_t st);
+// ... and straight from slot to slot (glv_slot_copy_kernel; glv_batch_copy_streams): stream src.idx[j] of one batch into stream dst.idx[j] of another, or of the same
+// one -- two tables of the same regions in the same order, each with its own bases, positions and streams (blob unused), count pairs; a pair with either entry
+// >= its side's streams is skipped where it is read.  Tables that differ in a region's start, sizes, unit or ring length are refused, like every malformed one.
+hipError_t launch_slot_copy(const SlotTable& src, const SlotTable& dst, hipStream_t st);
 hipError_t launch_lerp(const float* s0, const float* e0, float* out, size_t total, float mod, hipStream_t st);
 hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin, const int* smax, uint32_t asz, uint32_t reach,
                          uint32_t max_window, hipStream_t st);

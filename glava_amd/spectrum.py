@@ -153,6 +153,12 @@ def lib() -> C.CDLL:
             L.glv_batch_reset_streams.argtypes = [vp, vp, C.c_uint32, vp]
             L.glv_batch_save_streams.argtypes = [vp, vp, C.c_uint32, vp, SD, vp]
             L.glv_batch_load_streams.argtypes = [vp, vp, C.c_uint32, vp, SD, vp]
+        if hasattr(L, "glv_batch_copy_streams"):        # (likewise: the first `count` streams of a batch only; streams copied from slot to slot)
+            for name in ("s16", "f32", "f32_stereo"):
+                getattr(L, "glv_batch_process_first_" + name).argtypes = [vp, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_ring_update_first_s16.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint, vp]
+            L.glv_batch_ring_update_first_f32.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint, vp]
+            L.glv_batch_copy_streams.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
@@ -312,6 +318,32 @@ class Batch:
         bit as the saved one would have.  desc must match the batch (n, F, element size, regions: ERR_STATE), the gravity forms must agree unless one is
         still 0, a live blob (kept_bins < n) loads only into an OP_BARS_ONLY batch with the same live_bins().  Duplicates in d_idx are the caller's error."""
         _check(lib().glv_batch_load_streams(self._h, _ptr(d_idx), count, _ptr(d_blob), C.byref(desc), _ptr(stream)))
+
+    def copy_streams(self, d_dst_idx, src: "Batch", d_src_idx, count: int, stream: int | None = None) -> None:
+        """glv_batch_copy_streams, called on the destination: stream d_dst_idx[j] of this batch continues as stream d_src_idx[j] of `src` (another batch of
+        the same kind on the same device, or this one) would have -- save_streams + load_streams in one launch, without the blob, whatever positions the two
+        batches are at.  Both tables are uint32 [count] in device memory, read when the kernel runs; pairs with an entry >= its batch's streams are skipped.
+        Within one batch a destination must not be a source of the same call, and no destination may appear twice."""
+        _check(lib().glv_batch_copy_streams(self._h, _ptr(d_dst_idx), src._h, _ptr(d_src_idx), count, _ptr(stream)))
+
+    def process_first_s16(self, count: int, d_pcm, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
+        """process_s16 on streams [0, count) as a batch of `count` streams would run it (glv_batch_process_first_s16): d_pcm and d_out are dense for `count`
+        streams, the other streams are neither read nor written.  head and the gravity form are the batch's and advance as for a full call: a stream that
+        joins the prefix later is first the target of reset_streams, load_streams or copy_streams (glava_amd.stream_slots.DensePool keeps that protocol)."""
+        _check(lib().glv_batch_process_first_s16(self._h, count, _ptr(d_pcm), _ptr(d_out), ops, _ptr(stream)))
+
+    def process_first_f32(self, count: int, d_in, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
+        _check(lib().glv_batch_process_first_f32(self._h, count, _ptr(d_in), _ptr(d_out), ops, _ptr(stream)))
+
+    def process_first_f32_stereo(self, count: int, d_in, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
+        _check(lib().glv_batch_process_first_f32_stereo(self._h, count, _ptr(d_in), _ptr(d_out), ops, _ptr(stream)))
+
+    def ring_update_first_s16(self, count: int, d_new, new_frames: int, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
+        """ring_update_s16 on streams [0, count): d_new [count][new_frames][2]; the ring position is the batch's and advances as for a full call"""
+        _check(lib().glv_batch_ring_update_first_s16(self._h, count, _ptr(d_new), new_frames, _ptr(d_out), ops, _ptr(stream)))
+
+    def ring_update_first_f32(self, count: int, d_new, new_frames: int, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
+        _check(lib().glv_batch_ring_update_first_f32(self._h, count, _ptr(d_new), new_frames, _ptr(d_out), ops, _ptr(stream)))
 
     def process_s16(self, d_pcm, d_out, ops: int = OP_FFT, stream: int | None = None) -> None:
         """one update of every stream; stream-ordered (never allocates, never copies synchronously).  Chains ending in gravity

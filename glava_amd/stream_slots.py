@@ -9,7 +9,9 @@ A blob is, in this order and present regions only (desc.regions):
     bit 2  s16 PCM ring   [n][2] int16           oldest frame first: frame q is ring frame (ring position + q) mod n
     bit 3  f32 PCM ring   [n][2] float32         likewise
 
-elements are float32 (desc.elem_bytes 4) or GL_R16 texels, uint16 (2)."""
+elements are float32 (desc.elem_bytes 4) or GL_R16 texels, uint16 (2).
+
+DensePool is the other half of a service's bookkeeping: which slots of a batch hold listeners, kept as a prefix (Batch.process_first_* / copy_streams)."""
 from __future__ import annotations
 
 import numpy as np
@@ -78,3 +80,35 @@ def unrotate(rows, pos: int, axis: int = 0):
         raise ValueError(f"pos={pos}: must be in [0, {m})")
     return np.roll(rows, -pos, axis=axis)
 
+
+class DensePool:
+    """The listeners of one batch kept dense in slots [0, active), so that every update is Batch.process_first_*(active, ...): host bookkeeping only, the
+    caller issues the device calls it names.
+
+        slot = pool.attach()            # then batch.reset_streams([slot])
+        move = pool.detach(slot)        # (src, dst): then batch.copy_streams([dst], batch, [src]); None: the slot was the last one
+        pool.grow(new_capacity)         # then new_batch.copy_streams(range(active), old_batch, range(active)): the slots keep their numbers
+
+    A listener that detach moved is now known by `dst`: the caller renames it."""
+
+    def __init__(self, capacity: int):
+        if capacity < 1:
+            raise ValueError(f"capacity={capacity}: must be >= 1")
+        self.capacity, self.active = int(capacity), 0
+
+    def attach(self) -> int:
+        if self.active == self.capacity:
+            raise IndexError(f"all {self.capacity} slots are taken: grow() first")
+        self.active += 1
+        return self.active - 1
+
+    def detach(self, slot: int):
+        if not 0 <= slot < self.active:
+            raise IndexError(f"slot={slot}: the active slots are [0, {self.active})")
+        self.active -= 1
+        return None if slot == self.active else (self.active, slot)
+
+    def grow(self, new_capacity: int) -> None:
+        if new_capacity < self.capacity:
+            raise ValueError(f"new_capacity={new_capacity}: below the capacity {self.capacity}")
+        self.capacity = int(new_capacity)

@@ -900,6 +900,46 @@ int glv_batch_reset_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count,
 int glv_batch_save_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, void* d_blob, glv_stream_state_desc* d, void* hip_stream);
 int glv_batch_load_streams(glv_batch* b, const uint32_t* d_idx, uint32_t count, const void* d_blob, const glv_stream_state_desc* d, void* hip_stream);
 
+/* Elastic batches: update the FIRST `count` streams only, and copy streams from slot to slot.  Added within ABI 7: detect them by the symbol.  A batch created
+ * for a capacity then costs what its listeners cost: join = reset slot A, A += 1; leave slot i = copy slot A - 1 into i, A -= 1; every update = process the
+ * first A streams; grow = create a larger batch, copy the A streams across, destroy the old one (glava_amd/stream_slots.py DensePool is that bookkeeping).
+ *
+ * glv_batch_process_first_s16 / _f32 / _f32_stereo, glv_batch_ring_update_first_s16 / _f32: each is the un-suffixed call of a batch that has `count` streams.
+ * Input and output have the layouts of that call at streams = count, dense and stream-major (d_pcm [count][n][2], [count][k n][2] under bufscale k; d_out
+ * [count][2][n] or what ops imply).  Streams 0 .. count - 1 get the output, bit for bit, and are left in the state of a batch created with `count` streams and fed
+ * the same inputs since its creation or reset; nothing at or behind row 2 * count of d_out is written.  Every chain, gl_storage, GLV_OP_BARS, GLV_OP_BARS_ONLY,
+ * GLV_OP_WAVE, bufscale, GLV_OP_OUTPUT_IS_STATE and glv_batch_set_grid behave as on the un-suffixed call, the same things are refused in the same words, the
+ * launches and glv_batch_last_launches are the same; each call can be captured from the first call on and allocates nothing.  count == streams is exactly the
+ * un-suffixed call.  GLV_ERR_INVALID: count == 0 or count > streams; GLV_ERR_STATE: a single-row batch.
+ * THE BATCH'S LOCKSTEP POSITIONS ADVANCE AS FOR A FULL CALL -- head, the ring positions, the gravity form and the live flag are kept per batch.  Streams >= count
+ * are neither read nor written, so their stored state stops matching the positions: it is undefined from then on.  A stream that enters the prefix later must
+ * first be the target of glv_batch_reset_streams, glv_batch_load_streams or glv_batch_copy_streams: all three write whole streams at the batch's current
+ * positions (zero state reads the same at every rotation).  The library cannot check this protocol -- which streams a call listed is device memory -- so it is
+ * the caller's to keep.
+ * Not offered in a prefix form: the track entries (a track call works on recordings, and its batch is made for the job), glv_batch_ring_append_* and
+ * glv_batch_ring_planar, the tuners (glv_batch_autotune, glv_batch_tune_placement), glv_multi.
+ *
+ * glv_batch_copy_streams: for every j < count, stream d_dst_idx[j] of dst afterwards continues exactly as stream d_src_idx[j] of src would have -- the contract
+ * of glv_batch_save_streams(src) followed by glv_batch_load_streams(dst), bit for bit in output and state, whatever head and ring positions the two batches are
+ * at, without the blob: ONE launch (glv_slot_copy_kernel; glv_batch_last_launches(dst) == 1), stream-ordered, allocates nothing, can be captured.  Both tables are
+ * uint32 [count] in device memory, read when the kernel runs (a captured copy is re-aimed by rewriting them); positions are taken when the call is enqueued.
+ * A pair with either entry >= its batch's streams is skipped where it is read, and no launch touches memory outside the two batches' state arrays whatever the
+ * tables hold.  Every other stream of both batches is untouched; src is only read.
+ * dst == src is allowed (compaction): a stream named as a destination must then not be named as a source in the same call, and no destination may appear twice,
+ * in either case -- the caller's error: the named destinations then hold unspecified contents, nothing else is touched.  A pair with equal entries leaves its
+ * stream as it was.
+ * Checked on the host before anything runs, a refused call leaves both batches as they were: glv_batch_load_streams' checks with src's descriptor as it is now
+ * (glv_batch_stream_state_desc) in the blob's place -- n, avg_frames, elem_bytes, regions; the gravity form, which dst adopts when its own is still 0; kept_bins,
+ * after which dst counts as having run its live class -- and for BOTH batches what all stream-slot calls refuse (NULL or misaligned table, count == 0, a
+ * single-row batch, GLV_OP_OUTPUT_IS_STATE in force).  GLV_ERR_INVALID: batches on different devices (between devices a stream travels as a blob and the
+ * caller's peer copy).  GLV_ERR_STATE: two batches with neither state nor ring. */
+int glv_batch_process_first_s16(glv_batch* b, uint32_t count, const int16_t* d_pcm, float* d_out, unsigned ops, void* hip_stream);
+int glv_batch_process_first_f32(glv_batch* b, uint32_t count, const float* d_f32, float* d_out, unsigned ops, void* hip_stream);
+int glv_batch_process_first_f32_stereo(glv_batch* b, uint32_t count, const float* d_pcm, float* d_out, unsigned ops, void* hip_stream);
+int glv_batch_ring_update_first_s16(glv_batch* b, uint32_t count, const int16_t* d_new, uint32_t new_frames, float* d_out, unsigned ops, void* hip_stream);
+int glv_batch_ring_update_first_f32(glv_batch* b, uint32_t count, const float* d_new, uint32_t new_frames, float* d_out, unsigned ops, void* hip_stream);
+int glv_batch_copy_streams(glv_batch* dst, const uint32_t* d_dst_idx, glv_batch* src, const uint32_t* d_src_idx, uint32_t count, void* hip_stream);
+
 /* smooth_audio() bar sampling of spectra already in HBM (d_spec float [streams][2][n]) into
  * d_bars float [streams][2][bars]; what GLV_OP_BARS runs after the transform.  Refused on a gl_storage 3 batch (GLV_ERR_STATE): there GLV_OP_BARS samples the
  * upload's texels, and caller's float rows go through a gl_storage 0 batch. */
