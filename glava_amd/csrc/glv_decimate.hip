@@ -21,7 +21,8 @@ typedef uint32_t glv_u4 __attribute__((ext_vector_type(4)));
 
 // Four consecutive frames of a lane's span, both channels.  `aligned`: the lane's first byte lies on 16 bytes, and so does every group of four frames behind
 // it (16 bytes of s16 frames, 32 of float frames, 16 of each planar row) -- 16-byte loads; else naturally aligned loads of one frame (4 bytes of s16, 8 of
-// floats) or one sample (planar).  A track window begins at any frame, so s16 recordings promise 4 bytes and float ones 8.
+// floats) or one sample (planar).  A track window begins at any frame, so s16 recordings promise 4 bytes and float ones 8.  The planar track kind's windows
+// begin at any sample of a row and the second row lies pitch_frames floats on, any number: each row takes the 16-byte load where ITS first byte lies on 16.
 template <int KIND>
 __device__ __forceinline__ void decimate_group(const void* lane, const uint64_t row_pitch, const uint32_t g, const bool aligned, const int mono, float (&l)[4], float (&r)[4]) {
     if constexpr (KIND == DEC_S16) {
@@ -56,6 +57,18 @@ __device__ __forceinline__ void decimate_group(const void* lane, const uint64_t 
     } else {
         const float* const a = static_cast<const float*>(lane) + (size_t) g * 4u;
         const float* const b = a + row_pitch;
+        if constexpr (KIND == DEC_F32_PLANAR_TRACK) {
+            if (aligned) { const glv_f4 va = *reinterpret_cast<const glv_f4*>(a); l[0] = va.x; l[1] = va.y; l[2] = va.z; l[3] = va.w; }
+            else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) l[q] = a[q];
+            }
+            if ((reinterpret_cast<uintptr_t>(b) & 15u) == 0u) { const glv_f4 vb = *reinterpret_cast<const glv_f4*>(b); r[0] = vb.x; r[1] = vb.y; r[2] = vb.z; r[3] = vb.w; }
+            else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) r[q] = b[q];
+            }
+        } else
         if (aligned) {
             const glv_f4 va = *reinterpret_cast<const glv_f4*>(a), vb = *reinterpret_cast<const glv_f4*>(b);
             l[0] = va.x; l[1] = va.y; l[2] = va.z; l[3] = va.w; r[0] = vb.x; r[1] = vb.y; r[2] = vb.z; r[3] = vb.w;
@@ -73,6 +86,8 @@ __device__ __forceinline__ void decimate_group(const void* lane, const uint64_t 
 // Bounded reads: 4 k (i + 1) <= k n and a window's start is at most start_max = pitch_frames - k n behind its stream's first frame (a table's entry is clamped
 // where it is read: track_window_start), so whatever a table holds a lane reads inside the recording of a stream < streams; the table is read in [0, steps).
 // The planar kind (a process call's lb / rb rows, [streams][2][k n]) has no table and no hop: window s is rows 2 s and 2 s + 1.
+// The planar track kind (glv_batch_track_at_f32_planar under bufscale: [streams][2][pitch_frames]) cuts window t of stream s out of rows 2 s and 2 s + 1 by the
+// interleaved kinds' rules -- the same start within each row, the same clamp, the same output row -- with no mix, as the planar kind.
 template <int KIND>
 __global__ void __launch_bounds__(256) glv_decimate_kernel(const Decimate d, const uint32_t log_quads, const uint64_t items) {
     const float fk = (float) d.k;
@@ -87,7 +102,8 @@ __global__ void __launch_bounds__(256) glv_decimate_kernel(const Decimate d, con
         else {
             const uint64_t first = track_window_start(d.w, s, t, d.w.starts ? d.w.starts[t] : 0u) + lead;      // 64-bit: a recording may pass 2^32 frames
             if constexpr (KIND == DEC_S16) lane = static_cast<const uint32_t*>(d.in) + first;
-            else lane = static_cast<const glv_f2*>(d.in) + first;
+            else if constexpr (KIND == DEC_F32) lane = static_cast<const glv_f2*>(d.in) + first;
+            else lane = static_cast<const float*>(d.in) + (first + (uint64_t) s * d.w.pitch_frames);      // (a stream is two rows of pitch_frames floats: its channel-0 row)
         }
         const bool aligned = (reinterpret_cast<uintptr_t>(lane) & 15u) == 0u;      // (planar: the second row lies k n floats on, a multiple of 16 bytes)
         float suml = 0.0f, sumr = 0.0f, outl[4], outr[4];
@@ -96,7 +112,7 @@ __global__ void __launch_bounds__(256) glv_decimate_kernel(const Decimate d, con
         uint32_t count = 0, slot = 0;
         for (uint32_t g = 0; g < d.k; ++g) {
             float l[4], r[4];
-            decimate_group<KIND>(lane, span, g, aligned, (int) d.mono, l, r);
+            decimate_group<KIND>(lane, KIND == DEC_F32_PLANAR_TRACK ? d.w.pitch_frames : span, g, aligned, (int) d.mono, l, r);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 suml = suml + l[q]; sumr = sumr + r[q];                      // render.c:1774, in index order
@@ -129,6 +145,7 @@ hipError_t launch_decimate(int kind, const Decimate& d, hipStream_t st) {
     if (kind == DEC_S16) hipLaunchKernelGGL((glv_decimate_kernel<DEC_S16>), dim3(grid), dim3(256), 0, st, d, log_quads, items);
     else if (kind == DEC_F32) hipLaunchKernelGGL((glv_decimate_kernel<DEC_F32>), dim3(grid), dim3(256), 0, st, d, log_quads, items);
     else if (kind == DEC_F32_PLANAR) hipLaunchKernelGGL((glv_decimate_kernel<DEC_F32_PLANAR>), dim3(grid), dim3(256), 0, st, d, log_quads, items);
+    else if (kind == DEC_F32_PLANAR_TRACK) hipLaunchKernelGGL((glv_decimate_kernel<DEC_F32_PLANAR_TRACK>), dim3(grid), dim3(256), 0, st, d, log_quads, items);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

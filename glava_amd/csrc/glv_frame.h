@@ -29,8 +29,13 @@ enum InMode { IN_S16_STEREO = 0, IN_F32_PLANAR = 1, IN_S16_RING = 2, IN_F32_STER
 // Kinds of their own, not a run-time branch on a null table: the branch folded into the hop kinds gave 45 of the 120 IN_S16_TRACK kernels scratch they had not had
 // (N = 1024: 68-80 bytes a lane; N = 16384 / 32768: 180-224), so those stay byte for byte what they were and the table is a template constant.
 constexpr int IN_S16_TRACK_AT = 7, IN_F32_TRACK_AT = 8;
-constexpr int kFrameKinds = 9;       // every IN_MODE glv_frame_kernel is instantiated for: InMode and the table kinds
-GLV_HD constexpr bool in_track_table(int in_mode) { return in_mode == IN_S16_TRACK_AT || in_mode == IN_F32_TRACK_AT; }
+constexpr int kFrameKinds = 9;       // every IN_MODE glv_frame_kernel is instantiated for: InMode and the table kinds of interleaved recordings
+// The table kind of a PLANAR float recording (glv_batch_track_at_f32_planar): float [streams][2][pitch_frames], the lb / rb rows of glv_batch_process_f32 as one
+// long buffer -- the IN_F32_PLANAR pipeline over channel rows with TrackWindows' address per frame, the two rows of a stream pitch_frames floats apart and taken
+// as they are (no mono mix: the backend mixed them).  A table kind only: there is no hop kind, the host plans it as IN_F32_PLANAR.
+constexpr int IN_F32_PLANAR_TRACK_AT = kFrameKinds;
+constexpr int kPlanarTrackKinds = 1; // ... numbered behind kFrameKinds: [kFrameKinds, kFrameKinds + kPlanarTrackKinds) are instantiated too
+GLV_HD constexpr bool in_track_table(int in_mode) { return in_mode == IN_S16_TRACK_AT || in_mode == IN_F32_TRACK_AT || in_mode == IN_F32_PLANAR_TRACK_AT; }
 enum Epi { EPI_RAW = 0, EPI_MAG = 1, EPI_MAG_STATE = 2, EPI_RAW_STATE = 3 };
 
 // ops bits as in include/glv_spectrum.h
@@ -901,6 +906,32 @@ struct Frame {
     GLV_HD static void load_f32_raw(RawF& r, const void* row, int tid) {
 #pragma unroll
         for (int i = 0; i < E; ++i) r.p[i] = ld<cf>(row, (uint32_t) tid * 8u + (uint32_t) (i * T) * 8u);
+    }
+    // IN_F32_PLANAR_TRACK_AT: a window starts at ANY sample of a planar row, so its first byte is 4-byte aligned and no more (and the two rows of a stream
+    // differ in alignment where pitch_frames is odd).  A lane's unit is complex point c = samples (2c, 2c + 1) of ONE row, 8 bytes: a window whose first byte
+    // is 8-byte aligned takes the 8-byte loads of a back-to-back row, any other the point's two naturally aligned dwords -- IN_F32_TRACK's rule (below) with the
+    // sizes of this layout (wider loads would hand a lane points it does not own).  The choice is per window: uniform where a wave never straddles two slots
+    // (T % 64 == 0), a divergent branch at N = 256 / 512.  Either way the lane reads bytes [8 c, 8 c + 8) of the window, c < NN: exactly the window's n samples.
+    GLV_HD static void load_f32_raw_at(RawF& r, const void* window, int tid) {
+        if ((reinterpret_cast<uintptr_t>(window) & 7u) == 0u) { load_f32_raw(r, window, tid); return; }
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const uint32_t off = (uint32_t) tid * 8u + (uint32_t) (i * T) * 8u;
+            r.p[i].x = ld<float>(window, off);
+            r.p[i].y = ld<float>(window, off + 4u);
+        }
+    }
+    // ... and the loop that is not pipelined: load_f32_window with the same choice
+    GLV_HD static void load_f32_window_at(cf (&v)[E], const void* window, const void* win, int tid) {
+        if ((reinterpret_cast<uintptr_t>(window) & 7u) == 0u) { load_f32_window(v, window, win, tid); return; }
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const uint32_t off = (uint32_t) tid * 8u + (uint32_t) (i * T) * 8u;
+            const float x = ld<float>(window, off), y = ld<float>(window, off + 4u);
+            const d2 w = ld<d2>(win, (uint32_t) tid * 16u + (uint32_t) (i * T) * 16u);
+            v[i].x = apply_window(x, w.x);
+            v[i].y = apply_window(y, w.y);
+        }
     }
     // window table reads in chunks of WCHUNK like unpack_window_impl
     template <typename GET>

@@ -207,6 +207,7 @@ glv_frame_kernel(const FrameArgs a) {
     constexpr bool TRACK_TABLE = in_track_table(IN_MODE);   // a table call's kinds: the window's start comes from a.trk.starts (track_entry / track_at below)
     constexpr bool TRACK = IN_MODE == IN_S16_TRACK || IN_MODE == IN_S16_TRACK_AT;    // windows where they lie in a recording (a.trk): never a ring, stateless classes only (launch_variant)
     constexpr bool TRACKF = IN_MODE == IN_F32_TRACK || IN_MODE == IN_F32_TRACK_AT;   // the same over interleaved stereo f32 recordings: the f32 stereo pipeline and generic loop, another address per frame
+    constexpr bool TRACKP = IN_MODE == IN_F32_PLANAR_TRACK_AT;                       // the same over planar float recordings, a table kind only: the planar pipeline over rows and the generic loop, another address per row
     constexpr bool S16 = IN_MODE == IN_S16_STEREO || RING || TRACK;
     constexpr bool WSPLIT = S16 && win_split_of(LOG_NN, STATEFUL);     // s16 samples: the window product without fp64 (glv_core.h apply_window_split)
     // f32 rows may hold -0.0, Inf and NaN: no unit-twiddle shortcut, non-finite values through the bit-faithful log
@@ -461,9 +462,18 @@ glv_frame_kernel(const FrameArgs a) {
         uint64_t start;
         if constexpr (TRACK_TABLE) start = (uint64_t) s * a.trk.pitch_frames + (entry < a.trk.start_max ? entry : a.trk.start_max);      // (track_window_start with a table)
         else start = (uint64_t) s * a.trk.pitch_frames + (uint64_t) t * a.trk.hop;
+        if constexpr (TRACKP) start += (uint64_t) s * a.trk.pitch_frames;      // planar: a stream is TWO rows of pitch_frames floats, and this is where its channel-0 window begins
         return { static_cast<const char*>(a.in) + start * (TRACKF ? 8u : 4u), a.trk.step_major ? ((size_t) t * a.trk.streams + s) * 2u : (size_t) f * 2u };
     };
     (void) track_at; (void) track_entry;
+    // IN_F32_PLANAR_TRACK_AT: one slot = one channel ROW, as in the planar pipeline.  Row r of the launch is channel r & 1 of frame f = r >> 1, so track_at's rules
+    // hold with f < units / 2 (row_of clamps an idle slot and every look-ahead to the last row): the window of channel ch begins pitch_frames floats behind
+    // channel 0's, inside row 2 s + ch of the recording -- the clamp to start_max = pitch_frames - n keeps its n floats there, whatever the table holds.
+    auto track_row_at = [&](uint32_t row, uint32_t entry) -> TrackAt {
+        const TrackAt w = track_at(row >> 1, entry);
+        return { static_cast<const char*>(w.win) + (uint64_t) (row & 1u) * a.trk.pitch_frames * 4u, w.row0 + (row & 1u) };
+    };
+    (void) track_row_at;
 
     unsigned xcount = 0;
     // A workgroup with a single slot takes both channel rows of a frame back to back (SEQ = 2), so
@@ -573,6 +583,45 @@ glv_frame_kernel(const FrameArgs a) {
         }
         return;
     }
+    if constexpr (TRACKP && PREFETCH == 1 && LOG_E <= 4) {
+        // planar float recordings: the pipeline above with each row's window where the table says.  The entry of a row is asked for one step AHEAD of the address
+        // that uses it (stage A of the step before, retired by W), as the interleaved table kinds do per frame: no load an address depends on follows stores.
+        auto row_ahead = [&](uint32_t step, uint32_t base) -> uint32_t {      // the row the slot takes `step` steps in, or its current one beyond the last
+            const uint32_t nb = step_base(step);
+            return row_of(step < nsteps && nb < a.units ? nb : base);
+        };
+        cf v[E];
+        typename FR::RawF raw;
+        size_t trow = 0, trow_next = 0;      // where the slot's current row goes / the row whose samples `raw` holds
+        uint32_t tent = 0;                   // the table's entry for the row the NEXT stage A fetches
+        if (step_base(0) < a.units) {
+            int tid = tid_outer;
+            asm volatile("" : "+v"(tid));
+            const uint32_t r0 = row_of(step_base(0));
+            const TrackAt w = track_row_at(r0, track_entry(r0 >> 1)); FR::load_f32_raw_at(raw, w.win, tid); trow = w.row0;
+            tent = track_entry(row_ahead(1, step_base(0)) >> 1);
+            FR::window_f32_raw(v, raw, win, tid);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        for (uint32_t step = 0; step < nsteps; ++step) {
+            const uint32_t base = step_base(step);
+            if (base >= a.units) break;                          // uniform for the workgroup
+            int tid = tid_outer;
+            asm volatile("" : "+v"(tid));
+            const bool active = base + slot < a.units;
+            const TrackAt w = track_row_at(row_ahead(step + 1, base), tent);
+            FR::load_f32_raw_at(raw, w.win, tid); trow_next = w.row0;                            // A (unconditional)
+            tent = track_entry(row_ahead(step + 2, base) >> 1);                                  // (the entry of the row after: W retires it)
+            GLV_SCHED_FENCE();
+            BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);                    // B
+            GLV_SCHED_FENCE();
+            __builtin_amdgcn_s_waitcnt(0x0F70);                                                  // W
+            finish_row(v, trow, tid, active); trow = trow_next;                                  // D
+            GLV_SCHED_FENCE();
+            FR::window_f32_raw(v, raw, win, tid);                                                // C
+        }
+        return;
+    }
     constexpr bool F32S = IN_MODE == IN_F32_STEREO || IN_MODE == IN_F32_RING || TRACKF;
     constexpr bool RINGF = IN_MODE == IN_F32_RING;
     if constexpr (F32S && PREFETCH == 1 && LOG_E <= 4) {
@@ -659,6 +708,14 @@ glv_frame_kernel(const FrameArgs a) {
             FR::load_f32_stereo_window_at(v, w.win, win, tid, row & 1u, a.mono != 0);
             BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
             finish_row(v, w.row0 + (row & 1u), tid, active);
+            continue;
+        } else
+        if constexpr (TRACKP) {
+            // every chain where the configuration is not pipelined for f32 (LOG_E 5): one slot = one channel row, read where its frame's entry says
+            const TrackAt w = track_row_at(row, track_entry(row >> 1));
+            FR::load_f32_window_at(v, w.win, win, tid);
+            BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
+            finish_row(v, w.row0, tid, active);
             continue;
         } else
         if constexpr (S16) {

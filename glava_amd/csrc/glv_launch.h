@@ -76,10 +76,14 @@ struct WaveWindows {
     uint32_t units = 0, steps = 0, hop = 0, by_steps = 0;
     uint64_t pitch_frames = 0;
     const uint32_t* starts = nullptr;
-    uint32_t start_max = 0, pad = 0;
+    uint32_t start_max = 0, planar = 0;      // planar (the f32 kinds of a table call only): the recordings are float [streams][2][pitch_frames], channel rows apart, taken as they are
 };
+// (planar: the result counts floats into row 2 s of the recording, whose sibling 2 s + 1 lies pitch_frames floats on -- wave_planar_start)
 GLV_HD constexpr uint64_t wave_window_start(const WaveWindows& w, uint32_t s, uint32_t t, uint32_t entry = 0) {
     return (uint64_t) s * w.pitch_frames + (w.starts ? (uint64_t) (entry < w.start_max ? entry : w.start_max) : (uint64_t) t * w.hop);
+}
+GLV_HD constexpr uint64_t wave_planar_start(const WaveWindows& w, uint32_t s, uint32_t t, uint32_t entry) {
+    return wave_window_start(w, s, t, entry) + (uint64_t) s * w.pitch_frames;
 }
 hipError_t launch_bufscale(const float* in, float* out, size_t total_out, uint32_t k, hipStream_t st);
 // `setbufscale k` on the batched layer (glv_decimate.hip; glv_batch_set_bufscale): every window of a call is k * n frames and becomes a pair of planar float rows
@@ -88,7 +92,8 @@ hipError_t launch_bufscale(const float* in, float* out, size_t total_out, uint32
 // The interleaved kinds cut their windows out of [streams][pitch_frames][2] recordings by TrackWindows' rules with k n in the place of n: window t of stream s
 // begins track_window_start(w, s, t, starts[t]) frames in, w.start_max = w.pitch_frames - k n where a table is set, and its rows go to row
 // track_window_row(w, s, t) of `out` -- where the transform that reads them as IN_F32_PLANAR writes its own.  A process call: steps 1, hop 0, pitch k n.
-enum DecimateKind { DEC_S16 = 0, DEC_F32 = 1, DEC_F32_PLANAR = 2 };
+// ... and a track call's planar recording float [streams][2][pitch_frames] (no mix either): the interleaved kinds' windows, cut out of rows 2 s and 2 s + 1
+enum DecimateKind { DEC_S16 = 0, DEC_F32 = 1, DEC_F32_PLANAR = 2, DEC_F32_PLANAR_TRACK = 3 };
 struct Decimate {
     const void* in; float* out;
     uint32_t n, k, mono, pad;

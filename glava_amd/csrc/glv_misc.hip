@@ -228,6 +228,9 @@ typedef unsigned int glv_wave_u4 __attribute__((ext_vector_type(4)));
 // frames are dwords, so a group whose first frame is not 16-byte aligned takes its 8 frames one naturally aligned dword at a time.
 // KIND 4 (glv_batch_track_wave_f32): KIND 1's unpack over the same windows of float recordings, 8 bytes per frame.  A group's first frame is 8-byte
 // aligned and no more: 16-byte aligned it takes KIND 1's four 16-byte loads, otherwise its 8 frames one naturally aligned 8-byte load at a time.
+// KIND 5 (glv_batch_track_at_f32_planar): the same windows of PLANAR float recordings, float [streams][2][pitch_frames] (WaveWindows::planar) -- KIND 2's rows taken
+// as they are, no mix, each channel's 8 samples from its own row: two 16-byte loads where the group's first float of THAT row lies on 16 bytes, else 8 dwords
+// (a window begins at any sample and pitch_frames is any number, so the two rows of a stream may differ).  Bounded as KIND 3 and 4, within row 2 stream + c.
 // Bounded reads (KIND 3 and 4): s < steps * streams and t + 8 <= limit <= n, so a lane reads frames [t, t + 8) of a window the call names and no others.
 // A table call (WaveWindows::starts): the window of step t' begins min(starts[t'], pitch_frames - n) frames into the recording -- one lookup per lane and group
 // of 8 frames, t' < steps, from a table that sits in L2; the clamp keeps the window inside the recording whatever the table holds.
@@ -307,6 +310,22 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
             }
             emit(2 * s, t, l);
             emit(2 * s + 1, t, r);
+        } else if constexpr (KIND == 5) {
+            const uint32_t streams = w.units / 2u;
+            const uint32_t step = (uint32_t) (s / streams);
+            const float* src = static_cast<const float*>(in) + (wave_planar_start(w, (uint32_t) (s % streams), step, w.starts ? w.starts[step] : 0u) + t);
+#pragma unroll
+            for (uint32_t c = 0; c < 2u; ++c, src += w.pitch_frames) {     // channel c of the group: the same 8 samples of the row pitch_frames floats on
+                float x[8];
+                if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+                    const BarW4 a = ld<BarW4>(src, 0u), b = ld<BarW4>(src, 16u);
+                    x[0] = a.w[0]; x[1] = a.w[1]; x[2] = a.w[2]; x[3] = a.w[3]; x[4] = b.w[0]; x[5] = b.w[1]; x[6] = b.w[2]; x[7] = b.w[3];
+                } else {
+#pragma unroll
+                    for (uint32_t q = 0; q < 8; ++q) x[q] = src[q];
+                }
+                emit(2 * s + c, t, x);
+            }
         } else {
             float l[8], r[8];
             const bool whole = (rot & 7u) == 0u;                         // (uniform) bin and rot multiples of 8: the group does not wrap
@@ -604,6 +623,12 @@ hipError_t launch_wave_track(const void* pcm, bool f32, const WaveWindows& w, bo
     if (limit == 0 || limit > n || (limit & 7u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || (w.hop == 0 && !w.starts)) return hipErrorInvalidValue;
     const size_t total = (size_t) w.steps * (w.units / 2u) * (limit / 8u);
     const unsigned grid = grid_256(total);
+    if (w.planar) {
+        if (!f32 || !w.starts) return hipErrorInvalidValue;      // (planar float rows, a table call's only)
+        if (r16) hipLaunchKernelGGL((glv_wave_kernel<5, true>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, 0, w);
+        else hipLaunchKernelGGL((glv_wave_kernel<5, false>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, 0, w);
+        return hipGetLastError();
+    }
     if (f32) {
         if (r16) hipLaunchKernelGGL((glv_wave_kernel<4, true>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);
         else hipLaunchKernelGGL((glv_wave_kernel<4, false>), dim3(grid), dim3(256), 0, st, pcm, out, total, n, limit, 0u, mono ? 1 : 0, w);

@@ -29,12 +29,21 @@ namespace {
 // glv_decimate_kernel writes every window's decimated rows, steps * streams * 2 rows of n floats, into a region in FRONT of the workspace's others (TrackPlan::dec_bytes),
 // each at the row index the transform's result takes, and the stateless transform runs once over them as IN_F32_PLANAR -- and the stages behind it see no difference.
 // The residue form (whose trick rests on back-to-back windows of n frames) and the wave forms refuse such a batch.
+// What a recording holds, the one thing an entry adds to its plan: s16 frames, interleaved stereo float frames, or planar float rows float [streams][2][pitch_frames]
+// (the _f32_planar entries: table calls only).  True where it holds floats, so `f32 ? ... : ...` reads as it did while this was a boolean; a bool converts.
+struct TrackInput {
+    enum Kind { S16 = 0, F32 = 1, F32_PLANAR = 2 } kind;
+    TrackInput(bool f32 = false) : kind(f32 ? F32 : S16) {}
+    TrackInput(Kind k) : kind(k) {}
+    explicit operator bool() const { return kind != S16; }
+    bool planar() const { return kind == F32_PLANAR; }
+};
 struct TrackPlan {
     uint32_t q = 0, log_q = 0;          // residue launches
     uint64_t frames = 0;                // frames of the sequence the windows cover: the last window of the last stream ends here
     uint64_t k0 = 0;                    // windows of launch 0 (launch r: (frames - r * hop) / n, k0 or k0 - 1)
     bool windows = false;               // stage (1) is the one launch over the windows where they lie, else the q residue launches
-    bool f32 = false;                   // the recording is interleaved stereo f32 (8 bytes per frame), else s16; set by the entry, windows form only
+    TrackInput f32;                     // the recording is interleaved stereo f32 (8 bytes per frame) or planar f32 rows (f32.planar()), else s16; set by the entry, windows form only
     bool to_out = false;                // stage (1) writes d_out and nothing else runs, else it writes the start of the workspace
     bool scan = false;                  // stage (2) runs: the chain keeps state, or stage (1) left residues (which only the scan puts in step order)
     uint32_t hops_per_pitch = 0, residue_rows = 0;   // TrackGeometry, with log_q: where the scan finds window t of stream s among stage (1)'s rows
@@ -240,9 +249,10 @@ int plan_track_frames(const glv_batch* b, uint32_t pitch_frames, uint32_t steps,
     return plan_track_at(b, pitch_frames, 0u, steps, ops, tp);
 }
 
-int refuse_track_pointers(const void* d_pcm, bool f32, const void* d_out, const void* d_work) {
+int refuse_track_pointers(const void* d_pcm, TrackInput f32, const void* d_out, const void* d_work) {
     if (!d_pcm || !d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
-    if (f32 && (reinterpret_cast<uintptr_t>(d_pcm) & 7u)) return fail(GLV_ERR_INVALID, "d_pcm must be aligned like a float frame: 8 bytes");
+    if (f32.planar()) { if (reinterpret_cast<uintptr_t>(d_pcm) & 3u) return fail(GLV_ERR_INVALID, "d_rows must be aligned like a float: 4 bytes"); }
+    else if (f32 && (reinterpret_cast<uintptr_t>(d_pcm) & 7u)) return fail(GLV_ERR_INVALID, "d_pcm must be aligned like a float frame: 8 bytes");
     if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
     return GLV_OK;
 }
@@ -273,10 +283,11 @@ int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::Fra
     a.trk.pad = 0; a.trk.starts = tp.starts; a.trk.start_max = pitch_frames - b->p.n * b->bufscale; a.trk.pad2 = 0;      // (both plans' pitch rule: pitch_frames >= a window)
     int hop_mode = tp.f32 ? glv::IN_F32_TRACK : glv::IN_S16_TRACK;
     int mode = !tp.starts ? hop_mode : tp.f32 ? glv::IN_F32_TRACK_AT : glv::IN_S16_TRACK_AT;      // a table call: the kernel kinds that read it, planned as the hop kinds
+    if (tp.f32.planar()) { hop_mode = glv::IN_F32_PLANAR; mode = glv::IN_F32_PLANAR_TRACK_AT; }      // planar rows (a table call: track_at): the planar pipeline's plan and wisdom
     if (dec) {
         glv::Decimate d = {};
-        d.in = d_pcm; d.out = dec; d.n = b->p.n; d.k = b->bufscale; d.mono = b->p.channels == 1 ? 1u : 0u; d.w = a.trk;
-        const hipError_t e = glv::launch_decimate(tp.f32 ? glv::DEC_F32 : glv::DEC_S16, d, st); ++b->last_launches;
+        d.in = d_pcm; d.out = dec; d.n = b->p.n; d.k = b->bufscale; d.mono = b->p.channels == 1 && !tp.f32.planar() ? 1u : 0u; d.w = a.trk;      // (planar rows are taken as they are)
+        const hipError_t e = glv::launch_decimate(tp.f32.planar() ? glv::DEC_F32_PLANAR_TRACK : tp.f32 ? glv::DEC_F32 : glv::DEC_S16, d, st); ++b->last_launches;
         if (e != hipSuccess) return fail(GLV_ERR_HIP, "bufscale launch failed: %s", hipGetErrorString(e));
         a.in = dec; hop_mode = mode = glv::IN_F32_PLANAR;      // row r of the region becomes row r of `rows`: the index the windows kinds give window (s, t)
     }
@@ -385,7 +396,7 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
 // plan_wave's own choices (track and process cannot disagree); the rows between two launches live in the caller's workspace, not in the scratch rows
 // (sized for one update).
 struct TrackWavePlan {
-    bool f32 = false;               // the recording is interleaved stereo f32, else s16; set before the plan is made (the sizing query's is s16: the same bytes)
+    TrackInput f32;                 // the recording is interleaved stereo f32 or planar f32 rows, else s16; set before the plan is made (the sizing query's is s16: the same bytes)
     bool at = false;                // the windows lie where a table in device memory says (glv_batch_track_at_s16 / _f32); set before the plan is made
     ChainPlan pl;                   // the one or two launches of windows that start at any frame
     bool one_launch = false;        // with bars: plan_wave fuses where hop and pitch keep every window on a group of 8 frames -- of a 32-byte aligned d_pcm, which
@@ -436,20 +447,20 @@ int plan_track_wave(const glv_batch* b, uint32_t pitch_frames, uint32_t hop, uin
 // workspace in the format and up to the limit plan_wave chose for the waveform kernel's rows -- then the keyframes the next call starts from.
 int track_wave_frames(glv_batch* b, const TrackWavePlan& tp, const void* d_pcm, const glv::WaveWindows& w, void* rows, hipStream_t st) {
     const glv_track_frames& fr = *tp.render;
-    const bool mono = b->p.channels == 1;
+    const bool mono = b->p.channels == 1 && !w.planar;
     glv::WaveFrames t;
     t.from = fr.d_from; t.to = fr.d_to; t.mod = fr.d_mod; t.keys = fr.d_keys; t.out = rows;
     t.frames = fr.frames; t.n = b->p.n; t.limit = (tp.pl.wave_limit + 3u) & ~3u;      // (a lane owns four frames; n is a multiple of 4)
     t.segment = b->track_frames_segment != 0 ? b->track_frames_segment : glv::track_frames_segment(t.frames, b->streams, t.limit);
-    hipError_t e = glv::launch_wave_frames(d_pcm, tp.f32, w, mono, t, tp.pl.wave_r16, st); ++b->last_launches;
+    hipError_t e = glv::launch_wave_frames(d_pcm, (bool) tp.f32, w, mono, t, tp.pl.wave_r16, st); ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "frames launch failed: %s", hipGetErrorString(e));
-    e = glv::launch_wave_keys(d_pcm, tp.f32, w, mono, fr.d_keys, t.n, fr.keep_from, fr.keep_to, st); ++b->last_launches;
+    e = glv::launch_wave_keys(d_pcm, (bool) tp.f32, w, mono, fr.d_keys, t.n, fr.keep_from, fr.keep_to, st); ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "keyframe write-back launch failed: %s", hipGetErrorString(e));
     return GLV_OK;
 }
 // fr: the render frames of a frames call (track_frames_call has vetted them; a table call, so d_starts is set); nullptr: every other call
 // d_starts: the table of a table call (its entry has vetted the pointer), and `hop` is not looked at; nullptr: every `hop` frames
-int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
+int track_wave(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
                const glv_track_frames* fr = nullptr, const uint32_t* d_starts = nullptr) {
     if (int rc = refuse_track_pointers(d_pcm, f32, d_out, d_work)) return rc;
     TrackWavePlan tp;
@@ -459,10 +470,10 @@ int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames,
     const bool fused = tp.one_launch && (reinterpret_cast<uintptr_t>(d_pcm) & 31u) == 0u;
     b->last_launches = 0;
     HIP_TRY(hipSetDevice(b->device));
-    const bool mono = b->p.channels == 1, r16 = (ops & GLV_OP_R16) != 0;
+    const bool mono = b->p.channels == 1 && !f32.planar(), r16 = (ops & GLV_OP_R16) != 0;      // (planar rows are taken as they are)
     glv::WaveWindows w;
     w.units = b->streams * 2u; w.steps = steps; w.hop = hop; w.pitch_frames = pitch_frames;
-    w.starts = d_starts; w.start_max = pitch_frames - b->p.n;
+    w.starts = d_starts; w.start_max = pitch_frames - b->p.n; w.planar = f32.planar() ? 1u : 0u;
     // (a store's 32-bit lane offset spans 4 rows of the workgroup: `units` rows apart by steps)
     w.by_steps = b->track_wave_by_steps && (4ull * w.units + 2u) * b->p.bars * 4u <= 0xffffffffull ? 1u : 0u;
     if (int rc = timed_launch_begin(b, st)) return rc;
@@ -482,7 +493,7 @@ int track_wave(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames,
     } else {
         if (ops & GLV_OP_BARS) pl.out = pl.rows = static_cast<float*>(d_work);
         else pl.out = static_cast<float*>(d_out);
-        e = glv::launch_wave_track(d_pcm, f32, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
+        e = glv::launch_wave_track(d_pcm, (bool) f32, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
         b->kernel_name = "glv_wave_kernel";
     }
     ++b->last_launches;
@@ -507,7 +518,7 @@ uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, ui
 // glv_batch_track_at_s16 / _f32: the table's own refusals, then the form the ops and the batch select -- the wave form's executor, or the FFT forms'.
 // d_ur: the second table of a rates call (track_rates has vetted it, and that the ops have the gravity that reads it); nullptr: the batch's own ur
 // fr: the render frames of a frames call (track_frames_call has vetted them and the ops); nullptr: every other call
-int track_at(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
+int track_at(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
              const glv_track_frames* fr = nullptr, const float* d_ur = nullptr) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_starts) return fail(GLV_ERR_INVALID, "NULL device pointer");
@@ -521,7 +532,7 @@ int track_at(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, c
 }
 // glv_batch_track_rates_s16 / _f32: the rate table's own refusals, then the table call.  The wave form keeps no state and applies no gravity, and a chain
 // without gravity would leave the table unread: both are the caller's mistake, not a call that quietly ignores an argument.
-int track_rates(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
+int track_rates(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
                 unsigned ops, hipStream_t st, const glv_track_frames* fr = nullptr) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_ur) return fail(GLV_ERR_INVALID, "NULL device pointer");
@@ -533,7 +544,7 @@ int track_rates(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames
 // glv_batch_track_frames_s16 / _f32: what can be said of the frames without the batch's plan -- the pointers and the pair of keyframes kept -- then the rates call
 // or the table call with the frames handed on.  Nothing here launches; a refusal below (plan_track_frames, the table call's own) leaves the batch as untouched.
 // wave: the entry is the wave form (glv_batch_track_wave_frames_s16 / _f32), whose keyframes are read from the recording -- the table call's wave executor, no rates
-int track_frames_call(glv_batch* b, const void* d_pcm, bool f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, const glv_track_frames* fr,
+int track_frames_call(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, const glv_track_frames* fr,
                       void* d_out, void* d_work, unsigned ops, hipStream_t st, bool wave = false) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!fr) return fail(GLV_ERR_INVALID, "fr is NULL");
@@ -666,6 +677,12 @@ int glv_batch_track_at_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_fram
     return track_at(b, d_pcm, true, pitch_frames, d_starts, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
+// From a planar float recording, float [streams][2][pitch_frames]: the table call with the recording's type and nothing else (sized by glv_batch_track_at_work_bytes)
+int glv_batch_track_at_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work,
+                                  unsigned ops, void* hip_stream) {
+    return track_at(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, d_starts, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
 // (sized by glv_batch_track_at_work_bytes: the rate table adds no region.  d_where is the header's d_starts, handed on whole: tests/test_track_at_host.py pins
 // every entry named glv_batch_track_<form>_s16 / _f32 other than the `at` pair to a body that names no table of starts)
 int glv_batch_track_rates_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
@@ -676,6 +693,11 @@ int glv_batch_track_rates_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch
 int glv_batch_track_rates_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out, void* d_work,
                               unsigned ops, void* hip_stream) {
     return track_rates(b, d_pcm, true, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_rates_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out,
+                                     void* d_work, unsigned ops, void* hip_stream) {
+    return track_rates(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 // (one query for glv_batch_track_frames_s16 and _f32: the table call's regions with float rows in both, and with bars the frames' texel rows behind them; asked, like
@@ -703,6 +725,11 @@ int glv_batch_track_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_
     return track_frames_call(b, d_pcm, true, pitch_frames, d_where, d_ur, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
+int glv_batch_track_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps,
+                                      const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_frames_call(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, d_where, d_ur, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
 // (one query for glv_batch_track_wave_frames_s16 and _f32: 256 without bars, else the frames' rows in the format plan_wave gives the bars kernel; asked, like
 // glv_batch_track_at_work_bytes, with the shortest recording a call takes)
 uint64_t glv_batch_track_wave_frames_work_bytes(const glv_batch* b, uint32_t steps, uint32_t frames, unsigned ops) {
@@ -726,5 +753,10 @@ int glv_batch_track_wave_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t
 int glv_batch_track_wave_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
                                     void* d_out, void* d_work, unsigned ops, void* hip_stream) {
     return track_frames_call(b, d_pcm, true, pitch_frames, d_where, nullptr, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream, true);
+}
+
+int glv_batch_track_wave_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
+                                           void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_frames_call(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, d_where, nullptr, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream, true);
 }
 }  // extern "C"

@@ -6,6 +6,7 @@
 // ... and of a wave track call on any gl_storage (glv_batch_track_wave_frames_s16 / _f32), whose keyframes are read from the recording:
 //   glv_wave_frames_kernel    the same frame from keyframes (u + 1.0F) / 2.0F of the unpacked window of step k - 2 (render.c:777-778), as texels or their floats
 //   glv_wave_keys_kernel      the same write-back, as floats
+//   glv_wave_frames_planar_kernel / glv_wave_keys_planar_kernel   both from a planar float recording (glv_batch_track_wave_frames_f32_planar)
 #include <hip/hip_runtime.h>
 
 #include "glv_core.h"
@@ -135,7 +136,10 @@ hipError_t launch_track_keys(float* keys, const float* rows, uint32_t units, uin
 typedef float glv_f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t glv_u4 __attribute__((ext_vector_type(4)));
 
-template <bool F32_IN>
+// KIND: 0 s16 frames, 1 interleaved float frames (the kernels' F32_IN), 2 planar float rows [streams][2][pitch_frames] (WaveWindows::planar;
+// glv_batch_track_wave_frames_f32_planar): a lane's four frames of a channel are 16 contiguous bytes of that channel's row, taken as they are -- one 16-byte load
+// where they begin on 16 bytes, four dwords else, each row by its own address (pitch_frames is any number).
+template <int KIND>
 __device__ __forceinline__ void wave_key(const void* pcm, const WaveWindows& w, const int mono, const float* keys, const uint32_t n, const uint32_t k,
                                          const uint32_t stream, const uint32_t i, glv_f4& l, glv_f4& r) {
     if (k < 2u) {
@@ -147,7 +151,20 @@ __device__ __forceinline__ void wave_key(const void* pcm, const WaveWindows& w, 
     const uint32_t step = k - 2u;                                               // (< steps: k was clamped to steps + 1)
     const uint64_t first = wave_window_start(w, stream, step, w.starts[step]) + i;      // the lane's first frame, in 64-bit arithmetic
     float a[4], b[4];
-    if constexpr (F32_IN) {
+    if constexpr (KIND == 2) {
+        const float* const src = static_cast<const float*>(pcm) + (first + (uint64_t) stream * w.pitch_frames);      // (a stream is two rows: its channel-0 row)
+        const float* const sib = src + w.pitch_frames;
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) { const glv_f4 v = *reinterpret_cast<const glv_f4*>(src); a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w; }
+        else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[q] = src[q];
+        }
+        if ((reinterpret_cast<uintptr_t>(sib) & 15u) == 0u) { const glv_f4 v = *reinterpret_cast<const glv_f4*>(sib); b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w; }
+        else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = sib[q];
+        }
+    } else if constexpr (KIND == 1) {
         const glv_f2* const src = static_cast<const glv_f2*>(pcm) + first;
         glv_f2 f[4];
         if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
@@ -256,6 +273,77 @@ __global__ void __launch_bounds__(256) glv_wave_keys_kernel(const void* pcm, con
     }
 }
 
+// The planar kinds of both kernels (glv_batch_track_wave_frames_f32_planar): glv_wave_frames_kernel's walk and glv_wave_keys_kernel's write-back over wave_key<2>, word for
+// word -- kernels of their own, so that the s16 and float kinds above keep their names and their code (the kinds are template constants, and a third value of a bool
+// is another symbol).  `mono` is handed on and never read: planar rows are taken as they are.
+template <bool R16_OUT>
+__global__ void __launch_bounds__(kFramesLanes) glv_wave_frames_planar_kernel(const void* pcm, const WaveWindows w, const int mono, const WaveFrames t, const uint32_t groups,
+                                                                       const uint64_t items) {
+    const uint32_t last_key = w.steps + 1u;
+    const uint32_t streams = w.units / 2u;
+    for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const uint32_t group = (uint32_t) (item % groups);
+        const uint64_t rest = item / groups;
+        const uint32_t stream = (uint32_t) (rest % streams);
+        const uint32_t seg = (uint32_t) (rest / streams);
+        const uint32_t i = (group * (uint32_t) kFramesLanes + threadIdx.x) * 4u;
+        if (i >= t.limit) continue;                                         // the last group of a row: nothing of these lanes is read or written
+        const uint32_t j0 = seg * t.segment;                                // (< frames: the host counted the segments)
+        const uint32_t j1 = t.frames - j0 > t.segment ? j0 + t.segment : t.frames;
+        auto emit = [&](uint32_t j, uint32_t c, const glv_f4 v) {
+            const uint32_t lo = pack_unorm16(v.x, v.y), hi = pack_unorm16(v.z, v.w);      // render.c:521-524
+            const size_t at = ((size_t) j * w.units + 2u * stream + c) * t.n + i;
+            if constexpr (R16_OUT) *reinterpret_cast<glv_u2*>(static_cast<uint16_t*>(t.out) + at) = glv_u2{lo, hi};
+            else *reinterpret_cast<glv_f4*>(static_cast<float*>(t.out) + at) =
+                     glv_f4{unorm16_to_float(lo & 0xffffu), unorm16_to_float(lo >> 16), unorm16_to_float(hi & 0xffffu), unorm16_to_float(hi >> 16)};
+        };
+        uint32_t from[kFramesDepth], to[kFramesDepth];
+        float mod[kFramesDepth];
+#pragma unroll
+        for (int d = 0; d < kFramesDepth; ++d) {
+            const bool in = (uint32_t) d < j1 - j0;
+            from[d] = in ? t.from[j0 + (uint32_t) d] : 0u; to[d] = in ? t.to[j0 + (uint32_t) d] : 0u; mod[d] = in ? t.mod[j0 + (uint32_t) d] : 0.0f;
+        }
+        uint32_t ks = 0xffffffffu, ke = 0xffffffffu;                         // the keyframes in s and e: none yet (no clamped index is this)
+        glv_f4 sl = { 0.0f, 0.0f, 0.0f, 0.0f }, sr = sl, el = sl, er = sl;
+        for (uint32_t jb = j0; jb < j1; jb += (uint32_t) kFramesDepth) {
+#pragma unroll
+            for (int d = 0; d < kFramesDepth; ++d) {
+                const uint32_t j = jb + (uint32_t) d;
+                if (j >= j1) break;
+                const uint32_t kf = from[d] < last_key ? from[d] : last_key, kt = to[d] < last_key ? to[d] : last_key;
+                const float m = mod[d];
+                if (j1 - j > (uint32_t) kFramesDepth) {
+                    from[d] = t.from[j + (uint32_t) kFramesDepth]; to[d] = t.to[j + (uint32_t) kFramesDepth]; mod[d] = t.mod[j + (uint32_t) kFramesDepth];
+                }
+                glv_f4 nl = sl, nr = sr;
+                if (kf != ks) { if (kf == ke) { nl = el; nr = er; } else wave_key<2>(pcm, w, mono, t.keys, t.n, kf, stream, i, nl, nr); }
+                if (kt != ke) { if (kt == ks) { el = sl; er = sr; } else wave_key<2>(pcm, w, mono, t.keys, t.n, kt, stream, i, el, er); }
+                sl = nl; sr = nr; ks = kf; ke = kt;
+                glv_f4 wl = sl, wr = sr;
+                if (kf != kt) { wl = sl + ((el - sl) * m); wr = sr + ((er - sr) * m); }      // render.c:1806
+                emit(j, 0u, wl);
+                emit(j, 1u, wr);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) glv_wave_keys_planar_kernel(const void* pcm, const WaveWindows w, const int mono, float* keys, const uint32_t n, const size_t quads,
+                                                            const uint32_t keep_from, const uint32_t keep_to) {
+    const uint32_t per_stream = n / 4u;
+    for (size_t q = (size_t) blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t) gridDim.x * blockDim.x) {
+        const uint32_t stream = (uint32_t) (q / per_stream), i = (uint32_t) (q % per_stream) * 4u;
+        glv_f4 al, ar, bl, br;
+        wave_key<2>(pcm, w, mono, keys, n, keep_from, stream, i, al, ar);
+        wave_key<2>(pcm, w, mono, keys, n, keep_to, stream, i, bl, br);
+        float* const k0 = keys + (size_t) 2u * stream * n + i;
+        float* const k1 = k0 + (size_t) w.units * n;
+        *reinterpret_cast<glv_f4*>(k0) = al; *reinterpret_cast<glv_f4*>(k0 + n) = ar;
+        *reinterpret_cast<glv_f4*>(k1) = bl; *reinterpret_cast<glv_f4*>(k1 + n) = br;
+    }
+}
+
 hipError_t launch_wave_frames(const void* pcm, bool f32, const WaveWindows& w, bool mono, const WaveFrames& t, bool r16, hipStream_t st) {
     if (!pcm || !w.starts || !t.from || !t.to || !t.mod || !t.keys || !t.out) return hipErrorInvalidValue;
     if (t.frames == 0 || w.steps == 0 || w.steps > 0xfffffffdu || w.units == 0 || (w.units & 1u) || t.segment == 0 || t.limit == 0 || t.limit > t.n || (t.limit & 3u) ||
@@ -266,6 +354,11 @@ hipError_t launch_wave_frames(const void* pcm, bool f32, const WaveWindows& w, b
     const uint64_t items = segments * (w.units / 2u) * groups;              // (< 2^32 * 2^31 / 4: no overflow)
     const unsigned grid = capped_grid((size_t) items, 1, kFramesGridCap);
     const int m = mono ? 1 : 0;
+    if (w.planar) {
+        if (!f32) return hipErrorInvalidValue;
+        if (r16) hipLaunchKernelGGL((glv_wave_frames_planar_kernel<true>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, 0, t, groups, items);
+        else hipLaunchKernelGGL((glv_wave_frames_planar_kernel<false>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, 0, t, groups, items);
+    } else
     if (f32) {
         if (r16) hipLaunchKernelGGL((glv_wave_frames_kernel<true, true>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, groups, items);
         else hipLaunchKernelGGL((glv_wave_frames_kernel<true, false>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, groups, items);
@@ -282,6 +375,10 @@ hipError_t launch_wave_keys(const void* pcm, bool f32, const WaveWindows& w, boo
     if ((uint64_t) keep_from >= (uint64_t) w.steps + 2u || (uint64_t) keep_to >= (uint64_t) w.steps + 2u) return hipErrorInvalidValue;
     const size_t quads = (size_t) (w.units / 2u) * (n / 4u);
     const int m = mono ? 1 : 0;
+    if (w.planar) {
+        if (!f32) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(glv_wave_keys_planar_kernel, dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, pcm, w, 0, keys, n, quads, keep_from, keep_to);
+    } else
     if (f32) hipLaunchKernelGGL((glv_wave_keys_kernel<true>), dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, pcm, w, m, keys, n, quads, keep_from, keep_to);
     else hipLaunchKernelGGL((glv_wave_keys_kernel<false>), dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, pcm, w, m, keys, n, quads, keep_from, keep_to);
     return hipGetLastError();

@@ -143,6 +143,12 @@ def lib() -> C.CDLL:
             L.glv_batch_track_wave_frames_work_bytes.restype = C.c_uint64
             L.glv_batch_track_wave_frames_s16.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
             L.glv_batch_track_wave_frames_f32.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_at_f32_planar"):    # (likewise: the table, rates, frames and wave-frames calls from planar float rows [streams][2][pitch_frames])
+            FR = C.POINTER(TrackFrames)
+            L.glv_batch_track_at_f32_planar.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_rates_f32_planar.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_frames_f32_planar.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_wave_frames_f32_planar.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
         if hasattr(L, "glv_batch_set_bufscale"):        # (likewise: `setbufscale k` for a batch -- windows of k * n frames, decimated on the device)
             L.glv_batch_set_bufscale.argtypes = [vp, C.c_uint32]
             L.glv_batch_bufscale.argtypes = [vp]
@@ -261,6 +267,22 @@ def _ptr(x) -> C.c_void_p:
     if hasattr(x, "ctypes"):
         return C.c_void_p(x.ctypes.data)
     raise TypeError(type(x))
+
+
+def planar_pitch_frames(rows, streams: int) -> int:
+    """pitch_frames of a planar recording handed to the track_*_f32_planar methods: `rows` must be a contiguous float32 tensor (or array) of shape
+    [streams, 2, frames] -- its last dimension is returned.  Raises ValueError on anything else, before the library is called."""
+    shape = tuple(int(d) for d in getattr(rows, "shape", ()))
+    if len(shape) != 3 or shape[0] != streams or shape[1] != 2:
+        raise ValueError(f"a planar recording is a tensor [streams={streams}, 2, frames], not {list(shape) if shape else type(rows).__name__}")
+    if not str(getattr(rows, "dtype", "")).endswith("float32"):
+        raise ValueError(f"a planar recording holds float32 samples, not {getattr(rows, 'dtype', None)}")
+    contiguous = rows.is_contiguous() if hasattr(rows, "is_contiguous") else bool(rows.flags["C_CONTIGUOUS"])
+    if not contiguous:
+        raise ValueError("a planar recording must be contiguous: rows pitch_frames floats apart, two to a stream (call .contiguous())")
+    if shape[2] < 1 or shape[2] > 0xffffffff:
+        raise ValueError(f"frames={shape[2]} does not fit pitch_frames, a uint32 >= 1")
+    return shape[2]
 
 
 class Batch:
@@ -523,6 +545,31 @@ class Batch:
                               ops: int, stream: int | None = None) -> None:
         """track_wave_frames_s16 from a float recording (glv_batch_track_wave_frames_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
         self._track_wave_frames("f32", d_pcm, pitch_frames, d_starts, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
+
+    # ---- track mode from planar float recordings: a tensor [streams, 2, frames], the layout of process_f32's rows and of every channel-major decoder
+    def track_at_f32_planar(self, rows, d_starts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_at_f32 from a planar recording (glv_batch_track_at_f32_planar): `rows` a contiguous float32 tensor [streams, 2, frames] on the batch's device, any
+        4-byte aligned view of one included (rows[..., 1:] is not contiguous; a flat buffer sliced from any float and viewed as [streams, 2, frames] is);
+        pitch_frames is its last dimension.  Window t of stream s, channel c, begins min(d_starts[t], frames - bufscale * n) floats into rows[s, c].  No mono mix:
+        the rows are taken as they are whatever Params.channels says, so step t is bit for bit what process_f32 on the window's two rows would have written.
+        Forms, refusals, state and d_work (track_at_work_bytes) are track_at_f32's."""
+        pitch = planar_pitch_frames(rows, self.streams)
+        _check(lib().glv_batch_track_at_f32_planar(self._h, _ptr(rows), pitch, _ptr(d_starts), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_rates_f32_planar(self, rows, d_starts, d_ur, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_rates_f32 from a planar recording (glv_batch_track_rates_f32_planar); `rows` as track_at_f32_planar takes them"""
+        pitch = planar_pitch_frames(rows, self.streams)
+        _check(lib().glv_batch_track_rates_f32_planar(self._h, _ptr(rows), pitch, _ptr(d_starts), _ptr(d_ur), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_frames_f32_planar(self, rows, d_starts, d_ur, steps: int, d_from, d_to, d_mod, frames: int, d_keys, keep: tuple[int, int], d_out, d_work,
+                                ops: int, stream: int | None = None) -> None:
+        """track_frames_f32 from a planar recording (glv_batch_track_frames_f32_planar); `rows` as track_at_f32_planar takes them"""
+        self._track_frames("f32_planar", rows, planar_pitch_frames(rows, self.streams), d_starts, d_ur, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
+
+    def track_wave_frames_f32_planar(self, rows, d_starts, steps: int, d_from, d_to, d_mod, frames: int, d_keys, keep: tuple[int, int], d_out, d_work,
+                                     ops: int, stream: int | None = None) -> None:
+        """track_wave_frames_f32 from a planar recording (glv_batch_track_wave_frames_f32_planar); `rows` as track_at_f32_planar takes them"""
+        self._track_wave_frames("f32_planar", rows, planar_pitch_frames(rows, self.streams), d_starts, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

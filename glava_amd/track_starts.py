@@ -14,6 +14,15 @@ def _positive(**kw) -> None:
             raise ValueError(f"{name} must be an integer >= 1, not {v!r}")
 
 
+def hop_starts(steps: int, hop: int) -> list[int]:
+    """The table of a uniform hop: window t starts t * hop frames in -- what the hop entries (glv_batch_track_windows_s16 / _f32) compute themselves, for the
+    entries that take a table only (glv_batch_track_at_f32_planar).  Refuses a table whose last entry does not fit a uint32."""
+    _positive(steps=steps, hop=hop)
+    if (steps - 1) * hop >= 1 << 32:
+        raise ValueError(f"(steps - 1) * hop = {(steps - 1) * hop} does not fit a uint32 table entry: cut the track into chunks")
+    return [t * hop for t in range(steps)]
+
+
 def renderer_starts(rate: int, fps_num: int, fps_den: int, steps: int) -> list[int]:
     """Window starts of a renderer that draws `steps` frames at fps_num / fps_den frames per second from a recording of `rate` frames per second: frame
     t shows the window that starts floor(t * rate * fps_den / fps_num) frames in -- the audio position at the frame's time t * fps_den / fps_num,

@@ -789,6 +789,29 @@ int glv_batch_track_wave_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t
                                     void* d_out, void* d_work, unsigned ops, void* hip_stream);
 int glv_batch_track_wave_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
                                     void* d_out, void* d_work, unsigned ops, void* hip_stream);
+/* Track mode from PLANAR float recordings (added within ABI 7: detect them by the symbol).  The table, rates, frames and wave-frames calls above from the third
+ * layout a recording comes in: d_rows float [streams][2][pitch_frames] -- the lb / rb rows glv_batch_process_f32 takes ([streams][2][n]), as one long buffer per
+ * channel: a torch tensor [streams, channels, frames], a decoder that emits planar float, a host built around GLava's main loop.  Window t of stream s, channel c,
+ * is the w = bufscale * n floats that begin min(d_starts[t], pitch_frames - w) floats into row 2 s + c; the clamp is the kernels', whatever the table holds no
+ * launch reads outside the rows.  d_rows is 4-byte aligned and no more: a window begins at any sample, pitch_frames is any number >= w (the kernels take wide
+ * loads where a row's window lies on them and naturally aligned dwords elsewhere, row by row).
+ * NO MONO MIX: the rows are taken as they are, whatever glv_params.channels says -- glv_batch_process_f32's rule, the backend has already mixed lb / rb.  Step t
+ * is therefore bit for bit what glv_batch_process_f32 on the window's two rows would have written, and with channels == 2 bit for bit what the interleaved _f32
+ * sibling writes from the interleaved copy of the same samples, output and state.
+ * In every other respect each entry IS its _f32 sibling: the form the ops and the batch select (windows, live, columns, wave), the refusals in the same words before
+ * anything runs (under bufscale > 1 the wave forms refuse as theirs do), the state written back, kernels only on hip_stream, capturable into a hipGraph and
+ * re-aimed by rewriting the tables.  Workspace: the siblings' queries size these entries too -- glv_batch_track_at_work_bytes for the table and rates calls,
+ * glv_batch_track_frames_work_bytes and glv_batch_track_wave_frames_work_bytes for the frames calls; the layout of the recording changes no region.
+ * There are no hop entries: a table of t * hop (glava_amd.track_starts.hop_starts) is the hop form, and measured inside its spread.
+ * GLV_ERR_INVALID as the siblings, with d_rows misaligned for a float (4 bytes) in the place of their 8-byte rule. */
+int glv_batch_track_at_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps,
+                                  void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_rates_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_starts, const float* d_ur, uint32_t steps,
+                                     void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur /* NULL: the batch's ur */,
+                                      uint32_t steps, const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_wave_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
+                                           void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
