@@ -100,7 +100,10 @@ __global__ void __launch_bounds__(256) glv_decimate_kernel(const Decimate d, con
         const void* lane;
         if constexpr (KIND == DEC_F32_PLANAR) lane = static_cast<const float*>(d.in) + ((uint64_t) 2u * f * span + lead);
         else {
-            const uint64_t first = track_window_start(d.w, s, t, d.w.starts ? d.w.starts[t] : 0u) + lead;      // 64-bit: a recording may pass 2^32 frames
+            // (per-stream rows, table_len = windows: entry t of row s is entry f -- glv_frame.h track_table_entry, f < windows; uniform across the launch)
+            const bool rows = d.w.starts && d.w.table_len != d.w.steps;
+            const uint64_t first = (rows ? track_window_start(d.w, s, t, track_table_entry(d.w, f))
+                                         : track_window_start(d.w, s, t, d.w.starts ? d.w.starts[t] : 0u)) + lead;      // 64-bit: a recording may pass 2^32 frames
             if constexpr (KIND == DEC_S16) lane = static_cast<const uint32_t*>(d.in) + first;
             else if constexpr (KIND == DEC_F32) lane = static_cast<const glv_f2*>(d.in) + first;
             else lane = static_cast<const float*>(d.in) + (first + (uint64_t) s * d.w.pitch_frames);      // (a stream is two rows of pitch_frames floats: its channel-0 row)
@@ -135,6 +138,7 @@ hipError_t launch_decimate(int kind, const Decimate& d, hipStream_t st) {
     if ((reinterpret_cast<uintptr_t>(d.out) & 15u) || (reinterpret_cast<uintptr_t>(d.in) & (kind == DEC_F32 ? 7u : 3u))) return hipErrorInvalidValue;
     const uint64_t span = (uint64_t) d.k * d.n, windows = (uint64_t) d.w.steps * d.w.streams;
     if (windows > 0x7fffffffull) return hipErrorInvalidValue;
+    if (d.w.starts && d.w.table_len != d.w.steps && (uint64_t) d.w.table_len != windows) return hipErrorInvalidValue;      // a table is one row, or a row per stream
     if (kind == DEC_F32_PLANAR) { if (d.w.steps != 1u || d.w.starts) return hipErrorInvalidValue; }
     else if (d.w.pitch_frames < span || (d.w.starts ? (uint64_t) d.w.start_max != d.w.pitch_frames - span
                                                     : (uint64_t) (d.w.steps - 1u) * d.w.hop > d.w.pitch_frames - span)) return hipErrorInvalidValue;

@@ -35,7 +35,19 @@ constexpr int kFrameKinds = 9;       // every IN_MODE glv_frame_kernel is instan
 // as they are (no mono mix: the backend mixed them).  A table kind only: there is no hop kind, the host plans it as IN_F32_PLANAR.
 constexpr int IN_F32_PLANAR_TRACK_AT = kFrameKinds;
 constexpr int kPlanarTrackKinds = 1; // ... numbered behind kFrameKinds: [kFrameKinds, kFrameKinds + kPlanarTrackKinds) are instantiated too
-GLV_HD constexpr bool in_track_table(int in_mode) { return in_mode == IN_S16_TRACK_AT || in_mode == IN_F32_TRACK_AT || in_mode == IN_F32_PLANAR_TRACK_AT; }
+// The per-stream table kinds (glv_batch_track_each_s16 / _f32 / _f32_planar): the three table kinds with the entry of frame f = s * steps + t read from ROW s of a
+// table uint32 [streams][steps], starts[f % table_len] (TrackWindows::table_len = streams * steps).  Kinds of their own, numbered behind the planar one, for the
+// reason the table kinds are: beside their shared-table twins 58 of the 228 per-stream kernels need more VGPRs (+1 .. +4) or more scratch (+4 .. +20 bytes a lane)
+// for the other operand (profiles/r25/track_each_isa.txt), which folded into the twins would have been the twins' cost; so the shared-table frame kernels stay
+// byte for byte what they were (their index is f % steps, which the host tests hold them to).  Planned by the host as their shared-table siblings are.
+constexpr int IN_S16_TRACK_EACH = kFrameKinds + kPlanarTrackKinds, IN_F32_TRACK_EACH = IN_S16_TRACK_EACH + 1, IN_F32_PLANAR_TRACK_EACH = IN_S16_TRACK_EACH + 2;
+constexpr int kEachTrackKinds = 3;   // [kFrameKinds + kPlanarTrackKinds, ... + kEachTrackKinds) are instantiated too
+GLV_HD constexpr bool in_track_each(int in_mode) { return in_mode >= IN_S16_TRACK_EACH && in_mode < IN_S16_TRACK_EACH + kEachTrackKinds; }
+// the shared-table kind a per-stream kind runs the pipeline of (every other kind: itself)
+GLV_HD constexpr int track_shared_kind(int in_mode) {
+    return in_mode == IN_S16_TRACK_EACH ? IN_S16_TRACK_AT : in_mode == IN_F32_TRACK_EACH ? IN_F32_TRACK_AT : in_mode == IN_F32_PLANAR_TRACK_EACH ? IN_F32_PLANAR_TRACK_AT : in_mode;
+}
+GLV_HD constexpr bool in_track_table(int in_mode) { return in_mode == IN_S16_TRACK_AT || in_mode == IN_F32_TRACK_AT || in_mode == IN_F32_PLANAR_TRACK_AT || in_track_each(in_mode); }
 enum Epi { EPI_RAW = 0, EPI_MAG = 1, EPI_MAG_STATE = 2, EPI_RAW_STATE = 3 };
 
 // ops bits as in include/glv_spectrum.h
@@ -127,10 +139,14 @@ GLV_HD constexpr FrameClass frame_class(bool gl16, bool fused_bars, bool live, u
 struct TrackWindows {
     uint64_t pitch_frames, hop;
     uint32_t steps, streams;
-    uint32_t step_major, pad;
+    uint32_t step_major, table_len;     // table_len (a former pad word): entries of `starts` -- steps for a shared table, streams * steps for per-stream rows
     const uint32_t* starts;     // appended: every field above keeps its offset
     uint32_t start_max, pad2;
 };
+// The table's entry for frame f = s * steps + t of a launch: entry t of a shared table (table_len = steps), entry t of row s of per-stream rows (table_len =
+// streams * steps: glv_batch_track_each_*) -- one rule for both, and whatever f a look-ahead asks with, an entry the call names.  Read through this by the
+// per-stream kinds of the frame kernel and by glv_decimate_kernel; the frame kernel's shared-table kinds keep their own f % steps.
+GLV_HD uint32_t track_table_entry(const TrackWindows& w, uint32_t f) { return w.starts[f % w.table_len]; }
 // Where window t of stream s begins, in frames; `entry` is starts[t] as the caller read it (unused without a table).  The kernel's rule and the host side of
 // the same map, for the emulator and the tests' mirror.
 GLV_HD constexpr uint64_t track_window_start(const TrackWindows& w, uint32_t s, uint32_t t, uint32_t entry = 0) {

@@ -9,6 +9,7 @@
 //   part 5  part 3 with the windows' starts from a table in device memory (IN_S16_TRACK_AT: glv_batch_track_at_s16)
 //   part 6  part 4 likewise (IN_F32_TRACK_AT)
 //   part 7  planar float recordings at a table's starts (IN_F32_PLANAR_TRACK_AT: glv_batch_track_at_f32_planar), as parts 3-6 are built
+//   parts 8, 9, 10  parts 5, 6, 7 with a table row per stream (IN_S16_TRACK_EACH, IN_F32_TRACK_EACH, IN_F32_PLANAR_TRACK_EACH: glv_batch_track_each_*)
 // The knob set per size is the measured best of tools/tune.py
 // (profiles/tune_r01_final.txt, earlier sweeps in profiles/tune_r01.txt); see DESIGN.md "Kernel configuration".
 #include "glv_kernel_tmpl.h"
@@ -18,7 +19,7 @@
 #error "compile with -DGLV_LOG_NN=<7..14>"
 #endif
 #ifndef GLV_INST_PART
-#error "compile with -DGLV_INST_PART=<0..7>"
+#error "compile with -DGLV_INST_PART=<0..10>"
 #endif
 
 namespace glv {
@@ -87,6 +88,9 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part4)(int variant, int 
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part5)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part6)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part7)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part8)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part9)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part10)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 
 template <int IN_MODE, int V>
 static hipError_t launch_log(int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
@@ -152,10 +156,28 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part6)(int variant, int 
     if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_TRACK_AT, 1>(log_mode, cls, a, grid, st); }
     return hipErrorInvalidValue;
 }
-#else
+#elif GLV_INST_PART == 7
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part7)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     if (variant == 0) return launch_log<IN_F32_PLANAR_TRACK_AT, 0>(log_mode, cls, a, grid, st);
     if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_PLANAR_TRACK_AT, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#elif GLV_INST_PART == 8
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part8)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_S16_TRACK_EACH, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_S16_TRACK_EACH, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#elif GLV_INST_PART == 9
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part9)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_F32_TRACK_EACH, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_TRACK_EACH, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#else
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part10)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_F32_PLANAR_TRACK_EACH, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_PLANAR_TRACK_EACH, 1>(log_mode, cls, a, grid, st); }
     return hipErrorInvalidValue;
 }
 #endif
@@ -167,6 +189,9 @@ hipError_t GLV_CAT(launch_frame_, GLV_LOG_NN)(int in_mode, int log_mode, int var
     if (in_mode == IN_S16_TRACK_AT) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part5)(variant, log_mode, cls, a, grid, st);
     if (in_mode == IN_F32_TRACK_AT) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part6)(variant, log_mode, cls, a, grid, st);
     if (in_mode == IN_F32_PLANAR_TRACK_AT) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part7)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_S16_TRACK_EACH) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part8)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_F32_TRACK_EACH) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part9)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_F32_PLANAR_TRACK_EACH) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part10)(variant, log_mode, cls, a, grid, st);
     if (variant == 1) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(in_mode, log_mode, cls, a, grid, st);
     if (variant != 0) return hipErrorInvalidValue;
     if (in_mode == IN_S16_STEREO || in_mode == IN_S16_RING) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(in_mode, log_mode, cls, a, grid, st);

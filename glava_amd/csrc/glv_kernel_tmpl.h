@@ -196,13 +196,17 @@ static __device__ __forceinline__ uint32_t maybe_scalar(uint32_t v) {
     else return v;
 }
 
-template <int LOG_NN, int IN_MODE, int LOG_MODE, int SLOTS, int NBUF, int TWREG, bool WINLDS, int OCC, int PREFETCH, int TILTREG,
+template <int LOG_NN, int IN_KIND, int LOG_MODE, int SLOTS, int NBUF, int TWREG, bool WINLDS, int OCC, int PREFETCH, int TILTREG,
           int LOG_E, int STATEFUL, int WPRE = 0>
 __global__ void __launch_bounds__((Frame<LOG_NN, LOG_E>::T * SLOTS), OCC)
 glv_frame_kernel(const FrameArgs a) {
     using FR = Frame<LOG_NN, LOG_E>;
     constexpr int E = FR::E;
     constexpr int T = FR::T, N = FR::N;
+    // a per-stream table kind (glv_frame.h in_track_each) is its shared-table sibling in everything but the entry it reads (track_entry below): the pipeline is
+    // picked by IN_MODE, the sibling's kind, and every other kind is its own IN_MODE
+    constexpr int IN_MODE = track_shared_kind(IN_KIND);
+    constexpr bool TRACK_EACH = in_track_each(IN_KIND);
     constexpr bool RING = IN_MODE == IN_S16_RING;
     constexpr bool TRACK_TABLE = in_track_table(IN_MODE);   // a table call's kinds: the window's start comes from a.trk.starts (track_entry / track_at below)
     constexpr bool TRACK = IN_MODE == IN_S16_TRACK || IN_MODE == IN_S16_TRACK_AT;    // windows where they lie in a recording (a.trk): never a ring, stateless classes only (launch_variant)
@@ -455,8 +459,10 @@ glv_frame_kernel(const FrameArgs a) {
     // therefore asked for one frame AHEAD of the track_at(f, entry) that uses it, together with the previous frame's PCM loads, and W retires both (where f is
     // wave-uniform, WAVE_SLOT, the compiler may make it a scalar load, which vmcnt does not count: nothing here relies on that).  t < steps: the entry read is one the call names.  The hop kinds: 0, no load,
     // and track_at is what it was (the table is a template constant: their code does not change).
+    // The per-stream kinds (TRACK_EACH: glv_batch_track_each_*): the entry of frame f is starts[f % table_len], entry t of row s of uint32 [streams][steps] -- asked
+    // for where the shared-table kinds ask for theirs, clamped as theirs is, and for every f an entry of the table the call names.
     struct TrackAt { const void* win; size_t row0; };
-    auto track_entry = [&](uint32_t f) -> uint32_t { if constexpr (TRACK_TABLE) return a.trk.starts[f % a.trk.steps]; else return 0u; };
+    auto track_entry = [&](uint32_t f) -> uint32_t { if constexpr (TRACK_EACH) return track_table_entry(a.trk, f); else if constexpr (TRACK_TABLE) return a.trk.starts[f % a.trk.steps]; else return 0u; };
     auto track_at = [&](uint32_t f, uint32_t entry) -> TrackAt {
         const uint32_t s = f / a.trk.steps, t = f - s * a.trk.steps;
         uint64_t start;

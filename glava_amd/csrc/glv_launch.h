@@ -48,6 +48,16 @@ struct TrackGeometry {
     const float* ur;           //   kernel's rates kind -- float [steps] in device memory, read in [0, steps) only; nullptr: every other call, FrameArgs::g / grav_sub as they are
 };
 hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool rows_texels, hipStream_t st);
+// The scan of a per-stream track call (glv_track_each_scan_kernel; glv_batch_track_each_*): the windows form's geometry (log_q = 0, hops_per_pitch = steps) with a
+// row of the rate table and a count of steps per stream.  Stream s = channel row >> 1 walks its first c_s = min(counts[s], steps) steps (counts == nullptr: all) with
+// gravity's step from ur[s * steps + t] (ur == nullptr: FrameArgs::g / grav_sub as they are, the packed integer texel step included), writes zeros to the output
+// rows of the steps behind c_s, and leaves its ring where the BATCH's head will point: slot p of the stream's own walk is stored to slot (p + steps - c_s) % F.
+// Both tables are device memory, read when the kernel runs: counts in [0, streams), ur in [s * steps, s * steps + c_s) only.  TrackGeometry::ur stays null.
+struct TrackEach {
+    const uint32_t* counts;
+    const float* ur;
+};
+hipError_t launch_track_each_scan(const FrameArgs& a, const TrackGeometry& t, const TrackEach& e, bool rows_texels, hipStream_t st);
 // The render frames of a track call on gl_storage 3 (glv_track_frames.hip; glv_batch_track_frames_s16 / _f32).  Keyframe k of the call is block k of `keys`
 // (float [2][units][n]) for k < 2 and the finished float rows of step k - 2 in `rows` (float [steps][units][n]) beyond; frame j of row r is the GL_R16 upload
 // of keyframe from[j] itself where from[j] == to[j], of s + ((e - s) * mod[j]) of keyframes from[j] and to[j] else (render.c:1806, :2185).  The tables are
@@ -72,6 +82,9 @@ hipError_t launch_track_keys(float* keys, const float* rows, uint32_t units, uin
 // A table call (glv_batch_track_at_s16 / _f32, glv_wave_kernel only): `starts` is uint32 [steps] in device memory and window t of every stream begins
 // min(starts[t], start_max) frames into its recording, start_max = pitch_frames - n (glv_frame.h TrackWindows: the same table, the same clamp, in the kernel).
 // starts == nullptr: t * hop.
+// With a table nothing walks at a hop, and `hop` carries the table's own: the entries between the table rows of two streams -- 0: one row shared by all streams;
+// `steps`: uint32 [streams][steps], row s is stream s's (glv_batch_track_each_*), and the entry of window (s, t) is starts[s * hop + t] (glv_wave_kernel's window
+// kinds 3, 4, 5 only).  The structure keeps its size and every offset, so every kernel that takes one and does not read a table keeps its code.
 struct WaveWindows {
     uint32_t units = 0, steps = 0, hop = 0, by_steps = 0;
     uint64_t pitch_frames = 0;

@@ -179,6 +179,132 @@ __global__ void __launch_bounds__(kTrackLanes) glv_track_scan_kernel(const Frame
     } else if (grav) st<V>(reinterpret_cast<char*>(a.grav_w) + (size_t) row * row_bytes, off, gs);
 }
 
+// ---- the scan of a per-stream track call (glv_batch_track_each_s16 / _f32 / _f32_planar) ------------------------------------------------------------------
+// glv_track_scan_kernel's walk with what a stream of its own needs, in a kernel of its own: the kinds above keep their code and their arguments.
+// Counts: stream s = row >> 1 takes c = min(counts[s], steps) steps (uniform per workgroup: a workgroup lies inside one channel row; loaded once; no table: all
+// steps).  The walk, the look-ahead ring and the rate requests are bounded by c, so no row and no rate at or beyond step c is asked for; the output rows of steps
+// [c, steps) receive zeros -- the finished row of a step that did not run, which the call's last stage (bars, columns) turns into what it makes of a zero row.
+// Rates (RATES): step tt of stream s applies g = gravity_step * (1.0F / ur[s * steps + tt]), the rates kind's expression on the stream's own row; texel state then
+// takes the float form at every step, as there.  !RATES: FrameArgs::g and the packed integer texel step (gravity_r16), exactly as the plain kinds -- a call with
+// counts alone on texel state keeps the integer arm wherever the sequential calls take it.
+// State afterwards: the batch's head advances by `steps` for every stream (the host cannot see the counts), this stream's own by c.  The ring was loaded slot by
+// slot under the batch's head and walked under the stream's; slot p is written back to slot (p + steps - c) % F, so the row of age j under the stream's head sits
+// where age j sits under (head + steps) % F -- what the next call reads.  c = 0: the ring turned by steps % F and the gravity row as it was, every age in place.
+template <bool IN16, bool RATES>
+__global__ void __launch_bounds__(kTrackLanes) glv_track_each_scan_kernel(const FrameArgs a, const TrackGeometry t, const TrackEach e) {
+    using V = typename std::conditional<IN16, uint32_t, cf>::type;
+    extern __shared__ __attribute__((aligned(8))) unsigned char track_each_lds[];
+    V* const ring = reinterpret_cast<V*>(track_each_lds) + threadIdx.x;     // slot f of this lane: ring[f * kTrackLanes]
+    const uint32_t blocks_per_row = (t.kept + 2u * (uint32_t) kTrackLanes - 1u) / (2u * (uint32_t) kTrackLanes);
+    const uint32_t row = blockIdx.x / blocks_per_row;                       // uniform
+    const uint32_t pair = (blockIdx.x % blocks_per_row) * (uint32_t) kTrackLanes + threadIdx.x;
+    if (pair >= t.kept / 2u) return;
+    const uint32_t off = pair * (uint32_t) sizeof(V);
+    const size_t row_bytes = (size_t) t.n * (sizeof(V) / 2u);
+    const uint32_t F = a.F;
+    const bool grav = (a.ops & OP_GRAVITY) != 0, avg = (a.ops & OP_AVERAGE) != 0, windowed = a.avg_window != 0;
+    const bool out16 = t.out_texels != 0;
+    const uint32_t stream = row >> 1;
+    uint32_t c = t.steps;                                                   // the stream's steps: uniform
+    if (e.counts) { const uint32_t own = e.counts[stream]; c = own < t.steps ? own : t.steps; }
+    const float* const ur = RATES ? e.ur + (size_t) stream * t.steps : nullptr;      // the stream's row of the rate table, read in [0, c)
+    // ---- the lane's slice of the state, once
+    V gs = V();
+    if (avg) {
+        const char* h = reinterpret_cast<const char*>(a.hist) + (size_t) row * F * row_bytes;
+        for (uint32_t f = 0; f < F; ++f) ring[f * kTrackLanes] = ld<V>(h + (size_t) f * row_bytes, off);
+    } else if (grav) gs = ld<V>(reinterpret_cast<const char*>(a.grav) + (size_t) row * row_bytes, off);
+    uint32_t head = a.head;
+    // ---- where step tt's row lies (the windows form: row (stream * steps + tt) * 2 + channel), and where its result goes
+    const char* const in = static_cast<const char*>(a.in);
+    auto fetch = [&](uint32_t tt) -> V { return ld<V>(in + (((uint64_t) stream * t.steps + tt) * 2u + (row & 1u)) * row_bytes, off); };
+    char* const out = reinterpret_cast<char*>(a.out);
+    const size_t out_row_bytes = (size_t) t.n * (out16 ? 2u : 4u);
+    const uint32_t out_off = pair * (out16 ? 4u : 8u);
+    auto step = [&](V x, uint32_t tt, float g) {
+        char* const o = out + ((size_t) tt * a.units + row) * out_row_bytes;
+        if constexpr (IN16) {
+            uint32_t tex = x;                                               // apply_state_r16
+            if (grav) {
+                const uint32_t store = avg ? ring[(F == 1 ? head : ring_slot(head, F - 2, F)) * kTrackLanes] : gs;
+                if constexpr (RATES) tex = gravity_r16_flt(tex, store, g);
+                else tex = gravity_r16(tex, store, a.g, a.grav_sub, a.grav_int);
+                if (!avg) gs = tex;
+            }
+            if (avg) {
+                cf acc = { 0.0f, 0.0f };
+                for (uint32_t f = 0; f + 1 < F; ++f) weighted_texels(acc, ring[ring_slot(head, f, F) * kTrackLanes], a.wts32[f], windowed);
+                ring[head * kTrackLanes] = tex;
+                if (F > 1) {
+                    weighted_texels(acc, tex, a.wts32[F - 1], windowed);
+                    tex = pack_unorm16(div_frames(acc.x, a.F_as_float, a.F_rcp), div_frames(acc.y, a.F_as_float, a.F_rcp));
+                }
+                head = head + 1u == F ? 0u : head + 1u;
+            }
+            if (out16) st<uint32_t>(o, out_off, tex);
+            else st<cf>(o, out_off, texels_to_float(tex));
+        } else {
+            cf val = x;                                                     // apply_state, the float chain
+            if (avg) {
+                cf acc = { 0.0f, 0.0f }, prev = { 0.0f, 0.0f };
+                if (F == 1) prev = ring[head * kTrackLanes];
+                for (uint32_t f = 0; f + 1 < F; ++f) {
+                    prev = ring[ring_slot(head, f, F) * kTrackLanes];
+                    average_add(acc, prev, a.wts[f], windowed);
+                }
+                if (grav) { val.x = gravity(val.x, prev.x, g); val.y = gravity(val.y, prev.y, g); }
+                ring[head * kTrackLanes] = val;
+                average_add(acc, val, a.wts[F - 1], windowed);
+                val = average_end(acc, a.F_as_float);
+                head = head + 1u == F ? 0u : head + 1u;
+            } else if (grav) {
+                val.x = gravity(val.x, gs.x, g); val.y = gravity(val.y, gs.y, g);
+                gs = val;
+            }
+            if (out16) st<uint32_t>(o, out_off, pack_unorm16(val.x, val.y));    // render.c:521-524
+            else st<cf>(o, out_off, val);
+        }
+    };
+    // ---- the walk over the stream's own steps [0, c)
+    V ahead[kTrackDepth];
+    float rate[RATES ? kTrackDepth : 1];
+#pragma unroll
+    for (int j = 0; j < kTrackDepth; ++j) {
+        ahead[j] = (uint32_t) j < c ? fetch((uint32_t) j) : V();
+        if constexpr (RATES) rate[j] = (uint32_t) j < c ? ur[j] : 1.0f;
+    }
+    for (uint32_t t0 = 0; t0 < c; t0 += (uint32_t) kTrackDepth) {
+#pragma unroll
+        for (int j = 0; j < kTrackDepth; ++j) {
+            const uint32_t tt = t0 + (uint32_t) j;
+            if (tt >= c) break;
+            const V x = ahead[j];
+            float g = a.g;
+            if constexpr (RATES) g = t.gravity_step * (1.0F / rate[j]);    // render.c:728
+            if (tt + (uint32_t) kTrackDepth < c) {
+                ahead[j] = fetch(tt + (uint32_t) kTrackDepth);
+                if constexpr (RATES) rate[j] = ur[tt + (uint32_t) kTrackDepth];
+            }
+            step(x, tt, g);
+        }
+    }
+    // ---- the steps behind the count: a finished row of zeros each
+    for (uint32_t tt = c; tt < t.steps; ++tt) {
+        char* const o = out + ((size_t) tt * a.units + row) * out_row_bytes;
+        if (out16) st<uint32_t>(o, out_off, 0u);
+        else st<cf>(o, out_off, cf{0.0f, 0.0f});
+    }
+    // ---- the state c sequential calls would have left, presented at the batch's new head
+    if (avg) {
+        char* h = reinterpret_cast<char*>(a.hist) + (size_t) row * F * row_bytes;
+        const uint32_t turn = (t.steps - c) % F;
+        for (uint32_t f = 0; f < F; ++f) {
+            const uint32_t to = f + turn >= F ? f + turn - F : f + turn;
+            st<V>(h + (size_t) to * row_bytes, off, ring[f * kTrackLanes]);
+        }
+    } else if (grav) st<V>(reinterpret_cast<char*>(a.grav_w) + (size_t) row * row_bytes, off, gs);
+}
+
 __global__ void __launch_bounds__(256) glv_unpack_kernel(const int16_t* __restrict__ pcm, size_t frames, int mono,
                                                          float* __restrict__ l, float* __restrict__ r) {
     for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < frames; i += (size_t) gridDim.x * blockDim.x) {
@@ -233,7 +359,8 @@ typedef unsigned int glv_wave_u4 __attribute__((ext_vector_type(4)));
 // (a window begins at any sample and pitch_frames is any number, so the two rows of a stream may differ).  Bounded as KIND 3 and 4, within row 2 stream + c.
 // Bounded reads (KIND 3 and 4): s < steps * streams and t + 8 <= limit <= n, so a lane reads frames [t, t + 8) of a window the call names and no others.
 // A table call (WaveWindows::starts): the window of step t' begins min(starts[t'], pitch_frames - n) frames into the recording -- one lookup per lane and group
-// of 8 frames, t' < steps, from a table that sits in L2; the clamp keeps the window inside the recording whatever the table holds.
+// of 8 frames, t' < steps, from a table that sits in L2; the clamp keeps the window inside the recording whatever the table holds.  With per-stream rows
+// (with a table WaveWindows::hop is the table's: steps between two streams' rows, glv_batch_track_each_*; 0 for one shared row) the entry is starts[stream * steps + t'], stream < streams: inside uint32 [streams][steps].
 template <int KIND, bool R16>
 __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ in, void* __restrict__ out, size_t groups_total, uint32_t n, uint32_t limit,
                                                        uint32_t rot, int mono, const WaveWindows w) {
@@ -269,7 +396,8 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
         } else if constexpr (KIND == 3) {
             const uint32_t streams = w.units / 2u;
             const uint32_t step = (uint32_t) (s / streams);
-            const uint64_t first = wave_window_start(w, (uint32_t) (s % streams), step, w.starts ? w.starts[step] : 0u) + t;      // the group's first frame
+            const uint32_t stream = (uint32_t) (s % streams);
+            const uint64_t first = wave_window_start(w, stream, step, w.starts ? w.starts[(size_t) stream * w.hop + step] : 0u) + t;      // the group's first frame
             const uint32_t* src = static_cast<const uint32_t*>(in) + first;
             uint32_t f[8];
             if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
@@ -290,7 +418,8 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
         } else if constexpr (KIND == 4) {
             const uint32_t streams = w.units / 2u;
             const uint32_t step = (uint32_t) (s / streams);
-            const uint64_t first = wave_window_start(w, (uint32_t) (s % streams), step, w.starts ? w.starts[step] : 0u) + t;      // the group's first frame
+            const uint32_t stream = (uint32_t) (s % streams);
+            const uint64_t first = wave_window_start(w, stream, step, w.starts ? w.starts[(size_t) stream * w.hop + step] : 0u) + t;      // the group's first frame
             const cf* src = static_cast<const cf*>(in) + first;
             cf f[8];
             if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
@@ -313,7 +442,8 @@ __global__ void __launch_bounds__(256) glv_wave_kernel(const void* __restrict__ 
         } else if constexpr (KIND == 5) {
             const uint32_t streams = w.units / 2u;
             const uint32_t step = (uint32_t) (s / streams);
-            const float* src = static_cast<const float*>(in) + (wave_planar_start(w, (uint32_t) (s % streams), step, w.starts ? w.starts[step] : 0u) + t);
+            const uint32_t stream = (uint32_t) (s % streams);
+            const float* src = static_cast<const float*>(in) + (wave_planar_start(w, stream, step, w.starts ? w.starts[(size_t) stream * w.hop + step] : 0u) + t);
 #pragma unroll
             for (uint32_t c = 0; c < 2u; ++c, src += w.pitch_frames) {     // channel c of the group: the same 8 samples of the row pitch_frames floats on
                 float x[8];
@@ -592,6 +722,22 @@ hipError_t launch_track_scan(const FrameArgs& a, const TrackGeometry& t, bool ro
     return hipGetLastError();
 }
 
+hipError_t launch_track_each_scan(const FrameArgs& a, const TrackGeometry& t, const TrackEach& e, bool rows_texels, hipStream_t st) {
+    const uint64_t blocks = (uint64_t) a.units * ((t.kept + 2u * (uint32_t) kTrackLanes - 1u) / (2u * (uint32_t) kTrackLanes));
+    if (t.n < 2u * (uint32_t) kTrackLanes || t.kept == 0 || t.kept > t.n || t.kept % 64u != 0 || t.steps == 0 || blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (t.log_q != 0 || t.hops_per_pitch != t.steps || t.ur || (a.units & 1u)) return hipErrorInvalidValue;      // the windows form's rows; the rates are TrackEach's
+    if (!(a.ops & (OP_GRAVITY | OP_AVERAGE)) || (e.ur && !(a.ops & OP_GRAVITY))) return hipErrorInvalidValue;     // counts protect state, rates are gravity's
+    const size_t lds = (a.ops & OP_AVERAGE) ? (size_t) a.F * kTrackLanes * (rows_texels ? sizeof(uint32_t) : sizeof(cf)) : 0;   // <= 32 KiB (F <= 64)
+    if (e.ur) {
+        if (rows_texels) hipLaunchKernelGGL((glv_track_each_scan_kernel<true, true>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t, e);
+        else hipLaunchKernelGGL((glv_track_each_scan_kernel<false, true>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t, e);
+        return hipGetLastError();
+    }
+    if (rows_texels) hipLaunchKernelGGL((glv_track_each_scan_kernel<true, false>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t, e);
+    else hipLaunchKernelGGL((glv_track_each_scan_kernel<false, false>), dim3((uint32_t) blocks), dim3(kTrackLanes), lds, st, a, t, e);
+    return hipGetLastError();
+}
+
 hipError_t launch_unpack(const int16_t* pcm, size_t frames, int mono, float* l, float* r, hipStream_t st) {
     hipLaunchKernelGGL(glv_unpack_kernel, dim3(grid_256(frames)), dim3(256), 0, st, pcm, frames, mono, l, r);
     return hipGetLastError();
@@ -621,6 +767,7 @@ hipError_t launch_wave(const void* in, int in_mode, bool mono, uint32_t n, uint3
 }
 hipError_t launch_wave_track(const void* pcm, bool f32, const WaveWindows& w, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st) {
     if (limit == 0 || limit > n || (limit & 7u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || (w.hop == 0 && !w.starts)) return hipErrorInvalidValue;
+    if (w.starts && w.hop != 0 && w.hop != w.steps) return hipErrorInvalidValue;      // a table: one shared row (0), or uint32 [streams][steps] (steps), nothing else
     const size_t total = (size_t) w.steps * (w.units / 2u) * (limit / 8u);
     const unsigned grid = grid_256(total);
     if (w.planar) {

@@ -33,6 +33,7 @@ namespace {
 // (the _f32_planar entries: table calls only).  True where it holds floats, so `f32 ? ... : ...` reads as it did while this was a boolean; a bool converts.
 struct TrackInput {
     enum Kind { S16 = 0, F32 = 1, F32_PLANAR = 2 } kind;
+    bool rows = false;      // the call's tables have a row per stream (glv_batch_track_each_*: set by track_each, read where the wave form's windows are laid out)
     TrackInput(bool f32 = false) : kind(f32 ? F32 : S16) {}
     TrackInput(Kind k) : kind(k) {}
     explicit operator bool() const { return kind != S16; }
@@ -56,6 +57,8 @@ struct TrackPlan {
     bool at = false;                    // the windows lie where a table in device memory says (glv_batch_track_at_s16 / _f32), not every `hop` frames; set before the plan
     const uint32_t* starts = nullptr;   // ... and the table, uint32 [steps]; set by the entry as f32 is (the sizing query has none), windows form only
     const float* ur = nullptr;          // a rates call's table of update rates, float [steps]; set by track_at as starts is, read by the scan alone
+    bool each = false;                  // a per-stream call (glv_batch_track_each_*): `starts` and `ur` are [streams][steps], row s is stream s's; set by track_at with them
+    const uint32_t* counts = nullptr;   // ... and its steps per stream, uint32 [streams] or none; read by the scan alone, on the device
     bool live = false;                  // the entry is the live form (glv_batch_track_live_s16 / _f32)
     uint32_t kept = 0;                  // the live form's kept bins K, a multiple of 64 below n (kept_bins); 0: every bin -- the other entries, and the live form's full-row form
     const glv_track_frames* fr = nullptr;   // a frames call (glv_batch_track_frames_s16 / _f32): its render frames; set before the plan (the sizing query's holds `frames` alone)
@@ -280,10 +283,12 @@ int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::Fra
                         float* rows, float* dec, hipStream_t st) {
     a.in = d_pcm; a.out = rows; a.units = (uint32_t) tp.out_rows;
     a.trk.pitch_frames = pitch_frames; a.trk.hop = hop; a.trk.steps = steps; a.trk.streams = b->streams; a.trk.step_major = tp.state ? 0u : 1u;
-    a.trk.pad = 0; a.trk.starts = tp.starts; a.trk.start_max = pitch_frames - b->p.n * b->bufscale; a.trk.pad2 = 0;      // (both plans' pitch rule: pitch_frames >= a window)
+    a.trk.table_len = tp.each ? steps * b->streams : steps;      // (a row per stream, or one row for all; out_rows = 2 * steps * streams fits 32 bits)
+    a.trk.starts = tp.starts; a.trk.start_max = pitch_frames - b->p.n * b->bufscale; a.trk.pad2 = 0;      // (both plans' pitch rule: pitch_frames >= a window)
     int hop_mode = tp.f32 ? glv::IN_F32_TRACK : glv::IN_S16_TRACK;
     int mode = !tp.starts ? hop_mode : tp.f32 ? glv::IN_F32_TRACK_AT : glv::IN_S16_TRACK_AT;      // a table call: the kernel kinds that read it, planned as the hop kinds
     if (tp.f32.planar()) { hop_mode = glv::IN_F32_PLANAR; mode = glv::IN_F32_PLANAR_TRACK_AT; }      // planar rows (a table call: track_at): the planar pipeline's plan and wisdom
+    if (tp.each) mode = tp.f32.planar() ? glv::IN_F32_PLANAR_TRACK_EACH : tp.f32 ? glv::IN_F32_TRACK_EACH : glv::IN_S16_TRACK_EACH;      // a table row per stream: the kinds that index it, planned as their siblings
     if (dec) {
         glv::Decimate d = {};
         d.in = d_pcm; d.out = dec; d.n = b->p.n; d.k = b->bufscale; d.mono = b->p.channels == 1 && !tp.f32.planar() ? 1u : 0u; d.w = a.trk;      // (planar rows are taken as they are)
@@ -309,10 +314,14 @@ int track_scan(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, uint32_t st
     g.n = b->p.n; g.steps = steps; g.hops_per_pitch = tp.hops_per_pitch; g.log_q = tp.log_q; g.residue_rows = tp.residue_rows; g.out_texels = tp.out16 ? 1u : 0u;
     g.kept = tp.kept != 0 ? tp.kept : b->p.n;
     g.gravity_step = b->p.gravity_step; g.ur = tp.ur;
-    const hipError_t e = glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
+    glv::TrackEach rows;                // a per-stream call: the counts and the rate rows go to the scan kernel of that call, and `g` keeps a null rate table
+    rows.counts = tp.counts; rows.ur = tp.each ? tp.ur : nullptr;
+    if (tp.each) g.ur = nullptr;
+    const hipError_t e = tp.each ? glv::launch_track_each_scan(a, g, rows, tp.in16, st) : glv::launch_track_scan(a, g, tp.in16, st); ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
-    b->kernel_name = "glv_track_scan_kernel";
-    // the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
+    b->kernel_name = tp.each ? "glv_track_each_scan_kernel" : "glv_track_scan_kernel";
+    // A per-stream call: the head advances by `steps` all the same -- it is the batch's, and the counts are the device's; the kernel wrote every stream's ring
+    // where that head puts it.  Otherwise the state as `steps` sequential calls leave it: the ring's slots were written where the head implies, the gravity store is the batch's own
     if (ops & GLV_OP_AVERAGE) b->head = (uint32_t) (((uint64_t) b->head + steps) % b->p.avg_frames);
     if ((ops & GLV_OP_GRAVITY) && !(ops & GLV_OP_AVERAGE)) b->grav_cur = b->d_grav;
     return GLV_OK;
@@ -474,6 +483,7 @@ int track_wave(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_f
     glv::WaveWindows w;
     w.units = b->streams * 2u; w.steps = steps; w.hop = hop; w.pitch_frames = pitch_frames;
     w.starts = d_starts; w.start_max = pitch_frames - b->p.n; w.planar = f32.planar() ? 1u : 0u;
+    if (f32.rows) w.hop = steps;      // a per-stream call: with a table `hop` is the table's own -- uint32 [streams][steps], row s is stream s's
     // (a store's 32-bit lane offset spans 4 rows of the workgroup: `units` rows apart by steps)
     w.by_steps = b->track_wave_by_steps && (4ull * w.units + 2u) * b->p.bars * 4u <= 0xffffffffull ? 1u : 0u;
     if (int rc = timed_launch_begin(b, st)) return rc;
@@ -518,8 +528,9 @@ uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, ui
 // glv_batch_track_at_s16 / _f32: the table's own refusals, then the form the ops and the batch select -- the wave form's executor, or the FFT forms'.
 // d_ur: the second table of a rates call (track_rates has vetted it, and that the ops have the gravity that reads it); nullptr: the batch's own ur
 // fr: the render frames of a frames call (track_frames_call has vetted them and the ops); nullptr: every other call
+// each: the tables of a per-stream call (track_each has vetted them: d_starts and d_ur are its rows, [streams][steps]); nullptr: one row for all streams
 int track_at(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
-             const glv_track_frames* fr = nullptr, const float* d_ur = nullptr) {
+             const glv_track_frames* fr = nullptr, const glv_track_tables* each = nullptr, const float* d_ur = nullptr) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_starts) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (reinterpret_cast<uintptr_t>(d_starts) & 3u) return fail(GLV_ERR_INVALID, "d_starts must be 4-byte aligned");
@@ -528,6 +539,7 @@ int track_at(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_fra
     tp.fr = fr;
     if (int rc = fr ? plan_track_frames(b, pitch_frames, steps, ops, tp) : plan_track_at(b, pitch_frames, 0u, steps, ops, tp)) return rc;
     tp.f32 = f32; tp.starts = d_starts; tp.ur = d_ur;
+    if (each) { tp.each = true; tp.counts = each->d_counts; }
     return track(b, tp, d_pcm, pitch_frames, 0u, steps, d_out, d_work, ops, st);
 }
 // glv_batch_track_rates_s16 / _f32: the rate table's own refusals, then the table call.  The wave form keeps no state and applies no gravity, and a chain
@@ -539,7 +551,26 @@ int track_rates(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_
     if (reinterpret_cast<uintptr_t>(d_ur) & 3u) return fail(GLV_ERR_INVALID, "d_ur must be 4-byte aligned");
     if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE is stateless: no gravity reads the rate table (glv_batch_track_at_s16 / _f32; ops 0x%x)", ops);
     if (!(ops & GLV_OP_GRAVITY)) return fail(GLV_ERR_INVALID, "a rates track call needs GLV_OP_GRAVITY, which reads the rate table (ops 0x%x)", ops);
-    return track_at(b, d_pcm, f32, pitch_frames, d_where, steps, d_out, d_work, ops, st, fr, d_ur);
+    return track_at(b, d_pcm, f32, pitch_frames, d_where, steps, d_out, d_work, ops, st, fr, nullptr, d_ur);
+}
+// glv_batch_track_each_s16 / _f32 / _f32_planar: a table call whose tables have a row per stream, and a count of steps per stream.  What can be said of the three
+// tables without the batch's plan -- the pointers, and which chains have a reader for the rates and state for the counts to protect -- then the table call with the
+// rows handed on: its plan, its workspace, its refusals in its words.  Nothing here launches.
+int track_each(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops,
+               hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!tb) return fail(GLV_ERR_INVALID, "tb is NULL");
+    if (reinterpret_cast<uintptr_t>(tb) & (alignof(glv_track_tables) - 1u)) return fail(GLV_ERR_INVALID, "tb must be aligned like a pointer: %u bytes", (unsigned) alignof(glv_track_tables));
+    if (reinterpret_cast<uintptr_t>(tb->d_ur) & 3u) return fail(GLV_ERR_INVALID, "d_ur must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(tb->d_counts) & 3u) return fail(GLV_ERR_INVALID, "d_counts must be 4-byte aligned");
+    if (tb->d_ur) {
+        if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE is stateless: no gravity reads the rate table (glv_batch_track_at_s16 / _f32; ops 0x%x)", ops);
+        if (!(ops & GLV_OP_GRAVITY)) return fail(GLV_ERR_INVALID, "a rates track call needs GLV_OP_GRAVITY, which reads the rate table (ops 0x%x)", ops);
+    }
+    if (tb->d_counts && ((ops & GLV_OP_WAVE) || !(ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))))
+        return fail(GLV_ERR_INVALID, "the chain keeps no state for d_counts to protect: counts need GLV_OP_GRAVITY and / or GLV_OP_AVERAGE and no GLV_OP_WAVE (ops 0x%x)", ops);
+    f32.rows = true;
+    return track_at(b, d_pcm, f32, pitch_frames, tb->d_starts, steps, d_out, d_work, ops, st, nullptr, tb, tb->d_ur);
 }
 // glv_batch_track_frames_s16 / _f32: what can be said of the frames without the batch's plan -- the pointers and the pair of keyframes kept -- then the rates call
 // or the table call with the frames handed on.  Nothing here launches; a refusal below (plan_track_frames, the table call's own) leaves the batch as untouched.
@@ -698,6 +729,22 @@ int glv_batch_track_rates_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_f
 int glv_batch_track_rates_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps, void* d_out,
                                      void* d_work, unsigned ops, void* hip_stream) {
     return track_rates(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// A table row per stream, and a count of steps per stream (sized by glv_batch_track_at_work_bytes: the rows add no region).  The tables are handed on whole.
+int glv_batch_track_each_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops,
+                             void* hip_stream) {
+    return track_each(b, d_pcm, false, pitch_frames, tb, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_each_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops,
+                             void* hip_stream) {
+    return track_each(b, d_pcm, true, pitch_frames, tb, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_each_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops,
+                                    void* hip_stream) {
+    return track_each(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, tb, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 // (one query for glv_batch_track_frames_s16 and _f32: the table call's regions with float rows in both, and with bars the frames' texel rows behind them; asked, like

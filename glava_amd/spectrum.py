@@ -64,6 +64,12 @@ class TrackFrames(C.Structure):
                 ("keep_from", C.c_uint32), ("keep_to", C.c_uint32)]
 
 
+class TrackTables(C.Structure):
+    """glv_track_tables: the per-stream tables of a glv_batch_track_each_s16 / _f32 / _f32_planar call, all in device memory -- window starts uint32
+    [streams][steps], update rates float32 [streams][steps] or NULL (the batch's own ur), steps per stream uint32 [streams] or NULL (every stream takes all)"""
+    _fields_ = [("d_starts", C.c_void_p), ("d_ur", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
 class StreamStateDesc(C.Structure):
     """glv_stream_state_desc: what a blob of Batch.save_streams is -- the batch's n, F and element size, the form gravity's state was kept in, the regions
     present (bit 0 gravity rows, 1 average ring, 2 s16 PCM ring, 3 f32 PCM ring), the bins kept and the bytes of one stream (glava_amd/stream_slots.py
@@ -149,6 +155,11 @@ def lib() -> C.CDLL:
             L.glv_batch_track_rates_f32_planar.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_track_frames_f32_planar.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
             L.glv_batch_track_wave_frames_f32_planar.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, FR, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_each_s16"):      # (likewise: the table and rates calls with a table row and a count of steps per stream)
+            TT = C.POINTER(TrackTables)
+            L.glv_batch_track_each_s16.argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_each_f32.argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_each_f32_planar.argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, vp, vp, C.c_uint, vp]
         if hasattr(L, "glv_batch_set_bufscale"):        # (likewise: `setbufscale k` for a batch -- windows of k * n frames, decimated on the device)
             L.glv_batch_set_bufscale.argtypes = [vp, C.c_uint32]
             L.glv_batch_bufscale.argtypes = [vp]
@@ -570,6 +581,29 @@ class Batch:
                                      ops: int, stream: int | None = None) -> None:
         """track_wave_frames_f32 from a planar recording (glv_batch_track_wave_frames_f32_planar); `rows` as track_at_f32_planar takes them"""
         self._track_wave_frames("f32_planar", rows, planar_pitch_frames(rows, self.streams), d_starts, steps, d_from, d_to, d_mod, frames, d_keys, keep, d_out, d_work, ops, stream)
+
+    # ---- track mode per stream: a table row, a rate row and a count of steps for every stream of the batch
+    def _track_each(self, kind: str, d_pcm, pitch_frames: int, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream) -> None:
+        tb = TrackTables(_ptr(d_starts), _ptr(d_ur), _ptr(d_counts))
+        _check(getattr(lib(), "glv_batch_track_each_" + kind)(self._h, _ptr(d_pcm), pitch_frames, C.byref(tb), steps, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def track_each_s16(self, d_pcm, pitch_frames: int, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_at_s16 / track_rates_s16 with tables per stream (glv_batch_track_each_s16): d_starts uint32 [streams][steps], row s is stream s's table; d_ur
+        float32 [streams][steps] or None (the batch's own ur at every step; not None: OP_GRAVITY and no OP_WAVE); d_counts uint32 [streams] or None (every stream
+        takes all steps; not None: a chain with OP_GRAVITY and / or OP_AVERAGE).  Stream s runs its first c = min(d_counts[s], steps) steps as if alone in a batch
+        with its own row; the rows of d_out behind c are what the call's last stage makes of a row of zeros; the batch's head advances by `steps` and every
+        stream's ring is left where that head expects it, so the next call continues each bit for bit and a stream with count 0 keeps its state.  All three in
+        device memory, read when the kernels run.  Forms, refusals, d_out and d_work (track_at_work_bytes) are track_at_s16's.
+        Tables: glava_amd.track_starts.stack_tables."""
+        self._track_each("s16", d_pcm, pitch_frames, d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
+
+    def track_each_f32(self, d_pcm, pitch_frames: int, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_each_s16 from a float recording (glv_batch_track_each_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
+        self._track_each("f32", d_pcm, pitch_frames, d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
+
+    def track_each_f32_planar(self, rows, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_each_f32 from a planar recording (glv_batch_track_each_f32_planar); `rows` as track_at_f32_planar takes them, no mono mix"""
+        self._track_each("f32_planar", rows, planar_pitch_frames(rows, self.streams), d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

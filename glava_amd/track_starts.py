@@ -98,6 +98,43 @@ def live_session_rates(rate: int, fps: int, frames: int, update_frames: int) -> 
     return starts, step_of_frame, ur
 
 
+def stack_tables(rows, steps: int | None = None):
+    """The three tables of glv_batch_track_each_s16 / _f32 / _f32_planar (Batch.track_each_*) from one (starts, ur) pair per stream, of any lengths -- as
+    renderer_starts / live_update_starts (ur None) and live_session_rates return them.  Every pair is padded to `steps` entries (default: the longest pair) by
+    repeating its last entry -- an entry behind a stream's count is never applied to state, and a window the recording holds costs no clamp -- and its own
+    length is its count.  Returns numpy arrays (starts uint32 [streams][steps], ur float32 [streams][steps], counts uint32 [streams]); ur is None where every
+    pair's is None, and a stream without rates among streams with them runs at 1.0, the value gl->ur starts from.  An empty pair is a stream that stands
+    still: count 0, its rows zeros and ones.  Refuses a pair whose tables differ in length, one longer than `steps`, and a start that does not fit a uint32."""
+    import numpy as np
+    rows = [(list(s), None if u is None else list(u)) for s, u in rows]
+    if not rows:
+        raise ValueError("stack_tables needs at least one stream")
+    for s, u in rows:
+        if u is not None and len(u) != len(s):
+            raise ValueError(f"a stream's tables differ in length: {len(s)} starts, {len(u)} rates")
+    longest = max(len(s) for s, _ in rows)
+    if steps is None:
+        steps = longest
+    _positive(steps=steps)
+    if longest > steps:
+        raise ValueError(f"a stream has {longest} steps, more than steps = {steps}")
+    with_rates = any(u is not None for _, u in rows)
+    starts = np.zeros((len(rows), steps), dtype=np.uint32)
+    ur = np.ones((len(rows), steps), dtype=np.float32) if with_rates else None
+    counts = np.zeros((len(rows),), dtype=np.uint32)
+    for i, (s, u) in enumerate(rows):
+        if any(not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0 or v >= 1 << 32 for v in s):
+            raise ValueError("a start must be an integer in [0, 2^32)")
+        counts[i] = len(s)
+        if s:
+            starts[i, :len(s)] = s
+            starts[i, len(s):] = s[-1]
+        if with_rates and u:
+            ur[i, :len(u)] = u
+            ur[i, len(u):] = u[-1]
+    return starts, ur, counts
+
+
 def _f32(x: float) -> float:
     from struct import pack, unpack
     return unpack("f", pack("f", x))[0]

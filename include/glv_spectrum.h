@@ -812,6 +812,52 @@ int glv_batch_track_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_
                                       uint32_t steps, const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream);
 int glv_batch_track_wave_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
                                            void* d_out, void* d_work, unsigned ops, void* hip_stream);
+/* Track mode PER STREAM: the table, rates and planar calls above move every stream of a batch in lockstep -- one row of window starts, one row of rates and one
+ * number of steps for all of them.  Listeners of a service sit at different positions of different recordings, drop different frames, end at different lengths,
+ * and one that seeks has to catch up while the others stand still.  These entries take tables with ONE ROW PER STREAM and a count of steps per stream; stream s
+ * then behaves as if it were alone in a batch with its own table for its own number of updates, bit for bit.  Added within ABI 7; detect by the symbol.
+ * Everything not said here is glv_batch_track_at_s16 / _f32 / _f32_planar: d_pcm / d_rows, d_out and d_work and their layouts, the form the ops and the batch
+ * select, the launches.  Sized by glv_batch_track_at_work_bytes(b, steps, ops): the rows add no region, and there is no other query.
+ *   Windows.  Window t of stream s begins min(d_starts[s * steps + t], pitch_frames - k n) frames into that stream's recording, k the batch's bufscale.  The clamp
+ *           is the kernels', so no launch reads outside the recordings whatever any table holds.  The tables are read when the kernels run: rewriting them in
+ *           stream order re-aims a captured hipGraph.
+ *   Rates.  With d_ur set, step t of stream s applies gravity with gravity_step * (1.0F / d_ur[s * steps + t]) -- the rates call's expression, row by row.  A
+ *           non-NULL d_ur is refused (GLV_ERR_INVALID) with GLV_OP_WAVE or without GLV_OP_GRAVITY, as glv_batch_track_rates_* refuses it.  With d_ur NULL the
+ *           batch's own ur applies at every step, in the arithmetic of the table call (texel state: the packed integer step wherever the host accepted it).
+ *   Counts. c_s = min(d_counts[s], steps), evaluated on the device.  For t < c_s the output of step t of stream s is bit for bit what glv_batch_track_rates_* /
+ *           _at_* writes for that step on a one-stream batch that holds stream s's state, recording and table row.  For t >= c_s the row of d_out is what the
+ *           call's last stage produces from a finished row of all zeros: zeros without bars, and the bars, texels or columns of a zero row with them -- defined,
+ *           so nothing stale is left behind.  A non-NULL d_counts is refused (GLV_ERR_INVALID) on a chain without state (neither GLV_OP_GRAVITY nor
+ *           GLV_OP_AVERAGE, or GLV_OP_WAVE): there is nothing to protect, and the caller ignores the rows it does not want.
+ *   State afterwards.  The batch's head advances by `steps` -- the host cannot see the counts, and the head is the batch's.  Stream s's gravity row and average
+ *           ring are those of c_s sequential updates of that stream, presented at the batch's new head: the ring slot that holds the row of age j under the
+ *           stream's own head sits where age j sits under (head + steps) % F.  The next process, ring or track call on the batch therefore continues every
+ *           stream bit for bit, glv_batch_save_streams returns for stream s the blob a one-stream batch returns after c_s updates, and a stream with c_s == 0
+ *           keeps its state bit for bit (its ring turned, every age in place).
+ *   Forms.  All three FFT forms the table call selects (windows; live on GLV_OP_BARS_ONLY batches; columns), gl_storage 0, 1 and 3, channels 1 and 2 (planar: no
+ *           mix), bufscale up to 16; and the wave form (GLV_OP_WAVE [| BARS] [| R16], two launches with bars as a table call's), which takes d_starts alone.
+ *   Refused, launching nothing and leaving the batch untouched: everything glv_batch_track_at_* refuses, in the same words and with the same codes; and with
+ *           GLV_ERR_INVALID a NULL tb or one not aligned for its pointers, a NULL or misaligned d_starts, and a d_ur or d_counts not 4-byte aligned.
+ * Cost of a count: the transform stage still computes the windows of steps t >= c_s (clamped, therefore safe) and only the scan skips them -- a skip in the
+ * transform would have to live in the frame kernel and is left for later.  A batch of listeners of very different lengths pays for the longest in stage (1).
+ * Kernels: the transform in per-stream table kinds of the frame kernel (glv_frame.h in_track_each: the table kinds with the entry read at f % (streams * steps);
+ * kinds of their own, because the index operand costs 58 of their 228 kernels registers or scratch beside the shared-table twins -- every frame kernel that
+ * existed is byte for byte the parent's), glv_decimate_kernel's three track kinds and glv_wave_kernel's three window kinds, which CHANGED (one uniform test, one
+ * index: registers and instruction counts in profiles/r25/track_each_isa.txt, which lists every object and kernel that is identical and every one that is not),
+ * and glv_track_each_scan_kernel (glv_misc.hip), which glv_batch_kernel_name reports where the table call reports glv_track_scan_kernel: the walk bounded by the
+ * stream's count (the look-ahead of 8 steps asks for no row and no rate at or beyond it), zeros behind it, and the ring written back turned by steps - c_s.
+ * Python: glava_amd.track_starts.stack_tables(rows) pads per-stream (starts, ur) pairs of any lengths to the longest and returns the three arrays. */
+typedef struct glv_track_tables {
+    const uint32_t* d_starts;  /* uint32 [streams][steps], device memory, 4-byte aligned: row s is stream s's table */
+    const float*    d_ur;      /* float  [streams][steps] or NULL: the batch's own ur at every step             */
+    const uint32_t* d_counts;  /* uint32 [streams] or NULL: every stream takes all `steps` steps                */
+} glv_track_tables;
+int glv_batch_track_each_s16
+    (glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_each_f32
+    (glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_each_f32_planar
+    (glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
