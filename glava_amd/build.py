@@ -24,16 +24,17 @@ ARCH = "gfx950"
 HIPFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
             "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 SIZES = (7, 8, 9, 10, 11, 12, 13, 14)
-SMALL = ("glv_bars", "glv_misc", "glv_track_frames", "glv_decimate", "glv_slots")    # the kernels beside the frame kernel, one object each: the bars passes of a second launch (slow to compile) / the small kernels / a frames track call's two / the bufscale stage / the stream slots
+SMALL = ("glv_bars", "glv_misc", "glv_track_frames", "glv_decimate", "glv_slots", "glv_pool")    # the kernels beside the frame kernel, one object each: the bars passes of a second launch (slow to compile) / the small kernels / a frames track call's two / the bufscale stage / the stream slots / a pool call's bufscale and waveform stages
 HOST = ("glv_api", "glv_wisdom", "glv_device_state", "glv_bar_tables", "glv_chain", "glv_track", "glv_multi")    # the host units (.cpp, compiled as HIP for the launch syntax of the headers)
 PARTS = (0, 1, 2, 3, 4, 5, 6, 7)  # glv_inst.hip is compiled per (size, part): s16 inputs / f32 inputs / the runner-up configuration / a track call's s16 windows / its f32 windows / both at a table's starts / planar f32 rows at a table's starts
 EACH_PARTS = (8, 9, 10)  # ... / parts 5, 6 and 7 with a table row per stream (glv_batch_track_each_*): kinds of their own, so parts of their own
+POOL_PARTS = (11, 12, 13)  # ... / parts 8, 9 and 10 over one pool of recordings through a span per stream (glv_batch_track_pool_*)
 
 
 def _inst_jobs(obj_dir: str, sizes, extra: list[str]):
     """largest sizes first: they compile slowest, the pool should not end on them"""
     return [("glv_inst.hip", os.path.join(obj_dir, f"glv_inst_{k}_{p}.o"), [f"-DGLV_LOG_NN={k}", f"-DGLV_INST_PART={p}", *extra])
-            for k in sorted(sizes, reverse=True) for p in PARTS + EACH_PARTS]
+            for k in sorted(sizes, reverse=True) for p in PARTS + EACH_PARTS + POOL_PARTS]
 HEADERS = ["glv_core.h", "glv_frame.h", "glv_kernel_tmpl.h", "glv_launch.h", "glv_launch_util.h", "glv_tables.h", "glv_winsplit.h", "glv_host.h",
            os.path.join("..", "..", "include", "glv_spectrum.h")]
 
@@ -104,7 +105,7 @@ def build_variant(name: str, extra_flags: list[str], sizes=SIZES, kernels_only: 
     jobs = _inst_jobs(obj_dir, sizes, extra_flags)
     reused = []
     if kernels_only:
-        reused = [os.path.join(OBJ, f"glv_inst_{k}_{p}.o") for k in SIZES if k not in sizes for p in PARTS + EACH_PARTS]
+        reused = [os.path.join(OBJ, f"glv_inst_{k}_{p}.o") for k in SIZES if k not in sizes for p in PARTS + EACH_PARTS + POOL_PARTS]
         reused += [os.path.join(OBJ, f"{u}.o") for u in HOST]
         if misc:        # the flags (also) touch the kernels of glv_misc.hip / glv_bars.hip: sizes=() compiles nothing else
             jobs += [(f"{m}.hip", os.path.join(obj_dir, f"{m}.o"), list(extra_flags)) for m in SMALL]

@@ -104,7 +104,7 @@ int batch_prepare(glv_batch* b) {
         b->attr_log_mode = (int) b->p.log_mode;
         glv::FrameArgs a;
         std::memset(&a, 0, sizeof(a));
-        for (int in_mode = 0; in_mode < glv::kFrameKinds + glv::kPlanarTrackKinds + glv::kEachTrackKinds; ++in_mode)      // (InMode and a table call's kinds, the planar one and the per-stream ones behind them)
+        for (int in_mode = 0; in_mode < glv::kFrameKinds + glv::kPlanarTrackKinds + glv::kEachTrackKinds + glv::kPoolTrackKinds; ++in_mode)      // (InMode and a table call's kinds, the planar one, the per-stream ones and the pool ones behind them)
             for (int v = 0; v < glv::frame_variants(b->log_nn); ++v)
                 for (int c = 0; c < glv::kFrameClasses; ++c)
                     (void) glv::launch_frame(b->log_nn, in_mode, (int) b->p.log_mode, v, (glv::FrameClass) c, a, 0, nullptr);

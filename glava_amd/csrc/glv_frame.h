@@ -47,7 +47,19 @@ GLV_HD constexpr bool in_track_each(int in_mode) { return in_mode >= IN_S16_TRAC
 GLV_HD constexpr int track_shared_kind(int in_mode) {
     return in_mode == IN_S16_TRACK_EACH ? IN_S16_TRACK_AT : in_mode == IN_F32_TRACK_EACH ? IN_F32_TRACK_AT : in_mode == IN_F32_PLANAR_TRACK_EACH ? IN_F32_PLANAR_TRACK_AT : in_mode;
 }
-GLV_HD constexpr bool in_track_table(int in_mode) { return in_mode == IN_S16_TRACK_AT || in_mode == IN_F32_TRACK_AT || in_mode == IN_F32_PLANAR_TRACK_AT || in_track_each(in_mode); }
+// The pool kinds (glv_batch_track_pool_s16 / _f32 / _f32_planar): the per-stream kinds over ONE buffer of pool_frames frames that every stream reads through a span
+// of its own (TrackSpan: first frame and length of the stream's recording within the pool) -- the entry is the per-stream kinds', the window's start is
+// pool_window_start below.  Numbered behind the per-stream kinds and kinds of their own for the reason those are: the span is a second load and a 64-bit operand,
+// which the per-stream kernels do not pay for (profiles/r26/track_pool_isa.txt).  Planned by the host as their shared-table siblings are.
+constexpr int IN_S16_TRACK_POOL = IN_S16_TRACK_EACH + kEachTrackKinds, IN_F32_TRACK_POOL = IN_S16_TRACK_POOL + 1, IN_F32_PLANAR_TRACK_POOL = IN_S16_TRACK_POOL + 2;
+constexpr int kPoolTrackKinds = 3;   // [kFrameKinds + kPlanarTrackKinds + kEachTrackKinds, ... + kPoolTrackKinds) are instantiated too
+GLV_HD constexpr bool in_track_pool(int in_mode) { return in_mode >= IN_S16_TRACK_POOL && in_mode < IN_S16_TRACK_POOL + kPoolTrackKinds; }
+// the shared-table kind a pool kind runs the pipeline of (every other kind: track_shared_kind's answer)
+GLV_HD constexpr int track_pool_shared_kind(int in_mode) {
+    return in_mode == IN_S16_TRACK_POOL ? IN_S16_TRACK_AT : in_mode == IN_F32_TRACK_POOL ? IN_F32_TRACK_AT : in_mode == IN_F32_PLANAR_TRACK_POOL ? IN_F32_PLANAR_TRACK_AT
+                                                                                                                                                   : track_shared_kind(in_mode);
+}
+GLV_HD constexpr bool in_track_table(int in_mode) { return in_mode == IN_S16_TRACK_AT || in_mode == IN_F32_TRACK_AT || in_mode == IN_F32_PLANAR_TRACK_AT || in_track_each(in_mode) || in_track_pool(in_mode); }
 enum Epi { EPI_RAW = 0, EPI_MAG = 1, EPI_MAG_STATE = 2, EPI_RAW_STATE = 3 };
 
 // ops bits as in include/glv_spectrum.h
@@ -149,12 +161,41 @@ struct TrackWindows {
 GLV_HD uint32_t track_table_entry(const TrackWindows& w, uint32_t f) { return w.starts[f % w.table_len]; }
 // Where window t of stream s begins, in frames; `entry` is starts[t] as the caller read it (unused without a table).  The kernel's rule and the host side of
 // the same map, for the emulator and the tests' mirror.
+// NOT the rule of a pool call (glv_batch_track_pool_*): there `pitch_frames` carries the pool's frames and `hop` the address of the spans (track_pool_spans),
+// and a window begins where pool_window_start says -- evaluated on a pool call's TrackWindows this would give s * pool_frames.
 GLV_HD constexpr uint64_t track_window_start(const TrackWindows& w, uint32_t s, uint32_t t, uint32_t entry = 0) {
     return (uint64_t) s * w.pitch_frames + (w.starts ? (uint64_t) (entry < w.start_max ? entry : w.start_max) : (uint64_t) t * w.hop);
 }
 GLV_HD constexpr uint64_t track_window_row(const TrackWindows& w, uint32_t s, uint32_t t) {
     return w.step_major ? ((uint64_t) t * w.streams + s) * 2u : ((uint64_t) s * w.steps + t) * 2u;
 }
+// A pool call (glv_batch_track_pool_*): one record per stream in device memory, 16 bytes on 16 (include/glv_spectrum.h glv_track_span, field by field), read
+// with one 16-byte load when the kernels run.
+struct alignas(16) TrackSpan { uint64_t first; uint32_t frames, reserved; };
+// ... and the pool itself, as the small kernels take it (glv_pool.hip: an argument of their own).  The frame kernel's pool kinds find both in the TrackWindows
+// they already take, whose size and offsets stay: `pitch_frames` carries the pool's frames (the planar kind's channel stride) and `hop`, which no table call
+// walks at, carries the address of the spans (track_pool_spans) -- FrameArgs keeps its size, so every frame kernel that exists keeps its descriptor.
+struct TrackPool { const TrackSpan* spans; uint64_t frames; };
+static_assert(sizeof(TrackWindows::hop) >= sizeof(void*), "a pool call's TrackWindows::hop carries the address of its spans");
+GLV_HD const TrackSpan* track_pool_spans(const TrackWindows& w) { return reinterpret_cast<const TrackSpan*>(static_cast<uintptr_t>(w.hop)); }
+// Where a window of `window` = k n frames begins in a pool of pool_frames >= window frames, counted from the pool's first frame: `entry` frames into the span
+// [first, first + frames), clamped to the span's last whole window, and whatever the span holds clamped to the pool's last whole window --
+//     min(first + min(entry, frames >= window ? frames - window : 0), pool_frames - window)
+// in 64-bit arithmetic that cannot wrap (the sum is formed only where it lies below the pool's last window).  A well-formed span (frames >= window, first +
+// frames <= pool_frames) never meets the outer clamp, so no table moves a stream out of its own recording; a malformed one reads inside the pool all the same.
+// The kernels' rule (the frame kernel's pool kinds, glv_pool.hip), the launchers' and the tests' mirror (glava_amd.track_starts.pool_window_start).
+GLV_HD constexpr uint64_t pool_window_start(uint64_t first, uint32_t frames, uint32_t entry, uint64_t pool_frames, uint64_t window) {
+    const uint64_t ext = frames >= window ? frames - window : 0u, into = entry < ext ? entry : ext, last = pool_frames - window;
+    return first >= last || last - first <= into ? last : first + into;
+}
+static_assert(sizeof(TrackSpan) == 16 && alignof(TrackSpan) == 16, "a span is one 16-byte load");
+static_assert(pool_window_start(1ull << 33, 5000u, 100u, (1ull << 33) + 5000u, 1024u) == (1ull << 33) + 100u, "first = 2^33: the sum is 64-bit");
+static_assert(pool_window_start(1ull << 33, 5000u, 0xFFFFFFFFu, (1ull << 34), 1024u) == (1ull << 33) + 3976u, "entry 0xFFFFFFFF: clamped to the span's last window");
+static_assert(pool_window_start((1ull << 32) - 8u, 0xFFFFFFFFu, 0xFFFFF000u, 1ull << 34, 1024u) == (1ull << 33) - 4104u, "a large entry into a large span: no 32-bit wrap");
+static_assert(pool_window_start(700u, 1000u, 77u, 1ull << 20, 1024u) == 700u, "frames < k n: every entry clamps to 0");
+static_assert(pool_window_start(9000u, 5000u, 3000u, 10000u, 1024u) == 8976u, "first + frames > pool_frames: the pool's last window");
+static_assert(pool_window_start(10000u, 5000u, 0u, 10000u, 1024u) == 8976u && pool_window_start(~0ull, 5000u, 3000u, 10000u, 1024u) == 8976u, "first >= pool_frames");
+static_assert(pool_window_start(0u, 1024u, 5u, 1024u, 1024u) == 0u, "a pool of one window");
 
 struct FrameArgs {
     const void* in;        // s16: int16 [units/2][n][2] (a unit is one channel row of a frame);  f32 planar: float [units][n];

@@ -10,6 +10,7 @@
 //   part 6  part 4 likewise (IN_F32_TRACK_AT)
 //   part 7  planar float recordings at a table's starts (IN_F32_PLANAR_TRACK_AT: glv_batch_track_at_f32_planar), as parts 3-6 are built
 //   parts 8, 9, 10  parts 5, 6, 7 with a table row per stream (IN_S16_TRACK_EACH, IN_F32_TRACK_EACH, IN_F32_PLANAR_TRACK_EACH: glv_batch_track_each_*)
+//   parts 11, 12, 13  parts 8, 9, 10 over one pool through a span per stream (IN_S16_TRACK_POOL, IN_F32_TRACK_POOL, IN_F32_PLANAR_TRACK_POOL: glv_batch_track_pool_*)
 // The knob set per size is the measured best of tools/tune.py
 // (profiles/tune_r01_final.txt, earlier sweeps in profiles/tune_r01.txt); see DESIGN.md "Kernel configuration".
 #include "glv_kernel_tmpl.h"
@@ -19,7 +20,7 @@
 #error "compile with -DGLV_LOG_NN=<7..14>"
 #endif
 #ifndef GLV_INST_PART
-#error "compile with -DGLV_INST_PART=<0..10>"
+#error "compile with -DGLV_INST_PART=<0..13>"
 #endif
 
 namespace glv {
@@ -91,6 +92,9 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part7)(int variant, int 
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part8)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part9)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part10)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part11)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part12)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part13)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st);
 
 template <int IN_MODE, int V>
 static hipError_t launch_log(int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
@@ -174,10 +178,28 @@ hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part9)(int variant, int 
     if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_TRACK_EACH, 1>(log_mode, cls, a, grid, st); }
     return hipErrorInvalidValue;
 }
-#else
+#elif GLV_INST_PART == 10
 hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part10)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
     if (variant == 0) return launch_log<IN_F32_PLANAR_TRACK_EACH, 0>(log_mode, cls, a, grid, st);
     if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_PLANAR_TRACK_EACH, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#elif GLV_INST_PART == 11
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part11)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_S16_TRACK_POOL, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_S16_TRACK_POOL, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#elif GLV_INST_PART == 12
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part12)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_F32_TRACK_POOL, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_TRACK_POOL, 1>(log_mode, cls, a, grid, st); }
+    return hipErrorInvalidValue;
+}
+#else
+hipError_t GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part13)(int variant, int log_mode, FrameClass cls, const FrameArgs& a, int grid, hipStream_t st) {
+    if (variant == 0) return launch_log<IN_F32_PLANAR_TRACK_POOL, 0>(log_mode, cls, a, grid, st);
+    if constexpr (kNV > 1) { if (variant == 1) return launch_log<IN_F32_PLANAR_TRACK_POOL, 1>(log_mode, cls, a, grid, st); }
     return hipErrorInvalidValue;
 }
 #endif
@@ -192,6 +214,9 @@ hipError_t GLV_CAT(launch_frame_, GLV_LOG_NN)(int in_mode, int log_mode, int var
     if (in_mode == IN_S16_TRACK_EACH) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part8)(variant, log_mode, cls, a, grid, st);
     if (in_mode == IN_F32_TRACK_EACH) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part9)(variant, log_mode, cls, a, grid, st);
     if (in_mode == IN_F32_PLANAR_TRACK_EACH) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part10)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_S16_TRACK_POOL) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part11)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_F32_TRACK_POOL) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part12)(variant, log_mode, cls, a, grid, st);
+    if (in_mode == IN_F32_PLANAR_TRACK_POOL) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part13)(variant, log_mode, cls, a, grid, st);
     if (variant == 1) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part2)(in_mode, log_mode, cls, a, grid, st);
     if (variant != 0) return hipErrorInvalidValue;
     if (in_mode == IN_S16_STEREO || in_mode == IN_S16_RING) return GLV_CAT(GLV_CAT(launch_frame_, GLV_LOG_NN), _part0)(in_mode, log_mode, cls, a, grid, st);

@@ -196,6 +196,13 @@ static __device__ __forceinline__ uint32_t maybe_scalar(uint32_t v) {
     else return v;
 }
 
+// a pool call's span of stream s (glv_frame.h TrackSpan): one 16-byte load from global memory (the address travels as an integer: say so, or the load is a flat one)
+static __device__ __forceinline__ TrackSpan load_track_span(const TrackSpan* spans, uint32_t s) {
+    typedef uint32_t span_u4 __attribute__((ext_vector_type(4)));
+    const span_u4 v = *(const __attribute__((address_space(1))) span_u4*) (reinterpret_cast<uintptr_t>(spans) + (uintptr_t) s * sizeof(TrackSpan));
+    return TrackSpan{ (uint64_t) v.x | (uint64_t) v.y << 32, v.z, v.w };
+}
+
 template <int LOG_NN, int IN_KIND, int LOG_MODE, int SLOTS, int NBUF, int TWREG, bool WINLDS, int OCC, int PREFETCH, int TILTREG,
           int LOG_E, int STATEFUL, int WPRE = 0>
 __global__ void __launch_bounds__((Frame<LOG_NN, LOG_E>::T * SLOTS), OCC)
@@ -205,8 +212,10 @@ glv_frame_kernel(const FrameArgs a) {
     constexpr int T = FR::T, N = FR::N;
     // a per-stream table kind (glv_frame.h in_track_each) is its shared-table sibling in everything but the entry it reads (track_entry below): the pipeline is
     // picked by IN_MODE, the sibling's kind, and every other kind is its own IN_MODE
-    constexpr int IN_MODE = track_shared_kind(IN_KIND);
-    constexpr bool TRACK_EACH = in_track_each(IN_KIND);
+    // a pool kind (in_track_pool: glv_batch_track_pool_*) likewise, and it reads its entry as the per-stream kinds do; what differs is track_at, through the stream's span
+    constexpr int IN_MODE = track_pool_shared_kind(IN_KIND);
+    constexpr bool TRACK_POOL = in_track_pool(IN_KIND);
+    constexpr bool TRACK_EACH = in_track_each(IN_KIND) || TRACK_POOL;
     constexpr bool RING = IN_MODE == IN_S16_RING;
     constexpr bool TRACK_TABLE = in_track_table(IN_MODE);   // a table call's kinds: the window's start comes from a.trk.starts (track_entry / track_at below)
     constexpr bool TRACK = IN_MODE == IN_S16_TRACK || IN_MODE == IN_S16_TRACK_AT;    // windows where they lie in a recording (a.trk): never a ring, stateless classes only (launch_variant)
@@ -461,22 +470,33 @@ glv_frame_kernel(const FrameArgs a) {
     // and track_at is what it was (the table is a template constant: their code does not change).
     // The per-stream kinds (TRACK_EACH: glv_batch_track_each_*): the entry of frame f is starts[f % table_len], entry t of row s of uint32 [streams][steps] -- asked
     // for where the shared-table kinds ask for theirs, clamped as theirs is, and for every f an entry of the table the call names.
+    // The pool kinds (TRACK_POOL: glv_batch_track_pool_*): every stream reads ONE buffer of a.trk.pitch_frames frames through the 16-byte span of stream s = f / steps
+    // (glv_frame.h TrackSpan, track_pool_spans), and the window begins at pool_window_start -- clamped into the span, and whatever the span holds into the pool: the
+    // bound above holds with [start, + n) inside the pool.  The span is a second load an address depends on: track_span(f) is asked for exactly where track_entry(f)
+    // is, one frame ahead and together with the previous frame's PCM loads, and W retires all three; s < streams, so the record read is one the call names.  Every
+    // other kind: an empty value, no load, and track_at is what it was.  The planar pool kind's two rows lie pitch_frames = pool_frames floats apart
+    // (track_row_at, as ever) and a stream has no rows of its own to skip.
+    struct NoSpan {};
+    using TSpan = typename std::conditional<TRACK_POOL, TrackSpan, NoSpan>::type;
+    auto track_span = [&](uint32_t f) -> TSpan { if constexpr (TRACK_POOL) return load_track_span(track_pool_spans(a.trk), f / a.trk.steps); else return TSpan(); };
     struct TrackAt { const void* win; size_t row0; };
     auto track_entry = [&](uint32_t f) -> uint32_t { if constexpr (TRACK_EACH) return track_table_entry(a.trk, f); else if constexpr (TRACK_TABLE) return a.trk.starts[f % a.trk.steps]; else return 0u; };
-    auto track_at = [&](uint32_t f, uint32_t entry) -> TrackAt {
+    auto track_at = [&](uint32_t f, uint32_t entry, TSpan span = TSpan()) -> TrackAt {
         const uint32_t s = f / a.trk.steps, t = f - s * a.trk.steps;
         uint64_t start;
-        if constexpr (TRACK_TABLE) start = (uint64_t) s * a.trk.pitch_frames + (entry < a.trk.start_max ? entry : a.trk.start_max);      // (track_window_start with a table)
+        (void) span;
+        if constexpr (TRACK_POOL) start = pool_window_start(span.first, span.frames, entry, a.trk.pitch_frames, (uint64_t) N);
+        else if constexpr (TRACK_TABLE) start = (uint64_t) s * a.trk.pitch_frames + (entry < a.trk.start_max ? entry : a.trk.start_max);      // (track_window_start with a table)
         else start = (uint64_t) s * a.trk.pitch_frames + (uint64_t) t * a.trk.hop;
-        if constexpr (TRACKP) start += (uint64_t) s * a.trk.pitch_frames;      // planar: a stream is TWO rows of pitch_frames floats, and this is where its channel-0 window begins
+        if constexpr (TRACKP && !TRACK_POOL) start += (uint64_t) s * a.trk.pitch_frames;      // planar: a stream is TWO rows of pitch_frames floats, and this is where its channel-0 window begins
         return { static_cast<const char*>(a.in) + start * (TRACKF ? 8u : 4u), a.trk.step_major ? ((size_t) t * a.trk.streams + s) * 2u : (size_t) f * 2u };
     };
-    (void) track_at; (void) track_entry;
+    (void) track_at; (void) track_entry; (void) track_span;
     // IN_F32_PLANAR_TRACK_AT: one slot = one channel ROW, as in the planar pipeline.  Row r of the launch is channel r & 1 of frame f = r >> 1, so track_at's rules
     // hold with f < units / 2 (row_of clamps an idle slot and every look-ahead to the last row): the window of channel ch begins pitch_frames floats behind
     // channel 0's, inside row 2 s + ch of the recording -- the clamp to start_max = pitch_frames - n keeps its n floats there, whatever the table holds.
-    auto track_row_at = [&](uint32_t row, uint32_t entry) -> TrackAt {
-        const TrackAt w = track_at(row >> 1, entry);
+    auto track_row_at = [&](uint32_t row, uint32_t entry, TSpan span = TSpan()) -> TrackAt {
+        const TrackAt w = track_at(row >> 1, entry, span);
         return { static_cast<const char*>(w.win) + (uint64_t) (row & 1u) * a.trk.pitch_frames * 4u, w.row0 + (row & 1u) };
     };
     (void) track_row_at;
@@ -516,13 +536,15 @@ glv_frame_kernel(const FrameArgs a) {
         typename FR::Raw raw;
         size_t trow = 0, trow_next = 0;      // TRACK: channel-0 row of the slot's current frame / of the frame whose samples `raw` holds
         uint32_t tent = 0;                   // TRACK, a table call: the table's entry for the frame the NEXT stage A fetches, asked for by the stage A before it
-        (void) trow; (void) trow_next; (void) frame_ptr; (void) tent;
+        TSpan tspan = TSpan();               // ... and, a pool call, the span of that frame's stream, asked for with it
+        (void) trow; (void) trow_next; (void) frame_ptr; (void) tent; (void) tspan;
         if (blockIdx.x * SLOTS < nframes) {
             int tid = tid_outer;
             asm volatile("" : "+v"(tid));
             if constexpr (TRACK) {
-                const TrackAt w = track_at(frame_of(0), track_entry(frame_of(0))); FR::load_pcm_at(raw, w.win, tid); trow = w.row0;
+                const TrackAt w = track_at(frame_of(0), track_entry(frame_of(0)), track_span(frame_of(0))); FR::load_pcm_at(raw, w.win, tid); trow = w.row0;
                 if constexpr (TRACK_TABLE) tent = track_entry(frame_of(1));      // (guarded: the mere call cost the hop kinds registers)
+                if constexpr (TRACK_POOL) tspan = track_span(frame_of(1));
             } else
             FR::template load_pcm<RING>(raw, frame_ptr(frame_of(0)), tid, a.rot);
             FR::template unpack_window<0, WSPLIT>(v, raw, win, tid, 0u, a.mono != 0);
@@ -537,7 +559,8 @@ glv_frame_kernel(const FrameArgs a) {
             const bool active = fraw < nframes;
             const uint32_t f = frame_of(m);
             if constexpr (TRACK) {                                                               // A (and the entry of the frame after: W retires both)
-                if (ch) { const TrackAt w = track_at(frame_of(m + 1), tent); FR::load_pcm_at(raw, w.win, tid); trow_next = w.row0; if constexpr (TRACK_TABLE) tent = track_entry(frame_of(m + 2)); }
+                if (ch) { const TrackAt w = track_at(frame_of(m + 1), tent, tspan); FR::load_pcm_at(raw, w.win, tid); trow_next = w.row0; if constexpr (TRACK_TABLE) tent = track_entry(frame_of(m + 2));
+                          if constexpr (TRACK_POOL) tspan = track_span(frame_of(m + 2)); }
             } else
             if (ch) FR::template load_pcm<RING>(raw, frame_ptr(frame_of(m + 1)), tid, a.rot);   // A
             if constexpr (LIVE_PRE) { FR::live_prefetch(live_pre, (size_t) f * 2 + ch, tid, a); live_pre_ptr = &live_pre; }   // A': the row's old state (W awaits it)
@@ -600,12 +623,15 @@ glv_frame_kernel(const FrameArgs a) {
         typename FR::RawF raw;
         size_t trow = 0, trow_next = 0;      // where the slot's current row goes / the row whose samples `raw` holds
         uint32_t tent = 0;                   // the table's entry for the row the NEXT stage A fetches
+        TSpan tspan = TSpan();               // ... and, a pool call, the span of that row's stream
+        (void) tspan;
         if (step_base(0) < a.units) {
             int tid = tid_outer;
             asm volatile("" : "+v"(tid));
             const uint32_t r0 = row_of(step_base(0));
-            const TrackAt w = track_row_at(r0, track_entry(r0 >> 1)); FR::load_f32_raw_at(raw, w.win, tid); trow = w.row0;
+            const TrackAt w = track_row_at(r0, track_entry(r0 >> 1), track_span(r0 >> 1)); FR::load_f32_raw_at(raw, w.win, tid); trow = w.row0;
             tent = track_entry(row_ahead(1, step_base(0)) >> 1);
+            if constexpr (TRACK_POOL) tspan = track_span(row_ahead(1, step_base(0)) >> 1);
             FR::window_f32_raw(v, raw, win, tid);
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -615,9 +641,10 @@ glv_frame_kernel(const FrameArgs a) {
             int tid = tid_outer;
             asm volatile("" : "+v"(tid));
             const bool active = base + slot < a.units;
-            const TrackAt w = track_row_at(row_ahead(step + 1, base), tent);
+            const TrackAt w = track_row_at(row_ahead(step + 1, base), tent, tspan);
             FR::load_f32_raw_at(raw, w.win, tid); trow_next = w.row0;                            // A (unconditional)
             tent = track_entry(row_ahead(step + 2, base) >> 1);                                  // (the entry of the row after: W retires it)
+            if constexpr (TRACK_POOL) tspan = track_span(row_ahead(step + 2, base) >> 1);
             GLV_SCHED_FENCE();
             BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);                    // B
             GLV_SCHED_FENCE();
@@ -647,14 +674,17 @@ glv_frame_kernel(const FrameArgs a) {
             typename FR::RawF raw;
             size_t trow = 0, trow_next = 0;      // TRACKF: channel-0 row of the slot's current frame / of the frame whose channel-0 samples `raw` holds or held last
             uint32_t tent = 0, tent_next = 0;    // TRACKF, a table call: the table's entries for the slot's current frame and its next, each asked for a frame ahead
-            (void) trow; (void) trow_next; (void) frame_ptr; (void) tent; (void) tent_next;
+            TSpan tspan = TSpan(), tspan_next = TSpan();      // ... and, a pool call, the spans of those frames' streams
+            (void) trow; (void) trow_next; (void) frame_ptr; (void) tent; (void) tent_next; (void) tspan; (void) tspan_next;
             if (blockIdx.x * SLOTS < nframes) {
                 int tid = tid_outer;
                 asm volatile("" : "+v"(tid));
                 if constexpr (TRACKF) {
                     if constexpr (TRACK_TABLE) tent = track_entry(frame_of(0));
-                    const TrackAt w = track_at(frame_of(0), tent); FR::template load_f32s_raw<false>(raw, w.win, tid, 0u); trow = w.row0;
+                    if constexpr (TRACK_POOL) tspan = track_span(frame_of(0));
+                    const TrackAt w = track_at(frame_of(0), tent, tspan); FR::template load_f32s_raw<false>(raw, w.win, tid, 0u); trow = w.row0;
                     if constexpr (TRACK_TABLE) tent_next = track_entry(frame_of(1));
+                    if constexpr (TRACK_POOL) tspan_next = track_span(frame_of(1));
                 } else
                 FR::template load_f32s_raw<RINGF>(raw, frame_ptr(frame_of(0)), tid, 0u, a.rot);
                 FR::window_f32_raw(v, raw, win, tid);
@@ -668,9 +698,10 @@ glv_frame_kernel(const FrameArgs a) {
                 const bool active = blockIdx.x * SLOTS + m * fstride + slot < nframes;
                 const uint32_t f = frame_of(m);
                 if constexpr (TRACKF) {                                                              // A (unconditional): ch 0 fetches its own window's other channel
-                    const TrackAt w = track_at(frame_of(m + ch), ch ? tent_next : tent);
+                    const TrackAt w = track_at(frame_of(m + ch), ch ? tent_next : tent, ch ? tspan_next : tspan);
                     FR::template load_f32s_raw<false>(raw, w.win, tid, ch ^ 1u);
-                    if (ch) { trow_next = w.row0; if constexpr (TRACK_TABLE) { tent = tent_next; tent_next = track_entry(frame_of(m + 2)); } }      // (the entry of the frame after: W retires it)
+                    if (ch) { trow_next = w.row0; if constexpr (TRACK_TABLE) { tent = tent_next; tent_next = track_entry(frame_of(m + 2)); }
+                              if constexpr (TRACK_POOL) { tspan = tspan_next; tspan_next = track_span(frame_of(m + 2)); } }      // (the entry of the frame after: W retires it)
                 } else
                 FR::template load_f32s_raw<RINGF>(raw, frame_ptr(frame_of(m + ch)), tid, ch ^ 1u, a.rot);   // A (unconditional)
                 GLV_SCHED_FENCE();
@@ -700,7 +731,7 @@ glv_frame_kernel(const FrameArgs a) {
         if constexpr (TRACK) {
             // not pipelined (no production configuration): one slot = one channel row of the window its frame names, one division per row
             typename FR::Raw raw;
-            const TrackAt w = track_at(row >> 1, track_entry(row >> 1));
+            const TrackAt w = track_at(row >> 1, track_entry(row >> 1), track_span(row >> 1));
             FR::load_pcm_at(raw, w.win, tid);
             GLV_SCHED_FENCE();
             FR::template unpack_window<0, WSPLIT>(v, raw, win, tid, row & 1u, a.mono != 0);
@@ -710,7 +741,7 @@ glv_frame_kernel(const FrameArgs a) {
         } else
         if constexpr (TRACKF) {
             // mono at every size, every chain where the configuration is not pipelined for f32 (LOG_E 5): one slot = one channel row of the window its frame names
-            const TrackAt w = track_at(row >> 1, track_entry(row >> 1));
+            const TrackAt w = track_at(row >> 1, track_entry(row >> 1), track_span(row >> 1));
             FR::load_f32_stereo_window_at(v, w.win, win, tid, row & 1u, a.mono != 0);
             BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
             finish_row(v, w.row0 + (row & 1u), tid, active);
@@ -718,7 +749,7 @@ glv_frame_kernel(const FrameArgs a) {
         } else
         if constexpr (TRACKP) {
             // every chain where the configuration is not pipelined for f32 (LOG_E 5): one slot = one channel row, read where its frame's entry says
-            const TrackAt w = track_row_at(row, track_entry(row >> 1));
+            const TrackAt w = track_row_at(row, track_entry(row >> 1), track_span(row >> 1));
             FR::load_f32_window_at(v, w.win, win, tid);
             BD::template run<0>(v, tw_all, a.tw, xslot, tid, xcount, lds_tw, sy);
             finish_row(v, w.row0, tid, active);

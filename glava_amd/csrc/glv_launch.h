@@ -114,6 +114,14 @@ struct Decimate {
 };
 constexpr size_t kDecimateGridCap = 256 * 8;       // 256 CUs x 8 resident 256-lane workgroups; the kernel's loop takes what lies beyond
 hipError_t launch_decimate(int kind, const Decimate& d, hipStream_t st);
+// A pool call (glv_pool.hip; glv_batch_track_pool_s16 / _f32 / _f32_planar): the three track kinds of the decimation and the three window kinds of the waveform
+// kernel over ONE buffer of pool.frames frames, each stream through its span -- window (s, t) begins pool_window_start(spans[s].first, spans[s].frames, entry,
+// pool.frames, k n) frames into the pool (glv_frame.h: clamped into the span, and into the pool whatever the span holds), entry = starts[s * steps + t] of per-stream
+// rows.  The pool is an argument of its own: Decimate, TrackWindows and WaveWindows keep their size and offsets, and their pitch_frames is the planar kinds' channel
+// stride, pool.frames.  Kernels of their own beside glv_decimate_kernel and glv_wave_kernel, which keep their code; the arithmetic is theirs, line by line.
+// Refused: a null or misaligned span table, pool.frames below a window, a table that is not a row per stream, DEC_F32_PLANAR (a process call's kind).
+hipError_t launch_decimate_pool(int kind, const Decimate& d, const TrackPool& pool, hipStream_t st);
+hipError_t launch_wave_track_pool(const void* pool_pcm, bool f32, const WaveWindows& w, const TrackPool& pool, bool mono, uint32_t n, void* out, bool r16, uint32_t limit, hipStream_t st);
 // Chosen streams of a batch (glv_slots.hip; glv_batch_reset_streams / _save_streams / _load_streams): zero their state, gather it into blobs in the portable
 // form, or scatter blobs back -- one launch each.  A stream's portable bytes are the regions below back to back (`start` = the sum of the stream_bytes before);
 // a region is the stream's stream_bytes of one device array, one or two blocks of chan_bytes = mod << log_unit bytes, and portable unit u of a block is array

@@ -34,6 +34,7 @@ namespace {
 struct TrackInput {
     enum Kind { S16 = 0, F32 = 1, F32_PLANAR = 2 } kind;
     bool rows = false;      // the call's tables have a row per stream (glv_batch_track_each_*: set by track_each, read where the wave form's windows are laid out)
+    glv::TrackPool pool = {nullptr, 0};      // a pool call (glv_batch_track_pool_*: set by track_pool): d_pcm is ONE buffer of pool.frames frames, stream s reads it through pool.spans[s]
     TrackInput(bool f32 = false) : kind(f32 ? F32 : S16) {}
     TrackInput(Kind k) : kind(k) {}
     explicit operator bool() const { return kind != S16; }
@@ -289,10 +290,16 @@ int track_windows(glv_batch* b, const TrackPlan& tp, glv::FrameArgs& a, glv::Fra
     int mode = !tp.starts ? hop_mode : tp.f32 ? glv::IN_F32_TRACK_AT : glv::IN_S16_TRACK_AT;      // a table call: the kernel kinds that read it, planned as the hop kinds
     if (tp.f32.planar()) { hop_mode = glv::IN_F32_PLANAR; mode = glv::IN_F32_PLANAR_TRACK_AT; }      // planar rows (a table call: track_at): the planar pipeline's plan and wisdom
     if (tp.each) mode = tp.f32.planar() ? glv::IN_F32_PLANAR_TRACK_EACH : tp.f32 ? glv::IN_F32_TRACK_EACH : glv::IN_S16_TRACK_EACH;      // a table row per stream: the kinds that index it, planned as their siblings
+    const glv::TrackPool& pool = tp.f32.pool;
+    if (pool.spans) {      // a pool call (a per-stream call: track_pool): the pool's frames where the pitch was -- the planar kind's channel stride -- and the spans where no table call has a hop
+        a.trk.pitch_frames = pool.frames; a.trk.hop = (uint64_t) reinterpret_cast<uintptr_t>(pool.spans); a.trk.start_max = 0;
+        mode = tp.f32.planar() ? glv::IN_F32_PLANAR_TRACK_POOL : tp.f32 ? glv::IN_F32_TRACK_POOL : glv::IN_S16_TRACK_POOL;
+    }
     if (dec) {
         glv::Decimate d = {};
         d.in = d_pcm; d.out = dec; d.n = b->p.n; d.k = b->bufscale; d.mono = b->p.channels == 1 && !tp.f32.planar() ? 1u : 0u; d.w = a.trk;      // (planar rows are taken as they are)
-        const hipError_t e = glv::launch_decimate(tp.f32.planar() ? glv::DEC_F32_PLANAR_TRACK : tp.f32 ? glv::DEC_F32 : glv::DEC_S16, d, st); ++b->last_launches;
+        const int kind = tp.f32.planar() ? glv::DEC_F32_PLANAR_TRACK : tp.f32 ? glv::DEC_F32 : glv::DEC_S16;
+        const hipError_t e = pool.spans ? glv::launch_decimate_pool(kind, d, pool, st) : glv::launch_decimate(kind, d, st); ++b->last_launches;
         if (e != hipSuccess) return fail(GLV_ERR_HIP, "bufscale launch failed: %s", hipGetErrorString(e));
         a.in = dec; hop_mode = mode = glv::IN_F32_PLANAR;      // row r of the region becomes row r of `rows`: the index the windows kinds give window (s, t)
     }
@@ -484,6 +491,7 @@ int track_wave(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_f
     w.units = b->streams * 2u; w.steps = steps; w.hop = hop; w.pitch_frames = pitch_frames;
     w.starts = d_starts; w.start_max = pitch_frames - b->p.n; w.planar = f32.planar() ? 1u : 0u;
     if (f32.rows) w.hop = steps;      // a per-stream call: with a table `hop` is the table's own -- uint32 [streams][steps], row s is stream s's
+    if (f32.pool.spans) { w.pitch_frames = f32.pool.frames; w.start_max = 0; }      // a pool call: the planar kind's channel stride; the clamp is the span's and the pool's
     // (a store's 32-bit lane offset spans 4 rows of the workgroup: `units` rows apart by steps)
     w.by_steps = b->track_wave_by_steps && (4ull * w.units + 2u) * b->p.bars * 4u <= 0xffffffffull ? 1u : 0u;
     if (int rc = timed_launch_begin(b, st)) return rc;
@@ -503,7 +511,8 @@ int track_wave(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_f
     } else {
         if (ops & GLV_OP_BARS) pl.out = pl.rows = static_cast<float*>(d_work);
         else pl.out = static_cast<float*>(d_out);
-        e = glv::launch_wave_track(d_pcm, (bool) f32, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
+        e = f32.pool.spans ? glv::launch_wave_track_pool(d_pcm, (bool) f32, w, f32.pool, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st)
+                           : glv::launch_wave_track(d_pcm, (bool) f32, w, mono, b->p.n, pl.out, pl.wave_r16, pl.wave_limit, st);
         b->kernel_name = "glv_wave_kernel";
     }
     ++b->last_launches;
@@ -571,6 +580,22 @@ int track_each(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_f
         return fail(GLV_ERR_INVALID, "the chain keeps no state for d_counts to protect: counts need GLV_OP_GRAVITY and / or GLV_OP_AVERAGE and no GLV_OP_WAVE (ops 0x%x)", ops);
     f32.rows = true;
     return track_at(b, d_pcm, f32, pitch_frames, tb->d_starts, steps, d_out, d_work, ops, st, nullptr, tb, tb->d_ur);
+}
+// glv_batch_track_pool_s16 / _f32 / _f32_planar: a per-stream call over ONE buffer of pool_frames frames, stream s through d_spans[s].  What can be said of the pool
+// without the batch's plan -- the pointers, and that it holds one window -- then the per-stream call, and through it the table call, with the pool handed on in
+// TrackInput: their plan, their workspace, their refusals in their words.  With a pool the pitch rule is pool_frames >= k n and nothing else is asked: the plans
+// see pool_frames where they saw pitch_frames, saturated (their own rule for a table call is the same one: a recording holds a window).  Nothing here launches.
+static_assert(sizeof(glv_track_span) == sizeof(glv::TrackSpan) && offsetof(glv_track_span, first) == offsetof(glv::TrackSpan, first)
+              && offsetof(glv_track_span, frames) == offsetof(glv::TrackSpan, frames), "the kernels read the header's record");
+int track_pool(glv_batch* b, const void* d_pool, TrackInput f32, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, void* d_out,
+               void* d_work, unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!d_pool || !d_spans) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_spans) & 15u) return fail(GLV_ERR_INVALID, "d_spans must be 16-byte aligned");
+    if (pool_frames < window_frames(b))
+        return fail(GLV_ERR_INVALID, "pool_frames=%llu holds no window of n=%llu frames", (unsigned long long) pool_frames, (unsigned long long) window_frames(b));
+    f32.pool.spans = reinterpret_cast<const glv::TrackSpan*>(d_spans); f32.pool.frames = pool_frames;
+    return track_each(b, d_pool, f32, pool_frames > 0xffffffffull ? 0xffffffffu : (uint32_t) pool_frames, tb, steps, d_out, d_work, ops, st);
 }
 // glv_batch_track_frames_s16 / _f32: what can be said of the frames without the batch's plan -- the pointers and the pair of keyframes kept -- then the rates call
 // or the table call with the frames handed on.  Nothing here launches; a refusal below (plan_track_frames, the table call's own) leaves the batch as untouched.
@@ -745,6 +770,22 @@ int glv_batch_track_each_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_fr
 int glv_batch_track_each_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops,
                                     void* hip_stream) {
     return track_each(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, tb, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// One pool of recordings, a span per stream (sized by glv_batch_track_at_work_bytes, as the per-stream call is).  Pool, spans and tables are handed on whole.
+int glv_batch_track_pool_s16(glv_batch* b, const int16_t* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, void* d_out,
+                             void* d_work, unsigned ops, void* hip_stream) {
+    return track_pool(b, d_pool, false, pool_frames, d_spans, tb, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_pool_f32(glv_batch* b, const float* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, void* d_out,
+                             void* d_work, unsigned ops, void* hip_stream) {
+    return track_pool(b, d_pool, true, pool_frames, d_spans, tb, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_pool_f32_planar(glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
+                                    void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_pool(b, d_rows, TrackInput::F32_PLANAR, pool_frames, d_spans, tb, steps, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 // (one query for glv_batch_track_frames_s16 and _f32: the table call's regions with float rows in both, and with bars the frames' texel rows behind them; asked, like

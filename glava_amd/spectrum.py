@@ -70,6 +70,13 @@ class TrackTables(C.Structure):
     _fields_ = [("d_starts", C.c_void_p), ("d_ur", C.c_void_p), ("d_counts", C.c_void_p)]
 
 
+class TrackSpan(C.Structure):
+    """glv_track_span: where one stream's recording lies in the pool of a glv_batch_track_pool_s16 / _f32 / _f32_planar call -- its first frame counted from
+    the pool's first frame (64-bit: a pool may pass 2^32 frames), its length in frames, and a word that is never read.  One 16-byte record per stream, in
+    device memory, 16-byte aligned; as a numpy dtype: glava_amd.track_starts.SPAN_DTYPE."""
+    _fields_ = [("first", C.c_uint64), ("frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class StreamStateDesc(C.Structure):
     """glv_stream_state_desc: what a blob of Batch.save_streams is -- the batch's n, F and element size, the form gravity's state was kept in, the regions
     present (bit 0 gravity rows, 1 average ring, 2 s16 PCM ring, 3 f32 PCM ring), the bins kept and the bytes of one stream (glava_amd/stream_slots.py
@@ -160,6 +167,11 @@ def lib() -> C.CDLL:
             L.glv_batch_track_each_s16.argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_track_each_f32.argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_track_each_f32_planar.argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_pool_s16"):      # (likewise: the per-stream calls over one pool of recordings, a span per stream)
+            TT = C.POINTER(TrackTables)
+            L.glv_batch_track_pool_s16.argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_pool_f32.argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_track_pool_f32_planar.argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, vp, vp, C.c_uint, vp]
         if hasattr(L, "glv_batch_set_bufscale"):        # (likewise: `setbufscale k` for a batch -- windows of k * n frames, decimated on the device)
             L.glv_batch_set_bufscale.argtypes = [vp, C.c_uint32]
             L.glv_batch_bufscale.argtypes = [vp]
@@ -604,6 +616,30 @@ class Batch:
     def track_each_f32_planar(self, rows, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
         """track_each_f32 from a planar recording (glv_batch_track_each_f32_planar); `rows` as track_at_f32_planar takes them, no mono mix"""
         self._track_each("f32_planar", rows, planar_pitch_frames(rows, self.streams), d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
+
+    # ---- track mode over a pool of recordings: one buffer, a span per stream
+    def _track_pool(self, kind: str, d_pool, pool_frames: int, d_spans, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream) -> None:
+        tb = TrackTables(_ptr(d_starts), _ptr(d_ur), _ptr(d_counts))
+        _check(getattr(lib(), "glv_batch_track_pool_" + kind)(self._h, _ptr(d_pool), pool_frames, _ptr(d_spans), C.byref(tb), steps, _ptr(d_out), _ptr(d_work), ops,
+                                                              _ptr(stream)))
+
+    def track_pool_s16(self, d_pool, pool_frames: int, d_spans, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_each_s16 over ONE buffer of recordings (glv_batch_track_pool_s16): d_pool int16 [pool_frames][2]; d_spans one TrackSpan (16 bytes: first uint64,
+        frames uint32, a word never read) per stream in device memory, 16-byte aligned -- any number of streams may name the same span, overlapping spans or
+        disjoint ones.  Window t of stream s begins at pool frame min(first[s] + min(d_starts[s][t], frames[s] - k n or 0), pool_frames - k n), evaluated in the
+        kernels in 64-bit arithmetic (glava_amd.track_starts.pool_window_start): with well-formed spans no table moves a stream out of its own recording, with
+        malformed ones no launch reads outside the pool.  Everything else -- tables, forms, refusals, state, d_out, d_work (track_at_work_bytes) -- is
+        track_each_s16's, bit for bit on the materialised copy.  Spans: glava_amd.track_starts.pool_spans."""
+        self._track_pool("s16", d_pool, pool_frames, d_spans, d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
+
+    def track_pool_f32(self, d_pool, pool_frames: int, d_spans, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_pool_s16 from a float pool (glv_batch_track_pool_f32): d_pool float32 [pool_frames][2], interleaved L R, 8-byte aligned"""
+        self._track_pool("f32", d_pool, pool_frames, d_spans, d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
+
+    def track_pool_f32_planar(self, d_rows, pool_frames: int, d_spans, d_starts, d_ur, d_counts, steps: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_pool_f32 from a planar pool (glv_batch_track_pool_f32_planar): d_rows float32 [2][pool_frames], channel c of frame i at c * pool_frames + i,
+        4-byte aligned, any pool_frames, no mono mix"""
+        self._track_pool("f32_planar", d_rows, pool_frames, d_spans, d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

@@ -135,6 +135,45 @@ def stack_tables(rows, steps: int | None = None):
     return starts, ur, counts
 
 
+# one glv_track_span as a numpy record: what d_spans of Batch.track_pool_* holds, 16 bytes a stream (glava_amd.spectrum.TrackSpan field by field)
+SPAN_DTYPE = [("first", "<u8"), ("frames", "<u4"), ("reserved", "<u4")]       # numpy.dtype(SPAN_DTYPE)
+
+
+def pool_spans(lengths, align: int = 8):
+    """Where recordings of the given lengths (frames each) lie when packed into one pool for glv_batch_track_pool_s16 / _f32 / _f32_planar (Batch.track_pool_*):
+    back to back in the order given, each beginning on a multiple of `align` frames -- 8 by default, so that a window that begins on a group of 8 frames of its
+    recording lies on 32 bytes of an s16 pool and takes the wide loads.  Returns (first, pool_frames): the list of first frames and the frames the pool has to
+    hold (the last recording's end, unpadded).  A listener's span is (first[i], lengths[i]) of the recording it hears; any number of listeners share one.
+    Refuses an empty list, a length that is not an integer in [1, 2^32), and an `align` that is not a positive integer."""
+    import numpy as np
+    lengths = list(lengths)
+    _positive(align=align)
+    if not lengths:
+        raise ValueError("pool_spans needs at least one recording")
+    first, at = [], 0
+    for v in lengths:
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 1 or v >= 1 << 32:
+            raise ValueError("a recording's length must be an integer in [1, 2^32)")
+        at = (at + align - 1) // align * align
+        first.append(at)
+        at += int(v)
+    return first, at
+
+
+def pool_window_start(first: int, frames: int, entry: int, pool_frames: int, window: int) -> int:
+    """The pool frame at which a window of `window` = k * n frames begins in a glv_batch_track_pool_* call -- the kernels' rule (glv_frame.h pool_window_start)
+    restated in integers: `entry` frames into the span [first, first + frames), clamped to the span's last whole window, and whatever the span holds clamped
+    to the pool's last whole window.  first: uint64, frames and entry: uint32, pool_frames >= window >= 1."""
+    for name, v, top in (("first", first, 1 << 64), ("frames", frames, 1 << 32), ("entry", entry, 1 << 32), ("pool_frames", pool_frames, 1 << 64)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0 or v >= top:
+            raise ValueError(f"{name} must be an integer in [0, {top})")
+    _positive(window=window)
+    if pool_frames < window:
+        raise ValueError(f"pool_frames={pool_frames} holds no window of {window} frames")
+    ext = frames - window if frames >= window else 0
+    return min(first + min(entry, ext), pool_frames - window)
+
+
 def _f32(x: float) -> float:
     from struct import pack, unpack
     return unpack("f", pack("f", x))[0]

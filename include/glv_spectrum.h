@@ -858,6 +858,48 @@ int glv_batch_track_each_f32
     (glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops, void* hip_stream);
 int glv_batch_track_each_f32_planar
     (glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+/* Track mode over a POOL of recordings: the per-stream entries above take [streams][pitch_frames], a private copy of a recording per stream, each padded to the
+ * longest -- 1024 listeners of one five-minute recording hold it 1024 times, and a listener that joins, leaves or switches recordings costs a staging copy.
+ * These entries take ONE buffer of pool_frames frames and a span per stream: where that stream's recording begins in the pool and how long it is.  Any number of
+ * streams may name the same span, overlapping spans or disjoint ones; join, leave and switch are writes to d_spans and the tables.  Added within ABI 7; detect
+ * by the symbol.  Everything not said here is glv_batch_track_each_s16 / _f32 / _f32_planar, word for word: glv_track_tables (rates, counts, the NULL rules), the
+ * forms the ops and the batch select (windows; live on GLV_OP_BARS_ONLY batches; columns; the wave form), gl_storage 0, 1 and 3, channels 1 and 2, bufscale up to
+ * 16, d_out, and d_work sized by glv_batch_track_at_work_bytes(b, steps, ops) -- there is no other query.  Capturable from the first call; nothing is allocated
+ * or synchronised.
+ *   Pool.    d_pool holds pool_frames frames: int16 [pool_frames][2], float [pool_frames][2], or for the planar entry float [2][pool_frames] -- channel c of frame
+ *            i is d_rows[c * pool_frames + i], any pool_frames, no mono mix.  Aligned as the recordings of the per-stream entries are: 4, 8 and 4 bytes.  The pool
+ *            may exceed 2^32 frames, which is why `first` is 64-bit and travels to the kernels in the span and not through the 32-bit tables.
+ *   Windows. With k the batch's bufscale, window t of stream s begins at pool frame
+ *                ext = frames[s] >= k n ? frames[s] - k n : 0
+ *                w   = min(first[s] + min(d_starts[s * steps + t], ext), pool_frames - k n)
+ *            evaluated in the kernels, in 64-bit arithmetic.  With well-formed spans (frames >= k n, first + frames <= pool_frames) the outer min never binds and
+ *            no table can make a listener read another listener's recording: the guarantee is per stream, not per buffer.  With malformed spans no launch reads
+ *            outside the pool.  The spans and the tables are read when the kernels run: rewriting them in stream order re-aims a captured hipGraph.
+ *   Contract. Output, state afterwards, head, launches, glv_batch_last_launches and glv_batch_kernel_name are bit for bit those of glv_batch_track_each_* on the
+ *            materialised copy d_pcm[s][i] = pool[first[s] + i], i < frames[s], at pitch_frames = max frames[s], with table entries pre-clamped to
+ *            frames[s] - k n.
+ *   Refused, launching nothing and leaving the batch untouched: what glv_batch_track_each_* refuses, in its words (a message that names pitch_frames shows
+ *            pool_frames, saturated at 2^32 - 1); and with GLV_ERR_INVALID a NULL d_pool or d_spans, spans not 16-byte aligned, and pool_frames < k n.
+ * Kernels: the transform in pool kinds of the frame kernel (glv_frame.h in_track_pool: the per-stream kinds with the stream's 16-byte span loaded where the table
+ * entry is, one frame ahead of the address that needs it, and the start rule above -- glv_frame.h pool_window_start, which the tests mirror); under bufscale and in
+ * the wave form glv_decimate_pool_kernel and glv_wave_pool_kernel (glv_pool.hip), the arithmetic of glv_decimate_kernel's track kinds and glv_wave_kernel's window
+ * kinds behind the same rule.  The scan, bars, columns and slot kernels read no PCM and are the per-stream call's.  Every kernel that existed keeps its device
+ * code byte for byte; registers, scratch and instruction counts of the new kinds beside their siblings: profiles/r26/track_pool_isa.txt.
+ * Python: glava_amd.track_starts.pool_spans(lengths) packs recordings into a pool, each on a group of 8 frames, and returns the `first` offsets. */
+typedef struct glv_track_span {
+    uint64_t first;     /* first frame of the stream's recording, counted from the pool's first frame */
+    uint32_t frames;    /* its length in frames */
+    uint32_t reserved;  /* never read */
+} glv_track_span;       /* one per stream, device memory, 16-byte aligned records */
+int glv_batch_track_pool_s16
+    (glv_batch* b, const int16_t* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_pool_f32
+    (glv_batch* b, const float* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_pool_f32_planar
+    (glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
