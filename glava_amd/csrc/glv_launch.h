@@ -74,6 +74,20 @@ hipError_t launch_track_frames(const TrackFrames& t, hipStream_t st);
 // ... and the keyframes the next call starts from: keys[0] <- keyframe keep_from, keys[1] <- keyframe keep_to, element by element, both read before either is
 // written (the pairs (0, 1), (1, k >= 2) and (k, k') with 2 <= k < k': the host vets them)
 hipError_t launch_track_keys(float* keys, const float* rows, uint32_t units, uint32_t n, uint32_t keep_from, uint32_t keep_to, hipStream_t st);
+// The render frames of a per-stream frames call (glv_track_frames_each_kernel; glv_batch_track_each_frames_* / glv_batch_track_pool_frames_*): TrackFrames with
+// t.from / t.to / t.mod holding a row per stream, [units / 2][frames] -- row s is stream s's -- and t.steps the call's.  Stream s = channel row >> 1 clamps every
+// index to c_s + 1, c_s = min(counts[s], steps) (counts == nullptr: steps), walks its first f_s = min(frame_counts[s], frames) frames (nullptr: all) and stores
+// zero texels for the rest; no table entry at j >= f_s is read.  All device memory, read when the kernel runs.  A structure of its own: TrackFrames keeps its
+// size and offsets, and glv_track_frames_kernel its code.
+struct TrackFramesEach {
+    TrackFrames t;
+    const uint32_t* frame_counts;
+    const uint32_t* counts;
+};
+hipError_t launch_track_frames_each(const TrackFramesEach& e, hipStream_t st);
+// ... and its write-back: keys[0] <- keyframe keep[2 s], keys[1] <- keyframe keep[2 s + 1] of stream s, each clamped to c_s + 1 in the kernel (any pair is
+// safe: a lane reads and writes element i only)
+hipError_t launch_track_keys_each(float* keys, const float* rows, uint32_t units, uint32_t n, uint32_t steps, const uint32_t* counts, const uint32_t* keep, hipStream_t st);
 // Where the windows of the track sources of GLV_OP_WAVE lie (glv_wave_kernel, glv_bars_rows_i8_kernel).  A process call's windows lie back to back -- the
 // identity geometry, which those kernels' existing kinds have built in and never read from here.  A track call (glv_batch_track_wave_s16) cuts them
 // out of [streams][pitch_frames][2] recordings: output row r = t * units + 2 s + c is channel c of the n frames from s * pitch_frames + t * hop on,

@@ -34,6 +34,7 @@ namespace {
 struct TrackInput {
     enum Kind { S16 = 0, F32 = 1, F32_PLANAR = 2 } kind;
     bool rows = false;      // the call's tables have a row per stream (glv_batch_track_each_*: set by track_each, read where the wave form's windows are laid out)
+    const glv_track_frames_each* frames = nullptr;      // a per-stream frames call (glv_batch_track_each_frames_* / _pool_frames_*: set by track_each_frames_call): its render frames, read by track_at
     glv::TrackPool pool = {nullptr, 0};      // a pool call (glv_batch_track_pool_*: set by track_pool): d_pcm is ONE buffer of pool.frames frames, stream s reads it through pool.spans[s]
     TrackInput(bool f32 = false) : kind(f32 ? F32 : S16) {}
     TrackInput(Kind k) : kind(k) {}
@@ -63,6 +64,8 @@ struct TrackPlan {
     bool live = false;                  // the entry is the live form (glv_batch_track_live_s16 / _f32)
     uint32_t kept = 0;                  // the live form's kept bins K, a multiple of 64 below n (kept_bins); 0: every bin -- the other entries, and the live form's full-row form
     const glv_track_frames* fr = nullptr;   // a frames call (glv_batch_track_frames_s16 / _f32): its render frames; set before the plan (the sizing query's holds `frames` alone)
+    const glv_track_frames_each* fe = nullptr;   // ... of a per-stream frames call (glv_batch_track_each_frames_* / _pool_frames_*): a row of tables, a count of frames and a keep pair
+                                        //     per stream; set by track_at beside an `fr` that holds its `frames` and d_keys -- all the plan needs; track_frames picks its launchers by it
     uint64_t frame_rows = 0;            // ... fr->frames * streams * 2: the rows the frames kernel writes and the bars run over
     uint64_t frames_off = 0;            // ... and where its texel rows lie in the workspace when bars follow: behind the transform's region and the scan's
     uint64_t dec_bytes = 0;             // bufscale > 1: the decimated rows' region at the very start of the workspace (a multiple of 256 bytes); every other region lies behind it
@@ -356,9 +359,17 @@ int track_frames(glv_batch* b, const TrackPlan& tp, float*& rows, uint32_t steps
     const uint32_t bins = b->snapped() ? b->snap.bins : b->bar_x.bins_needed;
     if (bars && bins != 0 && bins < b->p.n) t.limit = (bins + 3u) & ~3u;
     t.segment = b->track_frames_segment != 0 ? b->track_frames_segment : glv::track_frames_segment(t.frames, t.units, t.limit);
-    hipError_t e = glv::launch_track_frames(t, st); ++b->last_launches;
+    hipError_t e;
+    if (tp.fe) {      // a per-stream frames call: stream s's rows of the tables, its count of steps (the scan's: tp.counts) and of frames, all read on the device
+        t.from = tp.fe->d_from; t.to = tp.fe->d_to; t.mod = tp.fe->d_mod;
+        const glv::TrackFramesEach each = {t, tp.fe->d_frame_counts, tp.counts};
+        e = glv::launch_track_frames_each(each, st);
+    } else e = glv::launch_track_frames(t, st);
+    ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "frames launch failed: %s", hipGetErrorString(e));
-    e = glv::launch_track_keys(fr.d_keys, rows, t.units, t.n, fr.keep_from, fr.keep_to, st); ++b->last_launches;
+    e = tp.fe ? glv::launch_track_keys_each(fr.d_keys, rows, t.units, t.n, steps, tp.counts, tp.fe->d_keep, st)
+              : glv::launch_track_keys(fr.d_keys, rows, t.units, t.n, fr.keep_from, fr.keep_to, st);
+    ++b->last_launches;
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "keyframe write-back launch failed: %s", hipGetErrorString(e));
     if (bars) rows = static_cast<float*>(t.out);
     return GLV_OK;
@@ -402,7 +413,7 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     if (tp.bars == ChainPlan::BARS_COLUMNS_TEXELS) { if (int rc = track_columns(b, pl.rows, units, out, st)) return rc; }
     else if (int rc = launch_bars_pass(b, pl, out, units, (ops & GLV_OP_R16) != 0, st)) return rc;
     else if (tp.live) b->kernel_name = bars_kernel_name(b, tp.bars);
-    if (tp.fr) b->kernel_name = "glv_track_frames_kernel";      // (a frames call names its own kernel, whatever follows it)
+    if (tp.fr) b->kernel_name = tp.fe ? "glv_track_frames_each_kernel" : "glv_track_frames_kernel";      // (a frames call names its own kernel, whatever follows it)
     return timed_launch_end(b, st);
 }
 
@@ -538,14 +549,18 @@ uint64_t planned_work_bytes(const glv_batch* b, int (*plan)(const glv_batch*, ui
 // d_ur: the second table of a rates call (track_rates has vetted it, and that the ops have the gravity that reads it); nullptr: the batch's own ur
 // fr: the render frames of a frames call (track_frames_call has vetted them and the ops); nullptr: every other call
 // each: the tables of a per-stream call (track_each has vetted them: d_starts and d_ur are its rows, [streams][steps]); nullptr: one row for all streams
+// f32.frames: the render frames of a per-stream frames call (track_each_frames_call has vetted them and refused GLV_OP_WAVE; `each` is set, `fr` is not)
 int track_at(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, const uint32_t* d_starts, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
              const glv_track_frames* fr = nullptr, const glv_track_tables* each = nullptr, const float* d_ur = nullptr) {
     if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
     if (!d_starts) return fail(GLV_ERR_INVALID, "NULL device pointer");
     if (reinterpret_cast<uintptr_t>(d_starts) & 3u) return fail(GLV_ERR_INVALID, "d_starts must be 4-byte aligned");
     if (ops & GLV_OP_WAVE) return track_wave(b, d_pcm, f32, pitch_frames, 0u, steps, d_out, d_work, ops, st, fr, d_starts);
+    glv_track_frames shape = {};      // what the plan and the frames stage read of a per-stream frames call through `fr`: the longest row and the keyframes
+    const glv_track_frames_each* const fe = f32.frames;
+    if (fe) { shape.frames = fe->frames; shape.d_keys = fe->d_keys; fr = &shape; }
     TrackPlan tp;
-    tp.fr = fr;
+    tp.fr = fr; tp.fe = fe;
     if (int rc = fr ? plan_track_frames(b, pitch_frames, steps, ops, tp) : plan_track_at(b, pitch_frames, 0u, steps, ops, tp)) return rc;
     tp.f32 = f32; tp.starts = d_starts; tp.ur = d_ur;
     if (each) { tp.each = true; tp.counts = each->d_counts; }
@@ -616,6 +631,26 @@ int track_frames_call(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t 
                     (unsigned long long) steps + 2u);
     if (d_ur) return track_rates(b, d_pcm, f32, pitch_frames, d_where, d_ur, steps, d_out, d_work, ops, st, fr);
     return track_at(b, d_pcm, f32, pitch_frames, d_where, steps, d_out, d_work, ops, st, fr);
+}
+// glv_batch_track_each_frames_* / glv_batch_track_pool_frames_*: what can be said of the per-stream frames without the batch's plan -- the structure, its pointers
+// and their alignment, and that the wave form has no per-stream frames -- then the pool call (d_spans set) or the per-stream call with the frames handed on: their
+// refusals in their words, then plan_track_frames' through track_at.  The keep pairs and the counts are device memory: the kernels clamp them.  Nothing here launches.
+int track_each_frames_call(glv_batch* b, const void* d_pcm, TrackInput f32, uint64_t frames_held, const glv_track_span* d_spans, bool pool, const glv_track_tables* tb,
+                           uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!fe) return fail(GLV_ERR_INVALID, "fe is NULL");
+    if (reinterpret_cast<uintptr_t>(fe) & (alignof(glv_track_frames_each) - 1u))
+        return fail(GLV_ERR_INVALID, "fe must be aligned like a pointer: %u bytes", (unsigned) alignof(glv_track_frames_each));
+    if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no keyframes: a frames track call takes an FFT chain (ops 0x%x)", ops);
+    if (!fe->d_from || !fe->d_to || !fe->d_mod || !fe->d_keep || !fe->d_keys) return fail(GLV_ERR_INVALID, "NULL device pointer in glv_track_frames_each");
+    if ((reinterpret_cast<uintptr_t>(fe->d_from) | reinterpret_cast<uintptr_t>(fe->d_to) | reinterpret_cast<uintptr_t>(fe->d_mod) | reinterpret_cast<uintptr_t>(fe->d_frame_counts)
+         | reinterpret_cast<uintptr_t>(fe->d_keep)) & 3u)
+        return fail(GLV_ERR_INVALID, "d_from, d_to, d_mod, d_frame_counts and d_keep must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(fe->d_keys) & 15u) return fail(GLV_ERR_INVALID, "d_keys must be 16-byte aligned");
+    if (fe->frames == 0) return fail(GLV_ERR_INVALID, "frames must be > 0");
+    f32.frames = fe;
+    if (pool) return track_pool(b, d_pcm, f32, frames_held, d_spans, tb, steps, d_out, d_work, ops, st);
+    return track_each(b, d_pcm, f32, (uint32_t) frames_held, tb, steps, d_out, d_work, ops, st);
 }
 }  // namespace
 
@@ -816,6 +851,39 @@ int glv_batch_track_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_
 int glv_batch_track_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, const float* d_ur, uint32_t steps,
                                       const glv_track_frames* fr, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
     return track_frames_call(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, d_where, d_ur, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// A row of frame tables, a count of frames and a keep pair per stream, on the per-stream call's updates (sized by glv_batch_track_frames_work_bytes with the longest row:
+// the rows add no region).  Tables and frames are handed on whole.
+int glv_batch_track_each_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+                                    void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_frames_call(b, d_pcm, false, pitch_frames, nullptr, false, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_each_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+                                    void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_frames_call(b, d_pcm, true, pitch_frames, nullptr, false, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_each_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+                                           void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_frames_call(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, nullptr, false, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// ... and on the pool call's: one buffer of recordings, a span per stream
+int glv_batch_track_pool_frames_s16(glv_batch* b, const int16_t* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
+                                    const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_frames_call(b, d_pool, false, pool_frames, d_spans, true, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_pool_frames_f32(glv_batch* b, const float* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
+                                    const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_frames_call(b, d_pool, true, pool_frames, d_spans, true, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_pool_frames_f32_planar(glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
+                                           const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_frames_call(b, d_rows, TrackInput::F32_PLANAR, pool_frames, d_spans, true, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 
 // (one query for glv_batch_track_wave_frames_s16 and _f32: 256 without bars, else the frames' rows in the format plan_wave gives the bars kernel; asked, like

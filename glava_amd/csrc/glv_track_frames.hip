@@ -3,6 +3,8 @@
 //
 //   glv_track_frames_kernel   frame j of row r = unorm16(s + ((e - s) * mod[j])) of keyframes from[j] and to[j] (render.c:1792-1809, :2185, :521-524)
 //   glv_track_keys_kernel     d_keys[0] <- keyframe keep_from, d_keys[1] <- keyframe keep_to (render.c:2347-2353 as it stands after the last frame)
+//   glv_track_frames_each_kernel / glv_track_keys_each_kernel   both with a row of tables, a count of steps, a count of frames and a keep pair per stream
+//                             (glv_batch_track_each_frames_* / glv_batch_track_pool_frames_*)
 // ... and of a wave track call on any gl_storage (glv_batch_track_wave_frames_s16 / _f32), whose keyframes are read from the recording:
 //   glv_wave_frames_kernel    the same frame from keyframes (u + 1.0F) / 2.0F of the unpacked window of step k - 2 (render.c:777-778), as texels or their floats
 //   glv_wave_keys_kernel      the same write-back, as floats
@@ -96,6 +98,94 @@ __global__ void __launch_bounds__(256) glv_track_keys_kernel(float* keys, const 
     }
 }
 
+// The frames stage of a per-stream frames call (glv_batch_track_each_frames_* / glv_batch_track_pool_frames_*): glv_track_frames_kernel's walk with a row of the three
+// tables per stream.  What differs, and nothing else: the table base of a work item is (row >> 1) * frames; `last_key` is c_s + 1 of the item's stream,
+// c_s = min(counts[s], steps) -- the clamp that stream's one-stream call applies, so no stream reads the zero rows the scan wrote behind its count; the walk
+// stops at f_s = min(frame_counts[s], frames), the rest of the segment is stored as zero texels, and no table entry at j >= f_s is requested.
+// Both counts are loaded once per item.  Every address the tables and the counts are read at derives from blockIdx.x and the kernel's arguments alone: the tables
+// and counts are separate __restrict__ arguments, never written here, so the loads are uniform (scalar memory loads, counted apart from the vector memory counter
+// that the chain of 512-byte stores in front of them fills).
+__global__ void __launch_bounds__(kFramesLanes) glv_track_frames_each_kernel(const TrackFrames t, const uint32_t* __restrict__ tfrom, const uint32_t* __restrict__ tto,
+                                                                             const float* __restrict__ tmod, const uint32_t* __restrict__ frame_counts,
+                                                                             const uint32_t* __restrict__ counts, const uint32_t groups, const uint64_t items) {
+    uint16_t* const out = static_cast<uint16_t*>(t.out);
+    for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const uint32_t group = (uint32_t) (item % groups);
+        const uint64_t rest = item / groups;
+        const uint32_t row = (uint32_t) (rest % t.units);
+        const uint32_t seg = (uint32_t) (rest / t.units);
+        const uint32_t bin = (group * (uint32_t) kFramesLanes + threadIdx.x) * 4u;
+        if (bin >= t.limit) continue;                                       // the last group of a row: nothing of these lanes is read or written
+        const uint32_t stream = row >> 1;                                   // (< units / 2: the tables and the counts have a row for it)
+        uint32_t c = t.steps, f = t.frames;
+        if (counts) { const uint32_t v = counts[stream]; c = v < c ? v : c; }
+        if (frame_counts) { const uint32_t v = frame_counts[stream]; f = v < f ? v : f; }
+        const uint32_t last_key = c + 1u;                                   // (<= steps + 1)
+        const uint32_t j0 = seg * t.segment;                                // (< frames: the host counted the segments)
+        const uint32_t j1 = t.frames - j0 > t.segment ? j0 + t.segment : t.frames;
+        const uint32_t jw = f <= j0 ? j0 : f < j1 ? f : j1;                 // the walk's end: frames [jw, j1) of the segment lie behind the stream's count
+        const uint32_t* const from_s = tfrom + (size_t) stream * t.frames;
+        const uint32_t* const to_s = tto + (size_t) stream * t.frames;
+        const float* const mod_s = tmod + (size_t) stream * t.frames;
+        auto key = [&](uint32_t k) -> glv_f4 {
+            const float* const base = k < 2u ? t.keys + ((size_t) k * t.units + row) * t.n : t.rows + ((size_t) (k - 2u) * t.units + row) * t.n;
+            return *reinterpret_cast<const glv_f4*>(base + bin);
+        };
+        uint32_t from[kFramesDepth], to[kFramesDepth];
+        float mod[kFramesDepth];
+#pragma unroll
+        for (int d = 0; d < kFramesDepth; ++d) {
+            const bool in = (uint32_t) d < jw - j0;
+            from[d] = in ? from_s[j0 + (uint32_t) d] : 0u; to[d] = in ? to_s[j0 + (uint32_t) d] : 0u; mod[d] = in ? mod_s[j0 + (uint32_t) d] : 0.0f;
+        }
+        uint32_t ks = 0xffffffffu, ke = 0xffffffffu;                         // the keyframes in s and e: none yet (no clamped index is this)
+        glv_f4 s = { 0.0f, 0.0f, 0.0f, 0.0f }, e = s;
+        for (uint32_t jb = j0; jb < jw; jb += (uint32_t) kFramesDepth) {
+#pragma unroll
+            for (int d = 0; d < kFramesDepth; ++d) {
+                const uint32_t j = jb + (uint32_t) d;
+                if (j >= jw) break;
+                const uint32_t kf = from[d] < last_key ? from[d] : last_key, kt = to[d] < last_key ? to[d] : last_key;
+                const float m = mod[d];
+                if (jw - j > (uint32_t) kFramesDepth) {
+                    from[d] = from_s[j + (uint32_t) kFramesDepth]; to[d] = to_s[j + (uint32_t) kFramesDepth]; mod[d] = mod_s[j + (uint32_t) kFramesDepth];
+                }
+                glv_f4 ns = s;
+                if (kf != ks) ns = kf == ke ? e : key(kf);
+                if (kt != ke) e = kt == ks ? s : key(kt);
+                s = ns; ks = kf; ke = kt;
+                glv_f4 w = s;
+                if (kf != kt) w = s + ((e - s) * m);                        // render.c:1806
+                const glv_u2 c2 = { pack_unorm16(w.x, w.y), pack_unorm16(w.z, w.w) };    // render.c:521-524
+                *reinterpret_cast<glv_u2*>(out + ((size_t) j * t.units + row) * t.n + bin) = c2;
+            }
+        }
+        for (uint32_t j = jw; j < j1; ++j) *reinterpret_cast<glv_u2*>(out + ((size_t) j * t.units + row) * t.n + bin) = glv_u2{ 0u, 0u };
+    }
+}
+
+// The write-back of a per-stream frames call: glv_track_keys_kernel's with the pair taken per stream from `keep` (uint32 [streams][2]) and clamped to c_s + 1.  A lane
+// reads element i of both kept keyframes before it writes element i of either destination, and no other lane touches element i: any pair is safe.
+// per_stream: the quads of one stream's two rows, 2 * n / 4.
+__global__ void __launch_bounds__(256) glv_track_keys_each_kernel(float* keys, const float* rows, const size_t quads, const uint32_t per_stream, const uint32_t steps,
+                                                                  const uint32_t* __restrict__ counts, const uint32_t* __restrict__ keep) {
+    glv_f4* const k0 = reinterpret_cast<glv_f4*>(keys);
+    glv_f4* const k1 = k0 + quads;
+    const glv_f4* const step_rows = reinterpret_cast<const glv_f4*>(rows);
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < quads; i += (size_t) gridDim.x * blockDim.x) {
+        const size_t stream = i / per_stream;
+        uint32_t c = steps;
+        if (counts) { const uint32_t v = counts[stream]; c = v < c ? v : c; }
+        const uint32_t last_key = c + 1u;
+        uint32_t kf = keep[2u * stream], kt = keep[2u * stream + 1u];
+        kf = kf < last_key ? kf : last_key; kt = kt < last_key ? kt : last_key;
+        const glv_f4* const a = kf < 2u ? k0 + (size_t) kf * quads : step_rows + (size_t) (kf - 2u) * quads;
+        const glv_f4* const b = kt < 2u ? k0 + (size_t) kt * quads : step_rows + (size_t) (kt - 2u) * quads;
+        const glv_f4 va = a[i], vb = b[i];
+        k0[i] = va; k1[i] = vb;
+    }
+}
+
 // The frames of a segment where the caller names none: long enough that a keyframe serves several frames, short enough that a single stream's call still
 // fills the chip -- two rounds of the 8192 resident waves where frames * units * groups allow them (a wave's walk is a chain of 512-byte stores: with one
 // segment, 64 streams x 3426 frames of N = 4096 ran on 2048 waves and wrote 2.3 TB/s, profiles/r19/track_frames.txt).
@@ -123,6 +213,26 @@ hipError_t launch_track_keys(float* keys, const float* rows, uint32_t units, uin
     if (!keys || !rows || units == 0 || n == 0 || (n & 3u)) return hipErrorInvalidValue;
     const size_t quads = (size_t) units * (n / 4u);
     hipLaunchKernelGGL(glv_track_keys_kernel, dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, keys, rows, quads, keep_from, keep_to);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_frames_each(const TrackFramesEach& e, hipStream_t st) {
+    const TrackFrames& t = e.t;
+    if (!t.from || !t.to || !t.mod || !t.keys || !t.rows || !t.out) return hipErrorInvalidValue;
+    if (t.frames == 0 || t.steps == 0 || t.units == 0 || (t.units & 1u) || t.segment == 0 || t.limit == 0 || t.limit > t.n || (t.limit & 3u) || (t.n & 3u) || t.steps > 0xfffffffdu)
+        return hipErrorInvalidValue;
+    const uint32_t groups = (t.limit / 4u + (uint32_t) kFramesLanes - 1u) / (uint32_t) kFramesLanes;
+    const uint64_t segments = ((uint64_t) t.frames + t.segment - 1u) / t.segment;
+    const uint64_t items = segments * t.units * groups;                      // (< 2^32 * 2^32 / 4: no overflow)
+    const unsigned grid = capped_grid((size_t) items, 1, kFramesGridCap);
+    hipLaunchKernelGGL(glv_track_frames_each_kernel, dim3(grid), dim3(kFramesLanes), 0, st, t, t.from, t.to, t.mod, e.frame_counts, e.counts, groups, items);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_keys_each(float* keys, const float* rows, uint32_t units, uint32_t n, uint32_t steps, const uint32_t* counts, const uint32_t* keep, hipStream_t st) {
+    if (!keys || !rows || !keep || units == 0 || (units & 1u) || n == 0 || (n & 3u) || steps == 0 || steps > 0xfffffffdu) return hipErrorInvalidValue;
+    const size_t quads = (size_t) units * (n / 4u);
+    hipLaunchKernelGGL(glv_track_keys_each_kernel, dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, keys, rows, quads, 2u * (n / 4u), steps, counts, keep);
     return hipGetLastError();
 }
 

@@ -70,6 +70,14 @@ class TrackTables(C.Structure):
     _fields_ = [("d_starts", C.c_void_p), ("d_ur", C.c_void_p), ("d_counts", C.c_void_p)]
 
 
+class TrackFramesEach(C.Structure):
+    """glv_track_frames_each: the render frames of a glv_batch_track_each_frames_* / glv_batch_track_pool_frames_* call, a row per stream -- three device tables
+    [streams][frames], frames per stream uint32 [streams] or NULL (every stream takes all), the keep pairs uint32 [streams][2], the longest row, and the
+    caller-owned keyframes"""
+    _fields_ = [("d_from", C.c_void_p), ("d_to", C.c_void_p), ("d_mod", C.c_void_p), ("d_frame_counts", C.c_void_p), ("d_keep", C.c_void_p), ("frames", C.c_uint32),
+                ("d_keys", C.c_void_p)]
+
+
 class TrackSpan(C.Structure):
     """glv_track_span: where one stream's recording lies in the pool of a glv_batch_track_pool_s16 / _f32 / _f32_planar call -- its first frame counted from
     the pool's first frame (64-bit: a pool may pass 2^32 frames), its length in frames, and a word that is never read.  One 16-byte record per stream, in
@@ -172,6 +180,11 @@ def lib() -> C.CDLL:
             L.glv_batch_track_pool_s16.argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_track_pool_f32.argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_track_pool_f32_planar.argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_each_frames_s16"):      # (likewise: the frames calls with frame tables, a frame count and a keep pair per stream)
+            TT, FE = C.POINTER(TrackTables), C.POINTER(TrackFramesEach)
+            for kind in ("s16", "f32", "f32_planar"):
+                getattr(L, "glv_batch_track_each_frames_" + kind).argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, FE, vp, vp, C.c_uint, vp]
+                getattr(L, "glv_batch_track_pool_frames_" + kind).argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, FE, vp, vp, C.c_uint, vp]
         if hasattr(L, "glv_batch_set_bufscale"):        # (likewise: `setbufscale k` for a batch -- windows of k * n frames, decimated on the device)
             L.glv_batch_set_bufscale.argtypes = [vp, C.c_uint32]
             L.glv_batch_bufscale.argtypes = [vp]
@@ -640,6 +653,55 @@ class Batch:
         """track_pool_f32 from a planar pool (glv_batch_track_pool_f32_planar): d_rows float32 [2][pool_frames], channel c of frame i at c * pool_frames + i,
         4-byte aligned, any pool_frames, no mono mix"""
         self._track_pool("f32_planar", d_rows, pool_frames, d_spans, d_starts, d_ur, d_counts, steps, d_out, d_work, ops, stream)
+
+    # ---- track mode at render frames per stream: frame tables, a frame count and a keep pair for every stream, on the per-stream or the pool call's updates
+    def _track_each_frames(self, kind: str, d_pcm, pitch_frames: int, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int, stream) -> None:
+        tb = TrackTables(*(_ptr(t) for t in tables))
+        fe = TrackFramesEach(*(_ptr(t) for t in frame_tables), frames, _ptr(d_keys))
+        _check(getattr(lib(), "glv_batch_track_each_frames_" + kind)(self._h, _ptr(d_pcm), pitch_frames, C.byref(tb), steps, C.byref(fe), _ptr(d_out), _ptr(d_work), ops,
+                                                                     _ptr(stream)))
+
+    def track_each_frames_s16(self, d_pcm, pitch_frames: int, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                              stream: int | None = None) -> None:
+        """track_frames_s16 with everything per stream (glv_batch_track_each_frames_s16).  tables = (d_starts, d_ur, d_counts) as track_each_s16 takes them: the
+        updates, state, head and refusals are that call's.  frame_tables = (d_from, d_to, d_mod, d_frame_counts, d_keep): uint32 / uint32 / float32
+        [streams][frames], row s is stream s's; d_frame_counts uint32 [streams] or None (every stream takes all `frames`); d_keep uint32 [streams][2], the
+        keyframes written back to d_keys[0] / d_keys[1] of each stream.  Every index is clamped on the device to c_s + 1, c_s = min(d_counts[s], steps); frames
+        behind a stream's count are what the call's last stage makes of a zero texel row.  d_out [frames][streams][2][w]; d_work at least
+        track_frames_work_bytes(steps, frames, ops) bytes.  Each stream is bit for bit track_frames_s16 on a one-stream batch.  OP_WAVE is refused.
+        Tables: glava_amd.track_starts.stack_frame_tables."""
+        self._track_each_frames("s16", d_pcm, pitch_frames, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_each_frames_f32(self, d_pcm, pitch_frames: int, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                              stream: int | None = None) -> None:
+        """track_each_frames_s16 from a float recording (glv_batch_track_each_frames_f32): d_pcm float32 [streams][pitch_frames][2], interleaved L R, 8-byte aligned"""
+        self._track_each_frames("f32", d_pcm, pitch_frames, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_each_frames_f32_planar(self, rows, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_each_frames_f32 from a planar recording (glv_batch_track_each_frames_f32_planar); `rows` as track_at_f32_planar takes them, no mono mix"""
+        self._track_each_frames("f32_planar", rows, planar_pitch_frames(rows, self.streams), tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def _track_pool_frames(self, kind: str, d_pool, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int, stream) -> None:
+        tb = TrackTables(*(_ptr(t) for t in tables))
+        fe = TrackFramesEach(*(_ptr(t) for t in frame_tables), frames, _ptr(d_keys))
+        _check(getattr(lib(), "glv_batch_track_pool_frames_" + kind)(self._h, _ptr(d_pool), pool_frames, _ptr(d_spans), C.byref(tb), steps, C.byref(fe), _ptr(d_out),
+                                                                     _ptr(d_work), ops, _ptr(stream)))
+
+    def track_pool_frames_s16(self, d_pool, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                              stream: int | None = None) -> None:
+        """track_each_frames_s16 over ONE buffer of recordings (glv_batch_track_pool_frames_s16): d_pool, pool_frames and d_spans as track_pool_s16 takes them,
+        everything else as track_each_frames_s16"""
+        self._track_pool_frames("s16", d_pool, pool_frames, d_spans, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_pool_frames_f32(self, d_pool, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                              stream: int | None = None) -> None:
+        """track_pool_frames_s16 from a float pool (glv_batch_track_pool_frames_f32): d_pool float32 [pool_frames][2], interleaved L R, 8-byte aligned"""
+        self._track_pool_frames("f32", d_pool, pool_frames, d_spans, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_pool_frames_f32_planar(self, d_rows, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                                     stream: int | None = None) -> None:
+        """track_pool_frames_f32 from a planar pool (glv_batch_track_pool_frames_f32_planar): d_rows float32 [2][pool_frames], 4-byte aligned, no mono mix"""
+        self._track_pool_frames("f32_planar", d_rows, pool_frames, d_spans, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

@@ -229,6 +229,44 @@ def keyframe_tables(modified, on, uratio, kcounter: int = 0) -> tuple[list[int],
     return frm, to, mod, start, end
 
 
+def stack_frame_tables(rows, frames: int | None = None):
+    """The frame tables of glv_batch_track_each_frames_* / glv_batch_track_pool_frames_* (Batch.track_each_frames_* / track_pool_frames_*) from one
+    (from, to, mod, keep_from, keep_to) tuple per stream, of any lengths -- as keyframe_tables returns them, and live_session_frames behind its first two tables.
+    Every tuple is padded to `frames` entries (default: the longest, at least 1) with from = to = 0 and mod = 0.0 -- an entry behind a stream's frame count is
+    never read -- and its own length is its frame count.  Returns numpy arrays (from uint32 [streams][frames], to uint32 [streams][frames], mod float32
+    [streams][frames], frame_counts uint32 [streams], keep uint32 [streams][2]).  An empty tuple is a stream that shows nothing: frame count 0, and its keep
+    pair as given ((0, 1) leaves its keyframes as they are).  Refuses tables of one stream that differ in length, one longer than `frames`, and an index or a
+    keep entry that does not fit a uint32."""
+    import numpy as np
+    rows = [(list(f), list(t), list(m), kf, kt) for f, t, m, kf, kt in rows]
+    if not rows:
+        raise ValueError("stack_frame_tables needs at least one stream")
+    for f, t, m, _, _ in rows:
+        if not (len(f) == len(t) == len(m)):
+            raise ValueError(f"a stream's tables differ in length: {len(f)} from, {len(t)} to, {len(m)} mod")
+    longest = max(len(f) for f, _, _, _, _ in rows)
+    if frames is None:
+        frames = max(longest, 1)
+    _positive(frames=frames)
+    if longest > frames:
+        raise ValueError(f"a stream has {longest} frames, more than frames = {frames}")
+    index = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v < 1 << 32      # noqa: E731
+    frm = np.zeros((len(rows), frames), dtype=np.uint32)
+    to = np.zeros((len(rows), frames), dtype=np.uint32)
+    mod = np.zeros((len(rows), frames), dtype=np.float32)
+    counts = np.zeros((len(rows),), dtype=np.uint32)
+    keep = np.zeros((len(rows), 2), dtype=np.uint32)
+    for i, (f, t, m, kf, kt) in enumerate(rows):
+        if not all(index(v) for v in f + t + [kf, kt]):
+            raise ValueError("a keyframe index must be an integer in [0, 2^32)")
+        counts[i] = len(f)
+        frm[i, :len(f)] = f
+        to[i, :len(t)] = t
+        mod[i, :len(m)] = m
+        keep[i] = (kf, kt)
+    return frm, to, mod, counts, keep
+
+
 def live_session_frames(rate: int, fps: int, frames: int, update_frames: int) -> tuple[list[int], list[float], list[int], list[int], list[float], int, int]:
     """live_session_rates extended by the measured frame rate gl->fr: a `setinterpolate true` session on `setaccelfft false` (gl_storage 3) over `frames`
     render frames.  Returns (starts, ur, from, to, mod, keep_from, keep_to): the first two are live_session_rates' tables, the rest keyframe_tables' for the

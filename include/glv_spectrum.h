@@ -900,6 +900,71 @@ int glv_batch_track_pool_f32
 int glv_batch_track_pool_f32_planar
     (glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, void* d_out, void* d_work,
      unsigned ops, void* hip_stream);
+/* Track mode at render frames PER STREAM: glv_batch_track_frames_* takes one row of frame tables, one frame count and one keep pair for the whole batch, and
+ * cannot reach the per-stream or pool updates.  Listeners at a 60 Hz and a 144 Hz display of the same recording have different frame counts, different d_mod
+ * rows and different keep pairs (glava_amd.track_starts.live_session_frames(22050, 60, ...) against (22050, 144, ...)).  These entries give every stream its own
+ * rows of the three frame tables, its own number of frames and its own keep pair, on the updates of glv_batch_track_each_* or glv_batch_track_pool_*; stream s
+ * then behaves as if it were alone in a one-stream batch running glv_batch_track_frames_*, bit for bit.  Added within ABI 7; detect by the symbol.
+ * Sized by glv_batch_track_frames_work_bytes(b, steps, frames, ops) with frames the longest row: the rows add no region, and there is no other query.
+ *   Updates.   tb, steps, d_pcm / d_rows and pitch_frames, or d_pool, pool_frames and d_spans, are glv_batch_track_each_* / _pool_* 's arguments, word for word:
+ *              their refusals in their words, and the batch's state afterwards, the head and the ring turned by steps - c_s exactly what those calls leave;
+ *              c_s = min(d_counts[s], steps), or steps where d_counts is NULL.
+ *   Keyframes. Keyframe k < 2 of stream s is d_keys[k]'s rows of stream s, keyframe k >= 2 the finished float row of that stream's step k - 2.  Every index read
+ *              from d_from, d_to or d_keep is clamped in the kernel to c_s + 1 -- the clamp that stream's one-stream call applies -- so no launch reads outside
+ *              d_keys, the steps' rows or the tables whatever they hold, and no stream sees a zero row written behind its count.  A stream with c_s == 0 lerps
+ *              between its two carried keyframes only.
+ *   Frames.    f_s = min(d_frame_counts[s], frames), evaluated on the device (NULL: frames).  For j < f_s rows 2 s and 2 s + 1 of block j of d_out follow
+ *              glv_batch_track_frames_* 's rule with stream s's entries d_from[s * frames + j], d_to[...], d_mod[...]: from == to gives that keyframe's own bits,
+ *              else s + ((e - s) * mod) in three float operations without contraction, then the upload's quantiser; the stage the ops select then runs over
+ *              frames * streams * 2 rows.  For j >= f_s the frames stage writes zero texels and the output row is what the last stage makes of a zero texel
+ *              row -- defined, nothing stale.  No table entry at j >= f_s is read.  d_out stays frame-major: [frames][streams][2][w].
+ *   Write-back. d_keys[0] of stream s <- keyframe d_keep[2 s], d_keys[1] <- keyframe d_keep[2 s + 1], both read before either is written.  Any pair is safe (a
+ *              lane reads and writes element i only): the host's rule (0, 1), (1, k), (k, k') cannot be checked for a table in device memory and is not
+ *              imposed.  (0, 1) leaves a stream's keys as they were.  Chunks compose per stream, as the lockstep call's do.
+ *   Equivalence. For every stream with c_s >= 1 and f_s >= 1 its rows of blocks j < f_s and its d_keys afterwards are bit for bit what glv_batch_track_frames_*
+ *              gives on a one-stream batch that holds the stream's state and recording (pool entries: its materialised span with pre-clamped entries), with
+ *              steps = c_s, frames = f_s, the stream's rows, and its keep pair where the host accepts that pair.  With equal rows for all streams, NULL counts
+ *              and equal keep pairs the call is bit for bit glv_batch_track_frames_*.
+ *   Refused, launching nothing and leaving the batch untouched: everything glv_batch_track_frames_* refuses about ops, storage and frames, everything the
+ *              per-stream or pool call refuses, and with GLV_ERR_INVALID fe NULL or not aligned like a pointer, any of its pointers NULL except
+ *              d_frame_counts, a table not 4-byte aligned, d_keys not 16-byte aligned, frames == 0.  GLV_OP_WAVE is refused: the wave form per stream is not
+ *              built (glv_batch_track_wave_frames_* remains the lockstep call).
+ * Launches (glv_batch_last_launches): the per-stream call's without bars, + 2 (glv_track_frames_each_kernel, glv_track_keys_each_kernel), + 1 with GLV_OP_BARS.
+ * Stream-ordered and capturable from the first call; all tables, counts and keep pairs are read when the kernels run, so rewriting them re-aims a captured
+ * graph.  glv_batch_kernel_name reports "glv_track_frames_each_kernel".
+ * Kernels (glv_track_frames.hip): glv_track_frames_kernel's walk -- four bins a lane, both keyframes in registers, table entries 4 frames ahead, one wave a
+ * workgroup looping over [segment][row][group] items -- with the table base (row >> 1) * frames, last_key from the stream's count, the walk stopped at f_s and
+ * zeros behind it.  The tables and counts are read through uniform (scalar) loads, which do not queue behind the chain of 512-byte stores.  Every kernel that
+ * existed keeps its source.
+ * Python: glava_amd.track_starts.stack_frame_tables(rows) pads per-stream (from, to, mod, keep_from, keep_to) tuples to the longest and returns the three
+ * tables, the frame counts and the keep array. */
+typedef struct glv_track_frames_each {
+    const uint32_t* d_from;          /* uint32 [streams][frames], device, 4-byte aligned: row s is stream s's table   */
+    const uint32_t* d_to;            /* uint32 [streams][frames]                                                       */
+    const float*    d_mod;           /* float  [streams][frames], applied as given                                     */
+    const uint32_t* d_frame_counts;  /* uint32 [streams] or NULL: every stream takes all `frames` frames               */
+    const uint32_t* d_keep;          /* uint32 [streams][2], device: the keyframes written back to d_keys[0] / [1]     */
+    uint32_t        frames;          /* longest row, >= 1                                                              */
+    float*          d_keys;          /* float [2][streams][2][n], caller-owned, 16-byte aligned                        */
+} glv_track_frames_each;
+int glv_batch_track_each_frames_s16
+    (glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_each_frames_f32
+    (glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_each_frames_f32_planar
+    (glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_pool_frames_s16
+    (glv_batch* b, const int16_t* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+     void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_pool_frames_f32
+    (glv_batch* b, const float* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+     void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_pool_frames_f32_planar
+    (glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+     void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
  * batch-owned buffer, or the caller's d_out of the latest call when that doubles as the state (GLV_OP_OUTPUT_IS_STATE).
  * GLV_ERR_STATE if the batch was created without GLV_OP_GRAVITY, after fused gravity + average calls (the state is
