@@ -218,6 +218,31 @@ struct WaveFrames {
 hipError_t launch_wave_frames(const void* pcm, bool f32, const WaveWindows& w, bool mono, const WaveFrames& t, bool r16, hipStream_t st);
 // ... and the keyframes the next call starts from, as floats: keys[0] <- keyframe keep_from, keys[1] <- keyframe keep_to (launch_track_keys' pairs, vetted by the host)
 hipError_t launch_wave_keys(const void* pcm, bool f32, const WaveWindows& w, bool mono, float* keys, uint32_t n, uint32_t keep_from, uint32_t keep_to, hipStream_t st);
+// The render frames of a per-stream wave frames call (glv_wave_frames_each_kernel; glv_batch_track_each_wave_frames_* / glv_batch_track_pool_wave_frames_*): WaveFrames
+// with t.from / t.to / t.mod holding a row per stream, [w.units / 2][frames], and w.starts a row per stream, uint32 [w.units / 2][w.steps].  Stream s clamps every
+// index to c_s + 1, c_s = min(counts[s], w.steps) (counts == nullptr: w.steps), walks its first f_s = min(frame_counts[s], frames) frames (nullptr: all) and stores
+// zero texels (or their floats) for the rest; no table entry at j >= f_s is read, and a stream with c_s == 0 reads neither starts, span nor recording.  Keyframe
+// 2 + t of stream s is read from the window that begins wave_window_start(w, s, t, starts[s * steps + t]) frames in (w.pitch_frames, w.start_max: the recordings'),
+// or with pool.spans set pool_window_start(spans[s].first, spans[s].frames, that entry, pool.frames, n) frames into the ONE buffer `pcm` (w.pitch_frames ==
+// pool.frames: the planar kind's channel stride).  kind: 0 s16 frames, 1 interleaved float frames, 2 planar float rows (w.planar set; no mono mix).  All device
+// memory, read when the kernel runs.  Structures of their own: WaveFrames and WaveWindows keep their size and offsets, the lockstep kernels their code.
+struct WaveFramesEach {
+    WaveFrames t;
+    const uint32_t* frame_counts;
+    const uint32_t* counts;
+    TrackPool pool;             // spans == nullptr: a recording per stream
+};
+hipError_t launch_wave_each_frames(const void* pcm, int kind, const WaveWindows& w, bool mono, const WaveFramesEach& e, bool r16, hipStream_t st);
+// ... and its write-back (glv_wave_keys_each_kernel): keys[0] <- keyframe keep[2 s], keys[1] <- keyframe keep[2 s + 1] of stream s, each clamped to c_s + 1 in the
+// kernel (any pair is safe: a lane reads and writes its own elements only)
+struct WaveKeysEach {
+    float* keys;                // float [2][w.units][n]
+    uint32_t n;
+    const uint32_t* counts;
+    const uint32_t* keep;       // uint32 [w.units / 2][2]
+    TrackPool pool;
+};
+hipError_t launch_wave_each_keys(const void* pcm, int kind, const WaveWindows& w, bool mono, const WaveKeysEach& k, hipStream_t st);
 // bars at texels of the pre-smoothing pass (glv_batch_set_bar_texels) over texel rows: uint16, or floats c / 65535 (rows_f32); one lane per bar and row
 hipError_t launch_bars_snap(const void* rows, bool rows_f32, void* bars_out, size_t nrows, uint32_t n, uint32_t bars, const BarDesc* desc, const uint32_t* wi,
                             hipStream_t st, bool r16);

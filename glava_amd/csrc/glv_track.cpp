@@ -34,7 +34,8 @@ namespace {
 struct TrackInput {
     enum Kind { S16 = 0, F32 = 1, F32_PLANAR = 2 } kind;
     bool rows = false;      // the call's tables have a row per stream (glv_batch_track_each_*: set by track_each, read where the wave form's windows are laid out)
-    const glv_track_frames_each* frames = nullptr;      // a per-stream frames call (glv_batch_track_each_frames_* / _pool_frames_*: set by track_each_frames_call): its render frames, read by track_at
+    const glv_track_frames_each* frames = nullptr;      // a per-stream frames call (glv_batch_track_each_frames_* / _pool_frames_*: set by track_each_frames_call; the wave module's: by track_each_wave_frames_call): its render frames, read by track_at, or by track_wave
+    const uint32_t* counts = nullptr;      // ... of the wave form (glv_batch_track_each_wave_frames_* / _pool_wave_frames_*): its steps per stream, uint32 [streams] or none (set by track_each)
     glv::TrackPool pool = {nullptr, 0};      // a pool call (glv_batch_track_pool_*: set by track_pool): d_pcm is ONE buffer of pool.frames frames, stream s reads it through pool.spans[s]
     TrackInput(bool f32 = false) : kind(f32 ? F32 : S16) {}
     TrackInput(Kind k) : kind(k) {}
@@ -485,11 +486,33 @@ int track_wave_frames(glv_batch* b, const TrackWavePlan& tp, const void* d_pcm, 
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "keyframe write-back launch failed: %s", hipGetErrorString(e));
     return GLV_OK;
 }
+// ... of a per-stream wave frames call (glv_batch_track_each_wave_frames_* / glv_batch_track_pool_wave_frames_*): the same two launches with stream s's rows of the
+// tables and of the starts, its count of steps and of frames and its keep pair, all read on the device (glv_wave_frames_each_kernel, glv_wave_keys_each_kernel) --
+// from the recordings, or with in.pool set through the spans of the one buffer.  The row format, the limit and the segment are track_wave_frames' own.
+int track_wave_each_frames(glv_batch* b, const TrackWavePlan& tp, const void* d_pcm, const glv::WaveWindows& w, const TrackInput& in, void* rows, hipStream_t st) {
+    const glv_track_frames_each& fe = *in.frames;
+    const bool mono = b->p.channels == 1 && !w.planar;
+    glv::WaveFramesEach e;
+    glv::WaveFrames& t = e.t;
+    t.from = fe.d_from; t.to = fe.d_to; t.mod = fe.d_mod; t.keys = fe.d_keys; t.out = rows;
+    t.frames = fe.frames; t.n = b->p.n; t.limit = (tp.pl.wave_limit + 3u) & ~3u;      // (a lane owns four frames; n is a multiple of 4)
+    t.segment = b->track_frames_segment != 0 ? b->track_frames_segment : glv::track_frames_segment(t.frames, b->streams, t.limit);
+    e.frame_counts = fe.d_frame_counts; e.counts = in.counts; e.pool = in.pool;
+    hipError_t err = glv::launch_wave_each_frames(d_pcm, (int) in.kind, w, mono, e, tp.pl.wave_r16, st); ++b->last_launches;
+    if (err != hipSuccess) return fail(GLV_ERR_HIP, "frames launch failed: %s", hipGetErrorString(err));
+    const glv::WaveKeysEach k = {fe.d_keys, t.n, in.counts, fe.d_keep, in.pool};
+    err = glv::launch_wave_each_keys(d_pcm, (int) in.kind, w, mono, k, st); ++b->last_launches;
+    if (err != hipSuccess) return fail(GLV_ERR_HIP, "keyframe write-back launch failed: %s", hipGetErrorString(err));
+    return GLV_OK;
+}
 // fr: the render frames of a frames call (track_frames_call has vetted them; a table call, so d_starts is set); nullptr: every other call
+// f32.frames: the render frames of a per-stream wave frames call (track_each_wave_frames_call has vetted them; `fr` is not set): the plan sees the longest row
 // d_starts: the table of a table call (its entry has vetted the pointer), and `hop` is not looked at; nullptr: every `hop` frames
 int track_wave(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_frames, uint32_t hop, uint32_t steps, void* d_out, void* d_work, unsigned ops, hipStream_t st,
                const glv_track_frames* fr = nullptr, const uint32_t* d_starts = nullptr) {
     if (int rc = refuse_track_pointers(d_pcm, f32, d_out, d_work)) return rc;
+    glv_track_frames shape = {};      // what the plan reads of a per-stream frames call through `fr`: the longest row (track_at's device for the FFT form)
+    if (f32.frames) { shape.frames = f32.frames->frames; shape.d_keys = f32.frames->d_keys; fr = &shape; }
     TrackWavePlan tp;
     tp.f32 = f32; tp.at = d_starts != nullptr; tp.render = fr;
     if (int rc = plan_track_wave(b, pitch_frames, hop, steps, ops, tp)) return rc;
@@ -510,9 +533,9 @@ int track_wave(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_f
     if (fr) {
         if (ops & GLV_OP_BARS) pl.out = pl.rows = static_cast<float*>(d_work);
         else pl.out = static_cast<float*>(d_out);
-        if (int rc = track_wave_frames(b, tp, d_pcm, w, pl.out, st)) return rc;
+        if (int rc = f32.frames ? track_wave_each_frames(b, tp, d_pcm, w, f32, pl.out, st) : track_wave_frames(b, tp, d_pcm, w, pl.out, st)) return rc;
         if (int rc = launch_bars_pass(b, pl, static_cast<float*>(d_out), (size_t) tp.frame_rows, r16, st)) return rc;
-        b->kernel_name = "glv_wave_frames_kernel";      // (a frames call names its own kernel, whatever follows it)
+        b->kernel_name = f32.frames ? "glv_wave_frames_each_kernel" : "glv_wave_frames_kernel";      // (a frames call names its own kernel, whatever follows it)
         return timed_launch_end(b, st);
     }
     if (fused) {
@@ -591,9 +614,10 @@ int track_each(glv_batch* b, const void* d_pcm, TrackInput f32, uint32_t pitch_f
         if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE is stateless: no gravity reads the rate table (glv_batch_track_at_s16 / _f32; ops 0x%x)", ops);
         if (!(ops & GLV_OP_GRAVITY)) return fail(GLV_ERR_INVALID, "a rates track call needs GLV_OP_GRAVITY, which reads the rate table (ops 0x%x)", ops);
     }
-    if (tb->d_counts && ((ops & GLV_OP_WAVE) || !(ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))))
+    const bool wave_frames = f32.frames && (ops & GLV_OP_WAVE);      // (track_each_wave_frames_call's: the counts bound the keyframes a stream contributes)
+    if (tb->d_counts && !wave_frames && ((ops & GLV_OP_WAVE) || !(ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))))
         return fail(GLV_ERR_INVALID, "the chain keeps no state for d_counts to protect: counts need GLV_OP_GRAVITY and / or GLV_OP_AVERAGE and no GLV_OP_WAVE (ops 0x%x)", ops);
-    f32.rows = true;
+    f32.rows = true; f32.counts = tb->d_counts;
     return track_at(b, d_pcm, f32, pitch_frames, tb->d_starts, steps, d_out, d_work, ops, st, nullptr, tb, tb->d_ur);
 }
 // glv_batch_track_pool_s16 / _f32 / _f32_planar: a per-stream call over ONE buffer of pool_frames frames, stream s through d_spans[s].  What can be said of the pool
@@ -641,7 +665,30 @@ int track_each_frames_call(glv_batch* b, const void* d_pcm, TrackInput f32, uint
     if (!fe) return fail(GLV_ERR_INVALID, "fe is NULL");
     if (reinterpret_cast<uintptr_t>(fe) & (alignof(glv_track_frames_each) - 1u))
         return fail(GLV_ERR_INVALID, "fe must be aligned like a pointer: %u bytes", (unsigned) alignof(glv_track_frames_each));
-    if (ops & GLV_OP_WAVE) return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no keyframes: a frames track call takes an FFT chain (ops 0x%x)", ops);
+    if (ops & GLV_OP_WAVE)
+        return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no keyframes: a frames track call takes an FFT chain (ops 0x%x; the wave module: glv_batch_track_each_wave_frames_* / glv_batch_track_pool_wave_frames_*)", ops);
+    if (!fe->d_from || !fe->d_to || !fe->d_mod || !fe->d_keep || !fe->d_keys) return fail(GLV_ERR_INVALID, "NULL device pointer in glv_track_frames_each");
+    if ((reinterpret_cast<uintptr_t>(fe->d_from) | reinterpret_cast<uintptr_t>(fe->d_to) | reinterpret_cast<uintptr_t>(fe->d_mod) | reinterpret_cast<uintptr_t>(fe->d_frame_counts)
+         | reinterpret_cast<uintptr_t>(fe->d_keep)) & 3u)
+        return fail(GLV_ERR_INVALID, "d_from, d_to, d_mod, d_frame_counts and d_keep must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(fe->d_keys) & 15u) return fail(GLV_ERR_INVALID, "d_keys must be 16-byte aligned");
+    if (fe->frames == 0) return fail(GLV_ERR_INVALID, "frames must be > 0");
+    f32.frames = fe;
+    if (pool) return track_pool(b, d_pcm, f32, frames_held, d_spans, tb, steps, d_out, d_work, ops, st);
+    return track_each(b, d_pcm, f32, (uint32_t) frames_held, tb, steps, d_out, d_work, ops, st);
+}
+// glv_batch_track_each_wave_frames_* / glv_batch_track_pool_wave_frames_*: track_each_frames_call's vetting for the wave form -- the structure, its pointers and their
+// alignment, and that the ops name the wave module -- then the pool call (d_spans set) or the per-stream call with the frames handed on: their refusals in their
+// words (a rate table among them), then plan_track_wave's through the table call's wave executor.  The keep pairs and the counts are device memory: the kernels
+// clamp them.  Nothing here launches.
+int track_each_wave_frames_call(glv_batch* b, const void* d_pcm, TrackInput f32, uint64_t frames_held, const glv_track_span* d_spans, bool pool, const glv_track_tables* tb,
+                                uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    if (!fe) return fail(GLV_ERR_INVALID, "fe is NULL");
+    if (reinterpret_cast<uintptr_t>(fe) & (alignof(glv_track_frames_each) - 1u))
+        return fail(GLV_ERR_INVALID, "fe must be aligned like a pointer: %u bytes", (unsigned) alignof(glv_track_frames_each));
+    if (!(ops & GLV_OP_WAVE))
+        return fail(GLV_ERR_INVALID, "a per-stream wave frames track call needs GLV_OP_WAVE (ops 0x%x; GLV_OP_FFT chains: glv_batch_track_each_frames_* / glv_batch_track_pool_frames_*)", ops);
     if (!fe->d_from || !fe->d_to || !fe->d_mod || !fe->d_keep || !fe->d_keys) return fail(GLV_ERR_INVALID, "NULL device pointer in glv_track_frames_each");
     if ((reinterpret_cast<uintptr_t>(fe->d_from) | reinterpret_cast<uintptr_t>(fe->d_to) | reinterpret_cast<uintptr_t>(fe->d_mod) | reinterpret_cast<uintptr_t>(fe->d_frame_counts)
          | reinterpret_cast<uintptr_t>(fe->d_keep)) & 3u)
@@ -914,5 +961,38 @@ int glv_batch_track_wave_frames_f32(glv_batch* b, const float* d_pcm, uint32_t p
 int glv_batch_track_wave_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const uint32_t* d_where, uint32_t steps, const glv_track_frames* fr,
                                            void* d_out, void* d_work, unsigned ops, void* hip_stream) {
     return track_frames_call(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, d_where, nullptr, steps, fr, d_out, d_work, ops, (hipStream_t) hip_stream, true);
+}
+
+// The wave module's render frames per stream (sized by glv_batch_track_wave_frames_work_bytes with the longest row: the rows add no region).  Tables and frames are
+// handed on whole.
+int glv_batch_track_each_wave_frames_s16(glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+                                         void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_wave_frames_call(b, d_pcm, false, pitch_frames, nullptr, false, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_each_wave_frames_f32(glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+                                         void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_wave_frames_call(b, d_pcm, true, pitch_frames, nullptr, false, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_each_wave_frames_f32_planar(glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps,
+                                                const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_wave_frames_call(b, d_rows, TrackInput::F32_PLANAR, pitch_frames, nullptr, false, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// ... and over one buffer of recordings, a span per stream
+int glv_batch_track_pool_wave_frames_s16(glv_batch* b, const int16_t* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
+                                         const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_wave_frames_call(b, d_pool, false, pool_frames, d_spans, true, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_pool_wave_frames_f32(glv_batch* b, const float* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
+                                         const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_wave_frames_call(b, d_pool, true, pool_frames, d_spans, true, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_track_pool_wave_frames_f32_planar(glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
+                                                const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return track_each_wave_frames_call(b, d_rows, TrackInput::F32_PLANAR, pool_frames, d_spans, true, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 }  // extern "C"

@@ -9,6 +9,8 @@
 //   glv_wave_frames_kernel    the same frame from keyframes (u + 1.0F) / 2.0F of the unpacked window of step k - 2 (render.c:777-778), as texels or their floats
 //   glv_wave_keys_kernel      the same write-back, as floats
 //   glv_wave_frames_planar_kernel / glv_wave_keys_planar_kernel   both from a planar float recording (glv_batch_track_wave_frames_f32_planar)
+//   glv_wave_frames_each_kernel / glv_wave_keys_each_kernel   both with a row of tables and of starts, a count of steps, a count of frames and a keep pair per stream,
+//                             from recordings or through a span of a pool (glv_batch_track_each_wave_frames_* / glv_batch_track_pool_wave_frames_*)
 #include <hip/hip_runtime.h>
 
 #include "glv_core.h"
@@ -493,5 +495,236 @@ hipError_t launch_wave_keys(const void* pcm, bool f32, const WaveWindows& w, boo
     else hipLaunchKernelGGL((glv_wave_keys_kernel<false>), dim3(capped_grid(quads, 256, kGridCap)), dim3(256), 0, st, pcm, w, m, keys, n, quads, keep_from, keep_to);
     return hipGetLastError();
 }
+
+// ---- the wave module's render frames per stream (glv_batch_track_each_wave_frames_* / glv_batch_track_pool_wave_frames_*) ------------------------------------
+// Both wave kernels above with what glv_track_frames_each_kernel added to its lockstep sibling: a row of the frame tables, a row of the starts, a count of steps, a
+// count of frames and a keep pair per stream -- and, for a pool call, the stream's span.  Kernels and a key helper of their own, so that the lockstep kernels and
+// wave_key keep their code; the arithmetic is theirs, line for line.
+//
+// wave_key with the window of step k - 2 of stream s where the per-stream and the pool calls put it: the entry is starts[s * steps + k - 2]; !POOL: wave_window_start's
+// clamp of it into the stream's recording, POOL: pool_window_start (glv_frame.h) of the stream's span, one 16-byte load, in 64-bit arithmetic.  Neither the starts
+// nor the span is read for k < 2, so a stream without steps (whose every index is clamped to 1) reads its two carried keyframes only.
+// KIND as wave_key's; the planar kind's channel rows lie w.pitch_frames floats apart -- the pool's frames in a pool call, whose one pair of rows every stream shares.
+// Bounded reads: k - 2 < c_s <= steps (the callers clamp k to c_s + 1), i + 4 <= n, and a window begins at most pitch_frames - n into a recording or pool_frames - n
+// into the pool whatever entry and span hold.
+template <int KIND, bool POOL>
+__device__ __forceinline__ void wave_each_key(const void* pcm, const WaveWindows& w, const int mono, const float* keys, const uint32_t n, const uint32_t k,
+                                              const uint32_t stream, const uint32_t i, const uint32_t* __restrict__ starts, const TrackSpan* __restrict__ spans,
+                                              const uint64_t pool_frames, glv_f4& l, glv_f4& r) {
+    if (k < 2u) {
+        const float* const base = keys + ((size_t) k * w.units + 2u * stream) * n + i;
+        l = *reinterpret_cast<const glv_f4*>(base);
+        r = *reinterpret_cast<const glv_f4*>(base + n);
+        return;
+    }
+    const uint32_t step = k - 2u;                                               // (< c_s <= steps: k was clamped to c_s + 1)
+    const uint32_t entry = starts[(size_t) stream * w.steps + step];
+    uint64_t first;                                                             // the lane's first frame, in 64-bit arithmetic
+    if constexpr (POOL) {
+        const glv_u4 v = *reinterpret_cast<const glv_u4*>(spans + stream);
+        first = pool_window_start((uint64_t) v.x | (uint64_t) v.y << 32, v.z, entry, pool_frames, (uint64_t) n) + i;
+    } else first = wave_window_start(w, stream, step, entry) + i;
+    float a[4], b[4];
+    if constexpr (KIND == 2) {
+        if constexpr (!POOL) first += (uint64_t) stream * w.pitch_frames;      // (a stream is two rows: its channel-0 row)
+        const float* const src = static_cast<const float*>(pcm) + first;
+        const float* const sib = src + w.pitch_frames;
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) { const glv_f4 v = *reinterpret_cast<const glv_f4*>(src); a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w; }
+        else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[q] = src[q];
+        }
+        if ((reinterpret_cast<uintptr_t>(sib) & 15u) == 0u) { const glv_f4 v = *reinterpret_cast<const glv_f4*>(sib); b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w; }
+        else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = sib[q];
+        }
+    } else if constexpr (KIND == 1) {
+        const glv_f2* const src = static_cast<const glv_f2*>(pcm) + first;
+        glv_f2 f[4];
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+            const glv_f4 lo = *reinterpret_cast<const glv_f4*>(src), hi = *reinterpret_cast<const glv_f4*>(src + 2);
+            f[0] = glv_f2{lo.x, lo.y}; f[1] = glv_f2{lo.z, lo.w}; f[2] = glv_f2{hi.x, hi.y}; f[3] = glv_f2{hi.z, hi.w};
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) f[q] = src[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (mono) { a[q] = (f[q].x + f[q].y) / 2; b[q] = a[q]; } else { a[q] = f[q].x; b[q] = f[q].y; }     // pulse_input.c:167
+        }
+    } else {
+        const uint32_t* const src = static_cast<const uint32_t*>(pcm) + first;
+        uint32_t f[4];
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+            const glv_u4 v = *reinterpret_cast<const glv_u4*>(src);
+            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) f[q] = src[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int x = (int16_t) (f[q] & 0xffffu), y = (int16_t) (f[q] >> 16);
+            if (mono) { a[q] = unpack_s16_mono(x, y); b[q] = a[q]; } else { a[q] = unpack_s16(x); b[q] = unpack_s16(y); }
+        }
+    }
+    l = glv_f4{(a[0] + 1.0f) / 2.0f, (a[1] + 1.0f) / 2.0f, (a[2] + 1.0f) / 2.0f, (a[3] + 1.0f) / 2.0f};       // render.c:777-778
+    r = glv_f4{(b[0] + 1.0f) / 2.0f, (b[1] + 1.0f) / 2.0f, (b[2] + 1.0f) / 2.0f, (b[3] + 1.0f) / 2.0f};
+}
+
+// glv_wave_frames_kernel's walk over a row of the tables per stream.  What differs, and nothing else (glv_track_frames_each_kernel's list): the table base of a work
+// item is stream * frames; `last_key` is c_s + 1 of the item's stream, c_s = min(counts[s], steps), so a keyframe index never names a window behind the stream's
+// count; the walk stops at f_s = min(frame_counts[s], frames), the rest of the segment is stored as zero texels (R16_OUT) or their floats 0.0f, and no table entry
+// at j >= f_s is requested.  Both counts are loaded once per item.  The frame tables, the counts, the starts and the spans are separate __restrict__ arguments,
+// never written here, and every address they are read at derives from blockIdx.x, the kernel's arguments and a uniform table entry: uniform loads, counted apart
+// from the vector memory counter that the chain of stores fills.
+template <int KIND, bool POOL, bool R16_OUT>
+__global__ void __launch_bounds__(kFramesLanes) glv_wave_frames_each_kernel(const void* pcm, const WaveWindows w, const int mono, const WaveFrames t,
+                                                                            const uint32_t* __restrict__ tfrom, const uint32_t* __restrict__ tto,
+                                                                            const float* __restrict__ tmod, const uint32_t* __restrict__ frame_counts,
+                                                                            const uint32_t* __restrict__ counts, const uint32_t* __restrict__ starts,
+                                                                            const TrackSpan* __restrict__ spans, const uint64_t pool_frames, const uint32_t groups,
+                                                                            const uint64_t items) {
+    const uint32_t streams = w.units / 2u;
+    for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const uint32_t group = (uint32_t) (item % groups);
+        const uint64_t rest = item / groups;
+        const uint32_t stream = (uint32_t) (rest % streams);                // (< streams: the tables, the counts and the spans have a row for it)
+        const uint32_t seg = (uint32_t) (rest / streams);
+        const uint32_t i = (group * (uint32_t) kFramesLanes + threadIdx.x) * 4u;
+        if (i >= t.limit) continue;                                         // the last group of a row: nothing of these lanes is read or written
+        uint32_t c = w.steps, f = t.frames;
+        if (counts) { const uint32_t v = counts[stream]; c = v < c ? v : c; }
+        if (frame_counts) { const uint32_t v = frame_counts[stream]; f = v < f ? v : f; }
+        const uint32_t last_key = c + 1u;                                   // (<= steps + 1)
+        const uint32_t j0 = seg * t.segment;                                // (< frames: the host counted the segments)
+        const uint32_t j1 = t.frames - j0 > t.segment ? j0 + t.segment : t.frames;
+        const uint32_t jw = f <= j0 ? j0 : f < j1 ? f : j1;                 // the walk's end: frames [jw, j1) of the segment lie behind the stream's count
+        const uint32_t* const from_s = tfrom + (size_t) stream * t.frames;
+        const uint32_t* const to_s = tto + (size_t) stream * t.frames;
+        const float* const mod_s = tmod + (size_t) stream * t.frames;
+        auto key = [&](uint32_t k, glv_f4& l, glv_f4& r) { wave_each_key<KIND, POOL>(pcm, w, mono, t.keys, t.n, k, stream, i, starts, spans, pool_frames, l, r); };
+        auto emit = [&](uint32_t j, uint32_t ch, const glv_f4 v) {
+            const uint32_t lo = pack_unorm16(v.x, v.y), hi = pack_unorm16(v.z, v.w);      // render.c:521-524
+            const size_t at = ((size_t) j * w.units + 2u * stream + ch) * t.n + i;
+            if constexpr (R16_OUT) *reinterpret_cast<glv_u2*>(static_cast<uint16_t*>(t.out) + at) = glv_u2{lo, hi};
+            else *reinterpret_cast<glv_f4*>(static_cast<float*>(t.out) + at) =
+                     glv_f4{unorm16_to_float(lo & 0xffffu), unorm16_to_float(lo >> 16), unorm16_to_float(hi & 0xffffu), unorm16_to_float(hi >> 16)};
+        };
+        uint32_t from[kFramesDepth], to[kFramesDepth];
+        float mod[kFramesDepth];
+#pragma unroll
+        for (int d = 0; d < kFramesDepth; ++d) {
+            const bool in = (uint32_t) d < jw - j0;
+            from[d] = in ? from_s[j0 + (uint32_t) d] : 0u; to[d] = in ? to_s[j0 + (uint32_t) d] : 0u; mod[d] = in ? mod_s[j0 + (uint32_t) d] : 0.0f;
+        }
+        uint32_t ks = 0xffffffffu, ke = 0xffffffffu;                         // the keyframes in s and e: none yet (no clamped index is this)
+        glv_f4 sl = { 0.0f, 0.0f, 0.0f, 0.0f }, sr = sl, el = sl, er = sl;
+        for (uint32_t jb = j0; jb < jw; jb += (uint32_t) kFramesDepth) {
+#pragma unroll
+            for (int d = 0; d < kFramesDepth; ++d) {
+                const uint32_t j = jb + (uint32_t) d;
+                if (j >= jw) break;
+                const uint32_t kf = from[d] < last_key ? from[d] : last_key, kt = to[d] < last_key ? to[d] : last_key;
+                const float m = mod[d];
+                if (jw - j > (uint32_t) kFramesDepth) {
+                    from[d] = from_s[j + (uint32_t) kFramesDepth]; to[d] = to_s[j + (uint32_t) kFramesDepth]; mod[d] = mod_s[j + (uint32_t) kFramesDepth];
+                }
+                glv_f4 nl = sl, nr = sr;
+                if (kf != ks) { if (kf == ke) { nl = el; nr = er; } else key(kf, nl, nr); }
+                if (kt != ke) { if (kt == ks) { el = sl; er = sr; } else key(kt, el, er); }
+                sl = nl; sr = nr; ks = kf; ke = kt;
+                glv_f4 wl = sl, wr = sr;
+                if (kf != kt) { wl = sl + ((el - sl) * m); wr = sr + ((er - sr) * m); }      // render.c:1806
+                emit(j, 0u, wl);
+                emit(j, 1u, wr);
+            }
+        }
+        for (uint32_t j = jw; j < j1; ++j) {                                // zero texels: pack_unorm16 of them is 0, and 0 / 65535 is 0.0f
+            const size_t at = ((size_t) j * w.units + 2u * stream) * t.n + i;
+            if constexpr (R16_OUT) {
+                *reinterpret_cast<glv_u2*>(static_cast<uint16_t*>(t.out) + at) = glv_u2{ 0u, 0u };
+                *reinterpret_cast<glv_u2*>(static_cast<uint16_t*>(t.out) + at + t.n) = glv_u2{ 0u, 0u };
+            } else {
+                *reinterpret_cast<glv_f4*>(static_cast<float*>(t.out) + at) = glv_f4{ 0.0f, 0.0f, 0.0f, 0.0f };
+                *reinterpret_cast<glv_f4*>(static_cast<float*>(t.out) + at + t.n) = glv_f4{ 0.0f, 0.0f, 0.0f, 0.0f };
+            }
+        }
+    }
+}
+
+// glv_wave_keys_kernel's body with the pair taken per stream from `keep` (uint32 [streams][2]) and clamped to c_s + 1: element i of both kept keyframes is read before
+// element i of either destination is written, and no other lane touches element i -- any pair is safe.
+template <int KIND, bool POOL>
+__global__ void __launch_bounds__(256) glv_wave_keys_each_kernel(const void* pcm, const WaveWindows w, const int mono, float* keys, const uint32_t n, const size_t quads,
+                                                                 const uint32_t* __restrict__ counts, const uint32_t* __restrict__ keep,
+                                                                 const uint32_t* __restrict__ starts, const TrackSpan* __restrict__ spans, const uint64_t pool_frames) {
+    const uint32_t per_stream = n / 4u;
+    for (size_t q = (size_t) blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t) gridDim.x * blockDim.x) {
+        const uint32_t stream = (uint32_t) (q / per_stream), i = (uint32_t) (q % per_stream) * 4u;
+        uint32_t c = w.steps;
+        if (counts) { const uint32_t v = counts[stream]; c = v < c ? v : c; }
+        const uint32_t last_key = c + 1u;
+        uint32_t kf = keep[2u * stream], kt = keep[2u * stream + 1u];
+        kf = kf < last_key ? kf : last_key; kt = kt < last_key ? kt : last_key;
+        glv_f4 al, ar, bl, br;
+        wave_each_key<KIND, POOL>(pcm, w, mono, keys, n, kf, stream, i, starts, spans, pool_frames, al, ar);
+        wave_each_key<KIND, POOL>(pcm, w, mono, keys, n, kt, stream, i, starts, spans, pool_frames, bl, br);
+        float* const k0 = keys + (size_t) 2u * stream * n + i;
+        float* const k1 = k0 + (size_t) w.units * n;
+        *reinterpret_cast<glv_f4*>(k0) = al; *reinterpret_cast<glv_f4*>(k0 + n) = ar;
+        *reinterpret_cast<glv_f4*>(k1) = bl; *reinterpret_cast<glv_f4*>(k1 + n) = br;
+    }
+}
+
+// what both launchers ask of the windows: a table with a row per stream, and a recording (or a pool behind an aligned span table) that holds one window
+static bool wave_each_ok(const void* pcm, int kind, const WaveWindows& w, const TrackPool& pool, uint32_t n) {
+    if (!pcm || !w.starts || kind < 0 || kind > 2 || (w.planar != 0u) != (kind == 2)) return false;
+    if (n == 0 || (n & 3u) || w.units == 0 || (w.units & 1u) || w.steps == 0 || w.steps > 0xfffffffdu) return false;
+    if (pool.spans) return (reinterpret_cast<uintptr_t>(pool.spans) & 15u) == 0u && pool.frames >= n && w.pitch_frames == pool.frames;      // (pool_window_start subtracts the window)
+    return w.pitch_frames >= n && w.start_max == w.pitch_frames - n;
+}
+
+#define GLV_WAVE_EACH_KINDS(GO) \
+    do { \
+        if (pooled) { if (kind == 2) GO(2, true); else if (kind == 1) GO(1, true); else GO(0, true); } \
+        else { if (kind == 2) GO(2, false); else if (kind == 1) GO(1, false); else GO(0, false); } \
+    } while (0)
+
+hipError_t launch_wave_each_frames(const void* pcm, int kind, const WaveWindows& w, bool mono, const WaveFramesEach& e, bool r16, hipStream_t st) {
+    const WaveFrames& t = e.t;
+    if (!wave_each_ok(pcm, kind, w, e.pool, t.n) || !t.from || !t.to || !t.mod || !t.keys || !t.out) return hipErrorInvalidValue;
+    if (t.frames == 0 || t.segment == 0 || t.limit == 0 || t.limit > t.n || (t.limit & 3u)) return hipErrorInvalidValue;
+    const uint32_t groups = (t.limit / 4u + (uint32_t) kFramesLanes - 1u) / (uint32_t) kFramesLanes;
+    const uint64_t segments = ((uint64_t) t.frames + t.segment - 1u) / t.segment;
+    const uint64_t items = segments * (w.units / 2u) * groups;              // (< 2^32 * 2^31 / 4: no overflow)
+    const unsigned grid = capped_grid((size_t) items, 1, kFramesGridCap);
+    const int m = mono && kind != 2 ? 1 : 0;
+    const bool pooled = e.pool.spans != nullptr;
+#define GLV_WAVE_EACH_FRAMES(KIND, POOL) \
+    do { if (r16) hipLaunchKernelGGL((glv_wave_frames_each_kernel<KIND, POOL, true>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, t.from, t.to, t.mod, \
+                                     e.frame_counts, e.counts, w.starts, e.pool.spans, e.pool.frames, groups, items); \
+         else hipLaunchKernelGGL((glv_wave_frames_each_kernel<KIND, POOL, false>), dim3(grid), dim3(kFramesLanes), 0, st, pcm, w, m, t, t.from, t.to, t.mod, \
+                                 e.frame_counts, e.counts, w.starts, e.pool.spans, e.pool.frames, groups, items); } while (0)
+    GLV_WAVE_EACH_KINDS(GLV_WAVE_EACH_FRAMES);
+#undef GLV_WAVE_EACH_FRAMES
+    return hipGetLastError();
+}
+
+hipError_t launch_wave_each_keys(const void* pcm, int kind, const WaveWindows& w, bool mono, const WaveKeysEach& k, hipStream_t st) {
+    if (!wave_each_ok(pcm, kind, w, k.pool, k.n) || !k.keys || !k.keep) return hipErrorInvalidValue;
+    const size_t quads = (size_t) (w.units / 2u) * (k.n / 4u);
+    const unsigned grid = capped_grid(quads, 256, kGridCap);
+    const int m = mono && kind != 2 ? 1 : 0;
+    const bool pooled = k.pool.spans != nullptr;
+#define GLV_WAVE_EACH_KEYS(KIND, POOL) \
+    hipLaunchKernelGGL((glv_wave_keys_each_kernel<KIND, POOL>), dim3(grid), dim3(256), 0, st, pcm, w, m, k.keys, k.n, quads, k.counts, k.keep, w.starts, k.pool.spans, \
+                       k.pool.frames)
+    GLV_WAVE_EACH_KINDS(GLV_WAVE_EACH_KEYS);
+#undef GLV_WAVE_EACH_KEYS
+    return hipGetLastError();
+}
+#undef GLV_WAVE_EACH_KINDS
 
 }  // namespace glv

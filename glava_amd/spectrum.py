@@ -185,6 +185,11 @@ def lib() -> C.CDLL:
             for kind in ("s16", "f32", "f32_planar"):
                 getattr(L, "glv_batch_track_each_frames_" + kind).argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, FE, vp, vp, C.c_uint, vp]
                 getattr(L, "glv_batch_track_pool_frames_" + kind).argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, FE, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_track_each_wave_frames_s16"):      # (likewise: the wave module's frames calls per stream, the same argument lists)
+            TT, FE = C.POINTER(TrackTables), C.POINTER(TrackFramesEach)
+            for kind in ("s16", "f32", "f32_planar"):
+                getattr(L, "glv_batch_track_each_wave_frames_" + kind).argtypes = [vp, vp, C.c_uint32, TT, C.c_uint32, FE, vp, vp, C.c_uint, vp]
+                getattr(L, "glv_batch_track_pool_wave_frames_" + kind).argtypes = [vp, vp, C.c_uint64, vp, TT, C.c_uint32, FE, vp, vp, C.c_uint, vp]
         if hasattr(L, "glv_batch_set_bufscale"):        # (likewise: `setbufscale k` for a batch -- windows of k * n frames, decimated on the device)
             L.glv_batch_set_bufscale.argtypes = [vp, C.c_uint32]
             L.glv_batch_bufscale.argtypes = [vp]
@@ -702,6 +707,56 @@ class Batch:
                                      stream: int | None = None) -> None:
         """track_pool_frames_f32 from a planar pool (glv_batch_track_pool_frames_f32_planar): d_rows float32 [2][pool_frames], 4-byte aligned, no mono mix"""
         self._track_pool_frames("f32_planar", d_rows, pool_frames, d_spans, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    # ---- ... for the wave module: keyframes read from each stream's own windows of its recording, or of its span of a pool
+    def _track_each_wave_frames(self, kind: str, d_pcm, pitch_frames: int, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int, stream) -> None:
+        tb = TrackTables(*(_ptr(t) for t in tables))
+        fe = TrackFramesEach(*(_ptr(t) for t in frame_tables), frames, _ptr(d_keys))
+        _check(getattr(lib(), "glv_batch_track_each_wave_frames_" + kind)(self._h, _ptr(d_pcm), pitch_frames, C.byref(tb), steps, C.byref(fe), _ptr(d_out), _ptr(d_work),
+                                                                          ops, _ptr(stream)))
+
+    def track_each_wave_frames_s16(self, d_pcm, pitch_frames: int, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                                   stream: int | None = None) -> None:
+        """track_wave_frames_s16 with everything per stream (glv_batch_track_each_wave_frames_s16).  tables = (d_starts, None, d_counts): d_starts uint32
+        [streams][steps], row s is stream s's; no rate table; d_counts uint32 [streams] or None -- stream s contributes its first c_s = min(d_counts[s], steps)
+        windows as keyframes 2 .. c_s + 1.  frame_tables = (d_from, d_to, d_mod, d_frame_counts, d_keep) as track_each_frames_s16 takes them.  Every index is
+        clamped on the device to c_s + 1; a stream with c_s = 0 lerps between its two carried keyframes; frames behind a stream's count are what the call's last
+        stage makes of a zero texel row.  ops OP_WAVE [| OP_BARS] [| OP_R16]; d_out [frames][streams][2][w]; d_work at least
+        track_wave_frames_work_bytes(steps, frames, ops) bytes.  Each stream is bit for bit track_wave_frames_s16 on a one-stream batch.
+        Tables: glava_amd.track_starts.stack_tables and stack_frame_tables."""
+        self._track_each_wave_frames("s16", d_pcm, pitch_frames, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_each_wave_frames_f32(self, d_pcm, pitch_frames: int, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                                   stream: int | None = None) -> None:
+        """track_each_wave_frames_s16 from a float recording (glv_batch_track_each_wave_frames_f32): d_pcm float32 [streams][pitch_frames][2], 8-byte aligned"""
+        self._track_each_wave_frames("f32", d_pcm, pitch_frames, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_each_wave_frames_f32_planar(self, rows, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """track_each_wave_frames_f32 from a planar recording (glv_batch_track_each_wave_frames_f32_planar); `rows` as track_at_f32_planar takes them, no mono mix"""
+        self._track_each_wave_frames("f32_planar", rows, planar_pitch_frames(rows, self.streams), tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def _track_pool_wave_frames(self, kind: str, d_pool, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                                stream) -> None:
+        tb = TrackTables(*(_ptr(t) for t in tables))
+        fe = TrackFramesEach(*(_ptr(t) for t in frame_tables), frames, _ptr(d_keys))
+        _check(getattr(lib(), "glv_batch_track_pool_wave_frames_" + kind)(self._h, _ptr(d_pool), pool_frames, _ptr(d_spans), C.byref(tb), steps, C.byref(fe), _ptr(d_out),
+                                                                          _ptr(d_work), ops, _ptr(stream)))
+
+    def track_pool_wave_frames_s16(self, d_pool, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                                   stream: int | None = None) -> None:
+        """track_each_wave_frames_s16 over ONE buffer of recordings (glv_batch_track_pool_wave_frames_s16): d_pool, pool_frames and d_spans as track_pool_s16 takes
+        them, everything else as track_each_wave_frames_s16"""
+        self._track_pool_wave_frames("s16", d_pool, pool_frames, d_spans, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_pool_wave_frames_f32(self, d_pool, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                                   stream: int | None = None) -> None:
+        """track_pool_wave_frames_s16 from a float pool (glv_batch_track_pool_wave_frames_f32): d_pool float32 [pool_frames][2], interleaved L R, 8-byte aligned"""
+        self._track_pool_wave_frames("f32", d_pool, pool_frames, d_spans, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
+
+    def track_pool_wave_frames_f32_planar(self, d_rows, pool_frames: int, d_spans, tables, steps: int, frame_tables, frames: int, d_keys, d_out, d_work, ops: int,
+                                          stream: int | None = None) -> None:
+        """track_pool_wave_frames_f32 from a planar pool (glv_batch_track_pool_wave_frames_f32_planar): d_rows float32 [2][pool_frames], 4-byte aligned, no mono mix"""
+        self._track_pool_wave_frames("f32_planar", d_rows, pool_frames, d_spans, tables, steps, frame_tables, frames, d_keys, d_out, d_work, ops, stream)
 
     def track_wave_work_bytes(self, pitch_frames: int, hop: int, steps: int, ops: int) -> int:
         """bytes of device workspace track_wave_s16 needs for these arguments (glv_batch_track_wave_work_bytes; 256 where the call needs none); raises on

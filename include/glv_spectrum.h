@@ -927,8 +927,8 @@ int glv_batch_track_pool_f32_planar
  *              and equal keep pairs the call is bit for bit glv_batch_track_frames_*.
  *   Refused, launching nothing and leaving the batch untouched: everything glv_batch_track_frames_* refuses about ops, storage and frames, everything the
  *              per-stream or pool call refuses, and with GLV_ERR_INVALID fe NULL or not aligned like a pointer, any of its pointers NULL except
- *              d_frame_counts, a table not 4-byte aligned, d_keys not 16-byte aligned, frames == 0.  GLV_OP_WAVE is refused: the wave form per stream is not
- *              built (glv_batch_track_wave_frames_* remains the lockstep call).
+ *              d_frame_counts, a table not 4-byte aligned, d_keys not 16-byte aligned, frames == 0.  GLV_OP_WAVE is refused: the wave form per stream has entries
+ *              of its own, glv_batch_track_each_wave_frames_* / glv_batch_track_pool_wave_frames_* below.
  * Launches (glv_batch_last_launches): the per-stream call's without bars, + 2 (glv_track_frames_each_kernel, glv_track_keys_each_kernel), + 1 with GLV_OP_BARS.
  * Stream-ordered and capturable from the first call; all tables, counts and keep pairs are read when the kernels run, so rewriting them re-aims a captured
  * graph.  glv_batch_kernel_name reports "glv_track_frames_each_kernel".
@@ -963,6 +963,61 @@ int glv_batch_track_pool_frames_f32
     (glv_batch* b, const float* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
      void* d_out, void* d_work, unsigned ops, void* hip_stream);
 int glv_batch_track_pool_frames_f32_planar
+    (glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+     void* d_out, void* d_work, unsigned ops, void* hip_stream);
+/* Track mode at render frames per stream FOR THE WAVE MODULE: the reference switches interpolation off only for binds that carry an fft transform (render.c:2131-2135,
+ * :2161-2168), so the wave module lerps on every gl_storage, the shipped `setaccelfft true` included -- listeners at 60 Hz and 144 Hz displays of shared
+ * recordings are its ordinary case.  These entries are glv_batch_track_wave_frames_* with everything per stream: the argument lists of
+ * glv_batch_track_each_frames_* / glv_batch_track_pool_frames_*, the same two structures, no new sizing query.  Added within ABI 7; detect by the symbol.
+ * Sized by glv_batch_track_wave_frames_work_bytes(b, steps, fe->frames, ops) with frames the longest row: 256 without bars, the frames' rows with bars.
+ *   ops.       GLV_OP_WAVE [| GLV_OP_BARS] [| GLV_OP_R16], on every batch glv_batch_track_wave_frames_* takes them on: any gl_storage, channels 1 and 2, the
+ *              pre-smoothing pass, bar texels, fewer than 256 bars, maximum / hybrid.  The planar kinds do no mono mix.
+ *   Steps.     tb->d_starts is uint32 [streams][steps]; tb->d_ur must be NULL (GLV_ERR_INVALID in the per-stream call's words: no gravity reads a rate table).
+ *              tb->d_counts is ACCEPTED here, unlike in glv_batch_track_each_* 's wave form: c_s = min(d_counts[s], steps) is the number of keyframes stream s
+ *              contributes, NULL means steps.  Nothing is computed per step.
+ *   Keyframes. Keyframe k < 2 of stream s is rows 2 s, 2 s + 1 of d_keys[k]; keyframe k >= 2 is (u + 1.0F) / 2.0F of the backend's unpack u of the window of
+ *              step k - 2, which begins min(d_starts[s * steps + k - 2], pitch_frames - n) frames into the stream's recording, or for the pool entries at pool frame
+ *              min(first[s] + min(entry, frames[s] - n or 0), pool_frames - n) of its span, evaluated in the kernel in 64-bit arithmetic (glv_batch_track_pool_* 's
+ *              rule).  Every index read from d_from, d_to or d_keep is clamped in the kernels to c_s + 1.  A stream with c_s == 0 lerps between its two carried
+ *              keyframes and reads neither its recording, its span nor its row of d_starts.  Whatever tables, counts and spans hold, no launch reads outside the
+ *              recordings or the pool, d_keys, [0, steps) of a stream's starts row, or [0, f_s) of its frame rows.
+ *   Frames.    f_s = min(d_frame_counts[s], frames), NULL: frames.  For j < f_s: from == to gives the keyframe's own bits, otherwise s + ((e - s) * mod) in three
+ *              float operations without contraction; then the upload's quantiser, then what a GLV_OP_WAVE process call with these ops does.  For j >= f_s the
+ *              frames stage writes zero texels and the output row is what the last stage makes of a zero texel row: 0 texels, 0.0f, or the bars of a zero row.
+ *              No table entry at j >= f_s is read.  d_out stays frame-major: [frames][streams][2][w].
+ *   Write-back. Per stream d_keys[0] <- keyframe d_keep[2 s], d_keys[1] <- keyframe d_keep[2 s + 1], both clamped, both read before either is written; any pair
+ *              is safe (a lane reads and writes its own elements only).  Chunks compose per stream.
+ *   Equivalence. A stream with c_s >= 1 and f_s >= 1 is bit for bit glv_batch_track_wave_frames_* on a one-stream batch with its recording (pool entries: its
+ *              materialised span with entries pre-clamped), steps = c_s, frames = f_s, its rows, its rows of d_keys, and its keep pair where the host accepts that
+ *              pair.  With equal rows, NULL counts and equal keep pairs the call is bit for bit the lockstep call.  The batch's state is not touched.
+ *   Refused, launching nothing: everything glv_batch_track_wave_frames_* refuses about ops, batch and frames (bufscale > 1 among it, as every wave form);
+ *              everything the vetting of glv_track_frames_each refuses (fe NULL or not aligned like a pointer, any of its pointers NULL except d_frame_counts, a
+ *              table not 4-byte aligned, d_keys not 16-byte aligned, frames == 0); the per-stream and pool calls' refusals about tb, d_starts, d_spans and
+ *              pool_frames; ops without GLV_OP_WAVE (FFT chains: glv_batch_track_each_frames_* / glv_batch_track_pool_frames_*).
+ * Launches (glv_batch_last_launches): 2 (glv_wave_frames_each_kernel, glv_wave_keys_each_kernel), 3 with GLV_OP_BARS.  Kernels only: nothing is allocated or
+ * synchronised, and the first call is capturable; all tables, counts, keep pairs and spans are read when the kernels run, so rewriting them re-aims a captured
+ * graph.  glv_batch_kernel_name reports "glv_wave_frames_each_kernel".
+ * Kernels (glv_track_frames.hip): glv_wave_frames_kernel's walk -- four frames of both channel rows a lane, both keyframes in registers, table entries 4 frames
+ * ahead, one wave a workgroup looping over [segment][stream][group] items -- with the table base stream * frames, last_key from the stream's count, the walk
+ * stopped at f_s and zeros behind it; tables, counts, starts and spans are read through uniform (scalar) loads.  Every kernel that existed keeps its device code
+ * byte for byte; registers, scratch and instruction counts of the new kernels beside their lockstep siblings: profiles/r28/track_wave_frames_each_isa.txt.
+ * Python: the tables are glava_amd.track_starts.stack_tables, stack_frame_tables and pool_spans, as for the FFT entries. */
+int glv_batch_track_each_wave_frames_s16
+    (glv_batch* b, const int16_t* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_each_wave_frames_f32
+    (glv_batch* b, const float* d_pcm, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_each_wave_frames_f32_planar
+    (glv_batch* b, const float* d_rows, uint32_t pitch_frames, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe, void* d_out, void* d_work,
+     unsigned ops, void* hip_stream);
+int glv_batch_track_pool_wave_frames_s16
+    (glv_batch* b, const int16_t* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+     void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_pool_wave_frames_f32
+    (glv_batch* b, const float* d_pool, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
+     void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_track_pool_wave_frames_f32_planar
     (glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps, const glv_track_frames_each* fe,
      void* d_out, void* d_work, unsigned ops, void* hip_stream);
 /* device pointer to the gravity state float [streams][2][n] == the latest output of a chain ending in gravity: the
