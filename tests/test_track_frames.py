@@ -337,7 +337,8 @@ def test_indices_beyond_the_last_keyframe_are_clamped(glvlib, n, streams):
 # ---- 6. launch caps ---------------------------------------------------------------------------------------------------------------------------------------
 def test_more_work_items_than_the_grid_has_workgroups(glvlib, oracle):
     """n = 256, one stream, segments of one frame: 2 * 5003 work items of the frames kernel against its 8192 workgroups (glv_track_frames.hip kFramesGridCap) --
-    the grid loops; the write-back's 128 lanes are below its cap at any number of frames"""
+    the grid loops; the write-back's 128 lanes are below its cap at any number of frames.  That cap is crossed through streams, not frames: from 4097
+    streams of n = 256 on, which tests/test_track_each_launch_geometry.py runs"""
     G = glvlib
     n, streams, frames = 256, 1, 5003
     assert 2 * frames > 256 * 32
