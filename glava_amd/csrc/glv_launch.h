@@ -158,6 +158,18 @@ hipError_t launch_slots(int kind, const SlotTable& t, hipStream_t st);
 // one -- two tables of the same regions in the same order, each with its own bases, positions and streams (blob unused), count pairs; a pair with either entry
 // >= its side's streams is skipped where it is read.  Tables that differ in a region's start, sizes, unit or ring length are refused, like every malformed one.
 hipError_t launch_slot_copy(const SlotTable& src, const SlotTable& dst, hipStream_t st);
+// The two copies of a ring track call (glv_ring_track.hip; glv_batch_ring_track_s16 / _f32).  launch_ring_track_stage (glv_ring_stage_kernel) writes every stream's
+// ring, oldest frame first, and its updates * new_frames new frames behind it into `stage` -- [streams][pitch] frames of 4 (s16) or 8 (f32) bytes, pitch a multiple of
+// 4 and >= n + updates * new_frames, the frames beyond those zeros -- and (t + 1) * new_frames into starts[t], t < updates.  fresh: [streams][updates * new_frames]
+// frames, frame aligned; null: zeros.  launch_ring_track_keep (glv_ring_keep_kernel) writes frames [updates * new_frames, updates * new_frames + n) of every staged
+// stream back as its ring, oldest frame at 0.  ring and stage 16-byte aligned, n a multiple of 4, pos < n: anything else is refused.
+struct RingTrack {
+    void* ring; const void* fresh; void* stage; uint32_t* starts;
+    uint32_t n, pos, new_frames, updates, pitch, streams;
+};
+constexpr size_t kRingTrackGridCap = 256 * 8;      // 256 CUs x 8 resident 256-lane workgroups of 256 pieces each; the kernels' loops take what lies beyond
+hipError_t launch_ring_track_stage(bool f32, const RingTrack& r, hipStream_t st);
+hipError_t launch_ring_track_keep(bool f32, const RingTrack& r, hipStream_t st);
 hipError_t launch_lerp(const float* s0, const float* e0, float* out, size_t total, float mod, hipStream_t st);
 hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin, const int* smax, uint32_t asz, uint32_t reach,
                          uint32_t max_window, hipStream_t st);

@@ -699,6 +699,80 @@ int track_each_wave_frames_call(glv_batch* b, const void* d_pcm, TrackInput f32,
     if (pool) return track_pool(b, d_pcm, f32, frames_held, d_spans, tb, steps, d_out, d_work, ops, st);
     return track_each(b, d_pcm, f32, (uint32_t) frames_held, tb, steps, d_out, d_work, ops, st);
 }
+
+// ---- track mode for ring batches: `updates` ring updates in one call (glv_batch_ring_track_s16 / _f32) -------------------------------------------
+// A ring batch's stream is a recording the library holds the last n frames of.  The call stages, per stream, those n frames oldest first with the updates *
+// new_frames new ones behind them in a region in FRONT of the workspace (glv_ring_stage_kernel, which also writes the table of window starts (t + 1) *
+// new_frames behind that region), runs the table call on the staged recordings -- its plan, its stages, its refusals in its words, its workspace behind the two
+// new regions -- and writes each stream's last n staged frames back as its ring (glv_ring_keep_kernel), oldest frame at 0.  Nothing of the batch moves before
+// every refusal has had its say; the ring and its position move last.
+struct RingTrackPlan {
+    uint32_t pitch = 0;                 // frames of a staged recording: n + updates * new_frames, rounded up to 4 frames (every stream starts on 16 bytes)
+    uint64_t stage_bytes = 0;           // the staged recordings, at the frame size of the widest ring the batch has: one query sizes both entries
+    uint64_t starts_bytes = 0;          // the table of window starts behind them
+    uint64_t work_bytes = 0;            // both and the table call's own workspace
+};
+// f32: the ring the call reads -- 0 s16, 1 f32; -1: the sizing query, which asks for any ring
+int plan_ring_track(const glv_batch* b, int f32, uint32_t new_frames, uint32_t updates, unsigned ops, RingTrackPlan& rp) {
+    const uint32_t n = b->p.n;
+    if (new_frames == 0 || new_frames > n) return fail(GLV_ERR_INVALID, "new_frames=%u: must be in [1, n=%u]", new_frames, n);
+    if (updates == 0) return fail(GLV_ERR_INVALID, "updates must be > 0");
+    const bool has_s16 = b->d_ring.get() != nullptr, has_f32 = b->d_ring_f32.get() != nullptr;
+    if (f32 < 0 ? !has_s16 && !has_f32 : f32 ? !has_f32 : !has_s16)
+        return fail(GLV_ERR_STATE, "the batch was created without GLV_OP_RING_%s in its ops_mask (rings are allocated at creation, a ring track call never allocates)",
+                    f32 < 0 ? "S16 / GLV_OP_RING_F32" : f32 ? "F32" : "S16");
+    if ((uint64_t) updates * new_frames > 0xffffffffull - 3u - n)
+        return fail(GLV_ERR_INVALID, "updates=%u of new_frames=%u: more than 2^32 frames in one call, cut the updates into chunks", updates, new_frames);
+    rp.pitch = (n + updates * new_frames + 3u) & ~3u;
+    uint64_t inner = 0;
+    if (ops & GLV_OP_WAVE) {
+        TrackWavePlan tp;
+        tp.at = true;
+        if (int rc = plan_track_wave(b, rp.pitch, 0u, updates, ops, tp)) return rc;
+        inner = tp.work_bytes;
+    } else {
+        TrackPlan tp;
+        if (int rc = plan_track_at(b, rp.pitch, 0u, updates, ops, tp)) return rc;
+        inner = tp.work_bytes;
+    }
+    rp.stage_bytes = up256((uint64_t) b->streams * rp.pitch * (has_f32 ? 8u : 4u));
+    rp.starts_bytes = up256((uint64_t) updates * 4u);
+    rp.work_bytes = rp.stage_bytes + rp.starts_bytes + inner;
+    return GLV_OK;
+}
+int ring_track(glv_batch* b, bool f32, const void* d_new, uint32_t new_frames, uint32_t updates, void* d_out, void* d_work, unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    RingTrackPlan rp;
+    if (int rc = plan_ring_track(b, f32 ? 1 : 0, new_frames, updates, ops, rp)) return rc;
+    if (!d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (f32 && !d_new) return fail(GLV_ERR_INVALID, "d_new is NULL (the PulseAudio backend has no zero-fill path)");
+    if (reinterpret_cast<uintptr_t>(d_new) & (f32 ? 7u : 3u)) return fail(GLV_ERR_INVALID, "d_new must be aligned like a frame: %u bytes", f32 ? 8u : 4u);
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
+    if (!(ops & GLV_OP_WAVE)) {      // what the executor of the FFT forms asks of the batch's past: said here, before the first launch
+        if (int rc = refuse_gravity_mix(b, ops)) return rc;
+        if (int rc = refuse_stale_tilt(b)) return rc;
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    uint32_t* const pos = f32 ? &b->ring_pos_f32 : &b->ring_pos;
+    char* const work = static_cast<char*>(d_work);
+    glv::RingTrack r;
+    r.ring = f32 ? static_cast<void*>(b->d_ring_f32.get()) : static_cast<void*>(b->d_ring.get());
+    r.fresh = d_new; r.stage = work; r.starts = reinterpret_cast<uint32_t*>(work + rp.stage_bytes);
+    r.n = b->p.n; r.pos = *pos; r.new_frames = new_frames; r.updates = updates; r.pitch = rp.pitch; r.streams = b->streams;
+    hipError_t e = glv::launch_ring_track_stage(f32, r, st);
+    if (e != hipSuccess) return fail(GLV_ERR_HIP, "ring staging launch failed: %s", hipGetErrorString(e));
+    // (a launch that fails behind this point leaves the ring and its position alone; head and the gravity form go back to what the caller saw)
+    const uint32_t head = b->head; const float* const grav_cur = b->grav_cur; const int grav_mode = b->grav_mode; const bool ran_live = b->ran_live;
+    int rc = track_at(b, r.stage, f32, rp.pitch, r.starts, updates, d_out, work + rp.stage_bytes + rp.starts_bytes, ops, st);
+    if (rc == GLV_OK) {
+        e = glv::launch_ring_track_keep(f32, r, st);
+        if (e != hipSuccess) rc = fail(GLV_ERR_HIP, "ring write-back launch failed: %s", hipGetErrorString(e));
+    }
+    if (rc != GLV_OK) { b->head = head; b->grav_cur = grav_cur; b->grav_mode = grav_mode; b->ran_live = ran_live; return rc; }
+    *pos = 0;                           // the oldest frame sits at frame 0 of every ring
+    b->last_launches += 2;              // the two copies around the table call's launches
+    return GLV_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -994,5 +1068,25 @@ int glv_batch_track_pool_wave_frames_f32(glv_batch* b, const float* d_pool, uint
 int glv_batch_track_pool_wave_frames_f32_planar(glv_batch* b, const float* d_rows, uint64_t pool_frames, const glv_track_span* d_spans, const glv_track_tables* tb, uint32_t steps,
                                                 const glv_track_frames_each* fe, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
     return track_each_wave_frames_call(b, d_rows, TrackInput::F32_PLANAR, pool_frames, d_spans, true, tb, steps, fe, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (one query for glv_batch_ring_track_s16 and _f32: the staged recordings at the frame size of the widest ring the batch has, the table of starts, and behind
+// them what glv_batch_track_at_work_bytes answers for the same updates and ops)
+uint64_t glv_batch_ring_track_work_bytes(const glv_batch* b, uint32_t new_frames, uint32_t updates, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    RingTrackPlan rp;
+    if (const int rc = plan_ring_track(b, -1, new_frames, updates, ops, rp)) {
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return rp.work_bytes;
+}
+
+int glv_batch_ring_track_s16(glv_batch* b, const int16_t* d_new, uint32_t new_frames, uint32_t updates, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return ring_track(b, false, d_new, new_frames, updates, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_ring_track_f32(glv_batch* b, const float* d_new, uint32_t new_frames, uint32_t updates, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
+    return ring_track(b, true, d_new, new_frames, updates, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 }  // extern "C"

@@ -209,6 +209,11 @@ def lib() -> C.CDLL:
         L.glv_batch_ring_append_s16.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_append_f32.argtypes = [vp, vp, C.c_uint32, vp]
         L.glv_batch_ring_planar.argtypes = [vp, C.c_int, vp, vp]
+        if hasattr(L, "glv_batch_ring_track_s16"):      # (likewise: several updates of a ring batch in one track call)
+            L.glv_batch_ring_track_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint]
+            L.glv_batch_ring_track_work_bytes.restype = C.c_uint64
+            L.glv_batch_ring_track_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
+            L.glv_batch_ring_track_f32.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
         L.glv_batch_gravity_state.argtypes = [vp, C.POINTER(C.c_void_p)]
         L.glv_prelude_bufscale.argtypes = [C.c_int, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp]
         L.glv_prelude_lerp.argtypes = [C.c_int, vp, vp, vp, C.c_size_t, C.c_float, C.c_int, vp]
@@ -797,6 +802,25 @@ class Batch:
     def ring_planar(self, d_planar, f32_ring: bool = False, stream: int | None = None) -> None:
         """the ring as the reference's backends publish it: float [streams][2][n], oldest sample first"""
         _check(lib().glv_batch_ring_planar(self._h, int(f32_ring), _ptr(d_planar), _ptr(stream)))
+
+    def ring_track_work_bytes(self, new_frames: int, updates: int, ops: int) -> int:
+        """bytes of device workspace ring_track_s16 / _f32 need for these arguments (glv_batch_ring_track_work_bytes: the staged recordings, the table of
+        starts, and what track_at_work_bytes(updates, ops) reports); raises on arguments the call refuses"""
+        nbytes = int(lib().glv_batch_ring_track_work_bytes(self._h, new_frames, updates, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)
+        return nbytes
+
+    def ring_track_s16(self, d_new, new_frames: int, updates: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """`updates` ring updates of new_frames frames each in one track call (glv_batch_ring_track_s16): d_new int16 [streams][updates * new_frames][2], each
+        stream's new frames back to back (None: zero fill); d_out [updates][streams * 2][row] as track_at_s16 lays it out for the batch and ops; d_work at
+        least ring_track_work_bytes(...) bytes, 256-byte aligned.  Output, state and rings bit for bit those of `updates` ring_update_s16 calls."""
+        _check(lib().glv_batch_ring_track_s16(self._h, _ptr(d_new), new_frames, updates, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def ring_track_f32(self, d_new, new_frames: int, updates: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """ring_track_s16 on the interleaved f32 ring (glv_batch_ring_track_f32): d_new float32 [streams][updates * new_frames][2], 8-byte aligned, never None"""
+        _check(lib().glv_batch_ring_track_f32(self._h, _ptr(d_new), new_frames, updates, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
 
     def bars(self, d_spec, d_bars, stream: int | None = None) -> None:
         _check(lib().glv_batch_bars(self._h, _ptr(d_spec), _ptr(d_bars), _ptr(stream)))

@@ -1080,6 +1080,38 @@ int glv_batch_ring_append_s16(glv_batch* b, const int16_t* d_new /* NULL = zero 
 int glv_batch_ring_append_f32(glv_batch* b, const float* d_new, uint32_t new_frames, void* hip_stream);
 int glv_batch_ring_planar(glv_batch* b, int f32_ring, float* d_planar, void* hip_stream);
 
+/* Ring batches in track mode: SEVERAL updates of a live stream in one call.  Added within ABI 7: detect them by the symbol.  A packet or a decoder block holds
+ * several updates' worth of frames, and a host that stalled has several to catch up; these entries run `updates` ring updates of new_frames frames each as one
+ * track call instead of a loop of glv_batch_ring_update_* calls.
+ *   d_new   [streams][updates * new_frames][2], each stream's new frames back to back: int16, 4-byte aligned (NULL: zero fill, as glv_batch_ring_update_s16), or
+ *           float, 8-byte aligned (NULL is refused, as by glv_batch_ring_update_f32).
+ *   d_out   the layout of glv_batch_track_at_s16 / _f32 on the same batch and ops: [updates][streams * 2][row], step-major -- floats, GL_R16 texels, bars, bar
+ *           texels or columns, as the ops and the batch's settings select.
+ *   d_work  glv_batch_ring_track_work_bytes(b, new_frames, updates, ops) bytes, 256-byte aligned; one query sizes both entries.
+ * Contract.  Let R_s be stream s's ring read oldest frame first (n frames) followed by its updates * new_frames new frames.  Update t (from 0) transforms frames
+ * [(t + 1) * new_frames, (t + 1) * new_frames + n) of R_s -- the window the t-th of `updates` sequential glv_batch_ring_update_* calls sees -- and every output
+ * row, the gravity and average state, head and the rings (read oldest first; where the library puts the ring's write position is its own business) are bit for
+ * bit those of the sequential calls.  updates * new_frames may be smaller than n, equal to it or larger.  The call is also bit for bit glv_batch_track_at_s16 /
+ * _f32 on the materialised R_s with starts[t] = (t + 1) * new_frames, and takes every form that entry selects on the batch (windows, live, columns, GLV_OP_WAVE;
+ * with and without GLV_OP_BARS / GLV_OP_R16; gl_storage 0, 1 and 3; channels 1 and 2); what that entry refuses for the batch and the ops is refused here in its
+ * words, before anything moves.
+ * Workspace, in order, each region a multiple of 256 bytes: the staged R_s, streams * pitch frames with pitch = n + updates * new_frames rounded up to 4 frames
+ * (at the frame size of the widest ring the batch has); the table of starts, updates * 4 bytes; then what glv_batch_track_at_work_bytes(b, updates, ops) answers.
+ * Launches (glv_batch_last_launches): the table call's for the form, plus 2 -- one that stages R_s and writes the table (glv_ring_stage_kernel) in front and one
+ * that writes the last n frames of every R_s back as the ring (glv_ring_keep_kernel) behind:
+ *       FFT chain                 3 without state and bars; + 1 with GLV_OP_GRAVITY / GLV_OP_AVERAGE (the scan); + 1 with GLV_OP_BARS (bars, bar texels or columns)
+ *       GLV_OP_WAVE               3; 4 with GLV_OP_BARS
+ * The call is stream-ordered, allocates nothing, synchronises nothing and can be captured into a hipGraph from the first call on.
+ * GLV_ERR_INVALID: a NULL batch, d_out or d_work; new_frames outside [1, n]; updates == 0; more than 2^32 rows (updates * streams * 2) or frames (n + updates *
+ * new_frames) in one call; d_new not aligned like a frame; the f32 entry with d_new == NULL; d_work not 256-byte aligned.  GLV_ERR_STATE: a batch without the
+ * ring of that kind (the query: without any ring), a single-row batch.  (A batch with bufscale cannot occur: glv_batch_set_bufscale refuses ring batches.)  A
+ * refused or failed call leaves ring, position, head and state as the caller saw them. */
+uint64_t glv_batch_ring_track_work_bytes(const glv_batch* b, uint32_t new_frames, uint32_t updates, unsigned ops);   /* 0: refused, glv_last_error says why */
+int glv_batch_ring_track_s16(glv_batch* b, const int16_t* d_new, uint32_t new_frames, uint32_t updates,
+                             void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_ring_track_f32(glv_batch* b, const float* d_new, uint32_t new_frames, uint32_t updates,
+                             void* d_out, void* d_work, unsigned ops, void* hip_stream);
+
 /* Stream slots: reset, save and load CHOSEN streams of a batch.  Added within ABI 7: detect them by the symbol.  In the reference every listener is a GLava of
  * its own that starts from calloc'd buffers and leaves when it likes; these calls give one stream of a batch that lifecycle (a listener that takes over a freed
  * slot: reset it), checkpoints for seeking under the track entries, moves between batches and compaction -- without touching the other streams.
