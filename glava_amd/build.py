@@ -24,7 +24,7 @@ ARCH = "gfx950"
 HIPFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
             "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 SIZES = (7, 8, 9, 10, 11, 12, 13, 14)
-SMALL = ("glv_bars", "glv_misc", "glv_track_frames", "glv_decimate", "glv_slots", "glv_pool", "glv_ring_track")    # the kernels beside the frame kernel, one object each: the bars passes of a second launch (slow to compile) / the small kernels / a frames track call's two / the bufscale stage / the stream slots / a pool call's bufscale and waveform stages / a ring track call's two copies
+SMALL = ("glv_bars", "glv_misc", "glv_track_frames", "glv_decimate", "glv_slots", "glv_pool", "glv_ring_track", "glv_ring_each")    # the kernels beside the frame kernel, one object each: the bars passes of a second launch (slow to compile) / the small kernels / a frames track call's two / the bufscale stage / the stream slots / a pool call's bufscale and waveform stages / a ring track call's two copies / a per-stream ring track call's two
 HOST = ("glv_api", "glv_wisdom", "glv_device_state", "glv_bar_tables", "glv_chain", "glv_track", "glv_multi")    # the host units (.cpp, compiled as HIP for the launch syntax of the headers)
 PARTS = (0, 1, 2, 3, 4, 5, 6, 7)  # glv_inst.hip is compiled per (size, part): s16 inputs / f32 inputs / the runner-up configuration / a track call's s16 windows / its f32 windows / both at a table's starts / planar f32 rows at a table's starts
 EACH_PARTS = (8, 9, 10)  # ... / parts 5, 6 and 7 with a table row per stream (glv_batch_track_each_*): kinds of their own, so parts of their own

@@ -170,6 +170,19 @@ struct RingTrack {
 constexpr size_t kRingTrackGridCap = 256 * 8;      // 256 CUs x 8 resident 256-lane workgroups of 256 pieces each; the kernels' loops take what lies beyond
 hipError_t launch_ring_track_stage(bool f32, const RingTrack& r, hipStream_t st);
 hipError_t launch_ring_track_keep(bool f32, const RingTrack& r, hipStream_t st);
+// ... of a per-stream ring track call (glv_ring_each.hip; glv_batch_ring_track_each_s16 / _f32): stream s takes c_s = min(counts[s], updates) of the updates, read
+// on the device (counts null: everybody takes all).  launch_ring_each_stage (glv_ring_stage_each_kernel) writes every stream's ring, oldest frame first, and the
+// FIRST c_s * new_frames of its new frames behind it into `stage`, zeros beyond them up to the pitch -- `fresh` is [streams][updates * new_frames] frames whatever
+// the counts are, and nothing of a stream at or beyond c_s * new_frames is read -- and (t + 1) * new_frames into starts[s * updates + t] for every s < streams,
+// t < updates: uint32 [streams][updates], the per-stream table call's rows.  launch_ring_each_keep (glv_ring_keep_each_kernel) writes frames [c_s * new_frames,
+// c_s * new_frames + n) of every staged stream back as its ring, oldest frame at 0.  What RingTrack's launchers refuse is refused, and counts off 4 bytes and more
+// than 2^32 - 1 table entries.
+struct RingTrackEach {
+    RingTrack r;
+    const uint32_t* counts;
+};
+hipError_t launch_ring_each_stage(bool f32, const RingTrackEach& e, hipStream_t st);
+hipError_t launch_ring_each_keep(bool f32, const RingTrackEach& e, hipStream_t st);
 hipError_t launch_lerp(const float* s0, const float* e0, float* out, size_t total, float mod, hipStream_t st);
 hipError_t launch_smooth(float* rows, size_t nrows, uint32_t n, const int* smin, const int* smax, uint32_t asz, uint32_t reach,
                          uint32_t max_window, hipStream_t st);

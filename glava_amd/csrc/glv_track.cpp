@@ -773,6 +773,63 @@ int ring_track(glv_batch* b, bool f32, const void* d_new, uint32_t new_frames, u
     b->last_launches += 2;              // the two copies around the table call's launches
     return GLV_OK;
 }
+
+// ---- ... per stream: stream s takes c_s = min(d_counts[s], updates) of the updates, update t of it at ur = d_ur[s][t] (glv_batch_ring_track_each_s16 / _f32) ----
+// The ring track call with the per-stream table call in the place of the table call.  The write-back rewrites every ring oldest frame first whatever the stream
+// took, so a stream that took c_s updates keeps the last n of ITS n + c_s * new_frames frames and the batch's one ring position, 0, is right for all of them: the
+// staging puts a stream's first c_s * new_frames new frames behind its ring and zeros behind those (glv_ring_stage_each_kernel, which also writes a row of starts
+// (t + 1) * new_frames per stream), the write-back reads from c_s * new_frames on (glv_ring_keep_each_kernel).  Windows behind a count lie in the staged region and
+// the scan discards their rows.  The wave form keeps no state, takes no rates and has no meaning for a count: the lockstep entries take it.
+// The plan: the lockstep call's (new_frames, updates, the ring, the 2^32 bounds, then plan_track_at's refusals and workspace), with a row of starts per stream.
+int plan_ring_track_each(const glv_batch* b, int f32, uint32_t new_frames, uint32_t updates, unsigned ops, RingTrackPlan& rp) {
+    if (ops & GLV_OP_WAVE)
+        return fail(GLV_ERR_INVALID, "GLV_OP_WAVE keeps no state for a count or a rate to act on: the wave form takes glv_batch_ring_track_s16 / _f32 (ops 0x%x)", ops);
+    if (int rc = plan_ring_track(b, f32, new_frames, updates, ops, rp)) return rc;
+    const uint64_t rows = up256((uint64_t) b->streams * updates * 4u);      // (rows of the output <= 2^32: no overflow)
+    rp.work_bytes += rows - rp.starts_bytes;
+    rp.starts_bytes = rows;
+    return GLV_OK;
+}
+int ring_track_each(glv_batch* b, bool f32, const void* d_new, uint32_t new_frames, uint32_t updates, const float* d_ur, const uint32_t* d_counts, void* d_out, void* d_work,
+                    unsigned ops, hipStream_t st) {
+    if (!b) return fail(GLV_ERR_INVALID, "batch is NULL");
+    RingTrackPlan rp;
+    if (int rc = plan_ring_track_each(b, f32 ? 1 : 0, new_frames, updates, ops, rp)) return rc;
+    if (!d_out || !d_work) return fail(GLV_ERR_INVALID, "NULL device pointer");
+    if (f32 && !d_new) return fail(GLV_ERR_INVALID, "d_new is NULL (the PulseAudio backend has no zero-fill path)");
+    if (reinterpret_cast<uintptr_t>(d_new) & (f32 ? 7u : 3u)) return fail(GLV_ERR_INVALID, "d_new must be aligned like a frame: %u bytes", f32 ? 8u : 4u);
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail(GLV_ERR_INVALID, "d_work must be 256-byte aligned");
+    // what the per-stream call says of the two tables, in its words, and what the executor of the FFT forms asks of the batch's past: said here, before the first launch
+    if (reinterpret_cast<uintptr_t>(d_ur) & 3u) return fail(GLV_ERR_INVALID, "d_ur must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_counts) & 3u) return fail(GLV_ERR_INVALID, "d_counts must be 4-byte aligned");
+    if (d_ur && !(ops & GLV_OP_GRAVITY)) return fail(GLV_ERR_INVALID, "a rates track call needs GLV_OP_GRAVITY, which reads the rate table (ops 0x%x)", ops);
+    if (d_counts && !(ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE)))
+        return fail(GLV_ERR_INVALID, "the chain keeps no state for d_counts to protect: counts need GLV_OP_GRAVITY and / or GLV_OP_AVERAGE and no GLV_OP_WAVE (ops 0x%x)", ops);
+    if (int rc = refuse_gravity_mix(b, ops)) return rc;
+    if (int rc = refuse_stale_tilt(b)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    uint32_t* const pos = f32 ? &b->ring_pos_f32 : &b->ring_pos;
+    char* const work = static_cast<char*>(d_work);
+    glv::RingTrackEach e;
+    e.r.ring = f32 ? static_cast<void*>(b->d_ring_f32.get()) : static_cast<void*>(b->d_ring.get());
+    e.r.fresh = d_new; e.r.stage = work; e.r.starts = reinterpret_cast<uint32_t*>(work + rp.stage_bytes);
+    e.r.n = b->p.n; e.r.pos = *pos; e.r.new_frames = new_frames; e.r.updates = updates; e.r.pitch = rp.pitch; e.r.streams = b->streams;
+    e.counts = d_counts;
+    hipError_t err = glv::launch_ring_each_stage(f32, e, st);
+    if (err != hipSuccess) return fail(GLV_ERR_HIP, "ring staging launch failed: %s", hipGetErrorString(err));
+    // (a launch that fails behind this point leaves the ring and its position alone; head and the gravity form go back to what the caller saw)
+    const uint32_t head = b->head; const float* const grav_cur = b->grav_cur; const int grav_mode = b->grav_mode; const bool ran_live = b->ran_live;
+    const glv_track_tables tb = {e.r.starts, d_ur, d_counts};
+    int rc = track_each(b, e.r.stage, f32, rp.pitch, &tb, updates, d_out, work + rp.stage_bytes + rp.starts_bytes, ops, st);
+    if (rc == GLV_OK) {
+        err = glv::launch_ring_each_keep(f32, e, st);
+        if (err != hipSuccess) rc = fail(GLV_ERR_HIP, "ring write-back launch failed: %s", hipGetErrorString(err));
+    }
+    if (rc != GLV_OK) { b->head = head; b->grav_cur = grav_cur; b->grav_mode = grav_mode; b->ran_live = ran_live; return rc; }
+    *pos = 0;                           // the oldest frame sits at frame 0 of every ring, whatever its stream took
+    b->last_launches += 2;              // the two copies around the per-stream table call's launches
+    return GLV_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1088,5 +1145,26 @@ int glv_batch_ring_track_s16(glv_batch* b, const int16_t* d_new, uint32_t new_fr
 
 int glv_batch_ring_track_f32(glv_batch* b, const float* d_new, uint32_t new_frames, uint32_t updates, void* d_out, void* d_work, unsigned ops, void* hip_stream) {
     return ring_track(b, true, d_new, new_frames, updates, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+// (one query for glv_batch_ring_track_each_s16 and _f32: the lockstep query's regions with a row of starts per stream in the place of its one row)
+uint64_t glv_batch_ring_track_each_work_bytes(const glv_batch* b, uint32_t new_frames, uint32_t updates, unsigned ops) {
+    if (!b) { (void) fail(GLV_ERR_INVALID, "batch is NULL"); return 0; }
+    RingTrackPlan rp;
+    if (const int rc = plan_ring_track_each(b, -1, new_frames, updates, ops, rp)) {
+        g_err = std::string(rc == GLV_ERR_STATE ? "GLV_ERR_STATE: " : "GLV_ERR_INVALID: ") + g_err;
+        return 0;
+    }
+    return rp.work_bytes;
+}
+
+int glv_batch_ring_track_each_s16(glv_batch* b, const int16_t* d_new, uint32_t new_frames, uint32_t updates, const float* d_ur, const uint32_t* d_counts, void* d_out,
+                                  void* d_work, unsigned ops, void* hip_stream) {
+    return ring_track_each(b, false, d_new, new_frames, updates, d_ur, d_counts, d_out, d_work, ops, (hipStream_t) hip_stream);
+}
+
+int glv_batch_ring_track_each_f32(glv_batch* b, const float* d_new, uint32_t new_frames, uint32_t updates, const float* d_ur, const uint32_t* d_counts, void* d_out,
+                                  void* d_work, unsigned ops, void* hip_stream) {
+    return ring_track_each(b, true, d_new, new_frames, updates, d_ur, d_counts, d_out, d_work, ops, (hipStream_t) hip_stream);
 }
 }  // extern "C"

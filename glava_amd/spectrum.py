@@ -214,6 +214,11 @@ def lib() -> C.CDLL:
             L.glv_batch_ring_track_work_bytes.restype = C.c_uint64
             L.glv_batch_ring_track_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
             L.glv_batch_ring_track_f32.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint, vp]
+        if hasattr(L, "glv_batch_ring_track_each_s16"):      # (likewise: ring updates in one track call with a count of updates and a rate row per stream)
+            L.glv_batch_ring_track_each_work_bytes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint]
+            L.glv_batch_ring_track_each_work_bytes.restype = C.c_uint64
+            L.glv_batch_ring_track_each_s16.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint, vp]
+            L.glv_batch_ring_track_each_f32.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint, vp]
         L.glv_batch_gravity_state.argtypes = [vp, C.POINTER(C.c_void_p)]
         L.glv_prelude_bufscale.argtypes = [C.c_int, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp]
         L.glv_prelude_lerp.argtypes = [C.c_int, vp, vp, vp, C.c_size_t, C.c_float, C.c_int, vp]
@@ -821,6 +826,30 @@ class Batch:
     def ring_track_f32(self, d_new, new_frames: int, updates: int, d_out, d_work, ops: int, stream: int | None = None) -> None:
         """ring_track_s16 on the interleaved f32 ring (glv_batch_ring_track_f32): d_new float32 [streams][updates * new_frames][2], 8-byte aligned, never None"""
         _check(lib().glv_batch_ring_track_f32(self._h, _ptr(d_new), new_frames, updates, _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def ring_track_each_work_bytes(self, new_frames: int, updates: int, ops: int) -> int:
+        """bytes of device workspace ring_track_each_s16 / _f32 need for these arguments (glv_batch_ring_track_each_work_bytes: the staged recordings, a row
+        of starts per stream, and what track_at_work_bytes(updates, ops) reports); raises on arguments the call refuses"""
+        nbytes = int(lib().glv_batch_ring_track_each_work_bytes(self._h, new_frames, updates, ops))
+        if nbytes == 0:
+            msg = lib().glv_last_error().decode()
+            raise GlvError(ERR_STATE if msg.startswith("GLV_ERR_STATE") else ERR_INVALID, msg)
+        return nbytes
+
+    def ring_track_each_s16(self, d_new, new_frames: int, updates: int, d_ur, d_counts, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """ring_track_s16 with a count of updates and a row of rates per stream (glv_batch_ring_track_each_s16): stream s takes its first c = min(d_counts[s],
+        updates) updates -- d_counts uint32 [streams] or None (everybody takes all) -- and update t of it applies gravity with d_ur[s * updates + t], d_ur
+        float32 [streams][updates] or None (the batch's own ur), both in device memory and read when the kernels run.  d_new int16 [streams][updates *
+        new_frames][2] (None: zero fill): of stream s only the first c * new_frames frames are read.  d_out [updates][streams * 2][row] as track_each_s16 lays
+        it out: the rows behind a count are what the call's last stage makes of a row of zeros.  Every stream is left, bit for bit, as c ring_update_s16
+        calls leave a one-stream batch at its state; a stream with count 0 keeps state and ring.  OP_WAVE is refused (ring_track_s16 takes it).  d_work at
+        least ring_track_each_work_bytes(...) bytes, 256-byte aligned.  Counts: glava_amd.track_starts.ring_update_counts."""
+        _check(lib().glv_batch_ring_track_each_s16(self._h, _ptr(d_new), new_frames, updates, _ptr(d_ur), _ptr(d_counts), _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
+
+    def ring_track_each_f32(self, d_new, new_frames: int, updates: int, d_ur, d_counts, d_out, d_work, ops: int, stream: int | None = None) -> None:
+        """ring_track_each_s16 on the interleaved f32 ring (glv_batch_ring_track_each_f32): d_new float32 [streams][updates * new_frames][2], 8-byte aligned,
+        never None"""
+        _check(lib().glv_batch_ring_track_each_f32(self._h, _ptr(d_new), new_frames, updates, _ptr(d_ur), _ptr(d_counts), _ptr(d_out), _ptr(d_work), ops, _ptr(stream)))
 
     def bars(self, d_spec, d_bars, stream: int | None = None) -> None:
         _check(lib().glv_batch_bars(self._h, _ptr(d_spec), _ptr(d_bars), _ptr(stream)))

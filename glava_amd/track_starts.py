@@ -135,6 +135,34 @@ def stack_tables(rows, steps: int | None = None):
     return starts, ur, counts
 
 
+def ring_update_counts(pending_frames, new_frames: int, cap: int | None = None):
+    """The counts of a per-stream ring track call (glv_batch_ring_track_each_s16 / _f32; Batch.ring_track_each_*) from the frames every listener has pending:
+    stream s takes counts[s] = pending_frames[s] // new_frames whole updates -- at most `cap` where one is given, the bound of a call's workspace or of what a
+    host wants to catch up in one call -- and keeps leftover[s] = pending_frames[s] - counts[s] * new_frames frames for the next call, its oldest pending
+    frames first in d_new.  Returns (counts, updates, leftover_frames): numpy uint32 [streams], the longest row (the call's `updates`; 0: nobody has a whole
+    update pending and there is nothing to call), and a list of Python ints.  Integer arithmetic only.  Refuses an empty list, a pending count that is not
+    an integer >= 0, and counts that do not fit a uint32."""
+    import numpy as np
+    pending = list(pending_frames)
+    _positive(new_frames=new_frames)
+    if cap is not None:
+        _positive(cap=cap)
+    if not pending:
+        raise ValueError("ring_update_counts needs at least one stream")
+    counts, leftover = [], []
+    for v in pending:
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
+            raise ValueError("a stream's pending frames must be an integer >= 0")
+        c = int(v) // new_frames
+        if cap is not None and c > cap:
+            c = cap
+        if c >= 1 << 32:
+            raise ValueError(f"{c} updates do not fit a uint32 count: give a cap")
+        counts.append(c)
+        leftover.append(int(v) - c * new_frames)
+    return np.asarray(counts, dtype=np.uint32), max(counts), leftover
+
+
 # one glv_track_span as a numpy record: what d_spans of Batch.track_pool_* holds, 16 bytes a stream (glava_amd.spectrum.TrackSpan field by field)
 SPAN_DTYPE = [("first", "<u8"), ("frames", "<u4"), ("reserved", "<u4")]       # numpy.dtype(SPAN_DTYPE)
 

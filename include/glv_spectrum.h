@@ -1112,6 +1112,44 @@ int glv_batch_ring_track_s16(glv_batch* b, const int16_t* d_new, uint32_t new_fr
 int glv_batch_ring_track_f32(glv_batch* b, const float* d_new, uint32_t new_frames, uint32_t updates,
                              void* d_out, void* d_work, unsigned ops, void* hip_stream);
 
+/* Ring batches in track mode PER STREAM: own update counts and rates.  Added within ABI 7: detect them by the symbol.  A live service is not in lockstep: one
+ * listener has four updates pending, the next one, a paused one none, and a live GLava applies gravity at the rate it measures (1.0, then 59.0, then 60.0).
+ * These entries are glv_batch_ring_track_s16 / _f32 with a count of updates and a row of rates for every stream, as glv_batch_track_each_* is the table call
+ * with them.
+ *   updates   the longest row: it sizes d_new, d_out and the workspace.
+ *   d_counts  uint32 [streams] in device memory, 4-byte aligned, or NULL: stream s takes c_s = min(d_counts[s], updates) updates; NULL: everybody takes all.
+ *   d_ur      float [streams][updates] in device memory, 4-byte aligned, or NULL: update t of stream s applies gravity with ur = d_ur[s * updates + t], as
+ *             glv_batch_track_each_* does; NULL: the batch's own ur.  The batch's ur stays.  Both tables are read when the kernels run.
+ *   d_new     [streams][updates * new_frames][2]: the pitch is set by `updates`; of stream s only the first c_s * new_frames frames are read, what lies behind
+ *             may be anything.  int16, 4-byte aligned (NULL: zero fill), or float, 8-byte aligned (NULL is refused).
+ *   d_out     [updates][streams * 2][row], the layout of glv_batch_track_each_*: rows of updates t >= c_s are what that call writes behind a count, the result
+ *             of a zero row.
+ *   d_work    glv_batch_ring_track_each_work_bytes(b, new_frames, updates, ops) bytes, 256-byte aligned; one query sizes both entries.
+ * Contract.  Let R_s be stream s's ring read oldest frame first (n frames) followed by its first c_s * new_frames new frames.  Update t < c_s transforms frames
+ * [(t + 1) * new_frames, (t + 1) * new_frames + n) of R_s, and after the call the stream's ring, read oldest first, is the last n frames of R_s (where the
+ * library puts the ring's write position is its own business: one position serves every stream).  Every stream is, bit for bit in output rows, gravity and
+ * average state and ring, what c_s sequential glv_batch_ring_update_* calls make of a one-stream ring batch holding that stream's state, with
+ * glv_batch_set_params(ur = d_ur[s][t]) before update t where a rate table is given.  A stream with c_s = 0 keeps its state and its ring (read oldest first) bit
+ * for bit.  head advances by `updates`, as in every per-stream call.  With d_counts == NULL and d_ur == NULL the call is bit for bit glv_batch_ring_track_*; it
+ * is also bit for bit glv_batch_track_each_* on the staged recordings (R_s padded with zeros) with the rows starts[s][t] = (t + 1) * new_frames, and takes every
+ * FFT form that entry selects on the batch (windows, live, columns; with and without GLV_OP_BARS / GLV_OP_R16; gl_storage 0, 1 and 3; channels 1 and 2).
+ * Workspace, in order, each region a multiple of 256 bytes: the staged R_s, streams * pitch frames with pitch = n + updates * new_frames rounded up to 4 frames
+ * (at the frame size of the widest ring the batch has); the table of starts, streams * updates * 4 bytes; then what glv_batch_track_at_work_bytes(b, updates,
+ * ops) answers.
+ * Launches (glv_batch_last_launches): the per-stream table call's for the form, plus 2 (glv_ring_stage_each_kernel in front, glv_ring_keep_each_kernel behind):
+ * 3 without state and bars; + 1 with GLV_OP_GRAVITY / GLV_OP_AVERAGE (the scan); + 1 with GLV_OP_BARS.  The transform runs for updates behind a count too.
+ * The call is stream-ordered, allocates nothing, synchronises nothing and can be captured into a hipGraph from the first call on; rewriting d_counts, d_ur or
+ * d_new re-aims a captured graph.
+ * GLV_ERR_INVALID: GLV_OP_WAVE (no state for a count or a rate to act on: glv_batch_ring_track_s16 / _f32 take the wave form); what glv_batch_ring_track_*
+ * refuses, in its words; d_ur or d_counts off 4 bytes; d_ur without GLV_OP_GRAVITY; d_counts on a chain without GLV_OP_GRAVITY and GLV_OP_AVERAGE -- the last
+ * three in glv_batch_track_each_*'s words.  GLV_ERR_STATE: as glv_batch_ring_track_*.  A refused or failed call leaves ring, position, head, gravity form and
+ * state as the caller saw them, and a refused call launches nothing. */
+uint64_t glv_batch_ring_track_each_work_bytes(const glv_batch* b, uint32_t new_frames, uint32_t updates, unsigned ops);   /* 0: refused, glv_last_error says why */
+int glv_batch_ring_track_each_s16(glv_batch* b, const int16_t* d_new, uint32_t new_frames, uint32_t updates,
+                                  const float* d_ur, const uint32_t* d_counts, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+int glv_batch_ring_track_each_f32(glv_batch* b, const float* d_new, uint32_t new_frames, uint32_t updates,
+                                  const float* d_ur, const uint32_t* d_counts, void* d_out, void* d_work, unsigned ops, void* hip_stream);
+
 /* Stream slots: reset, save and load CHOSEN streams of a batch.  Added within ABI 7: detect them by the symbol.  In the reference every listener is a GLava of
  * its own that starts from calloc'd buffers and leaves when it likes; these calls give one stream of a batch that lifecycle (a listener that takes over a freed
  * slot: reset it), checkpoints for seeking under the track entries, moves between batches and compaction -- without touching the other streams.
