@@ -199,11 +199,12 @@ int glv_batch_set_params(glv_batch* b, const glv_params* p) {
     const glv_params old = b->p;
     b->p = *p;
     int rc = batch_prepare(b);
-    // a GLV_OP_BARS_ONLY batch that has run its live class keeps no state beyond the live bins: parameters under which the bars sample further than the
-    // live classes keep (or that take the live class away: log_mode 2) would read state that was never maintained -- refused until the state is reset
-    if (rc == GLV_OK && b->ran_live && b->live_bins() == 0)
-        rc = fail(GLV_ERR_STATE, "this GLV_OP_BARS_ONLY batch has run its live kernel class: the state beyond the live bins was not kept, and these parameters "
-                                 "(smooth_factor=%g bars=%u log_mode=%u) need the full chain -- glv_batch_reset first, or a new batch", (double) p->smooth_factor, p->bars, p->log_mode);
+    // a GLV_OP_BARS_ONLY batch that has run its live class keeps no state beyond the bins its live calls kept (glv_batch::kept_live): parameters under which
+    // the bars sample further (or that take the live class away: log_mode 2) would read state that was never maintained -- refused until the state is reset
+    if (rc == GLV_OK && !b->keeps_live(b->live_bins()))
+        rc = fail(GLV_ERR_STATE, "this GLV_OP_BARS_ONLY batch has run its live kernel class: the state beyond bin %u was not kept, and these parameters "
+                                 "(smooth_factor=%g bars=%u log_mode=%u sample_scale=%g sample_range=%g) sample %s -- glv_batch_reset first, or a new batch", b->kept_live,
+                  (double) p->smooth_factor, p->bars, p->log_mode, (double) p->sample_scale, (double) p->sample_range, b->live_bins() == 0 ? "every bin (the full chain)" : "beyond it");
     if (rc != GLV_OK) { const std::string said = g_err; b->p = old; (void) batch_prepare(b); g_err = said; }   // a rejected change leaves the batch as it was
     for (auto& row : b->plan_cache) for (auto& pc : row) pc.gen = 0;        // log_mode is part of the wisdom key
     return rc;

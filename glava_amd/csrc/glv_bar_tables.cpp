@@ -306,6 +306,9 @@ static int set_snap_texels(glv_batch* b, const uint32_t* texels, uint32_t count,
     HIP_TRY(hipDeviceSynchronize());
     if (texels == nullptr || count == 0) {                 // off: the unsnapped tables, untouched meanwhile, serve again
         if (b->snapped() && b->columns() != cols) return GLV_OK;      // (the other kind of table is set: this kind is off already)
+        // (the unsnapped bars sample what they sampled: the live bins stay or shrink -- the one check of every change all the same)
+        if (!b->keeps_live(b->live_bins_with(0u)))
+            return fail(GLV_ERR_STATE, "%s: without the table the bars sample beyond the bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first", what);
         b->snap = BarTableSet(); b->snap_x = SnapExtras();
         b->update_live_bins();
         return GLV_OK;
@@ -337,8 +340,8 @@ static int set_snap_texels(glv_batch* b, const uint32_t* texels, uint32_t count,
     SnapExtras extras;
     if (int rc = build_snap_tables(b, tex, cols, set, extras)) return rc;
     // (as glv_batch_set_params: a GLV_OP_BARS_ONLY batch that ran its live class cannot start sampling beyond the bins it kept)
-    if (b->ran_live && b->live_bins_with(set.bins) != b->live_bins())
-        return fail(GLV_ERR_STATE, "%s: these taps reach beyond the live bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first", what);
+    if (!b->keeps_live(b->live_bins_with(set.bins)))
+        return fail(GLV_ERR_STATE, "%s: these taps reach beyond the bins this GLV_OP_BARS_ONLY batch has kept -- glv_batch_reset first", what);
     if (cols) {
         HIP_TRY(extras.col_map.upload(map));
         extras.col_tex.assign(texels, texels + (size_t) count * 3);

@@ -357,7 +357,7 @@ int run_chain(glv_batch* b, const ChainPlan& pl, const void* d_in, int in_mode, 
     if (pl.route == ChainPlan::POST && (ops & (GLV_OP_GRAVITY | GLV_OP_AVERAGE))) a.gl_storage = upload_storage(b->p) ? 0u : b->p.gl_storage;   // the post kernel models it directly (3: the float operators)
     if (pl.route == ChainPlan::GL_PASSES && !pl.out)
         return fail(GLV_ERR_STATE, "this gl_storage chain needs the internal spectra rows (created for gl_storage 2 batches with state, and with GLV_OP_BARS in the ops_mask)");
-    if (pl.live_points != 0) { a.live_points = pl.live_points; b->ran_live = true; }
+    if (pl.live_points != 0) { a.live_points = pl.live_points; b->ran_live_over(b->live_bins()); }
 
     if (int rc = timed_launch_begin(b, st)) return rc;
     if (int rc = decimate_stage(b, pl, st)) return rc;

@@ -193,7 +193,7 @@ void stream_desc(const glv_batch* b, glv_stream_state_desc* d) {
     std::memset(d, 0, sizeof(*d));
     d->n = b->p.n; d->avg_frames = b->p.avg_frames; d->elem_bytes = (uint32_t) elem; d->gravity_form = (uint32_t) b->grav_mode;
     d->regions = (b->d_grav ? 1u : 0u) | (b->d_hist ? 2u : 0u) | (b->d_ring ? 4u : 0u) | (b->d_ring_f32 ? 8u : 0u);
-    d->kept_bins = (b->ops_mask & GLV_OP_BARS_ONLY) && b->ran_live && b->live_bins() != 0 ? b->live_bins() : b->p.n;
+    d->kept_bins = b->kept_bins();      // (n while no live call has run; else what every live call since the last reset has kept)
     d->bytes = (b->d_grav ? 2u * n * elem : 0u) + (b->d_hist ? 2u * n * elem * b->p.avg_frames : 0u) + (b->d_ring ? 4u * n : 0u) + (b->d_ring_f32 ? 8u * n : 0u);
 }
 // The region table of the launch: the stream's part of each array in the portable order, rotated by the batch's positions as they are now (`rotated`;
@@ -234,7 +234,7 @@ int slots_launch(glv_batch* b, int kind, const uint32_t* d_idx, uint32_t count, 
 }
 // Whether streams described by *d -- `what`: the blob of a load, the source batch of a copy -- can become streams of batch b, whose own descriptor is `now`;
 // checked on the host before anything runs, refused in the entry's name.  *fit: what the batch adopts once the launch went through (adopt_streams).
-struct StreamsFit { unsigned form_ops = 0; bool live = false; };
+struct StreamsFit { unsigned form_ops = 0; bool live = false; uint32_t kept = 0; };
 int streams_fit(const glv_batch* b, const char* entry, const char* what, const glv_stream_state_desc* d, const glv_stream_state_desc& now, StreamsFit* fit) {
     if (d->n != now.n || d->avg_frames != now.avg_frames || d->elem_bytes != now.elem_bytes || d->regions != now.regions || d->bytes != now.bytes)
         return fail(GLV_ERR_STATE, "%s: %s (n=%u, F=%u, %u-byte elements, regions 0x%x) is not of this batch's kind (n=%u, F=%u, %u-byte elements, "
@@ -243,16 +243,16 @@ int streams_fit(const glv_batch* b, const char* entry, const char* what, const g
     // the form gravity's state is kept in: a batch keeps one (refuse_gravity_mix says why, and its words refuse the streams of the other)
     fit->form_ops = d->gravity_form == 0u ? 0u : d->gravity_form == 2u ? (unsigned) (GLV_OP_GRAVITY | GLV_OP_AVERAGE) : (unsigned) GLV_OP_GRAVITY;
     if (int rc = refuse_gravity_mix(b, fit->form_ops)) return rc;
-    fit->live = d->kept_bins != now.n;
-    if (fit->live && (!(b->ops_mask & GLV_OP_BARS_ONLY) || b->live_bins() == 0 || b->live_bins() != d->kept_bins))
+    fit->live = d->kept_bins != now.n; fit->kept = d->kept_bins;
+    if (fit->live && (!(b->ops_mask & GLV_OP_BARS_ONLY) || b->live_bins() == 0 || b->live_bins() > d->kept_bins || d->kept_bins > now.n))
         return fail(GLV_ERR_STATE, "%s: %s keeps bins [0, %u) of n=%u only (a GLV_OP_BARS_ONLY batch that has run its live class): it loads into a "
-                                   "GLV_OP_BARS_ONLY batch whose glv_batch_live_bins() equals that (this batch: %u)", entry, what, d->kept_bins, now.n,
+                                   "GLV_OP_BARS_ONLY batch whose glv_batch_live_bins() are no more than that (this batch: %u)", entry, what, d->kept_bins, now.n,
                     (b->ops_mask & GLV_OP_BARS_ONLY) ? b->live_bins() : 0u);
     return GLV_OK;
 }
 void adopt_streams(glv_batch* b, const StreamsFit& fit) {
     commit_gravity_form(b, fit.form_ops);    // (form 0: nothing to adopt)
-    if (fit.live) b->ran_live = true;
+    if (fit.live) b->ran_live_over(fit.kept);      // the batch keeps what all of its streams keep
 }
 }  // namespace
 

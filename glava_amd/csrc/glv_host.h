@@ -204,7 +204,7 @@ struct glv_batch {
     size_t grav_bytes() const { return (state16 ? sizeof(uint16_t) : sizeof(float)) * rows * p.n; }          // GL_R16 state: texels
     size_t hist_bytes() const { return grav_bytes() * p.avg_frames; }
     // the bookkeeping of a batch whose state arrays were just cleared -- or can no longer be trusted (a failed placement candidate)
-    void rewind_state() { head = 0; grav_mode = 0; grav_cur = d_grav; ran_live = false; }
+    void rewind_state() { head = 0; grav_mode = 0; grav_cur = d_grav; ran_live = false; kept_live = 0; }
     bool snapped() const { return !snap_x.tex.empty(); }
     bool columns() const { return !snap_x.col_tex.empty(); }
     // GLV_OP_BARS_ONLY: the chain lives below the bins the bars sample (the last bin any bar has a tap on, rounded up to 64) -- when EVERY kernel configuration
@@ -215,6 +215,13 @@ struct glv_batch {
     uint32_t live_bins_now = 0;                     // refreshed with the bar tables and when the batch is prepared (update_live_bins)
     uint32_t live_bins() const { return live_bins_now; }
     bool ran_live = false;                          // a live kernel class has run since creation / the last reset: the state beyond the live bins is stale
+    // ... and how far it is not: the smallest extent any live call since then has kept (a process call its live bins, a live track call its kept bins, adopted
+    // live streams theirs).  Bins [0, kept_live) of every stream are maintained, nothing beyond is; meaningful while ran_live
+    uint32_t kept_live = 0;
+    void ran_live_over(uint32_t bins) { kept_live = ran_live && kept_live < bins ? kept_live : bins; ran_live = true; }
+    uint32_t kept_bins() const { return ran_live ? kept_live : p.n; }
+    // may the bars sample `live` bins from now on (0: every bin)?  Once a live call has run, only what every such call kept
+    bool keeps_live(uint32_t live) const { return !ran_live || (live != 0 && live <= kept_live); }
     // the live bins with snapped bars that sample `snap_bins` bins of a row (0: none set)
     uint32_t live_bins_with(uint32_t snap_bins) const {
         // (snapped bars sample positions in [0, 1) -- the unsnapped bars' last taps reach scale_audio(1) n once smooth_factor >= 1 / bars; a smaller

@@ -399,7 +399,7 @@ int track(glv_batch* b, const TrackPlan& tp, const void* d_pcm, uint32_t pitch_f
     fill_common(a, b->p, b->tab);
     a.ops = GLV_OP_FFT | (tp.in16 ? (unsigned) GLV_OP_R16 : 0u); a.log_mode = b->p.log_mode;
     const glv::FrameClass cls = glv::frame_class(false, false, false, a.ops);
-    if (tp.kept != 0) b->ran_live = true;      // the live form over the kept bins: the scan leaves the state at and beyond bin `kept` as it finds it
+    if (tp.kept != 0) b->ran_live_over(tp.kept);      // the live form over the kept bins: the scan leaves the state at and beyond bin `kept` as it finds it
     if (int rc = tp.windows ? track_windows(b, tp, a, cls, d_pcm, pitch_frames, hop, steps, tp.to_out ? out : reinterpret_cast<float*>(work),
                                             tp.dec_bytes != 0 ? static_cast<float*>(d_work) : nullptr, st)
                             : track_residues(b, tp, a, cls, static_cast<const int16_t*>(d_pcm), hop, work, st)) return rc;
@@ -762,13 +762,13 @@ int ring_track(glv_batch* b, bool f32, const void* d_new, uint32_t new_frames, u
     hipError_t e = glv::launch_ring_track_stage(f32, r, st);
     if (e != hipSuccess) return fail(GLV_ERR_HIP, "ring staging launch failed: %s", hipGetErrorString(e));
     // (a launch that fails behind this point leaves the ring and its position alone; head and the gravity form go back to what the caller saw)
-    const uint32_t head = b->head; const float* const grav_cur = b->grav_cur; const int grav_mode = b->grav_mode; const bool ran_live = b->ran_live;
+    const uint32_t head = b->head; const float* const grav_cur = b->grav_cur; const int grav_mode = b->grav_mode; const bool ran_live = b->ran_live; const uint32_t kept_live = b->kept_live;
     int rc = track_at(b, r.stage, f32, rp.pitch, r.starts, updates, d_out, work + rp.stage_bytes + rp.starts_bytes, ops, st);
     if (rc == GLV_OK) {
         e = glv::launch_ring_track_keep(f32, r, st);
         if (e != hipSuccess) rc = fail(GLV_ERR_HIP, "ring write-back launch failed: %s", hipGetErrorString(e));
     }
-    if (rc != GLV_OK) { b->head = head; b->grav_cur = grav_cur; b->grav_mode = grav_mode; b->ran_live = ran_live; return rc; }
+    if (rc != GLV_OK) { b->head = head; b->grav_cur = grav_cur; b->grav_mode = grav_mode; b->ran_live = ran_live; b->kept_live = kept_live; return rc; }
     *pos = 0;                           // the oldest frame sits at frame 0 of every ring
     b->last_launches += 2;              // the two copies around the table call's launches
     return GLV_OK;
@@ -818,14 +818,14 @@ int ring_track_each(glv_batch* b, bool f32, const void* d_new, uint32_t new_fram
     hipError_t err = glv::launch_ring_each_stage(f32, e, st);
     if (err != hipSuccess) return fail(GLV_ERR_HIP, "ring staging launch failed: %s", hipGetErrorString(err));
     // (a launch that fails behind this point leaves the ring and its position alone; head and the gravity form go back to what the caller saw)
-    const uint32_t head = b->head; const float* const grav_cur = b->grav_cur; const int grav_mode = b->grav_mode; const bool ran_live = b->ran_live;
+    const uint32_t head = b->head; const float* const grav_cur = b->grav_cur; const int grav_mode = b->grav_mode; const bool ran_live = b->ran_live; const uint32_t kept_live = b->kept_live;
     const glv_track_tables tb = {e.r.starts, d_ur, d_counts};
     int rc = track_each(b, e.r.stage, f32, rp.pitch, &tb, updates, d_out, work + rp.stage_bytes + rp.starts_bytes, ops, st);
     if (rc == GLV_OK) {
         err = glv::launch_ring_each_keep(f32, e, st);
         if (err != hipSuccess) rc = fail(GLV_ERR_HIP, "ring write-back launch failed: %s", hipGetErrorString(err));
     }
-    if (rc != GLV_OK) { b->head = head; b->grav_cur = grav_cur; b->grav_mode = grav_mode; b->ran_live = ran_live; return rc; }
+    if (rc != GLV_OK) { b->head = head; b->grav_cur = grav_cur; b->grav_mode = grav_mode; b->ran_live = ran_live; b->kept_live = kept_live; return rc; }
     *pos = 0;                           // the oldest frame sits at frame 0 of every ring, whatever its stream took
     b->last_launches += 2;              // the two copies around the per-stream table call's launches
     return GLV_OK;

@@ -389,7 +389,7 @@ class Batch:
     def load_streams(self, d_idx, count: int, d_blob, desc: StreamStateDesc, stream: int | None = None) -> None:
         """glv_batch_load_streams: blobs of save_streams into the listed streams, rotated by THIS batch's positions -- the stream then continues bit for
         bit as the saved one would have.  desc must match the batch (n, F, element size, regions: ERR_STATE), the gravity forms must agree unless one is
-        still 0, a live blob (kept_bins < n) loads only into an OP_BARS_ONLY batch with the same live_bins().  Duplicates in d_idx are the caller's error."""
+        still 0, a live blob (kept_bins < n) loads only into an OP_BARS_ONLY batch whose live_bins() are no more than that.  Duplicates in d_idx are the caller's error."""
         _check(lib().glv_batch_load_streams(self._h, _ptr(d_idx), count, _ptr(d_blob), C.byref(desc), _ptr(stream)))
 
     def copy_streams(self, d_dst_idx, src: "Batch", d_src_idx, count: int, stream: int | None = None) -> None:

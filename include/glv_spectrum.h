@@ -110,8 +110,9 @@ enum {
                                    kernel computes itself (fewer than 256 bars, every kernel configuration of the size fusable); any other
                                    batch (and log_mode 2) runs the full chain: the bars are bit-identical either way (no smooth_factor makes a
                                    bar sample further: smooth_audio() clamps its positions to [0, 1]).  A stateful call without GLV_OP_BARS and glv_batch_gravity_state are refused
-                                   (GLV_ERR_STATE); so is a glv_batch_set_params that would take a batch which has run its live class to the
-                                   full chain (the state beyond the live bins was never kept) -- until glv_batch_reset */
+                                   (GLV_ERR_STATE); so is a glv_batch_set_params (or a texel table) that would take a batch which has run its live class to the
+                                   full chain or to live bins beyond what its live calls have kept (glv_stream_state_desc.kept_bins: the state beyond
+                                   was never kept; shrinking and growing back within it are accepted) -- until glv_batch_reset */
     GLV_OP_WAVE     = 1u << 14, /* the wave module's bind (shaders/glava/wave/1.frag:7-9 requests `window`, `wrange`; `window` has no CPU stage,
                                    render.c:850): per channel row the backend's unpack (fifo.c:94-110 / pulse_input.c:155-178; channels == 1: the mono mix
                                    into both rows; planar f32 rows are taken as they are), transform_wrange (render.c:773-781: b += 1.0F; b /= 2.0F) and
@@ -1183,7 +1184,7 @@ int glv_batch_ring_track_each_f32(glv_batch* b, const float* d_new, uint32_t new
  *       gravity_form 0 loads anywhere; a batch whose form is still 0 adopts the blob's (all its streams are zero, and zero is the same state in both
  *       forms); otherwise the forms must be equal (a batch keeps one form: see glv_batch_gravity_state); a blob with kept_bins == n loads into any such
  *       batch, a GLV_OP_BARS_ONLY one included (whole rows are a superset of what it keeps); a blob with kept_bins < n loads only into a GLV_OP_BARS_ONLY
- *       batch whose glv_batch_live_bins() equals it, which then counts as having run its live class.
+ *       batch whose glv_batch_live_bins() are no more than it, which then counts as having run its live class and keeps the smaller of its own kept_bins and the blob's.
  * All three: GLV_ERR_INVALID for a NULL or misaligned pointer (d_idx 4 bytes, d_blob 16) and count == 0; GLV_ERR_STATE for a single-row batch (the glv_state
  * drop-ins') and while the batch's latest gravity output lives in the caller's buffer (GLV_OP_OUTPUT_IS_STATE in force: the library does not own that
  * memory); save and load also for a batch with neither state nor ring.  `setbufscale` plays no part: its staging rows are not state.
@@ -1193,7 +1194,7 @@ typedef struct glv_stream_state_desc {   /* host side; what a blob is, filled by
     uint32_t elem_bytes;      /* 4: float state (gl_storage 0 / 2 / 3), 2: GL_R16 texels (gl_storage 1) */
     uint32_t gravity_form;    /* the batch's form when asked: 0 none yet, 1 the gravity store, 2 the newest ring slot (gravity fused with average) */
     uint32_t regions;         /* bit 0 gravity rows, 1 average ring, 2 s16 PCM ring, 3 f32 PCM ring */
-    uint32_t kept_bins;       /* n, or glv_batch_live_bins() of a GLV_OP_BARS_ONLY batch that has run its live class */
+    uint32_t kept_bins;       /* n, or how far a GLV_OP_BARS_ONLY batch that has run its live class has kept its state: the smallest extent of its live calls since creation / glv_batch_reset (a process call: its live bins then; a live track call: its kept bins), not what it samples now */
     uint64_t bytes;           /* per stream */
 } glv_stream_state_desc;
 int glv_batch_stream_state_desc(const glv_batch* b, glv_stream_state_desc* d);
@@ -1265,7 +1266,8 @@ int glv_batch_bars(glv_batch* b, const float* d_spec, float* d_bars, void* hip_s
  *   table's taps.  glv_batch_reset keeps the table, glv_batch_destroy frees it.
  * glv_batch_live_bins: every snapped position lies in [0, 1), which the live bins already cover whenever smooth_factor >= 1 / bars (the unsnapped
  * last bar then reaches smooth_audio()'s last bin); a smaller factor grows them to the snapped taps' reach -- refused on a GLV_OP_BARS_ONLY batch
- * that has already run its live class (glv_batch_reset first). */
+ * that has already run its live class when that is beyond what it kept (glv_stream_state_desc.kept_bins; glv_batch_reset first).  A table that shrinks the
+ * live bins, and clearing one, are accepted. */
 int glv_batch_set_bar_texels(glv_batch* b, const uint32_t* texels, uint32_t count);
 
 /* GLV_OP_BARS as the columns of the graph module: the float mean of THREE texels of the pre-smoothed texture per column, which is what graph/1.frag:87-88

@@ -27,4 +27,16 @@ uint32_t live_emu_kept(uint32_t n, uint32_t bars, float smooth_factor, float pha
         if (it.w_byte != zero_off * 4u && it.tex_byte / 4u + chunk > *reach) *reach = it.tex_byte / 4u + chunk;
     return track_kept_bins(*live, bar_chunk_reach(desc, chunk));
 }
+
+// The bins `bars` bars of a row of n bins sample, in whole 64s, under a shape (sinusoidal, averaging; scale / range as glv_params sample_scale / sample_range
+// reach the tables): what glv_batch_live_bins reports where the chain has a live class for that many (tests/test_live_bins_changes_host.py pins the ladder
+// tests/test_live_bins_changes.py climbs).
+uint32_t live_emu_sampled(uint32_t n, uint32_t bars, float smooth_factor, float phase, float scale, float range) {
+    std::vector<BarDesc> desc;
+    std::vector<float> w;
+    make_bar_taps(desc, w, n, bars, smooth_factor, phase, BarShape{0u, scale, range, true});
+    uint32_t sampled = 0;
+    for (const BarDesc& d : desc) sampled = d.first_bin + d.count > sampled ? d.first_bin + d.count : sampled;
+    return (sampled + 63u) & ~63u;
+}
 }

@@ -1,5 +1,7 @@
 """Helpers shared by several GPU test files: a plain module, like oracle_lib.py and src_scan.py (default collection does not pick it up; torch is imported
 inside the functions, as in the tests).  A test file imports what it shares with another from here or from track_lib.py, never from that file."""
+import ctypes as C
+
 import numpy as np
 
 from oracle_lib import Oracle, Ref, lcg_pcm_fast
@@ -158,3 +160,64 @@ def gl_schedule(updates, seed=728):
         if u == 9: scale, cutoff = 10.2, 0.3
         out.append(dict(k, fft_scale=scale, fft_cutoff=cutoff, avg_window=u not in (2, 3, 8)))
     return out
+
+
+# ---- what the files that change parameters between updates share (tests/test_knob_changes.py, tests/test_live_bins_changes.py) ------------------------------
+KNOBS = ("ur", "gravity_step", "fft_scale", "fft_cutoff", "avg_window", "channels", "avg_window_kind")
+
+
+def knob_params(G, base, k, **more):
+    return G.Params(**{**base, **{key: v for key, v in k.items() if key in KNOBS}, **more})
+
+
+def frames(seed, u, streams, n, levels=(1, 8, 64)):
+    """int16 [streams][n][2] of update u: every stream at a level of its own, which moves from update to update"""
+    x = lcg_pcm_fast(seed + 31 * u, streams * n * 2).reshape(streams, n, 2).copy()
+    for s in range(streams):
+        x[s] //= levels[(s + u) % len(levels)]
+    return x
+
+
+def nan_rows(rows, w):
+    import torch
+    return torch.full((rows, w), float("nan"), dtype=torch.float32, device="cuda")
+
+
+def texel_rows(rows, w):
+    import torch
+    return torch.full((rows, w), -1, dtype=torch.int16, device="cuda")
+
+
+def u16(t):
+    return t.cpu().numpy().view(np.uint16)
+
+
+def refused(G, b, p, code):
+    import pytest
+    with pytest.raises(G.GlvError) as ei:
+        b.set_params(p)
+    assert ei.value.code == code, (ei.value.code, str(ei.value))
+
+
+class GLModel:
+    """the oracle's model of the GL passes for `rows` channel rows: transform_fft + glvo_gl_chain_r16 with each update's knobs, on float arrays of texel values"""
+
+    def __init__(self, rows, n, F, average):
+        self.n, self.F, self.average = n, F, average
+        self.store = np.zeros((rows, n), np.float32); self.hist = np.zeros((rows, F, n), np.float32)
+        self.heads = [C.c_size_t(0) for _ in range(rows)]
+
+    def row(self, r, samples, k):
+        """row r one update further on n float samples -> its GL_R16 texels"""
+        want = Oracle.transform_fft(samples, k["fft_scale"], k["fft_cutoff"])
+        Oracle.lib().glvo_gl_chain_r16(want, self.store[r], self.hist[r], C.byref(self.heads[r]), self.n, self.F, int(k["avg_window"]), int(self.average),
+                                       k["gravity_step"], k["ur"])
+        return Oracle.texels_r16(want)
+
+    def update(self, x, k):
+        """every row one update further on int16 [streams][n][2] -> texels [streams * 2][n]"""
+        out = np.empty((2 * len(x), self.n), np.uint16)
+        for s in range(len(x)):
+            for c, samples in enumerate(Oracle.unpack_s16(x[s], 2)):
+                out[2 * s + c] = self.row(2 * s + c, samples, k)
+        return out

@@ -14,44 +14,17 @@ import numpy as np
 import pytest
 
 from glava_amd.bar_positions import graph_column_texels, radial_bar_texels
-from gpu_lib import SIZES, bits, float_schedule, gl_schedule, oracle_bars as _oracle_bars, updates_of
-from oracle_lib import Oracle, StreamOracle, lcg_pcm_fast
+from gpu_lib import (SIZES, GLModel as _GLModel, bits, float_schedule, frames as _frames, gl_schedule, knob_params as _params, nan_rows as _nan,
+                     oracle_bars as _oracle_bars, refused as _refused, texel_rows as _texels, u16 as _u16, updates_of)
+from oracle_lib import Oracle, StreamOracle
 from track_lib import eq, hop_windows, pcm, pitch_odd, rec, seq, to_device, track
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("ur", "gravity_step", "fft_scale", "fft_cutoff", "avg_window", "channels", "avg_window_kind")
 
 
 def _same(got, want, what):
     bad = bits(got) != bits(want)
     assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:3].tolist(), np.asarray(got)[bad][:3], np.asarray(want)[bad][:3])
-
-
-def _params(G, base, k, **more):
-    return G.Params(**{**base, **{key: v for key, v in k.items() if key in KNOBS}, **more})
-
-
-def _frames(seed, u, streams, n, levels=(1, 8, 64)):
-    """int16 [streams][n][2] of update u: every stream at a level of its own, which moves from update to update"""
-    x = lcg_pcm_fast(seed + 31 * u, streams * n * 2).reshape(streams, n, 2).copy()
-    for s in range(streams):
-        x[s] //= levels[(s + u) % len(levels)]
-    return x
-
-
-def _nan(rows, w):
-    import torch
-    return torch.full((rows, w), float("nan"), dtype=torch.float32, device="cuda")
-
-
-def _texels(rows, w):
-    import torch
-    return torch.full((rows, w), -1, dtype=torch.int16, device="cuda")
-
-
-def _u16(t):
-    return t.cpu().numpy().view(np.uint16)
 
 
 def _set(so, k):
@@ -231,30 +204,6 @@ def test_bar_knobs_change_between_calls_of_stateless_bars(glvlib, oracle):
 
 
 # ---- c. the GL_R16 chain in one launch -----------------------------------------------------------------------------------------------------------------
-class _GLModel:
-    """the oracle's model of the GL passes for `rows` channel rows: transform_fft + glvo_gl_chain_r16 with each update's knobs, on float arrays of texel values"""
-
-    def __init__(self, rows, n, F, average):
-        self.n, self.F, self.average = n, F, average
-        self.store = np.zeros((rows, n), np.float32); self.hist = np.zeros((rows, F, n), np.float32)
-        self.heads = [C.c_size_t(0) for _ in range(rows)]
-
-    def row(self, r, samples, k):
-        """row r one update further on n float samples -> its GL_R16 texels"""
-        want = Oracle.transform_fft(samples, k["fft_scale"], k["fft_cutoff"])
-        Oracle.lib().glvo_gl_chain_r16(want, self.store[r], self.hist[r], C.byref(self.heads[r]), self.n, self.F, int(k["avg_window"]), int(self.average),
-                                       k["gravity_step"], k["ur"])
-        return Oracle.texels_r16(want)
-
-    def update(self, x, k):
-        """every row one update further on int16 [streams][n][2] -> texels [streams * 2][n]"""
-        out = np.empty((2 * len(x), self.n), np.uint16)
-        for s in range(len(x)):
-            for c, samples in enumerate(Oracle.unpack_s16(x[s], 2)):
-                out[2 * s + c] = self.row(2 * s + c, samples, k)
-        return out
-
-
 def _want_sm(G, b, texels, factor, phase=0.5):
     """the pre-smoothing pass over one row of `av` texels in the arithmetic the batch reports: the exact integer mean, or the fma chain of the texels' floats"""
     bars = b.params.bars
@@ -592,12 +541,6 @@ def test_track_calls_cut_at_a_knob_change_equal_the_sequential_calls(glvlib, ora
 
 
 # ---- g. refused and forced ----------------------------------------------------------------------------------------------------------------------------
-def _refused(G, b, p, code):
-    with pytest.raises(G.GlvError) as ei:
-        b.set_params(p)
-    assert ei.value.code == code, (ei.value.code, str(ei.value))
-
-
 def test_a_refused_change_leaves_a_batch_with_bar_texels_as_it_was(glvlib):
     """glv_batch_set_params refused by the validation (channels = 3) and with GLV_ERR_STATE (n, avg_frames, gl_storage across the storage class, gl_storage 0
     and another bar count while a bar-texel table is set), each asking for other tables as well: the next F + 2 updates equal an unperturbed twin's"""
